@@ -22,6 +22,11 @@ cpu_baseline = the C/OpenMP oracle (oracle/gptq_oracle.c, a port of the referenc
              rides along as `replicas_reported_only`.  `--tp megatron` N-shards qkv / gate / up and K-shards o / down (2 all-reduces
              per layer); `--allreduce p2p` is the one-shot exchange over IPC peer mappings (csrc/p2p.hip).  quant/tensor_parallel.py is
              the module-level counterpart (world_size-2 gloo tests).
+--full     = everything beyond the headline figure: per-shape timings, the side legs (prefill, small batch, prompt, config 4, the
+             world-1 65B stack, decode tokens/s), the CPU baselines, the committed PMC traffic figure, and at N > 1 the all-reduce
+             latencies, the replicas leg and the world-1 figure.  A plain run sets up, warms up, times --steps steps and prints the line.
+--dump-outputs DIR = after the timed steps, the buffers the last step wrote (what a caller of the pass receives) as DIR/<name>.npy
+             in float32; the inputs are seeded, so two builds given the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -126,6 +131,11 @@ class DecodeLinears:
             self._mm(self.x_h, L, 'o', self.y_h, s)
             self._mlp(self.x_h, L, self.y_i, s)
             self._mm(self.x_i, L, 'down', self.y_h, s)
+
+    def outputs(self):
+        """what one step leaves to its caller: the last layer's fused qkv, gate/up+SiLU and down_proj outputs (o_proj writes y_h
+        before down_proj overwrites it)"""
+        return {'y_qkv': self.y_qkv, 'y_down': self.y_h, 'y_gate_up_silu': self.y_i}
 
     def per_shape(self, reps=20):
         """event-timed launches per shape, rotating over the 32 layers' distinct weights (cold)."""
@@ -324,6 +334,21 @@ class TPLayers:
                 self._full(self.x_h, L['mlp'], self.y_i_loc, H65, self.nb_i[1] - self.nb_i[0], 2)           # SiLU fused: columns are local
                 self._partial(self.x_i[:, ki], L['down'], self.p_h, Ki, H65, 1)
                 self._reduce_round(self.p_h, self.y_h)
+
+    def outputs(self):
+        """what one step leaves to this rank: the last layer's qkv, gate/up+SiLU (this rank's columns in megatron mode) and the
+        all-reduced down_proj output"""
+        if self.mode == 'row':
+            return {'y_qkv': self.y_qkv, 'y_down': self.y_h, 'y_gate_up_silu': self.y_i}
+        return {'y_qkv_local': self.y_qkv_loc, 'y_down': self.y_h, 'y_gate_up_silu_local': self.y_i_loc}
+
+
+def dump_outputs(work, out_dir):
+    """--dump-outputs: the step's output buffers as float32 .npy files (a few hundred KB in all)"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in work.outputs().items():
+        np.save(os.path.join(out_dir, name + '.npy'), t.detach().float().cpu().numpy())
 
 
 def tp_world1_leg(dev, mode, layers, steps=20):
@@ -852,9 +877,16 @@ def main():
     ap.add_argument('--no-config4', action='store_true')
     ap.add_argument('--no-small-batch', action='store_true')
     ap.add_argument('--pmc-file', default=None, help='traffic.json of a `rocprofv3 --pmc FETCH_SIZE` pass over this command (tools/pmc_traffic.py)')
+    ap.add_argument('--full', action='store_true',
+                    help='also run everything beyond the headline figure: per-shape timings, side legs, CPU baselines, PMC traffic, '
+                         'all-reduce latencies, replicas and world-1 legs (the --no-* options trim this set)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last step computed as DIR/<name>.npy (float32, rank 0)')
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error('--gpus must be >= 1')
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # `python bench.py --gpus N` without a launcher: start the N ranks ourselves (one process per GPU under torch.distributed.run,
         # rendezvous on 127.0.0.1) -- the reference spreads over GPUs from one command too (llama.py:328-382).  Rank 0 prints the line.
@@ -954,9 +986,11 @@ def main():
     if distributed:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     wall_max = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(work, args.dump_outputs)
 
     tp_lat = None
-    if args.tp:   # collectives: every rank takes part
+    if args.tp and args.full:   # collectives: every rank takes part
         tp_lat = {'32KB_fp32_8192': round(allreduce_latency_us(dev, world, H65), 2), '96KB_fp32_24576': round(allreduce_latency_us(dev, world, 3 * H65), 2),
                   '172KB_fp32_2x22016': round(allreduce_latency_us(dev, world, 2 * I65), 2)}
         if work.p2p is not None:
@@ -965,7 +999,7 @@ def main():
                            'p2p_172KB': round(allreduce_latency_us(dev, world, 2 * I65, p2p=work.p2p), 2),
                            'p2p_status': work.p2p.status()})
     replicas = None
-    if args.tp and distributed and not os.environ.get('GPTQ_BENCH_NO_REPLICAS'):
+    if args.tp and distributed and args.full and not os.environ.get('GPTQ_BENCH_NO_REPLICAS'):
         # reported-only side leg: the N = 1 workload (BASELINE configs[1]) as N independent replicas, no data-path collective
         try:
             del graph
@@ -1001,10 +1035,10 @@ def main():
         us_per_launch = ev_ms * 1e3 / (args.steps * work.launches_per_step)
         bytes_per_launch = work.bytes_per_step / work.launches_per_step
         achieved = bytes_per_launch / us_per_launch / 1e3
-        traffic, traffic_src = pmc_traffic(args.pmc_file)
+        traffic, traffic_src = pmc_traffic(args.pmc_file) if (args.full or args.pmc_file) else (None, 'not read: --full or --pmc-file reads a PMC pass')
         if args.tp:
             try:   # rank 0 alone (the other ranks wait in the final barrier): same stack, world 1
-                tp1 = tp_world1_leg(dev, args.tp, args.tp_layers) if not os.environ.get('GPTQ_BENCH_NO_TP1') else None
+                tp1 = tp_world1_leg(dev, args.tp, args.tp_layers) if args.full and not os.environ.get('GPTQ_BENCH_NO_TP1') else None
             except Exception as e:
                 tp1 = {'error': repr(e)[:200]}
             out = {
@@ -1065,36 +1099,37 @@ def main():
             except Exception as e:        # the headline line must survive a failure of a side leg
                 out[key] = {'error': repr(e)[:200]}
             out['memory_MiB'][key] = round(torch.cuda.max_memory_allocated() / 2**20, 1)
-        # the side legs run at N = 1 only (the other ranks would sit in the final barrier meanwhile)
-        if not args.no_per_shape and world == 1:
-            out['per_shape'] = work.per_shape()
-            try:
-                out['per_shape_llama65b_reported_only'] = larger_model_shapes(dev)
-            except Exception as e:
-                out['per_shape_llama65b_reported_only'] = {'error': repr(e)[:200]}
-        if world == 1:
-            work = graph = run = None       # free the 6.8 GB of the matvec pass: every later leg reports its OWN peak
-        if not args.no_prefill and world == 1:
-            leg('prefill_config3_reported_only', lambda: prefill_leg(dev))
-        if not args.no_small_batch and world == 1:
-            leg('small_batch_reported_only', lambda: small_batch_leg(dev))
-            leg('prompt_reported_only', lambda: prompt_leg(dev))
-        if not args.no_config4 and world == 1:
-            leg('config4_reported_only', lambda: config4_leg(dev))
-        if world == 1 and not os.environ.get('GPTQ_BENCH_NO_TP1'):
-            # the N = 1 point of the OTHER curve: `--gpus N > 1` runs BASELINE configs[4] (65B stack, row-sharded); this is that stack at world 1
-            leg('tp1_same_workload_as_gpus_gt_1', lambda: tp_world1_leg(dev, 'row', args.tp_layers))
-        if not args.no_decode and world == 1:
-            leg('decode', lambda: decode_tokens_per_s(dev))
-        if not args.no_cpu_baseline and world == 1:
-            try:
-                out['cpu_baseline'] = cpu_baseline()
-            except Exception as e:
-                out['cpu_baseline'] = {'error': repr(e)[:200]}
-            try:
-                out['gptq_loop_reported_only'] = gptq_loop_baseline(dev)
-            except Exception as e:
-                out['gptq_loop_reported_only'] = {'error': repr(e)[:200]}
+        if args.full:     # everything beyond the headline figure
+            # the side legs run at N = 1 only (the other ranks would sit in the final barrier meanwhile)
+            if not args.no_per_shape and world == 1:
+                out['per_shape'] = work.per_shape()
+                try:
+                    out['per_shape_llama65b_reported_only'] = larger_model_shapes(dev)
+                except Exception as e:
+                    out['per_shape_llama65b_reported_only'] = {'error': repr(e)[:200]}
+            if world == 1:
+                work = graph = run = None       # free the 6.8 GB of the matvec pass: every later leg reports its OWN peak
+            if not args.no_prefill and world == 1:
+                leg('prefill_config3_reported_only', lambda: prefill_leg(dev))
+            if not args.no_small_batch and world == 1:
+                leg('small_batch_reported_only', lambda: small_batch_leg(dev))
+                leg('prompt_reported_only', lambda: prompt_leg(dev))
+            if not args.no_config4 and world == 1:
+                leg('config4_reported_only', lambda: config4_leg(dev))
+            if world == 1 and not os.environ.get('GPTQ_BENCH_NO_TP1'):
+                # the N = 1 point of the OTHER curve: `--gpus N > 1` runs BASELINE configs[4] (65B stack, row-sharded); this is that stack at world 1
+                leg('tp1_same_workload_as_gpus_gt_1', lambda: tp_world1_leg(dev, 'row', args.tp_layers))
+            if not args.no_decode and world == 1:
+                leg('decode', lambda: decode_tokens_per_s(dev))
+            if not args.no_cpu_baseline and world == 1:
+                try:
+                    out['cpu_baseline'] = cpu_baseline()
+                except Exception as e:
+                    out['cpu_baseline'] = {'error': repr(e)[:200]}
+                try:
+                    out['gptq_loop_reported_only'] = gptq_loop_baseline(dev)
+                except Exception as e:
+                    out['gptq_loop_reported_only'] = {'error': repr(e)[:200]}
         print(json.dumps(out))
     if distributed:
         dist.barrier()

@@ -22,7 +22,8 @@ def pytest_configure(config):
     ora = os.path.join(ROOT, 'oracle', 'libgptq_oracle.so')
     if not (os.path.exists(lib) and os.path.exists(ora)):
         import subprocess
-        subprocess.check_call(['make', '-C', os.path.join(PKG, 'csrc'), '-j', str(max(1, os.cpu_count() or 1))])
+        jobs = os.environ.get('MAX_JOBS') or str(max(1, min(16, os.cpu_count() or 1)))
+        subprocess.check_call(['make', '-C', os.path.join(PKG, 'csrc'), '-j', jobs])
         subprocess.check_call(['make', '-C', os.path.join(ROOT, 'oracle')])
 
 

@@ -1228,7 +1228,7 @@ def test_bench_gpus2_prints_the_tensor_parallel_contract_line():
     s.close()
     env = dict(os.environ, GPTQ_BENCH_BACKEND='gloo', GPTQ_BENCH_ONE_DEVICE='1', HSA_ENABLE_IPC_MODE_LEGACY='0')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1', '--master-port', str(port),
-           os.path.join(ROOT_DIR, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1', '--tp-layers', '2']
+           os.path.join(ROOT_DIR, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1', '--tp-layers', '2', '--full']
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith('{')]
@@ -1249,7 +1249,7 @@ def test_bench_gpus8_really_runs_eight_processes(allreduce):
     import sys
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT')}
     env.update(GPTQ_BENCH_BACKEND='gloo', GPTQ_BENCH_ONE_DEVICE='1', HSA_ENABLE_IPC_MODE_LEGACY='0', GPTQ_BENCH_NO_REPLICAS='1', GPTQ_BENCH_NO_TP1='1')
-    cmd = [sys.executable, os.path.join(ROOT_DIR, 'bench.py'), '--gpus', '8', '--steps', '3', '--warmup', '1', '--tp-layers', '1', '--allreduce', allreduce]
+    cmd = [sys.executable, os.path.join(ROOT_DIR, 'bench.py'), '--gpus', '8', '--steps', '3', '--warmup', '1', '--tp-layers', '1', '--allreduce', allreduce, '--full']
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith('{')]
@@ -1271,7 +1271,7 @@ def test_bench_tp_falls_back_to_eager_when_the_capture_fails():
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT')}
     env.update(GPTQ_BENCH_BACKEND='gloo', GPTQ_BENCH_ONE_DEVICE='1', HSA_ENABLE_IPC_MODE_LEGACY='0', GPTQ_BENCH_NO_REPLICAS='1', GPTQ_BENCH_NO_TP1='1',
                GPTQ_BENCH_FORCE_EAGER_TP='1')
-    cmd = [sys.executable, os.path.join(ROOT_DIR, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1', '--tp-layers', '1', '--allreduce', 'p2p']
+    cmd = [sys.executable, os.path.join(ROOT_DIR, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1', '--tp-layers', '1', '--allreduce', 'p2p', '--full']
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith('{')][0])
@@ -1286,7 +1286,7 @@ def test_bench_gpus2_without_a_launcher_starts_its_own_ranks():
     import sys
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT')}
     env.update(GPTQ_BENCH_BACKEND='gloo', GPTQ_BENCH_ONE_DEVICE='1', HSA_ENABLE_IPC_MODE_LEGACY='0', GPTQ_BENCH_NO_REPLICAS='1')
-    cmd = [sys.executable, os.path.join(ROOT_DIR, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1', '--tp-layers', '2']
+    cmd = [sys.executable, os.path.join(ROOT_DIR, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1', '--tp-layers', '2', '--full']
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith('{')]
@@ -1295,3 +1295,39 @@ def test_bench_gpus2_without_a_launcher_starts_its_own_ranks():
     assert d['n_gpus'] == 2 and d['config']['world_size_reported_by_backend'] == 2 and d['config']['parallelism'] == 'tp2 row'
     t1 = d['tp1_same_workload']
     assert t1['n_gpus'] == 1 and t1['GBps'] > 0 and t1['ms_per_step'] > 0, t1
+
+
+def test_bench_plain_run_times_the_pass_and_dumps_its_outputs(tmp_path):
+    """`bench.py --gpus 1` without --full: the headline line alone, --steps timed steps; --dump-outputs writes what the last step
+    computed, which is the last layer's products of the seeded weights (regenerated here in the bench's draw order) against the oracle"""
+    import json
+    import subprocess
+    import sys
+    import bench
+    env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT')}
+    dump = tmp_path / 'out'
+    cmd = [sys.executable, os.path.join(ROOT_DIR, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--dump-outputs', str(dump)]
+    out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith('{')]
+    assert len(lines) == 1, out.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d['steps'] == 3 and d['warmup'] == 1 and d['ms_per_step'] > 0 and d['value'] > 0 and d['unit'] == 'GB/s' and d['higher_is_better'] is True
+    assert not {'per_shape', 'decode', 'cpu_baseline', 'prefill_config3_reported_only', 'tp1_same_workload_as_gpus_gt_1'} & set(d)
+    got = {n: np.load(str(dump / (n + '.npy'))) for n in ('y_qkv', 'y_down', 'y_gate_up_silu')}
+    assert all(v.dtype == np.float32 for v in got.values())
+    gen = torch.Generator(device='cuda:0')
+    gen.manual_seed(0)
+    for _ in range(bench.LAYERS):     # DecodeLinears(seed=0) draws qkv, o, gate, up, down per layer, then x_h and x_i
+        L = {k: bench.PackedSet(K, N, 'cuda:0', gen) for k, K, N in (('qkv', bench.HIDDEN, 3 * bench.HIDDEN), ('o', bench.HIDDEN, bench.HIDDEN),
+             ('gate', bench.HIDDEN, bench.INTER), ('up', bench.HIDDEN, bench.INTER), ('down', bench.INTER, bench.HIDDEN))}
+    x_h = torch.randn((1, bench.HIDDEN), device='cuda:0', generator=gen).half().cpu().numpy()
+    x_i = (torch.randn((1, bench.INTER), device='cuda:0', generator=gen) * 0.5).half().cpu().numpy()
+    ws = {k: (w.qweight.cpu().numpy(), w.scales.cpu().numpy(), w.qzeros.cpu().numpy(), oracle.trivial_g_idx(w.K, bench.GS)) for k, w in L.items()}
+    del L
+    ref = {'y_qkv': oracle.matmul248(x_h, *ws['qkv'], bench.BITS), 'y_down': oracle.matmul248(x_i, *ws['down'], bench.BITS),
+           'y_gate_up_silu': oracle.fused_mlp(x_h, ws['gate'], ws['up'], bench.BITS)}
+    for n, r in ref.items():
+        assert got[n].shape == r.shape, (n, got[n].shape, r.shape)
+        err = float(np.abs(got[n] - r.astype(np.float64)).max() / np.abs(r.astype(np.float64)).max())
+        assert err < 1e-3, (n, err)

@@ -1,22 +1,19 @@
 """The acceptance callers of the drop-in boundary (BASELINE north_star: "so llama_inference.py runs unmodified").
 
-CPU leg (``-m "not gpu"``, needs the read-only upstream tree, skipped where it is absent): the reference's OWN
-``llama_inference.load_quant`` (/root/reference/llama_inference.py:27-72) and ``llama.load_quant``
-(/root/reference/llama.py:279-325) are imported unmodified with this package answering ``import quant`` / ``import gptq``
-(``utils`` is the reference's own; ``texttable`` / ``toml`` are absent from the image and stubbed), and run on a tiny
-config + a checkpoint saved in the reference's state_dict format: module surgery, checkpoint keys, buffer contents.
-The warm-ups need a GPU (the reference moves buffers with ``.cuda()``, quant_linear.py:409), so the CPU leg passes
-``warmup_autotune=False``.
+The upstream scripts are not part of this repository, so ``load_quant_flow`` below restates their ``load_quant``
+(llama_inference.py:27-72; llama.py:279-325 is the same flow with a strict ``load_state_dict``) line by line, each step
+cited, on top of the package, which answers ``import quant`` / ``import gptq`` as it does for the scripts.
 
-GPU leg (``-m gpu``): the default load path, warm-ups included.  /root/reference does not exist on the GPU box, so
-``load_quant_flow`` below restates the reference function line by line (each step cited) on top of the package; when
-the tree IS present the real function is used instead.  Then ``model.to(DEV)`` and ``model.generate`` as
+CPU leg (``-m "not gpu"``): that flow on a tiny config + a checkpoint saved in the reference's state_dict format: module
+surgery, checkpoint keys, buffer contents.  The warm-ups need a GPU (the reference moves buffers with ``.cuda()``,
+quant_linear.py:409), so the CPU leg passes ``warmup_autotune=False``.
+
+GPU leg (``-m gpu``): the default load path, warm-ups included, then ``model.to(DEV)`` and ``model.generate`` as
 llama_inference.py:117-127 does, and the two warm-ups once more on their own with the buffer placement the reference
 leaves behind (``autotune_warmup_fused`` ends with ``fused2cpu``, fused_mlp.py:283-286).
 """
 import os
 import sys
-import types
 
 import numpy as np
 import pytest
@@ -25,7 +22,6 @@ import torch
 import quant
 from quant import decode as D
 
-REF = '/root/reference'
 TINY = dict(hidden_size=256, intermediate_size=512, num_hidden_layers=2, num_attention_heads=2, num_key_value_heads=2,
             vocab_size=320, max_position_embeddings=256, rms_norm_eps=1e-6)
 WBITS, GROUPSIZE = 4, 128
@@ -63,28 +59,6 @@ def _tiny_checkpoint(tmp_path, config_dir, seed=0):
     return path, sd
 
 
-def _import_reference(name):
-    """import /root/reference/<name>.py unmodified with this package shadowing `quant` and `gptq`."""
-    for stub in ('texttable', 'toml'):
-        if stub not in sys.modules:
-            try:
-                __import__(stub)
-            except ImportError:
-                m = types.ModuleType(stub)
-                if stub == 'texttable':
-                    m.Texttable = type('Texttable', (), {})
-                sys.modules[stub] = m
-    import gptq as product_gptq          # gptq-for-llama_amd/gptq.py (conftest puts the package first on sys.path)
-    assert 'gptq-for-llama_amd' in os.path.abspath(product_gptq.__file__)
-    assert 'gptq-for-llama_amd' in os.path.abspath(quant.__file__)
-    if REF not in sys.path:
-        sys.path.append(REF)             # behind the package: only `utils`, `llama`, `llama_inference` resolve there
-    mod = __import__(name)
-    assert os.path.abspath(mod.__file__).startswith(REF)
-    assert mod.quant is quant
-    return mod
-
-
 def _restore_torch_defaults(saved):
     torch.nn.init.kaiming_uniform_, torch.nn.init.uniform_, torch.nn.init.normal_ = saved
     torch.set_default_dtype(torch.float)
@@ -114,30 +88,29 @@ def _check_loaded_model(model, sd):
     assert model.seqlen == 2048
 
 
-needs_reference = pytest.mark.skipif(not os.path.isdir(REF), reason='the upstream tree is not present on this machine')
-
-
-@needs_reference
 @pytest.mark.parametrize('module', ['llama_inference', 'llama'])
 def test_reference_load_quant_runs_unmodified_on_the_package(tmp_path, module, capsys):
+    """the scripts' load_quant flow (llama.py's loads the checkpoint strictly) on the package's `quant` and `gptq`"""
+    import gptq as product_gptq          # gptq-for-llama_amd/gptq.py (conftest puts the package first on sys.path)
+    assert 'gptq-for-llama_amd' in os.path.abspath(product_gptq.__file__)
+    assert 'gptq-for-llama_amd' in os.path.abspath(quant.__file__)
     saved = (torch.nn.init.kaiming_uniform_, torch.nn.init.uniform_, torch.nn.init.normal_)
     try:
         cfg_dir = _tiny_config_dir(tmp_path)
         ckpt, sd = _tiny_checkpoint(tmp_path, cfg_dir)
-        ref = _import_reference(module)
-        model = ref.load_quant(cfg_dir, ckpt, WBITS, GROUPSIZE, warmup_autotune=False)
+        model = load_quant_flow(cfg_dir, ckpt, WBITS, GROUPSIZE, warmup_autotune=False, strict=(module == 'llama'))
     finally:
         _restore_torch_defaults(saved)
     out = capsys.readouterr().out
     assert 'Loading model ...' in out and 'Done.' in out
     _check_loaded_model(model, sd)
     # find_layers(model, [quant.QuantLinear]) is an exact type match (utils/modelutils.py:8; llama.py:269)
-    q = ref.find_layers(model, [quant.QuantLinear])
+    q = D.find_layers(model, [quant.QuantLinear])
     assert len(q) == 3 * TINY['num_hidden_layers']                    # qkv_proj, o_proj, down_proj per layer
 
 
-def load_quant_flow(model, checkpoint, wbits, groupsize=-1, fused_mlp=True, eval=True, warmup_autotune=True):
-    """llama_inference.py:27-72 restated on the package (the tree is absent on the GPU box)."""
+def load_quant_flow(model, checkpoint, wbits, groupsize=-1, fused_mlp=True, eval=True, warmup_autotune=True, strict=False):
+    """llama_inference.py:27-72 restated on the package; strict=True: llama.py:279-325, which differs only there (:306-310)."""
     from transformers import LlamaConfig, LlamaForCausalLM
     config = LlamaConfig.from_pretrained(model)                        # :29
     torch.set_default_dtype(torch.half)                                # :38-41
@@ -153,7 +126,7 @@ def load_quant_flow(model, checkpoint, wbits, groupsize=-1, fused_mlp=True, eval
             del layers[name]                                           # :46-48
     quant.make_quant_linear(model, layers, wbits, groupsize)           # :49
     print('Loading model ...')
-    model.load_state_dict(torch.load(checkpoint), strict=False)        # :58-60
+    model.load_state_dict(torch.load(checkpoint), strict=strict)       # :58-60
     if eval:
         quant.make_quant_attn(model)                                   # :61-63
         quant.make_quant_norm(model)
@@ -176,8 +149,7 @@ def test_default_load_path_with_warmups_then_generate(tmp_path, capsys):
     try:
         cfg_dir = _tiny_config_dir(tmp_path)
         ckpt, sd = _tiny_checkpoint(tmp_path, cfg_dir)
-        load = _import_reference('llama_inference').load_quant if os.path.isdir(REF) else load_quant_flow
-        model = load(cfg_dir, ckpt, WBITS, GROUPSIZE)
+        model = load_quant_flow(cfg_dir, ckpt, WBITS, GROUPSIZE)
     finally:
         _restore_torch_defaults(saved)
     out = capsys.readouterr().out
@@ -198,8 +170,8 @@ def test_default_load_path_with_warmups_then_generate(tmp_path, capsys):
     assert int(greedy.max()) < TINY['vocab_size']
 
 
-# llama_inference.py:75-128 restated (the tree is absent on the GPU box): the script's own argument names, its load / to(DEV) / tokenizer / generate /
-# decode / print sequence -- run as a PROCESS below.  `load_quant` = this file's restatement of :27-72 (or the reference's own function where the tree is).
+# llama_inference.py:75-128 restated: the script's own argument names, its load / to(DEV) / tokenizer / generate /
+# decode / print sequence -- run as a PROCESS below.  `load_quant` = this file's restatement of :27-72.
 MAIN_FLOW = r"""
 import argparse, os, sys
 import torch
@@ -222,7 +194,7 @@ parser.add_argument('--fused_mlp', action='store_true')
 parser.add_argument('--no_fused_mlp', dest='fused_mlp', action='store_false')
 parser.set_defaults(fused_mlp=True)
 args = parser.parse_args()
-load_quant = T._import_reference('llama_inference').load_quant if os.path.isdir(T.REF) else T.load_quant_flow
+load_quant = T.load_quant_flow
 model = load_quant(args.model, args.load, args.wbits, args.groupsize, fused_mlp=args.fused_mlp)     # :110-111
 model.to(DEV)                                                           # :116
 tokenizer = AutoTokenizer.from_pretrained(args.model, use_fast=False)   # :117

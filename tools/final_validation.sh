@@ -10,7 +10,7 @@ timeout 1200 python -m pytest tests -q -m gpu > $O/pytest_gpu.txt 2>&1; tail -6 
 # round 5: the PMC pass FIRST, stamped with the kernel-source hash (tools/pmc_traffic.py), then the bench line takes its traffic from THIS pass
 (cd /tmp && export TMPDIR=/tmp && GPTQ_BENCH_NO_TP1=1 timeout 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace -f csv -d $GRAFT_REPO_ROOT/$O/pmc -- python $GRAFT_REPO_ROOT/bench.py --steps 2 --warmup 1 --eager --no-decode --no-cpu-baseline --no-per-shape --no-prefill --no-config4 --no-small-batch > $GRAFT_REPO_ROOT/$O/pmc_bench.txt 2>&1)
 CC=$(find $O/pmc -name "*counter_collection.csv" | head -1); python tools/pmc_traffic.py "$CC" $O/traffic.json | tail -4
-timeout 1200 python bench.py --pmc-file $O/traffic.json > $O/bench.json.txt 2> $O/bench.err; tail -c 400 $O/bench.json.txt
+timeout 1200 python bench.py --full --pmc-file $O/traffic.json > $O/bench.json.txt 2> $O/bench.err; tail -c 400 $O/bench.json.txt
 fi
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
