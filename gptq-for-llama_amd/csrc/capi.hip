@@ -125,13 +125,19 @@ static int run_rowwave3(const Problem &q, hipStream_t s) {
     if (fs >= 1) split_k = fs;
     if (split_k > nchunk) split_k = nchunk;
     if (split_k > (q.fused2 ? SPLITK_MAX_PAIR : SPLITK_MAX_SINGLE)) split_k = q.fused2 ? SPLITK_MAX_PAIR : SPLITK_MAX_SINGLE;
-    // the per-column combine words live in the first SPLITK_TICKET_OFFSET bytes of the workspace (the rest belongs
-    // to the stream kernel's tickets / partial tiles and is not zero): wider layers run without a K split
-    const size_t ws_need = (size_t)q.N * 8 * (q.fused2 ? 2 : 1);   // one combine word per column (two for gate/up)
-    const bool ws_ok = q.ws && aligned(q.ws, 8) && q.ws_bytes >= ws_need && ws_need <= SPLITK_TICKET_OFFSET;
-    if (split_k > 1 && !ws_ok) {
+    // the per-column arrival counts live in the first SPLITK_TICKET_OFFSET bytes of the workspace (the rest belongs
+    // to the stream kernel's tickets and to the partials): wider layers run without a K split, and the slices are
+    // limited to the partials that fit
+    const int ns = q.fused2 ? 2 : 1;
+    const bool ws_ok = q.ws && aligned(q.ws, 8) && q.ws_bytes > SPLITK_PART_OFFSET && (size_t)q.N * 4 <= SPLITK_TICKET_OFFSET;
+    const int split_fit = ws_ok ? (int)((q.ws_bytes - SPLITK_PART_OFFSET) / splitk_part_bytes(1, q.N, ns)) : 1;
+    if (split_k > 1 && (!ws_ok || split_fit < 2)) {
         if (fs >= 1) return GPTQ_E_WORKSPACE;
         split_k = 1;
+    }
+    if (split_k > split_fit) {
+        if (fs >= 1) return GPTQ_E_WORKSPACE;   // as the stream kernel: a forced split the workspace cannot hold is refused
+        split_k = split_fit;
     }
     for (int m = 0; m < q.M; m++) {
         GemvParams p;
@@ -180,13 +186,19 @@ static int run_rowwave(const Problem &q, hipStream_t s) {
     if (fs >= 1) split_k = fs;
     if (split_k > nchunk) split_k = nchunk;
     if (split_k > split_max) split_k = split_max;
-    // the per-column combine words live in the first SPLITK_TICKET_OFFSET bytes of the workspace (the rest belongs
-    // to the stream kernel's tickets / partial tiles and is not zero): wider layers run without a K split
-    const size_t ws_need = (size_t)q.N * 8 * (q.fused2 ? 2 : 1);   // one combine word per column (two for gate/up)
-    const bool ws_ok = q.ws && aligned(q.ws, 8) && q.ws_bytes >= ws_need && ws_need <= SPLITK_TICKET_OFFSET;
-    if (split_k > 1 && !ws_ok) {
+    // the per-column arrival counts live in the first SPLITK_TICKET_OFFSET bytes of the workspace (the rest belongs
+    // to the stream kernel's tickets and to the partials): wider layers run without a K split, and the slices are
+    // limited to the partials that fit
+    const int ns = q.fused2 ? 2 : 1;
+    const bool ws_ok = q.ws && aligned(q.ws, 8) && q.ws_bytes > SPLITK_PART_OFFSET && (size_t)q.N * 4 <= SPLITK_TICKET_OFFSET;
+    const int split_fit = ws_ok ? (int)((q.ws_bytes - SPLITK_PART_OFFSET) / splitk_part_bytes(1, q.N, ns)) : 1;
+    if (split_k > 1 && (!ws_ok || split_fit < 2)) {
         if (fs >= 1) return GPTQ_E_WORKSPACE;
         split_k = 1;
+    }
+    if (split_k > split_fit) {
+        if (fs >= 1) return GPTQ_E_WORKSPACE;   // as the stream kernel: a forced split the workspace cannot hold is refused
+        split_k = split_fit;
     }
     for (int m = 0; m < q.M; m++) {
         GemvParams p;
@@ -264,8 +276,9 @@ static int run_rowwave_mr(const Problem &q, hipStream_t s) {
     if (split_k > nchunk) split_k = nchunk;
     const int split_max = q.fused2 ? SPLITK_MAX_PAIR : SPLITK_MAX_SINGLE;
     if (split_k > split_max) split_k = split_max;
-    const size_t words = (size_t)q.M * q.N * 8 * (q.fused2 ? 2 : 1);
-    const bool ws_ok = q.ws && aligned(q.ws, 8) && q.ws_bytes >= words && words <= SPLITK_TICKET_OFFSET;
+    const size_t ncomb = (size_t)q.M * q.N;   // one arrival count per output element ({gate, up} pair)
+    const bool ws_ok = q.ws && aligned(q.ws, 8) && q.ws_bytes > SPLITK_PART_OFFSET && ncomb * 4 <= SPLITK_TICKET_OFFSET &&
+                       q.ws_bytes - SPLITK_PART_OFFSET >= splitk_part_bytes(split_k, ncomb, q.fused2 ? 2 : 1);
     if (split_k > 1 && !ws_ok) return GPTQ_E_VARIANT;   // the per-row / stream paths handle it
     GemvParams p;
     fill_params(q, 0, q.M, p);

@@ -16,8 +16,8 @@
 //    the offset and the zero point are removed once per (group, column):
 //        y += s * (sum_k x_k (OFF + q_k) - (OFF + z) * sum_k x_k);
 //  * the 4 waves of a workgroup take 4 consecutive U-row blocks (one LDS reduce), K is split over
-//    S workgroups per 256-column tile and combined with ONE returning 64-bit fixed-point atomic
-//    per output (gptq_device.h): bit-reproducible, no second pass.
+//    S workgroups per 256-column tile: each stores its fp32 partial, the last to arrive (one returning
+//    atomic per output) sums them in slice order (splitk_combine, gptq_internal.h): bit-reproducible.
 //  * act-order / odd group sizes / 3-bit go through gemv_generic_kernel, which keeps a per-tile
 //    {scale, zero} table in LDS indexed by g_idx[k].
 #include "gptq_device.h"
@@ -244,8 +244,12 @@ __global__ void __launch_bounds__(256) gemv_rowwave_kernel(
     if (n < (uint32_t)N) {
         bool mine = true;
         if (S > 1) {
-            if constexpr (FUSED2) mine = splitk_add2(ws + 2 * (size_t)n, t0, t1, S, t0, t1);
-            else mine = splitk_add1(ws + n, t0, S, t0);
+            if constexpr (FUSED2) {
+                float2_t v2 = {t0, t1};
+                mine = splitk_combine(ws, n, (uint32_t)N, slice, S, v2);
+                t0 = v2[0], t1 = v2[1];
+            } else
+                mine = splitk_combine(ws, n, (uint32_t)N, slice, S, t0);
         }
         if (mine) {
             float v = t0;
@@ -385,8 +389,12 @@ __global__ void __launch_bounds__(256) gemv_rowwave3_kernel(const uint32_t *__re
     if (n < (uint32_t)N) {
         bool mine = true;
         if (S > 1) {
-            if constexpr (FUSED2) mine = splitk_add2(ws + 2 * (size_t)n, t0, t1, S, t0, t1);
-            else mine = splitk_add1(ws + n, t0, S, t0);
+            if constexpr (FUSED2) {
+                float2_t v2 = {t0, t1};
+                mine = splitk_combine(ws, n, (uint32_t)N, slice, S, v2);
+                t0 = v2[0], t1 = v2[1];
+            } else
+                mine = splitk_combine(ws, n, (uint32_t)N, slice, S, t0);
         }
         if (mine) {
             float v = t0;
@@ -755,8 +763,12 @@ __global__ void __launch_bounds__(256) gemv_rowwave_mr_kernel(const uint32_t *__
         bool mine = true;
         if (S > 1) {
             const size_t wi = (size_t)m * (uint32_t)N + n;
-            if constexpr (FUSED2) mine = splitk_add2(ws + 2 * wi, t0, t1, S, t0, t1);
-            else mine = splitk_add1(ws + wi, t0, S, t0);
+            if constexpr (FUSED2) {
+                float2_t v2 = {t0, t1};
+                mine = splitk_combine(ws, wi, (size_t)M * (uint32_t)N, slice, S, v2);
+                t0 = v2[0], t1 = v2[1];
+            } else
+                mine = splitk_combine(ws, wi, (size_t)M * (uint32_t)N, slice, S, t0);
         }
         if (mine) {
             float v = t0;
@@ -933,8 +945,12 @@ __global__ void __launch_bounds__(256) gemv_rowwave_mfma_kernel(const uint32_t *
         bool mine = true;
         if (S > 1) {
             const size_t wi = (size_t)m * (uint32_t)N + n;
-            if constexpr (FUSED2) mine = splitk_add2(ws + 2 * wi, t0, t1, S, t0, t1);
-            else mine = splitk_add1(ws + wi, t0, S, t0);
+            if constexpr (FUSED2) {
+                float2_t v2 = {t0, t1};
+                mine = splitk_combine(ws, wi, (size_t)M * (uint32_t)N, slice, S, v2);
+                t0 = v2[0], t1 = v2[1];
+            } else
+                mine = splitk_combine(ws, wi, (size_t)M * (uint32_t)N, slice, S, t0);
         }
         if (mine) {
             float v = t0;

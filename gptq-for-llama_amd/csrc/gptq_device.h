@@ -174,64 +174,9 @@ GPTQ_DEV float wave_sum_xor(float v, int from) {
     return v;
 }
 
-// ---------------------------------------------------------------------------------------
-// Split-K combine in ONE memory round trip, order-independent (bit-reproducible):
-// every K-slice adds its partial sum as a biased fixed-point integer together with an arrival
-// count in the top bits of the SAME 64-bit word, with one returning agent-scope atomic.  The
-// slice whose returned value completes the count owns the total: it decodes it, stores zero
-// back (the workspace is all-zero between launches) and writes the output.  No ticket, no
-// second pass, no fence; integer addition makes the sum independent of arrival order.
-//   word : [63:56] count (S <= 64) | [55:0] sum of (trunc(v * 2^24) + 2^49), |v| <= 2^24
-//          64 slices add at most 64 * (2^49 + 2^48) = 1.5 * 2^55 < 2^56: the sum never carries into the count
-//          (with S = 128 it would: 128 * 2^49 = 2^56 -- the arrival count would read S + 1 and no slice would own it).
-// The fused gate/up kernel keeps TWO such words per column (gate, up): same range and resolution as the single
-// combine -- no clamp on the partial sums (the reference accumulates in fp32 without range limits,
-// fused_mlp.py:128-160).
-// ---------------------------------------------------------------------------------------
 typedef unsigned long long u64_t;
 constexpr int SPLITK_MAX_SINGLE = 64;
 constexpr int SPLITK_MAX_PAIR = 64;
-
-GPTQ_DEV u64_t splitk_encode(float v) {
-    const float c = fminf(fmaxf(v, -16777216.0f), 16777216.0f);               // |v| <= 2^24 (fp16 max is 65504)
-    const long long fx = (long long)(c * 16777216.0f) + (1LL << 49);            // exact: power-of-two scale
-    return (u64_t)fx + (1ULL << 56);
-}
-GPTQ_DEV float splitk_decode(u64_t now, int S) {
-    const long long sum = (long long)(now & ((1ULL << 56) - 1)) - (long long)S * (1LL << 49);
-    return (float)sum * (1.0f / 16777216.0f);
-}
-
-GPTQ_DEV bool splitk_add1(u64_t *word, float v, int S, float &total) {
-    const u64_t add = splitk_encode(v);
-    const u64_t old = __hip_atomic_fetch_add(word, add, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const u64_t now = old + add;
-    if ((int)(now >> 56) != S) return false;
-    __hip_atomic_store(word, 0ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    total = splitk_decode(now, S);
-    return true;
-}
-
-// words[0] = gate, words[1] = up.  Both atomics are in flight together; the slice that completes the count of word 0
-// owns the column.  Atomics to different addresses may retire out of order, so in the rare case that another
-// slice's addend to word 1 is still in flight the owner re-reads word 1 until its count is complete (the other
-// slice issued that atomic before the one the owner has already seen: it needs nothing from the owner to land;
-// the spin is bounded anyway).
-GPTQ_DEV bool splitk_add2(u64_t *words, float a, float b, int S, float &ta, float &tb) {
-    const u64_t addb = splitk_encode(b), adda = splitk_encode(a);
-    const u64_t oldb = __hip_atomic_fetch_add(words + 1, addb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const u64_t olda = __hip_atomic_fetch_add(words, adda, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const u64_t nowa = olda + adda;
-    if ((int)(nowa >> 56) != S) return false;
-    u64_t nowb = oldb + addb;
-    for (int spin = 0; (int)(nowb >> 56) != S && spin < (1 << 22); spin++)
-        nowb = __hip_atomic_load(words + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(words, 0ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(words + 1, 0ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    ta = splitk_decode(nowa, S);
-    tb = splitk_decode(nowb, S);
-    return true;
-}
 
 // Opaque register-resident constants: (a & mask) | magic is ONE v_and_or_b32 only when the mask
 // sits in an SGPR and the magic in a VGPR (VOP3 on gfx9 takes no literals); with literal operands

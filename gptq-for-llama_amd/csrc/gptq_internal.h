@@ -38,12 +38,93 @@ struct LdsOptIn {
 constexpr int GEMV_MAX_M = 4;         // rows served by the wavefront-reduction GEMV
 constexpr int SKINNY_MAX_M = 64;      // rows served by the weight-streaming MFMA kernel
 constexpr int GEMV_NUM_VARIANTS = 3;   // packed rows in flight per wave: variant v -> U = 8 >> v
-// split-K workspace: one 64-bit word per output element ([M][N]), all-zero between launches
+// split-K workspace: arrival counts (all-zero between launches) and fp32 partials of the K slices
 constexpr size_t WS_BYTES = (size_t)SKINNY_MAX_M * 32768 * 8;
-// workspace layout: [0, 512 KiB) one u64 word per output element of the rowwave GEMV combine ([M <= 4][N]) | 4 KiB of per-tile
-// arrival tickets of the stream kernel (u32, zero between launches) | the stream kernel's partial tiles
-constexpr size_t SPLITK_TICKET_OFFSET = 65536 * 8;   // 512 KiB of combine words: [M <= 4][N] for the small-batch rowwave
+// workspace layout: [0, 512 KiB) one u32 arrival count per combined element of the rowwave GEMV ([M <= 4][N]) | 4 KiB of per-tile
+// arrival tickets of the stream kernel (u32, zero between launches) | the partials of either kernel (scratch, overwritten freely)
+constexpr size_t SPLITK_TICKET_OFFSET = 65536 * 8;   // 512 KiB of combine counts: [M <= 4][N] for the small-batch rowwave
 constexpr size_t SPLITK_PART_OFFSET = SPLITK_TICKET_OFFSET + 4096;
+
+// ---------------------------------------------------------------------------------------
+// Split-K combine of the rowwave GEMV kernels, per combined element c (one output element, or one {gate, up} pair of them):
+// every K slice stores its fp32 partial(s) to parts[slice][c][NS] with system-scope (write-through) stores, waits for them
+// (vmcnt(0)), then adds 1 to the element's arrival count with one returning agent-scope atomic.  The slice whose add completes
+// the count owns the element: it stores the count back to zero (the counts are all-zero between launches), reads the S partials
+// with system-scope loads and sums them in slice order -- an fp32 sum of the partials, the same bits whatever the arrival
+// order, and no absolute resolution (a fixed-point encoding of the partials loses every output below its spacing).
+// Publication follows MI355X_MICROARCH.md "Valid forms" (sc1 stores and loads, the storer's wait before its add, the last adder
+// loads after its add has returned), as the stream kernel's partial tiles do.
+// ---------------------------------------------------------------------------------------
+GPTQ_DEV void splitk_store_part(float *p, float v) {
+    asm volatile("global_store_dword %0, %1, off sc0 sc1" ::"v"(p), "v"(v) : "memory");
+}
+GPTQ_DEV void splitk_store_part(float *p, float2_t v) {
+    asm volatile("global_store_dwordx2 %0, %1, off sc0 sc1" ::"v"(p), "v"(v) : "memory");
+}
+// Eight system-scope loads and their wait as ONE asm statement (see load_sys16_x8: issue and wait must not be separable)
+template <typename T>
+GPTQ_DEV void splitk_load_parts8(T (&v)[8], const float *const (&p)[8]) {
+    if constexpr (sizeof(T) == 4)
+        asm volatile(
+            "global_load_dword %0, %8, off sc0 sc1\n\t"
+            "global_load_dword %1, %9, off sc0 sc1\n\t"
+            "global_load_dword %2, %10, off sc0 sc1\n\t"
+            "global_load_dword %3, %11, off sc0 sc1\n\t"
+            "global_load_dword %4, %12, off sc0 sc1\n\t"
+            "global_load_dword %5, %13, off sc0 sc1\n\t"
+            "global_load_dword %6, %14, off sc0 sc1\n\t"
+            "global_load_dword %7, %15, off sc0 sc1\n\t"
+            "s_waitcnt vmcnt(0)"
+            : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]), "=&v"(v[3]), "=&v"(v[4]), "=&v"(v[5]), "=&v"(v[6]), "=&v"(v[7])
+            : "v"(p[0]), "v"(p[1]), "v"(p[2]), "v"(p[3]), "v"(p[4]), "v"(p[5]), "v"(p[6]), "v"(p[7])
+            : "memory");
+    else
+        asm volatile(
+            "global_load_dwordx2 %0, %8, off sc0 sc1\n\t"
+            "global_load_dwordx2 %1, %9, off sc0 sc1\n\t"
+            "global_load_dwordx2 %2, %10, off sc0 sc1\n\t"
+            "global_load_dwordx2 %3, %11, off sc0 sc1\n\t"
+            "global_load_dwordx2 %4, %12, off sc0 sc1\n\t"
+            "global_load_dwordx2 %5, %13, off sc0 sc1\n\t"
+            "global_load_dwordx2 %6, %14, off sc0 sc1\n\t"
+            "global_load_dwordx2 %7, %15, off sc0 sc1\n\t"
+            "s_waitcnt vmcnt(0)"
+            : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]), "=&v"(v[3]), "=&v"(v[4]), "=&v"(v[5]), "=&v"(v[6]), "=&v"(v[7])
+            : "v"(p[0]), "v"(p[1]), "v"(p[2]), "v"(p[3]), "v"(p[4]), "v"(p[5]), "v"(p[6]), "v"(p[7])
+            : "memory");
+}
+
+// T = float (one value per element) or float2_t ({gate, up}); ncomb = combined elements of the launch (N, or M * N).
+// Returns true in the owning slice, with v replaced by the sum over all slices.
+template <typename T>
+GPTQ_DEV bool splitk_combine(u64_t *ws, size_t c, size_t ncomb, uint32_t slice, int S, T &v) {
+    constexpr int NS = sizeof(T) / 4;
+    const float *parts = (const float *)((const char *)ws + SPLITK_PART_OFFSET);
+    unsigned *count = (unsigned *)ws + c;
+    splitk_store_part((float *)parts + ((size_t)slice * ncomb + c) * NS, v);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const unsigned t = __hip_atomic_fetch_add(count, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (t != (unsigned)(S - 1)) return false;
+    __hip_atomic_store(count, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    {
+#pragma clang fp reassociate(off)   // the objects are built with -ffast-math: keep the sum in slice order
+        T tot = (T)0.f;
+        for (int s0 = 0; s0 < S; s0 += 8) {   // 8 slices in flight per wait, summed in slice order
+            T pv[8];
+            const float *src[8];
+#pragma unroll
+            for (int i = 0; i < 8; i++) src[i] = parts + ((size_t)min(s0 + i, S - 1) * ncomb + c) * NS;
+            splitk_load_parts8(pv, src);
+#pragma unroll
+            for (int i = 0; i < 8; i++)
+                if (s0 + i < S) tot += pv[i];
+        }
+        v = tot;
+    }
+    return true;
+}
+// bytes of partials a launch of S slices over ncomb elements of NS values needs behind SPLITK_PART_OFFSET
+inline size_t splitk_part_bytes(int S, size_t ncomb, int NS) { return (size_t)S * ncomb * NS * 4; }
 
 struct GemvParams {
     const half_t *x;

@@ -18,8 +18,8 @@
 //    unpacks (no shuffles, no int->float converts, no per-weight zero/scale arithmetic);
 //  * x is staged per workgroup in LDS in the field order the unpack produces (M <= 16), or read
 //    from L2 and permuted in registers (16 < M <= 64);
-//  * waves split K inside the workgroup (LDS reduce); workgroups split K further through the
-//    one-round-trip fixed-point combine of gptq_device.h (bit-reproducible).
+//  * waves split K inside the workgroup (LDS reduce); workgroups split K further through fp32
+//    partial tiles summed in slice order by the last slice of a tile (bit-reproducible).
 #include "gptq_device.h"
 #include "gptq_internal.h"
 

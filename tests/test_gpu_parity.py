@@ -148,8 +148,8 @@ def test_gemv_ragged_shapes(K, N, bits, gs):
 @pytest.mark.parametrize('split_k', [1, 2, 3, 8, 32, 128])
 @pytest.mark.parametrize('variant', [0, 1, 2])
 def test_gemv_split_k(split_k, variant):
-    """K slices combined through the one-round-trip fixed-point atomic; run twice: the last arriver
-    must leave the workspace zeroed for the next launch, and the result is bit-reproducible."""
+    """K slices combined through fp32 partials summed in slice order by the last arriver; run twice: the last arriver
+    must leave the arrival counts zeroed for the next launch, and the result is bit-reproducible."""
     L = make_random_layer(4, 128, 2048, 512, seed=7)
     x = np.random.default_rng(3).standard_normal((2, 2048)).astype(np.float16)
     lib = _native.lib()
@@ -158,7 +158,7 @@ def test_gemv_split_k(split_k, variant):
     try:
         y1, _ = check_forward(x, L, family='gemv')
         y2, _ = check_forward(x, L, family='gemv')
-        # the fixed-point combine is order independent: bit-identical run to run
+        # the combine sums in slice order whatever the arrival order: bit-identical run to run
         assert np.array_equal(y1.view(np.uint16), y2.view(np.uint16))
     finally:
         lib.gptq_set_gemv_variant(-1)
@@ -1323,7 +1323,7 @@ def test_stripe_copy_follows_buffer_updates():
 
 
 def test_split_k_64_with_positive_sums():
-    """with 128 slices the 2^49 biases of the fixed-point combine carry into the arrival count.  The cap is 64
+    """with 128 slices the 2^49 biases of the former fixed-point combine carried into the arrival count.  The cap is 64
     now; all-positive partial sums at the cap (and a request above it) must still find their owner."""
     K, N = 16384, 256
     L = make_random_layer(4, 128, K, N, seed=3)

@@ -636,3 +636,107 @@ def test_bench_refuses_a_pmc_pass_of_another_build(tmp_path):
     v, src = bench.pmc_traffic(str(old))
     assert v == 456 and 'unstamped' in src
     assert len(bench.csrc_sha16()) == 16
+
+
+# ---------------------------------------------------------------------------------------
+# Premises of tests/test_gpu_ranges.py, checked on the oracle: power-of-two scaling is bit-exact inside the exact domain, and the
+# realistic layers / activations have the statistics they promise.
+# ---------------------------------------------------------------------------------------
+
+from util import (ACTIVATION_KINDS, activations, exact_scaling_domain, in_domain_normal, pow2_layer, pow2_scaled,  # noqa: E402
+                  realistic_layer, rowwise_rel_err)
+
+
+def _assert_pow2_exact(y0, y, j, mask):
+    assert mask.mean() > 0.5, mask.mean()
+    want = y0.astype(np.float64) * 2.0 ** j
+    assert np.array_equal(y.astype(np.float64)[mask], want[mask]), (j, int((mask & (y.astype(np.float64) != want)).sum()))
+
+
+@pytest.mark.parametrize('bits,gs,act', [(4, 128, False), (4, 128, True), (3, -1, False), (8, 64, False), (2, 64, False)])
+def test_oracle_matmul_obeys_pow2_scaling(bits, gs, act):
+    K, N, M = 512, 256, 5
+    L = pow2_layer(bits, gs, K, N, act_order=act, seed=bits)
+    x = in_domain_normal(np.random.default_rng(bits), (M, K))
+    W = oracle.dequant(L['qweight'], L['qzeros'], L['scales'], L['g_idx'], bits, faithful=True)
+    f = lambda xx, LL: oracle.matmul248(xx, LL['qweight'], LL['scales'], LL['qzeros'], LL['g_idx'], bits)
+    y0 = f(x, L)
+    for j in (-5, 4):
+        _assert_pow2_exact(y0, f(x, pow2_scaled(L, j)), j, exact_scaling_domain(y0, j, x=x, w=W, jw=j))
+    for j in (-4, 3):
+        xs = (x.astype(np.float64) * 2.0 ** j).astype(np.float16)
+        _assert_pow2_exact(y0, f(xs, L), j, exact_scaling_domain(y0, j, x=x, jx=j, w=W))
+
+
+def test_oracle_transpose_and_fused_mlp_obey_pow2_scaling():
+    K, N, M = 512, 256, 3
+    L = pow2_layer(4, 128, K, N, seed=5)
+    W = oracle.dequant(L['qweight'], L['qzeros'], L['scales'], L['g_idx'], 4, faithful=True)
+    dy = in_domain_normal(np.random.default_rng(5), (M, N), lo=0.25)
+    t = lambda d: oracle.transpose_matmul248(d, L['qweight'], L['scales'], L['qzeros'], L['g_idx'], 4)
+    dx0 = t(dy)
+    for j in (-12, -4, 3):
+        _assert_pow2_exact(dx0, t((dy.astype(np.float64) * 2.0 ** j).astype(np.float16)), j, exact_scaling_domain(dx0, j, x=dy, jx=j, w=W.T))
+    A, B = pow2_layer(4, 128, K, N, seed=6), pow2_layer(4, 128, K, N, seed=7)
+    WB = oracle.dequant(B['qweight'], B['qzeros'], B['scales'], B['g_idx'], 4, faithful=True)
+    x = (in_domain_normal(np.random.default_rng(6), (M, K)).astype(np.float32) * 0.25).astype(np.float16)
+    sets = lambda L: (L['qweight'], L['scales'], L['qzeros'], L['g_idx'])
+    c0 = oracle.fused_mlp(x, sets(A), sets(B), 4)
+    for j in (-5, 4):
+        _assert_pow2_exact(c0, oracle.fused_mlp(x, sets(A), sets(pow2_scaled(B, j)), 4), j, exact_scaling_domain(c0, j, x=x, w=WB, jw=j))
+
+
+def test_oracle_rmsnorm_eps0_ignores_pow2_scaling():
+    rng = np.random.default_rng(8)
+    x = in_domain_normal(rng, (4, 4096))
+    w = (1 + 0.1 * rng.standard_normal(4096)).astype(np.float16)
+    y0 = oracle.rmsnorm(x, w, 0.0)
+    for j in (-4, 3):
+        y = oracle.rmsnorm((x.astype(np.float64) * 2.0 ** j).astype(np.float16), w, 0.0)
+        assert np.array_equal(y.view(np.uint16), y0.view(np.uint16)), j
+
+
+@pytest.mark.parametrize('bits,act,sym', [(4, False, False), (4, True, False), (3, False, False), (8, False, True), (2, False, False)])
+def test_realistic_layer_statistics(bits, act, sym):
+    """centred q - z (zero points near mid-range), scales over >= two decades, dead columns, and the packed fields reproduce the
+    quantised weight"""
+    K, N = 1024, 512
+    L = realistic_layer(bits, 128, K, N, act_order=act, sym=sym, seed=bits)
+    maxq = 2 ** bits - 1
+    q = oracle.np_unpack_rows(L['qweight'], bits)
+    z = oracle.np_unpack_cols(L['qzeros'], bits) + 1
+    d = q - z[L['g_idx']]
+    assert abs(d.mean()) < 0.05 * maxq, d.mean()
+    assert abs(z.mean() - (maxq + 1) / 2) < 0.15 * maxq + 0.5, z.mean()
+    live = np.abs(L['w']).max(0) > 0
+    assert (~live).sum() >= 1
+    s = L['scales'].astype(np.float64)[:, live]
+    assert s.max() / s.min() >= 100, (s.min(), s.max())
+    W = oracle.dequant(L['qweight'], L['qzeros'], L['scales'], L['g_idx'], bits, faithful=False)
+    assert np.all(W[:, ~live] == 0)
+    # quantisation error at most half a step where the grid was not clipped (min/max grid: nothing clipped but rounding of z)
+    step = L['scales'].astype(np.float32)[L['g_idx']]
+    assert np.mean(np.abs(W - L['w']) <= 0.5 * step + 1e-6) > 0.98
+
+
+def test_activation_kinds_have_their_statistics():
+    M, K = 16, 4096
+    xs = {k: activations(k, M, K, seed=1).astype(np.float64) for k in ACTIVATION_KINDS}
+    o = xs['outliers']
+    loud = np.abs(o).max(0) > 15
+    assert 0.002 * K <= loud.sum() <= 0.005 * K and np.abs(o).max() >= 20 and np.all((np.abs(o[:, loud]) > 0).all(0))
+    mr = xs['massive_row']
+    assert 900 <= np.abs(mr[M // 2]).max() <= 1100 and np.abs(np.delete(mr, M // 2, 0)).max() < 10
+    p = xs['positive']
+    assert p.mean() > 0.1 and p.max() > 2 * -p.min() and ((p - p.mean()) ** 3).mean() > 0
+    t = xs['tiny']
+    assert 0.5e-3 < t.std() < 2e-3 and np.abs(t).max() < 1e-2
+    for x in xs.values():
+        assert np.isfinite(x).all()
+
+
+def test_rowwise_rel_err_uses_each_rows_own_maximum():
+    exact = np.array([[1000.0, 1.0], [1e-3, 2e-3]])
+    y = exact + np.array([[0.0, 0.0], [1e-5, 0.0]])
+    assert rowwise_rel_err(y, exact)[0] == 0 and abs(rowwise_rel_err(y, exact)[1] - 5e-3) < 1e-12
+    assert rel_err(y, exact) < 1e-7          # the max-normalised error of the whole array would not see it

@@ -14,6 +14,19 @@
 
 #include "../gptq-for-llama_amd/csrc/gptq_device.h"
 
+// The lab's own split-K combine: the one-round-trip fixed-point atomic its measurements were taken with (the product's
+// rowwave kernels now combine fp32 partials in slice order, csrc/gptq_internal.h splitk_combine).  One u64 word per column:
+// [63:56] arrival count | [55:0] sum of (trunc(v * 2^24) + 2^49); the slice that completes the count owns the total.
+static __device__ __forceinline__ bool splitk_add1(u64_t *word, float v, int S, float &total) {
+    const float c = fminf(fmaxf(v, -16777216.0f), 16777216.0f);
+    const u64_t add = (u64_t)((long long)(c * 16777216.0f) + (1LL << 49)) + (1ULL << 56);
+    const u64_t now = __hip_atomic_fetch_add(word, add, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + add;
+    if ((int)(now >> 56) != S) return false;
+    __hip_atomic_store(word, 0ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    total = (float)((long long)(now & ((1ULL << 56) - 1)) - (long long)S * (1LL << 49)) * (1.0f / 16777216.0f);
+    return true;
+}
+
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP error %s at line %d\n", hipGetErrorString(e_), __LINE__); exit(1);} } while (0)
 
 // ------------------------------------------------------------------------------------------
