@@ -997,6 +997,28 @@ int gptq_decode_attn_splits(int batch, int heads, int head_dim, int t_max) {
     return decode_attn_grid_splits(heads, t_max, batch);
 }
 
+/* a PROMPT chunk: `rows` consecutive tokens of one sequence at positions start .. start + rows - 1 (csrc/prompt_attn.hip).  start is a host value:
+ * prefill is not graph-captured. */
+size_t gptq_prompt_attn_workspace_bytes(int rows, int heads, int head_dim, int t_max) {
+    if (rows <= 0 || heads <= 0 || head_dim != 128 || t_max <= 0 || rows > t_max) return 0;
+    return prompt_attn_ws_bytes(rows, heads);
+}
+
+int gptq_prompt_attn_f16(const void *qkv, int64_t ldq, int rows, int64_t start, void *k_cache, void *v_cache, void *out, int64_t ldo, void *workspace,
+                         size_t workspace_bytes, int heads, int head_dim, int t_max, float base, float scale, const float *rope_table,
+                         gptq_stream_t stream) {
+    if (!qkv || !k_cache || !v_cache || !out || !workspace) return GPTQ_E_NULL;
+    if (rows <= 0 || heads <= 0 || heads > 65535 || head_dim != 128 || t_max <= 0 || start < 0 || start + rows > t_max ||
+        ldq < 3 * (int64_t)heads * head_dim || ldo < (int64_t)heads * head_dim)
+        return GPTQ_E_SHAPE;
+    if (!aligned(qkv, 16) || !aligned(k_cache, 16) || !aligned(v_cache, 16) || !aligned(workspace, 16) || (rope_table && !aligned(rope_table, 8)) ||
+        ldq % 8 != 0 || ldo % 8 != 0 || !aligned(out, 8))
+        return GPTQ_E_ALIGN;
+    if (workspace_bytes < prompt_attn_ws_bytes(rows, heads)) return GPTQ_E_WORKSPACE;
+    return prompt_attn_launch((const half_t *)qkv, ldq, rows, start, (half_t *)k_cache, (half_t *)v_cache, (half_t *)out, ldo, (half_t *)workspace, heads,
+                              t_max, base, scale, rope_table, (hipStream_t)stream);
+}
+
 // ---- stripe16: no-split-K decode GEMV on a load-time repacked copy (stripe*.hip) ----
 size_t gptq_stripe_bytes(int K, int N, int bits, int groupsize, int nsets) { return stripe_total_bytes(K, N, bits, groupsize, nsets); }
 

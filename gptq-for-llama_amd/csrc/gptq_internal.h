@@ -254,4 +254,10 @@ int decode_attn_grid_splits(int heads, int t_max, int batch);   // S of the laun
 int decode_attn_tps(bool rec);                                  // default tokens per split of the mode
 int rope_table_launch(float *table, int t_max, int head_dim, float base, hipStream_t s);
 
+// prompt_attn.hip: RoPE + cache append of `rows` tokens at positions start .. start + rows - 1, then causal attention over cache rows [0, start + rows);
+// ws = prompt_attn_ws_bytes(rows, heads) bytes (the rotated q)
+size_t prompt_attn_ws_bytes(int rows, int heads);
+int prompt_attn_launch(const half_t *qkv, int64_t ldq, int rows, int64_t start, half_t *kc, half_t *vc, half_t *out, int64_t ldo, half_t *ws,
+                       int heads, int t_max, float base, float scale, const float *rope_table, hipStream_t s);
+
 }  // namespace gptq

@@ -1,0 +1,264 @@
+// prompt_attn.hip -- causal multi-row attention of a PROMPT chunk over the decode engine's own K/V cache: what
+// F.scaled_dot_product_attention does for a prompt between the reference's Triton kernels (quant/fused_attn.py:126-158), with the
+// RoPE (triton_rotate_half_ :126) and the cache append (torch.cat :142-143) of all rows in front of it.
+//
+// `rows` consecutive tokens of one sequence at positions start .. start + rows - 1; two launches:
+//   1. prompt_rope_kv_kernel: the arithmetic of rope_kv_kernel (decode_attn.hip) per (row, head) -- rotated k and v go to cache rows
+//      start + r (bit-identical to a token-by-token feed: same instructions, same flags, see the Makefile), the rotated q to a
+//      workspace copy; qkv itself is never written.
+//   2. prompt_attn_kernel: flash-style attention, grid = (q tile, head), q tiles issued last (longest) first.  A workgroup is four
+//      waves x 32 query rows; it walks the keys [0, last position of the tile] in tiles of 64 with an online softmax (log2 domain).
+//      Q fragments live in registers; the K / V tile is requested into registers BEFORE the current tile is computed and written to
+//      LDS behind the barrier that ends it.  Both LDS images are plain 256-byte rows with the chunk swizzle
+//      ch ^ (((row & 3) << 2) | ((row >> 2) & 3)): conflict-free for the ds_read_b128 row reads of K and for the ds_read_b64_tr_b16
+//      transposed reads of V.  S^T = K Q^T (v_mfma_f32_32x32x16_f16, keys on the registers, the query on the lane: a lane owns half a
+//      score row, its partner lane ^ 32 the other half -> max / sum are in-lane plus one permlane32 swap), P is rounded to fp16 in
+//      registers and IS the B operand of O^T = V^T P^T (the accumulator layout of the first product is the operand layout of the
+//      second, with V^T taken through the transposed read in the same permuted key order).  fp32 accumulation, one fp16 rounding at
+//      the store.  No atomics, no scores in memory.
+// Masking is a select (-inf before the maximum); cache rows at and beyond start + rows are never loaded (their slots of a tile are
+// zeros: 0 * NaN would poison P V).
+#include <algorithm>
+
+#include "gptq_device.h"
+#include "gptq_internal.h"
+
+namespace gptq {
+
+constexpr int PA_HD = 128;    // head_dim served
+constexpr int PA_NW = 4;      // waves per workgroup
+constexpr int PA_QT = 32 * PA_NW;   // query rows per workgroup (32 per wave: one 32x32 MFMA column block)
+constexpr int PA_KT = 64;     // keys per tile
+
+__global__ void __launch_bounds__(64) prompt_rope_kv_kernel(const half_t *__restrict__ qkv, int64_t ldq, int64_t start, half_t *__restrict__ kc,
+                                                            half_t *__restrict__ vc, half_t *__restrict__ qrot, int heads, float inv_base,
+                                                            const float2 *__restrict__ tab) {
+    const int r = blockIdx.x, h = blockIdx.y, c = threadIdx.x, half = PA_HD / 2;
+    const int64_t pos = start + r;
+    float cs, sn;
+    if (tab) {   // {cos, sin} of (pos, c) from the table rope_table_kernel filled with the SAME instructions
+        const float2 e = tab[(size_t)pos * half + c];
+        cs = e.x;
+        sn = e.y;
+    } else {
+        const float freq = expf((float)c * inv_base) * (float)pos;
+        cs = cosf(freq);
+        sn = sinf(freq);
+    }
+    const int hd = heads * PA_HD;
+    const half_t *q = qkv + (size_t)r * ldq + (size_t)h * PA_HD + c;
+    const half_t *k = q + hd;
+    const half_t *v = q + 2 * hd;
+    const float qx = (float)q[0], qy = (float)q[half];
+    half_t *qd = qrot + (size_t)r * hd + (size_t)h * PA_HD + c;
+    qd[0] = (half_t)(qx * cs - qy * sn);
+    qd[half] = (half_t)(qx * sn + qy * cs);
+    const float kx = (float)k[0], ky = (float)k[half];
+    half_t *kd = kc + (size_t)pos * hd + (size_t)h * PA_HD + c;
+    kd[0] = (half_t)(kx * cs - ky * sn);
+    kd[half] = (half_t)(kx * sn + ky * cs);
+    half_t *vd = vc + (size_t)pos * hd + (size_t)h * PA_HD + c;
+    vd[0] = v[0];
+    vd[half] = v[half];
+}
+
+// byte offset of 16-byte chunk ch (0..15) of row `row` in a [rows][128 fp16] LDS image
+GPTQ_DEV int pa_off(int row, int ch) { return 256 * row + 16 * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3))); }
+
+typedef short pa_short4 __attribute__((__vector_size__(4 * sizeof(short))));
+#define PA_LDS __attribute__((address_space(3)))
+
+GPTQ_DEV half8_t pa_row_read(const half_t *img, int off) { return *(const PA_LDS half8_t *)((const PA_LDS char *)img + off); }
+// ds_read_b64_tr_b16: per 16-lane group a block of 4 rows x 16 columns, lane i receives column i (row q in element q).  Every lane supplies
+// an address (EXEC must be full: only ever called under wave-uniform control flow).
+GPTQ_DEV half4_t pa_tr_read(const half_t *img, int off) {
+    return __builtin_bit_cast(half4_t, __builtin_amdgcn_ds_read_tr16_b64_v4i16((PA_LDS pa_short4 *)((PA_LDS char *)img + off)));
+}
+GPTQ_DEV float pa_max_halves(float v) {
+    const uint32_t u = __builtin_bit_cast(uint32_t, v);
+    auto a = __builtin_amdgcn_permlane32_swap(u, u, false, false);
+    return fmaxf(__builtin_bit_cast(float, (uint32_t)a[0]), __builtin_bit_cast(float, (uint32_t)a[1]));
+}
+GPTQ_DEV float pa_sum_halves(float v) {
+    const uint32_t u = __builtin_bit_cast(uint32_t, v);
+    auto a = __builtin_amdgcn_permlane32_swap(u, u, false, false);
+    return __builtin_bit_cast(float, (uint32_t)a[0]) + __builtin_bit_cast(float, (uint32_t)a[1]);
+}
+
+struct PromptAttnArgs {
+    const half_t *q;             // rotated q [rows][heads * 128]
+    const half_t *kc, *vc;       // [t_max][heads * 128]; rows [0, start + rows) are read
+    half_t *out;
+    int rows, start, heads;
+    int64_t ldo;
+    float scale2;                // softmax scale x log2(e)
+};
+
+__global__ void __launch_bounds__(PA_NW * 64) prompt_attn_kernel(const PromptAttnArgs a) {
+    __shared__ __attribute__((aligned(16))) half_t ks[PA_KT * PA_HD];
+    __shared__ __attribute__((aligned(16))) half_t vs[PA_KT * PA_HD];
+    const int qt = (int)gridDim.x - 1 - (int)blockIdx.x;   // the last q tile has the longest key range: first
+    const int h = blockIdx.y;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int l31 = lane & 31, hi = lane >> 5;
+    const int hd = a.heads * PA_HD;
+    const int q0 = qt * PA_QT;
+    const int qrow = q0 + wave * 32 + l31;                 // this lane's query row of the chunk (its partner lane ^ 32 has the same)
+    const int qpos = a.start + qrow;
+    const int kv_end = a.start + min(q0 + PA_QT, a.rows);  // keys the workgroup reads: [0, kv_end)
+    const int ntiles = (kv_end + PA_KT - 1) / PA_KT;
+    const int wq_min = a.start + q0 + wave * 32, wq_max = wq_min + 31;   // positions of the wave's rows
+    const bool wave_active = q0 + wave * 32 < a.rows;      // (wave-uniform) a wave of padding rows only stages tiles
+
+    // ---- Q^T fragments (B operand of K Q^T): lane = query, element j of k-step s = dim 16 s + 8 hi + j --------------------------
+    half8_t qf[8];
+#pragma unroll
+    for (int s = 0; s < 8; s++) {
+        qf[s] = half8_t{0, 0, 0, 0, 0, 0, 0, 0};
+        if (qrow < a.rows) qf[s] = *(const half8_t *)(a.q + (size_t)qrow * hd + (size_t)h * PA_HD + 16 * s + 8 * hi);
+    }
+
+    // ---- staging: 1024 16-byte chunks per image and tile, four per thread (16 lanes = one 256-byte head row) ----------------------
+    const int srow = tid >> 4, sch = tid & 15;             // chunk i of this thread: row srow + 16 i, chunk sch
+    u32x4 kreg[4], vreg[4];
+    auto request = [&](int kb) {
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const int key = kb + srow + 16 * i;
+            kreg[i] = u32x4{0u, 0u, 0u, 0u};
+            vreg[i] = u32x4{0u, 0u, 0u, 0u};
+            if (key < kv_end) {
+                const size_t g = (size_t)key * hd + (size_t)h * PA_HD + sch * 8;
+                kreg[i] = *(const u32x4 *)(a.kc + g);
+                vreg[i] = *(const u32x4 *)(a.vc + g);
+            }
+        }
+    };
+    auto commit = [&]() {
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const int off = pa_off(srow + 16 * i, sch);
+            *(PA_LDS u32x4 *)((PA_LDS char *)ks + off) = kreg[i];
+            *(PA_LDS u32x4 *)((PA_LDS char *)vs + off) = vreg[i];
+        }
+    };
+
+    // ---- running state of the lane's query row: m (log2 domain), l (this lane's half of the keys), O^T[dim][query] ---------------
+    float m = -INFINITY, l = 0.f;
+    float16_t acc[4];
+#pragma unroll
+    for (int d = 0; d < 4; d++)
+#pragma unroll
+        for (int r = 0; r < 16; r++) acc[d][r] = 0.f;
+
+    const int g16 = lane & 15, tq = g16 >> 2, tp = g16 & 3, g1 = (lane >> 4) & 1;   // transposed read: row tq of the block, columns 4 tp .. 4 tp + 3
+
+    request(0);
+    commit();
+    __syncthreads();
+    for (int t = 0; t < ntiles; t++) {
+        const int kb = t * PA_KT;
+        if (t + 1 < ntiles) request(kb + PA_KT);           // in flight under the products of this tile
+        if (wave_active && kb <= wq_max) {                 // (wave-uniform) tiles above the wave's diagonal are skipped
+            // S^T[key][query] = K Q^T: two blocks of 32 keys
+            float16_t sc[2];
+#pragma unroll
+            for (int b = 0; b < 2; b++) {
+#pragma unroll
+                for (int r = 0; r < 16; r++) sc[b][r] = 0.f;
+#pragma unroll
+                for (int s = 0; s < 8; s++) {
+                    const half8_t kf = pa_row_read(ks, pa_off(32 * b + l31, 2 * s + hi));
+                    sc[b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[s], sc[b], 0, 0, 0);
+                }
+            }
+            // scale into the log2 domain, causal mask (a select), tile maximum of the row
+            const bool diag = kb + PA_KT - 1 > wq_min;     // (wave-uniform) the tile reaches past the wave's first row
+            float mt = -INFINITY;
+#pragma unroll
+            for (int b = 0; b < 2; b++)
+#pragma unroll
+                for (int r = 0; r < 16; r++) {
+                    const int key = kb + 32 * b + (r & 3) + 8 * (r >> 2) + 4 * hi;
+                    float v = sc[b][r] * a.scale2;
+                    if (diag && key > qpos) v = -INFINITY;
+                    sc[b][r] = v;
+                    mt = fmaxf(mt, v);
+                }
+            mt = pa_max_halves(mt);
+            const float mn = fmaxf(m, mt);
+            const float msub = mn == -INFINITY ? 0.f : mn;   // a row with nothing unmasked so far: exp2(-inf - 0) = 0, never -inf - -inf
+            const float alpha = __builtin_amdgcn_exp2f(m - msub);
+            m = mn;
+            float ps = 0.f;
+            half8_t pf[2][2];
+#pragma unroll
+            for (int b = 0; b < 2; b++)
+#pragma unroll
+                for (int r = 0; r < 16; r++) {
+                    const float p = __builtin_amdgcn_exp2f(sc[b][r] - msub);
+                    ps += p;
+                    pf[b][r >> 3][r & 7] = (half_t)p;
+                }
+            l = __builtin_fmaf(l, alpha, ps);
+#pragma unroll
+            for (int d = 0; d < 4; d++)
+#pragma unroll
+                for (int r = 0; r < 16; r++) acc[d][r] *= alpha;
+            // O^T[dim][query] += V^T P^T.  k-step s of key block b: element j of lane half hi is key 32 b + 16 s + 8 (j >> 2) + 4 hi + (j & 3)
+            // -- the order the accumulator registers 8 s .. 8 s + 7 of S^T hold -- so V^T comes as two transposed 4-key blocks, 8 keys apart.
+#pragma unroll
+            for (int d = 0; d < 4; d++)
+#pragma unroll
+                for (int b = 0; b < 2; b++)
+#pragma unroll
+                    for (int s = 0; s < 2; s++) {
+                        const int r0 = 32 * b + 16 * s + 4 * hi + tq;
+                        const int ch = 4 * d + 2 * g1 + (tp >> 1);
+                        const half4_t lo = pa_tr_read(vs, pa_off(r0, ch) + 8 * (tp & 1));
+                        const half4_t up = pa_tr_read(vs, pa_off(r0 + 8, ch) + 8 * (tp & 1));
+                        const half8_t vf = half8_t{lo[0], lo[1], lo[2], lo[3], up[0], up[1], up[2], up[3]};
+                        acc[d] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf[b][s], acc[d], 0, 0, 0);
+                    }
+        }
+        __syncthreads();                                   // every wave is done with the tile
+        if (t + 1 < ntiles) {
+            commit();
+            __syncthreads();
+        }
+    }
+
+    // ---- out[query][32 d + 8 g + 4 hi + (0..3)] = O^T / l: four dims per register quad, one fp16 rounding ----------------------
+    l = pa_sum_halves(l);
+    if (qrow < a.rows) {
+        const float inv = 1.0f / l;
+        half_t *o = a.out + (size_t)qrow * a.ldo + (size_t)h * PA_HD + 4 * hi;
+#pragma unroll
+        for (int d = 0; d < 4; d++)
+#pragma unroll
+            for (int g = 0; g < 4; g++) {
+                half4_t v;
+#pragma unroll
+                for (int j = 0; j < 4; j++) v[j] = (half_t)(acc[d][4 * g + j] * inv);
+                *(half4_t *)(o + 32 * d + 8 * g) = v;
+            }
+    }
+}
+
+size_t prompt_attn_ws_bytes(int rows, int heads) { return ((size_t)rows * heads * PA_HD * sizeof(half_t) + 255) & ~(size_t)255; }
+
+int prompt_attn_launch(const half_t *qkv, int64_t ldq, int rows, int64_t start, half_t *kc, half_t *vc, half_t *out, int64_t ldo, half_t *ws,
+                       int heads, int t_max, float base, float scale, const float *rope_table, hipStream_t s) {
+    const float inv_base = -2.0f * logf(base) / (float)PA_HD;   // reference fused_attn.py:91
+    hipLaunchKernelGGL(prompt_rope_kv_kernel, dim3(rows, heads), dim3(PA_HD / 2), 0, s, qkv, ldq, start, kc, vc, ws, heads, inv_base,
+                       (const float2 *)rope_table);
+    PromptAttnArgs a{};
+    a.q = ws; a.kc = kc; a.vc = vc; a.out = out;
+    a.rows = rows; a.start = (int)start; a.heads = heads; a.ldo = ldo;
+    a.scale2 = scale * 1.44269504088896340736f;
+    hipLaunchKernelGGL(prompt_attn_kernel, dim3((rows + PA_QT - 1) / PA_QT, heads), dim3(PA_NW * 64), 0, s, a);
+    return (int)hipGetLastError();
+}
+
+}  // namespace gptq

@@ -143,6 +143,10 @@ _SIGNATURES = {
                               c_void_p, c_size_t, c_void_p],
     'gptq_layer_decode_next_norm_f16': [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_float, c_void_p, c_int64, c_void_p, c_float, c_void_p,
                                         c_int64, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p],
+    # prompt prefill: causal attention of a chunk over the engine's cache (csrc/prompt_attn.hip)
+    'gptq_prompt_attn_workspace_bytes': [c_int, c_int, c_int, c_int],
+    'gptq_prompt_attn_f16': [c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_size_t, c_int, c_int, c_int,
+                             c_float, c_float, c_void_p, c_void_p],
 }
 
 
@@ -180,6 +184,7 @@ def lib():
             L.gptq_layer_fallback_scratch_bytes.restype = c_size_t
             L.gptq_layer_decode_scratch_bytes.restype = c_size_t
             L.gptq_decode_attn_batch_workspace_bytes.restype = c_size_t
+            L.gptq_prompt_attn_workspace_bytes.restype = c_size_t
             L.gptq_layer_destroy.restype = None
             L.gptq_strerror.argtypes = [c_int]
             L.gptq_strerror.restype = ctypes.c_char_p

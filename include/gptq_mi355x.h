@@ -549,6 +549,21 @@ int gptq_layer_decode_attn_f16(const gptq_layer_t *layer, const void *attn_works
                                int heads, int head_dim, int t_max, int tokens_per_split, void *y, int64_t ldy, const void *residual, int64_t ldr,
                                gptq_stream_t stream);
 
+/* ---- prompt prefill: causal attention of a chunk of tokens over the decode engine's own cache (csrc/prompt_attn.hip) ----------------------------
+ * Replaces, for a prompt, what QuantLlamaAttention.forward does between qkv_proj and o_proj (quant/fused_attn.py:126-158: triton_rotate_half_ on q and
+ * k, torch.cat onto the past, F.scaled_dot_product_attention with is_causal) on the cache layout of the decode entries above: `rows` consecutive
+ * tokens of ONE sequence at positions start .. start + rows - 1, their fused projection qkv [rows][3 heads 128] (q | k | v, rows ldq apart, left
+ * untouched), the sequence's cache slices k_cache / v_cache [t_max][heads 128].  The rotated k rows and the v rows are written to cache rows
+ * start .. start + rows - 1, bit-identical to what gptq_decode_rope_kv_f16 writes for the same row and position; out[r][h] = softmax(scale q_r .
+ * K[0 .. start + r]) V[0 .. start + r] (fp32 accumulation, one fp16 rounding, rows ldo apart).  Rows below start are read as earlier calls left
+ * them, rows at and beyond start + rows are never touched.  Flash-style on the matrix core (no score matrix in memory, no atomics: bit-identical
+ * from run to run); rope_table = NULL computes the trig in the kernel, bit-identical to the table of gptq_rope_table_f32.  start is a host value
+ * (prefill is not graph-captured).  The workspace holds one fp16 copy of the rotated q.  head_dim must be 128. */
+size_t gptq_prompt_attn_workspace_bytes(int rows, int heads, int head_dim, int t_max);
+int gptq_prompt_attn_f16(const void *qkv, int64_t ldq, int rows, int64_t start, void *k_cache, void *v_cache, void *out, int64_t ldo,
+                         void *workspace, size_t workspace_bytes, int heads, int head_dim, int t_max, float base, float scale,
+                         const float *rope_table, gptq_stream_t stream);
+
 /* ---- GPTQ solver (the caller that PRODUCES the weights; reference gptq.py:128-228) -------------------------------
  * One column block [i1, i1 + count), count <= 128, of the sequential quantise / error-feedback loop (gptq.py:177-199)
  * for all rows at once, in the reference's own fp32 arithmetic (IEEE division, round-half-even, no contraction).
