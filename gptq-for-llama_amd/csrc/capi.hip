@@ -1392,25 +1392,20 @@ int gptq_layer_unpack_checkpoint(const gptq_layer_t *layer, int set, int32_t *qw
 
 // rows of x the decode kernel (its 4x4x4 row groups) takes before the 16-row MFMA tiles do: 8 while ONE round of workgroups covers N, else 4
 //  -- and 8 for a wide gate | up pair the C-stripes kernel serves (round 5, stripe_kernel.inc stripe_launch_c: more than 512 stripes,
-// at most five row blocks per wave, not 2-bit).  A/B knobs (read once): GPTQ_DECODE_ROWS_WIDE = rows on wider single layers, GPTQ_DECODE_ROWS_PAIR =
-// rows of a wide gate/up pair.
+// at most five row blocks per wave, not 2-bit).
 static int decode_rows_max(int K, int N, int nsets, int bits, int groupsize) {
-    static const int wide = [] { const char *e = getenv("GPTQ_DECODE_ROWS_WIDE"); return e ? atoi(e) : 4; }();
-    static const int pair = [] { const char *e = getenv("GPTQ_DECODE_ROWS_PAIR"); return e ? atoi(e) : -1; }();
-    static const int mf8 = [] { const char *e = getenv("GPTQ_DECODE_MF8"); return e ? atoi(e) : 1; }();
     const int bk = bits == 8 ? 64 : 128;     // k per row block of the image (stripe_unpack.inc BK)
     // round 6: 5 .. 8 rows through the 16x16x16 inner product of the decode kernel (stripe_kernel.inc, MF) cost what four rows cost -- every
     // shape it serves keeps eight rows in the decode launch: groups that span a row block, not 2-bit, eight rows of x in LDS (K <= 9216; at
     // most five row blocks per wave when a workgroup walks several stripes), or a single set on a K up to 12288 (x in two halves)
-    if (mf8 && bits != 2) {
+    if (bits != 2) {
         const int gq = stripe_gq_shift(K, N, bits, groupsize);
         const int nu = (K / bk + 7) / 8;
         if ((gq == -1 || gq >= 2) && ((N / 16 <= 256 && nu * 8 * bk <= 9216) || (N / 16 > 256 && nu <= 5) || (nsets == 1 && nu * 8 * bk > 9216 && nu * 8 * bk <= 12288)))
             return 8;
     }
     if (N <= 4608) return 8;
-    if (nsets != 2) return wide;
-    if (pair >= 0) return pair;
+    if (nsets != 2) return 4;
     return (bits != 2 && N / 16 > 512 && K <= 5 * 8 * bk) ? 8 : 4;
 }
 
@@ -1420,16 +1415,12 @@ static int decode_rows_max(int K, int N, int nsets, int bits, int groupsize) {
 // with the norm fused 17.3 / 17.6 (tiles + the stand-alone norm launch): every one of the 230 workgroups normalises all 16 x 4096 elements itself,
 // ~330 VALU instructions per thread, more than the launch boundary of the 16-workgroup norm kernel costs; qkv plain 9.4 / 9.5, fused norm 13.2 / 12.1;
 // o_proj plain 6.5 / 5.4.  So: the pair takes this kernel PLAIN behind the norm launch (16.0 against 17.6), single sets stay on the tiles.
-// GPTQ_DECODE_MF16 = mask pins it for every shape (A/B).
 static int decode_rows_mf16(int K, int N, int nsets, int bits, int groupsize) {
-    static const int mode = [] { const char *e = getenv("GPTQ_DECODE_MF16"); return e ? atoi(e) : -1; }();
-    static const int mf8 = [] { const char *e = getenv("GPTQ_DECODE_MF8"); return e ? atoi(e) : 1; }();
-    if (!mode || !mf8 || bits == 2) return 0;
+    if (bits == 2) return 0;
     const int bk = bits == 8 ? 64 : 128;
     const int gq = stripe_gq_shift(K, N, bits, groupsize);
     const int nu = (K / bk + 7) / 8;
     if (!(gq == -1 || gq >= 2) || nu * 8 * bk > 4096 || (N / 16 > 256 && nu > 5) || N / 16 > 1024) return 0;
-    if (mode > 0) return mode;
     return nsets == 2 ? 2 : 0;
 }
 
@@ -1708,8 +1699,7 @@ int gptq_layer_decode_next_norm_f16(const gptq_layer_t *layer, const void *x, in
     if (!h_written) return GPTQ_E_NULL;
     *h_written = 0;
     if (!layer) return GPTQ_E_NULL;
-    static const int on = [] { const char *e = getenv("GPTQ_NEXT_NORM"); return e ? atoi(e) : 1; }();
-    if (!on || !next_norm_weight || !h || ldh < layer->N || M < 1 || M > 16)
+    if (!next_norm_weight || !h || ldh < layer->N || M < 1 || M > 16)
         return layer_decode(layer, x, ldx, y, ldy, M, norm_weight, norm_eps, residual, ldr, workspace, workspace_bytes, scratch, scratch_bytes, stream, nullptr);
     NextNorm nn{next_norm_weight, next_norm_eps, h, ldh, h_written};
     return layer_decode(layer, x, ldx, y, ldy, M, norm_weight, norm_eps, residual, ldr, workspace, workspace_bytes, scratch, scratch_bytes, stream, &nn);

@@ -7,7 +7,6 @@
 //
 // HBM-bound elementwise / reduction work (K,V rows are read once per token): no MFMA.
 #include <algorithm>
-#include <cstdlib>
 #include <type_traits>
 
 #include "attn_split.h"
@@ -520,24 +519,17 @@ int decode_attn_launch(const half_t *q, const half_t *kc, const half_t *vc, cons
 }
 
 // S of a launch's grid: enough workgroups to stream K / V at the chip's rate once a context is long (about 128 of them: a CU keeps ~36 KB of loads
-// in flight, i.e. ~80 GB/s against a quiet HBM), never more than ATT_MAX_SPLITS (what a merging consumer reads) -- heads x rows x S ~ 128.
-// GPTQ_ATTN_SPLITS pins it (A/B).
+// in flight, i.e. ~80 GB/s against a quiet HBM), never more than ATT_MAX_SPLITS (what a merging consumer reads) -- heads x rows x S <= 256, and at
+// most one split per tile of tokens.
 int decode_attn_grid_splits(int heads, int t_max, int batch) {
-    static const int pin = [] { const char *e = getenv("GPTQ_ATTN_SPLITS"); return e ? atoi(e) : 0; }();
-    static const int wgs = [] { const char *e = getenv("GPTQ_ATTN_WGS"); return e ? atoi(e) : 256; }();
-    int S = pin > 0 ? pin : wgs / std::max(1, heads * batch);
-    S = std::min(std::max(S, 1), ATT_MAX_SPLITS);
+    const int S = std::min(std::max(256 / std::max(1, heads * batch), 1), ATT_MAX_SPLITS);
     return std::min(S, (t_max + ATT_TILE - 1) / ATT_TILE);
 }
 
 // tokens a split owns at least.  With a merging consumer a further split costs one more record per x piece of o_proj's staging (~0.1 us): cut as
 // soon as a tile is full.  With the in-kernel merge it costs the ticket's dependent round trips (~4-5 us): one workgroup per head up to
-// ~768 tokens.  GPTQ_ATTN_TPS_REC / GPTQ_ATTN_TPS override (A/B).
-int decode_attn_tps(bool rec) {
-    static const int t_rec = [] { const char *e = getenv("GPTQ_ATTN_TPS_REC"); return e ? atoi(e) : 128; }();
-    static const int t_own = [] { const char *e = getenv("GPTQ_ATTN_TPS"); return e ? atoi(e) : 768; }();
-    return std::max(1, rec ? t_rec : t_own);
-}
+// ~768 tokens.  Callers override it through the tps argument of the attention entries.
+int decode_attn_tps(bool rec) { return rec ? 128 : 768; }
 
 // rec: leave the records to the next launch (out is not written); tps <= 0: the default of the mode
 int decode_attn_fused_launch(const half_t *qkv, const int64_t *pos, half_t *kc, half_t *vc, half_t *out, float *ws, int heads, int t_max,

@@ -7,7 +7,6 @@
 // workgroup in LDS (optionally RMS-normalised on the way: the final norm of the model, arithmetic of triton_norm.py:22-39, fp16-rounded
 // like the stand-alone launch it replaces), a wave owns whole rows -- 8 KiB contiguous each at K = 4096 -- and keeps two of them (16
 // wave loads of 1 KiB) in flight, non-temporal; products by v_dot2_f32_f16 into fp32, one DPP / permlane sum per row, fp16 store.
-#include <cstdlib>
 
 #include "gptq_device.h"
 #include "gptq_internal.h"
@@ -276,19 +275,16 @@ int dense_mm16_launch(const half_t *x, int64_t ldx, const half_t *W, int64_t ldw
     return (int)hipGetLastError();
 }
 
-// rows from which the matrix-core kernel takes over (A/B runs: GPTQ_LM_HEAD_MFMA_MIN_ROWS; 17 = never).  Measured on the 32000 x 4096 head
-// (gpurun_out r5c, us, dot2 / matrix core): 1 row 43.1 / 46.7, 2: 44.9 / 46.8, 4: 48.4 / 47.4, 5: 83 / 47.4, 8: 84 / 49.0, 16: 205 / 53.3
-int dense_mm16_min_rows() {
-    static const int v = [] { const char *e = getenv("GPTQ_LM_HEAD_MFMA_MIN_ROWS"); return e ? atoi(e) : 4; }();
-    return v;
-}
+// rows from which the matrix-core kernel takes over.  Measured on the 32000 x 4096 head (us, dot2 / matrix core): 1 row 43.1 / 46.7, 2: 44.9 / 46.8,
+// 4: 48.4 / 47.4, 5: 83 / 47.4, 8: 84 / 49.0, 16: 205 / 53.3
+constexpr int DENSE_MM16_MIN_ROWS = 4;
 
 }  // namespace
 
 // M rows of x (1 <= M <= 16; rows ldx apart, rows of y ldy apart): one pass over W for all of them
 int dense_gemv_launch(const half_t *x, const half_t *W, int64_t ldw, const half_t *bias, half_t *y, int N, int K, const half_t *norm_w, float eps,
                       hipStream_t s, int M, int64_t ldx, int64_t ldy) {
-    if (M >= dense_mm16_min_rows() && M <= 16 && K % DM_KQ == 0) {
+    if (M >= DENSE_MM16_MIN_ROWS && M <= 16 && K % DM_KQ == 0) {
         switch (K / DM_KQ) {   // K = waves x 1024 k: LLaMA-7B 4096, 13B 5120, 65B 8192
             case 4: return dense_mm16_launch<4>(x, ldx, W, ldw, bias, y, ldy, M, N, norm_w, eps, s);
             case 5: return dense_mm16_launch<5>(x, ldx, W, ldw, bias, y, ldy, M, N, norm_w, eps, s);

@@ -1018,7 +1018,6 @@ int stripe_launch_one(const StripeParams &p, hipStream_t s) {
 // against 8.2 / 12.3 plain: every variant; ONE row -- 6.9 / 10.5 against 7.2 / 10.8 with the norm, but 7.0 / 10.8 against 6.7 / 10.4 plain: NORM only;
 // 5 .. 8 rows (against the 16-row tiles + a norm launch) -- the pair 15.6 / 16.2 against 16.4 / 17.4, qkv a tie (11.7 / 11.3 against 11.7 / 11.5) and
 // slower plain: the pair only (capi.hip decode_rows_max).  Engine: 955 against 922 tok/s at B = 1, 3134 against 2851 at B = 4, 4694 against 4547 at B = 8.
-// GPTQ_DECODE_C=0: off (A/B), =n: pin C; GPTQ_DECODE_C1=0: one row stays on the one-stripe kernel.
 template <int NU, int NS, bool NORM, int C, int MR, int DU, bool MF = false>
 int stripe_launch_cdu(const StripeParams &p, hipStream_t s) {
     auto kern = stripe_gemvc_kernel<NU, NS, DU, NORM, MR, C, MF>;
@@ -1036,8 +1035,8 @@ int stripe_launch_cdu(const StripeParams &p, hipStream_t s) {
 
 template <int NU, int NS, bool NORM, int C, int MR>
 int stripe_launch_c(const StripeParams &p, hipStream_t s) {
-    // row blocks in flight per wave across the stripe boundaries: swept on qkv / the pair at one and four rows (profiles/r5i_c_stripes/
-    // row_blocks_in_flight_sweep_GPTQ_DECODE_CDU.txt, us with the fused norm at 1 / 4 rows): single set 2 / 3 / 4 / 6 / 8 blocks: 6.81 / 6.86 / 6.79 / 7.02 /
+    // row blocks in flight per wave across the stripe boundaries: swept on qkv / the pair at one and four rows (the sweep in
+    // profiles/r5i_c_stripes/, us with the fused norm at 1 / 4 rows): single set 2 / 3 / 4 / 6 / 8 blocks: 6.81 / 6.86 / 6.79 / 7.02 /
     // 7.28 and 8.63 / 8.36 / 7.99 / 8.15 / 8.98; pair 2 / 3 / 4: 10.6 / 11.0 / 11.5 and 11.7 / 12.1 / 12.2 -- deeper is slower here too (r5k_du_long)
     return stripe_launch_cdu<NU, NS, NORM, C, MR, (NS == 2 ? 2 : 4)>(p, s);
 }
@@ -1054,14 +1053,11 @@ int stripe_launch_c_pick(const StripeParams &p, hipStream_t s) {
     if constexpr (NU > 5 || SB == 2 || (MR == 8 && NS == 1)) {
         return GPTQ_E_VARIANT;
     } else {
-        static const int pin = [] { const char *e = getenv("GPTQ_DECODE_C"); return e ? atoi(e) : -1; }();
-        static const int one = [] { const char *e = getenv("GPTQ_DECODE_C1"); return e ? atoi(e) : 1; }();
         // more than two stripes per CU; with the fused norm already more than ONE (x is normalised once per workgroup: 5120 x 5120 at four rows 7.9
-        // against 9.2 us, 4096 x 6144 6.7 against 7.2, 4096 x 8192 7.2 against 7.6; plain launches of those shapes are a tie) -- GPTQ_DECODE_C_MIN pins it
-        static const int min_pin = [] { const char *e = getenv("GPTQ_DECODE_C_MIN"); return e ? atoi(e) : -1; }();
-        const int nstripes = p.N / 16, min_stripes = min_pin >= 0 ? min_pin : (p.norm_w ? 256 : 512);
-        if (pin == 0 || nstripes <= min_stripes || (MR == 1 && !one)) return GPTQ_E_VARIANT;
-        const int c = pin > 0 ? pin : (nstripes + 255) / 256;
+        // against 9.2 us, 4096 x 6144 6.7 against 7.2, 4096 x 8192 7.2 against 7.6; plain launches of those shapes are a tie)
+        const int nstripes = p.N / 16, min_stripes = p.norm_w ? 256 : 512;
+        if (nstripes <= min_stripes) return GPTQ_E_VARIANT;
+        const int c = (nstripes + 255) / 256;
         if (c == 2) return stripe_launch_c_norm<NU, NS, MR, 2>(p, s);
         if (c == 3) return stripe_launch_c_norm<NU, NS, MR, 3>(p, s);
         if (c == 4) return stripe_launch_c_norm<NU, NS, MR, 4>(p, s);
@@ -1070,10 +1066,9 @@ int stripe_launch_c_pick(const StripeParams &p, hipStream_t s) {
 }
 
 // 5 .. 8 rows through the 16x16x16 inner product (stripe_gemvc_kernel / stripe_gemv2p_kernel, MF): any number of stripes per workgroup (C = 1 on
-// one-round shapes), with or without the fused norm.  GPTQ_DECODE_MF8=0: off (A/B: the 4x4x4 row groups / 16-row tiles of round 5).
+// one-round shapes), with or without the fused norm.  Everything else keeps the 4x4x4 row groups / 16-row tiles of round 5.
 inline bool stripe_mf8_ok(const StripeParams &p) {
-    static const int on = [] { const char *e = getenv("GPTQ_DECODE_MF8"); return e ? atoi(e) : 1; }();
-    return on && SB != 2 && (p.gq_shift == -1 || p.gq_shift >= 2) && !p.y32 && !p.xperm && p.M > 4 && p.M <= 16;
+    return SB != 2 && (p.gq_shift == -1 || p.gq_shift >= 2) && !p.y32 && !p.xperm && p.M > 4 && p.M <= 16;
 }
 template <int NU, int NS, int C, int MR>
 int stripe_launch_mf8_c(const StripeParams &p, hipStream_t s) {

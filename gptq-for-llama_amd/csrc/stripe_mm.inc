@@ -24,7 +24,6 @@
 //    stripe_mm2_kernel below: a stripe x whole K per workgroup, x streamed through LDS).  Their bound is what one CU pulls from
 //    L2: ~45-50 GB/s (~1 KiB per 60-80 cycles) whether the bytes return to registers or land in LDS by DMA -- both are built.
 // Eligibility: bits 4 / 8, group size a multiple of the row block (BK = 128 / 64 k) or one group.  Dispatch: the end of this file.
-#include <cstdlib>
 
 #include "gptq_device.h"
 #include "gptq_internal.h"
@@ -95,18 +94,11 @@ GPTQ_DEV void mm_epilogue(const float4_t (&yacc)[NS][TM], const MMArgs &a, int s
 // PS ("prescale"): the group is smaller than a row block (or the width is 2-bit at g128: BK = 256), so the MFMA would sum across
 // groups -- each lane multiplies its exact q - z by its own group's fp16 scale first (one rounding, the reference's own dequantisation,
 // quant_linear.py:128) and the accumulator needs no per-row-block scale.  Any width with a stripe image runs here (2 / 3 / 4 / 8 bits).
-// C (round 5) = stripes per WAVE: wave w of workgroup `group` owns stripes (group C + c) 8 + w, c < C -- C consecutive 8-stripe groups of the
-// C = 1 numbering, so the partial tiles and the reduce kernel see C groups and do not change.  Why: an A fragment (1 KiB out of LDS) per
-// v_mfma_f32_16x16x32_f16 is 256 B / clk for the four SIMDs of a CU, LDS delivers 128 -- with three and four row tiles the C = 1 kernel is bound by
-// its A-fragment reads (4096 x 12288 at 64 rows: 1.6 MB per CU = 5 us), not by the matrix core (2.6 us) or HBM.  With C = 2 every fragment feeds two
-// MFMAs, the column groups halve (48 for N = 12288: five K slices fill the chip ONCE where C = 1 needs 1.5 rounds of workgroups), and so does the x
-// every CU pulls out of L2.
-template <int TM, int NS, bool PS, int C = 1>
+template <int TM, int NS, bool PS>
 __global__ void __launch_bounds__(STRIPE_NW * 64) stripe_mm_kernel(const MMArgs a) {
     typedef uint32_t wvec_t __attribute__((ext_vector_type(WPL)));
-    constexpr int NW = STRIPE_NW, RD = C > 1 ? 2 : MM_RD, ROWS = 16 * TM, RPW = ROWS / NW;   // RPW rows of x per wave while staging
+    constexpr int NW = STRIPE_NW, RD = MM_RD, ROWS = 16 * TM, RPW = ROWS / NW;   // RPW rows of x per wave while staging
     constexpr int TILE = NS * TM * 256;                                          // floats of one wave's accumulators (per stripe)
-    constexpr int NSC = NS * C;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     half_t *xl = (half_t *)smem;   // [ROWS][XS]
     const int tid = threadIdx.x, lane = tid & 63;
@@ -118,25 +110,19 @@ __global__ void __launch_bounds__(STRIPE_NW * 64) stripe_mm_kernel(const MMArgs 
     const UnpackConsts uc = unpack_consts();
 
     // ---- the first RD row blocks of this wave's stripes (HBM: the longest latency goes first), then the x slice ----
-    wvec_t w[RD][NSC];
-    uint32_t tw[RD][NSC];
-    const uint32_t *wbase[C], *tbase[C];
-#pragma unroll
-    for (int c = 0; c < C; c++) {
-        const int sc = min((group * C + c) * NW + wave, a.nstripes - 1);
-        wbase[c] = a.R + ((size_t)sc * a.nrb * NS * 64 + lane) * WPL;
-        tbase[c] = a.tab + (size_t)sc * NS * a.G * 16 + col;
-    }
+    wvec_t w[RD][NS];
+    uint32_t tw[RD][NS];
+    const int stripe = group * NW + wave, sc = min(stripe, a.nstripes - 1);
+    const uint32_t *wbase = a.R + ((size_t)sc * a.nrb * NS * 64 + lane) * WPL;
+    const uint32_t *tbase = a.tab + (size_t)sc * NS * a.G * 16 + col;
     auto issue = [&](int slot, int u) {
         const int rb = min(rb0 + u, a.nrb - 1);   // past the slice: a valid address, the scale is zeroed below
         const int g = PS ? ((rb * 4 + rq) >> a.gq_shift) : (a.grp_shift >= 0 ? (rb >> a.grp_shift) : 0);
 #pragma unroll
-        for (int c = 0; c < C; c++)
-#pragma unroll
-            for (int s = 0; s < NS; s++) {
-                w[slot][c * NS + s] = __builtin_nontemporal_load((const wvec_t *)(wbase[c] + ((size_t)rb * NS + s) * (64 * WPL)));
-                tw[slot][c * NS + s] = tbase[c][((size_t)s * a.G + g) * 16];
-            }
+        for (int s = 0; s < NS; s++) {
+            w[slot][s] = __builtin_nontemporal_load((const wvec_t *)(wbase + ((size_t)rb * NS + s) * (64 * WPL)));
+            tw[slot][s] = tbase[((size_t)s * a.G + g) * 16];
+        }
     };
 #pragma unroll
     for (int u = 0; u < RD; u++) issue(u, u);
@@ -157,9 +143,9 @@ __global__ void __launch_bounds__(STRIPE_NW * 64) stripe_mm_kernel(const MMArgs 
     }
     __syncthreads();
 
-    float4_t yacc[NSC][TM];
+    float4_t yacc[NS][TM];
 #pragma unroll
-    for (int s = 0; s < NSC; s++)
+    for (int s = 0; s < NS; s++)
 #pragma unroll
         for (int t = 0; t < TM; t++) yacc[s][t] = float4_t{0.f, 0.f, 0.f, 0.f};
     half2_t negoff[MM_NOFFC];
@@ -169,10 +155,10 @@ __global__ void __launch_bounds__(STRIPE_NW * 64) stripe_mm_kernel(const MMArgs 
     auto step = [&](int i, int u, bool refill) {
         const bool valid = rb0 + u < rb1;
         const int kk = u * BK + LK * rq;   // this lane's k block inside the slice
-        mm_h8_t B[NSC][PPB];
-        float scale[NSC];
+        mm_h8_t B[NS][PPB];
+        float scale[NS];
 #pragma unroll
-        for (int s = 0; s < NSC; s++) {
+        for (int s = 0; s < NS; s++) {
             const half2_t e = as_half2(tw[i][s]);
             scale[s] = valid ? (float)e[0] : 0.f;
             const half2_t zz = {e[1], e[1]};
@@ -190,16 +176,15 @@ __global__ void __launch_bounds__(STRIPE_NW * 64) stripe_mm_kernel(const MMArgs 
             }
 #pragma unroll
             for (int b = 0; b < PPB; b++) B[s][b] = __builtin_bit_cast(mm_h8_t, u32x4{d[4 * b], d[4 * b + 1], d[4 * b + 2], d[4 * b + 3]});
-            if constexpr (C > 1) __builtin_amdgcn_sched_barrier(0);      // one stripe's unpack temporaries at a time
         }
         if (refill) {
             issue(i, u + RD);   // the slot's words are unpacked: refill it before the math
             __builtin_amdgcn_sched_barrier(0);
         }
         const int kc = valid ? kk : LK * rq;   // past the slice: read inside the staged rows
-        float4_t acc[NSC][TM];
+        float4_t acc[NS][TM];
 #pragma unroll
-        for (int s = 0; s < NSC; s++)
+        for (int s = 0; s < NS; s++)
 #pragma unroll
             for (int t = 0; t < TM; t++) acc[s][t] = PS ? yacc[s][t] : float4_t{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -208,11 +193,11 @@ __global__ void __launch_bounds__(STRIPE_NW * 64) stripe_mm_kernel(const MMArgs 
             for (int t = 0; t < TM; t++) {
                 const mm_h8_t A = *(const mm_h8_t *)(xl + (size_t)(16 * t + col) * XS + kc + 8 * b);
 #pragma unroll
-                for (int s = 0; s < NSC; s++) acc[s][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A, B[s][b], acc[s][t], 0, 0, 0);
+                for (int s = 0; s < NS; s++) acc[s][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A, B[s][b], acc[s][t], 0, 0, 0);
             }
         }
 #pragma unroll
-        for (int s = 0; s < NSC; s++)
+        for (int s = 0; s < NS; s++)
 #pragma unroll
             for (int t = 0; t < TM; t++) {
                 if constexpr (PS) {
@@ -231,34 +216,25 @@ __global__ void __launch_bounds__(STRIPE_NW * 64) stripe_mm_kernel(const MMArgs 
 #pragma unroll
     for (int i = 0; i < RD; i++) step(i, u0 + i, false);   // the last round (blocks past the slice carry a zero scale)
 
+    if constexpr (TM == 1 && NS == 1) {
+        if (S > 1 && a.rowmajor) {   // rows for the combine + norm launch: [slice][16][N], 64-byte runs per row and stripe
+            if (stripe < a.nstripes) {
+                float *pr = a.partials + ((size_t)slice * 16 + 4 * rq) * ((size_t)a.nstripes * 16) + (size_t)stripe * 16 + col;
 #pragma unroll
-    for (int c = 0; c < C; c++) {
-        const int stripe = (group * C + c) * NW + wave;
-        if constexpr (TM == 1 && NS == 1) {
-            if (S > 1 && a.rowmajor) {   // rows for the combine + norm launch: [slice][16][N], 64-byte runs per row and stripe
-                if (stripe < a.nstripes) {
-                    float *pr = a.partials + ((size_t)slice * 16 + 4 * rq) * ((size_t)a.nstripes * 16) + (size_t)stripe * 16 + col;
-#pragma unroll
-                    for (int r = 0; r < 4; r++) pr[(size_t)r * a.nstripes * 16] = yacc[c][0][r];
-                }
-                continue;
+                for (int r = 0; r < 4; r++) pr[(size_t)r * a.nstripes * 16] = yacc[0][0][r];
             }
+            return;
         }
-        if (S > 1) {
-            // ---- K slices meet in the reduce kernel: this wave's fp32 tile, [64 lanes][4] per (set, row tile): 1 KiB stores ----
-            float *mine = a.partials + ((((size_t)group * C + c) * S + slice) * NW + wave) * TILE + lane * 4;
+    }
+    if (S > 1) {
+        // ---- K slices meet in the reduce kernel: this wave's fp32 tile, [64 lanes][4] per (set, row tile): 1 KiB stores ----
+        float *mine = a.partials + (((size_t)group * S + slice) * NW + wave) * TILE + lane * 4;
 #pragma unroll
-            for (int s = 0; s < NS; s++)
+        for (int s = 0; s < NS; s++)
 #pragma unroll
-                for (int t = 0; t < TM; t++) *(float4_t *)(mine + (s * TM + t) * 256) = yacc[c * NS + s][t];
-        } else {
-            float4_t yc[NS][TM];
-#pragma unroll
-            for (int s = 0; s < NS; s++)
-#pragma unroll
-                for (int t = 0; t < TM; t++) yc[s][t] = yacc[c * NS + s][t];
-            mm_epilogue<TM, NS>(yc, a, stripe, stripe < a.nstripes, rq, col);
-        }
+            for (int t = 0; t < TM; t++) *(float4_t *)(mine + (s * TM + t) * 256) = yacc[s][t];
+    } else {
+        mm_epilogue<TM, NS>(yacc, a, stripe, stripe < a.nstripes, rq, col);
     }
 }
 
@@ -963,10 +939,10 @@ int stripe_mm3c_dispatch(int tm, const StripeParams &p, int grp_shift, hipStream
     }
 }
 // round 5: the gate | up PAIR with C stripes per workgroup, one row tile (5 .. 16 rows of a decode batch): 2 C weight streams per wave on the
-// same staged x.  PFP = sub-slots of x in flight (A/B: GPTQ_MM3C_PAIR_PF)
-template <int C, int PFP>
+// same staged x, ONE sub-slot of x in flight (two measured no faster: DESIGN 3.8)
+template <int C>
 int stripe_mm3c_pair_dispatch(int tm, const StripeParams &p, int grp_shift, hipStream_t s) {
-    if (tm == 1) return stripe_mm3_launch<1, 2, PFP, C>(p, grp_shift, s);
+    if (tm == 1) return stripe_mm3_launch<1, 2, 1, C>(p, grp_shift, s);
     return GPTQ_E_VARIANT;
 }
 
@@ -1004,6 +980,7 @@ int stripe_mm3w4_dispatch(int tm, const StripeParams &p, int grp_shift, hipStrea
 // every wait inside the workgroup is bounded (a launch takes < 0.1 ms; 2^20 polls with s_sleep are > 20 ms): a wave that runs into the limit goes on with what
 // is there -- a wrong result that the parity tests would see, never a hung device
 constexpr int MMR_SPIN_LIMIT = 1 << 20;
+constexpr int MMR_NL = 2, MMR_INF = 2;      // loader waves, chunks in flight per loader (2 / 3 / 4 and 1 / 2 / 3 measured within 5 % of each other: profiles/r6s_mmr/)
 constexpr int MMR_NSLOT = 8;      // ring chunks (at most 64 rows x 128 k = 16 KiB each); six consumers hold one chunk each, the loaders fill the others
 // NH = 2 (five to eight row tiles): the consumers split into two ROW HALVES -- consumer cw owns pass cw % 2 of the row blocks cw / 2, cw / 2 + 3, .. -- instead
 // of running both passes on one set of B fragments: the sums of four row tiles per wave instead of eight (the eight-tile instance of three stripes spilled its
@@ -1012,7 +989,7 @@ constexpr int MMR_NSLOT = 8;      // ring chunks (at most 64 rows x 128 k = 16 K
 // fragment and chunk-sum registers take turns; only the sums per set are doubled), one set's packed words requested ahead; SiLU(gate) * up on the fp32 sums.
 // SS = 1 (the pair): the consumers split by SET instead -- consumer cw runs set cw % 2 (its k lane: cw / 2) with the registers of the single-set instance
 // and unpacks nothing twice; a chunk is released when the consumers of both sets are done with it.
-template <int TM, int C, int MMR_NL = 2, int MMR_INF = 2, int NH = 1, int NS = 1, int SS = 0>      // .., loader waves, chunks in flight per loader, row halves, weight sets, set split
+template <int TM, int C, int NH = 1, int NS = 1, int SS = 0>      // row tiles, stripes per workgroup, row halves, weight sets, set split
 __global__ void __launch_bounds__(STRIPE_NW * 64) stripe_mmr_kernel(const MMArgs a) {
     constexpr int MMR_NCW = STRIPE_NW - MMR_NL;
     typedef uint32_t wvec_t __attribute__((ext_vector_type(WPL)));
@@ -1295,10 +1272,10 @@ __global__ void __launch_bounds__(256) mmr_combine_kernel(const float *__restric
     }
 }
 
-template <int TM, int C, int NH = 1, int NS = 1, int SS = 0, int NL = 2, int INF = 2>
+template <int TM, int C, int NH = 1, int NS = 1, int SS = 0>
 int stripe_mmr_launch(const StripeParams &p, int grp_shift, hipStream_t s, int S = 1, void *ws = nullptr, size_t ws_bytes = 0) {
-    auto kern = stripe_mmr_kernel<TM, C, NL, INF, NH, NS, SS>;
-    constexpr size_t ring = (size_t)MMR_NSLOT * 16 * (TM <= 4 ? TM : 4) * BK * 2, red = (size_t)(STRIPE_NW - NL) * (SS ? 1 : NS) * C * (NH == 2 ? 4 : TM) * 1024;
+    auto kern = stripe_mmr_kernel<TM, C, NH, NS, SS>;
+    constexpr size_t ring = (size_t)MMR_NSLOT * 16 * (TM <= 4 ? TM : 4) * BK * 2, red = (size_t)(STRIPE_NW - MMR_NL) * (SS ? 1 : NS) * C * (NH == 2 ? 4 : TM) * 1024;
     constexpr size_t lds = (ring > red ? ring : red) + 256;
     static_assert(lds <= 160 * 1024 - 64, "LDS");
     static LdsOptIn opt_in;   // per instantiation; per device inside
@@ -1318,61 +1295,51 @@ int stripe_mmr_launch(const StripeParams &p, int grp_shift, hipStream_t s, int S
     if (a.S > 1) hipLaunchKernelGGL(mmr_combine_kernel, dim3((p.N / 8 + 255) / 256, p.M), dim3(256), 0, s, a.partials, a.S, p.M, p.N, p.bias, p.ldb, p.y, p.ldy);
     return (int)hipGetLastError();
 }
-// K slices (long K, one round of stripes): C stripes per workgroup x S slices = one round of workgroups, a quarter (half) of x per workgroup
-template <int C>
+// K slices (long K, one round of stripes): four stripes per workgroup x S slices = one round of workgroups, a quarter of x per workgroup
 int stripe_mmr_sliced_dispatch(int tm, int S, const StripeParams &p, int grp_shift, void *ws, size_t ws_bytes, hipStream_t s) {
-    switch (tm) {
-        case 1: return stripe_mmr_launch<1, C>(p, grp_shift, s, S, ws, ws_bytes);
-        case 2: return stripe_mmr_launch<2, C>(p, grp_shift, s, S, ws, ws_bytes);
-        case 3: return stripe_mmr_launch<3, C>(p, grp_shift, s, S, ws, ws_bytes);
-        case 4: return stripe_mmr_launch<4, C>(p, grp_shift, s, S, ws, ws_bytes);
-        case 5: return stripe_mmr_launch<5, C, 1>(p, grp_shift, s, S, ws, ws_bytes);
-        case 6: return stripe_mmr_launch<6, C, 2>(p, grp_shift, s, S, ws, ws_bytes);      // (two passes spill from six row tiles on with four stripes)
-        case 7: return stripe_mmr_launch<7, C, 2>(p, grp_shift, s, S, ws, ws_bytes);
-        case 8: return stripe_mmr_launch<8, C, 2>(p, grp_shift, s, S, ws, ws_bytes);
-        default: return GPTQ_E_VARIANT;
+    if constexpr (SB == 4) {      // (the loader / consumer kernel is built for 4 bits: BK = 128)
+        constexpr int C = 4;
+        switch (tm) {
+            case 2: return stripe_mmr_launch<2, C>(p, grp_shift, s, S, ws, ws_bytes);
+            case 3: return stripe_mmr_launch<3, C>(p, grp_shift, s, S, ws, ws_bytes);
+            case 4: return stripe_mmr_launch<4, C>(p, grp_shift, s, S, ws, ws_bytes);
+            case 5: return stripe_mmr_launch<5, C, 1>(p, grp_shift, s, S, ws, ws_bytes);
+            case 6: return stripe_mmr_launch<6, C, 2>(p, grp_shift, s, S, ws, ws_bytes);      // (two passes spill from six row tiles on with four stripes)
+            case 7: return stripe_mmr_launch<7, C, 2>(p, grp_shift, s, S, ws, ws_bytes);
+            case 8: return stripe_mmr_launch<8, C, 2>(p, grp_shift, s, S, ws, ws_bytes);
+            default: break;
+        }
     }
+    return GPTQ_E_VARIANT;
 }
 // the gate | up pair: the consumers split by set (SS = 1).  Measured (profiles/r6z_pair/, us, 2 x 4096 x 11008 at 32 / 48 / 64 / 80 / 96 / 112 / 128 rows): set split
-// 16.2 / 19.2 / 21.9 / 26.1 / 28.7 / 31.0 / 51.0 (eight row tiles of three stripes spill), both sets per consumer (row halves from five row tiles on) 16.4 / 20.6 /
+// 16.2 / 19.2 / 21.9 / 26.1 / 28.7 / 31.0 / 51.0 (eight row tiles of three stripes spilled: not built), both sets per consumer (row halves from five row tiles on) 16.4 / 20.6 /
 // 32.7 / 46.7 / 47.2 / 48.6 / 52.6 (spills from four row tiles on), the routes before 21.3 / 35.0 / 36.0 / 49.2 / 55.5 / 70.5 / 71.8
 template <int C>
 int stripe_mmr_pair_dispatch(int tm, const StripeParams &p, int grp_shift, hipStream_t s) {
     switch (tm) {
-        case 1: return stripe_mmr_launch<1, C, 1, 2, 1>(p, grp_shift, s);
         case 2: return stripe_mmr_launch<2, C, 1, 2, 1>(p, grp_shift, s);
         case 3: return stripe_mmr_launch<3, C, 1, 2, 1>(p, grp_shift, s);
         case 4: return stripe_mmr_launch<4, C, 1, 2, 1>(p, grp_shift, s);
         case 5: return stripe_mmr_launch<5, C, 1, 2, 1>(p, grp_shift, s);
         case 6: return stripe_mmr_launch<6, C, 1, 2, 1>(p, grp_shift, s);
         case 7: return stripe_mmr_launch<7, C, 1, 2, 1>(p, grp_shift, s);
-        case 8: return stripe_mmr_launch<8, C, 1, 2, 1>(p, grp_shift, s);
+        case 8: if constexpr (C == 2) return stripe_mmr_launch<8, C, 1, 2, 1>(p, grp_shift, s);   // (three stripes: two launches of four row tiles, see the dispatcher)
         default: return GPTQ_E_VARIANT;
     }
 }
+// two to eight row tiles.  Five to seven run both passes per consumer (NH = 1), eight the row halves (NH = 2: its two-pass instance spilled) -- measured in
+// profiles/r6y_mmr_halves/, the table in DESIGN 3.3a, round 6
 template <int C>
 int stripe_mmr_dispatch(int tm, const StripeParams &p, int grp_shift, hipStream_t s) {
-    // five to eight row tiles: both passes per consumer (NH = 1) or row halves (NH = 2); GPTQ_MMR_NH=1|2 pins either (A/B).  Measured (profiles/r6y_mmr_halves/,
-    // us, two passes / halves): 4096 x 12288 at 80 / 96 / 112 / 128 rows 20.6 / 21.8 / 23.4 / 33.1 (spills) against 22.4 / 22.6 / 23.5 / 24.0, 4096 x 11008 19.1 / 20.4 /
-    // 21.9 / 31.4 against 20.5 / 21.3 / 22.0 / 22.5, 4096 x 8192 16.5 / 18.1 / 18.9 / 20.5 against 17.4 / 18.2 / 19.1 / 19.4: halves for eight row tiles, two passes below
-    static const int nh_mode = [] { const char *e = getenv("GPTQ_MMR_NH"); return e ? atoi(e) : 0; }();
-    if (tm >= 5 && tm <= 8 && (nh_mode == 2 || (nh_mode == 0 && tm == 8))) {
-        switch (tm) {
-            case 5: return stripe_mmr_launch<5, C, 2>(p, grp_shift, s);
-            case 6: return stripe_mmr_launch<6, C, 2>(p, grp_shift, s);
-            case 7: return stripe_mmr_launch<7, C, 2>(p, grp_shift, s);
-            default: return stripe_mmr_launch<8, C, 2>(p, grp_shift, s);
-        }
-    }
     switch (tm) {
-        case 1: return stripe_mmr_launch<1, C>(p, grp_shift, s);
         case 2: return stripe_mmr_launch<2, C>(p, grp_shift, s);
         case 3: return stripe_mmr_launch<3, C>(p, grp_shift, s);
         case 4: return stripe_mmr_launch<4, C>(p, grp_shift, s);
         case 5: return stripe_mmr_launch<5, C>(p, grp_shift, s);
         case 6: return stripe_mmr_launch<6, C>(p, grp_shift, s);
         case 7: return stripe_mmr_launch<7, C>(p, grp_shift, s);
-        case 8: return stripe_mmr_launch<8, C>(p, grp_shift, s);
+        case 8: return stripe_mmr_launch<8, C, 2>(p, grp_shift, s);
         default: return GPTQ_E_VARIANT;
     }
 }
@@ -1380,9 +1347,9 @@ int stripe_mmr_dispatch(int tm, const StripeParams &p, int grp_shift, hipStream_
 // K slices for a launch (profiles/r2c_mm/slices.txt): as many workgroups as fill the chip ONCE (256; 128 for four row tiles, whose x
 // slices are the largest) -- a second, partial round of workgroups costs more than larger slices -- and never more x per workgroup
 // than LDS holds.  Returns the row blocks per slice.
-int mm_pick_slices(int tm, int nrb, int groups, int forced, int target = 0) {
+int mm_pick_slices(int tm, int nrb, int groups, int forced) {
     const int max_span_k = 135 * 1024 / (32 * tm) - 8;   // rows * (span + 8) * 2 bytes <= 135 KB
-    if (target <= 0) target = tm >= 4 ? 128 : 256;
+    const int target = tm >= 4 ? 128 : 256;
     int s = forced > 0 ? forced : target / groups;
     if (s > nrb) s = nrb;
     if (s < 1) s = 1;
@@ -1392,15 +1359,15 @@ int mm_pick_slices(int tm, int nrb, int groups, int forced, int target = 0) {
     return (nrb + s - 1) / s;   // equal slices: the longest one sets the time
 }
 
-template <int TM, int NS, bool PS, int C = 1>
+template <int TM, int NS, bool PS>
 int stripe_mm_launch(const StripeParams &p, int grp_shift, void *ws, size_t ws_bytes, int forced_slices, hipStream_t s) {
-    auto kern = stripe_mm_kernel<TM, NS, PS, C>;
-    const int nrb = p.K / BK, nstripes = p.N / 16, groups8 = (nstripes + STRIPE_NW - 1) / STRIPE_NW, groups = (groups8 + C - 1) / C;
-    const int span = mm_pick_slices(TM, nrb, groups, forced_slices, C > 1 ? 256 : 0);     // (C > 1: half the column groups -- one full round of workgroups)
+    auto kern = stripe_mm_kernel<TM, NS, PS>;
+    const int nrb = p.K / BK, nstripes = p.N / 16, groups = (nstripes + STRIPE_NW - 1) / STRIPE_NW;
+    const int span = mm_pick_slices(TM, nrb, groups, forced_slices);
     const int S = (nrb + span - 1) / span;
     const size_t lds = (size_t)16 * TM * (span * BK + 8) * 2;
     if (lds > 160 * 1024 - 256) return GPTQ_E_VARIANT;
-    const size_t part_bytes = S > 1 ? (size_t)groups * C * S * STRIPE_NW * NS * TM * 256 * 4 : 0;
+    const size_t part_bytes = S > 1 ? (size_t)groups * S * STRIPE_NW * NS * TM * 256 * 4 : 0;
     if (S > 1 && (!ws || ws_bytes < part_bytes)) return GPTQ_E_WORKSPACE;
     static LdsOptIn opt_in;   // per instantiation; per device inside
     if (int rc = opt_in.ensure((const void *)kern, lds)) return rc;
@@ -1409,10 +1376,9 @@ int stripe_mm_launch(const StripeParams &p, int grp_shift, void *ws, size_t ws_b
     a.partials = (float *)ws;
     a.K = p.K; a.nrb = nrb; a.G = p.G; a.grp_shift = grp_shift; a.M = p.M; a.ldx = (int)p.ldx; a.ldy = (int)p.ldy;
     a.nstripes = nstripes; a.S = S; a.span = span; a.gq_shift = p.gq_shift;
-    // (the reduce kernel numbers 8-stripe groups: the C groups of a workgroup are consecutive ones)
     if constexpr (TM == 1 && NS == 1) {
         // round 6: the caller wants h = rmsnorm(y) * w for the NEXT linear -- the combine launch owns whole rows and writes it too
-        if (S > 1 && C == 1 && p.next_norm_w && p.h && p.next_norm_done && p.N / 8 <= 4096 && p.ldy % 8 == 0 && p.ldh % 8 == 0 && (!p.bias || p.ldb % 8 == 0) &&
+        if (S > 1 && p.next_norm_w && p.h && p.next_norm_done && p.N / 8 <= 4096 && p.ldy % 8 == 0 && p.ldh % 8 == 0 && (!p.bias || p.ldb % 8 == 0) &&
             ((uintptr_t)p.y % 16 == 0) && ((uintptr_t)p.h % 16 == 0) && ((uintptr_t)p.next_norm_w % 16 == 0) && (!p.bias || (uintptr_t)p.bias % 16 == 0) &&
             (size_t)S * 16 * p.N * 4 <= ws_bytes) {
             a.rowmajor = 1;
@@ -1422,7 +1388,7 @@ int stripe_mm_launch(const StripeParams &p, int grp_shift, void *ws, size_t ws_b
         }
     }
     hipLaunchKernelGGL(kern, dim3(groups * S), dim3(STRIPE_NW * 64), lds, s, a);
-    if (S > 1) hipLaunchKernelGGL((stripe_mm_reduce_kernel<TM, NS>), dim3(groups * C * TM), dim3(STRIPE_NW * 64), 0, s, a);
+    if (S > 1) hipLaunchKernelGGL((stripe_mm_reduce_kernel<TM, NS>), dim3(groups * TM), dim3(STRIPE_NW * 64), 0, s, a);
     return (int)hipGetLastError();
 }
 
@@ -1721,9 +1687,9 @@ int stripe_gemm_sliced_launch(const StripeParams &p, int grp_shift, void *ws, si
     // sliced too -- one launch, row tile x group x slice workgroups, the reduce kernel walks the row tiles; before, 256 x 4096 x 11008 ran 64 workgroups
     // over the whole K each (87.7 us against 81.9 for the library, the one cell of the prompt table below it: profiles/r5e_gemm8_tile/)
     const int mtiles = (p.M + 32 * RT - 1) / (32 * RT);
-    // (the limit was swept -- GPTQ_SGS_MT_TILES=128|192|256, profiles/r5e_gemm8_tile/image_route_k_slices_tile_limit_128_192_256.txt: with 129 .. 256 tiles
-    // two slices are SLOWER than none -- 4096 x 12288 at 129 .. 256 rows 48-50 us against 39, 4096^2 at 640 rows 48 against 38)
-    static const int mt_tiles = [] { const char *e = getenv("GPTQ_SGS_MT_TILES"); return e ? atoi(e) : 128; }();
+    // (the limit of 128 tiles was swept, profiles/r5e_gemm8_tile/image_route_k_slices_tile_limit_128_192_256.txt: with 129 .. 256 tiles two slices are
+    // SLOWER than none -- 4096 x 12288 at 129 .. 256 rows 48-50 us against 39, 4096^2 at 640 rows 48 against 38)
+    constexpr int mt_tiles = 128;
     if (nrb < 2 * SG_PFW || (mtiles > 1 && (mtiles * ngroups > mt_tiles || forced_slices > 0))) return GPTQ_E_VARIANT;
     int S = forced_slices > 0 ? forced_slices : std::max(2, 256 / (ngroups * mtiles));     // at most ONE round of workgroups (a partial second round costs a whole one)
     int span = ((nrb + S - 1) / S + SG_PFW - 1) / SG_PFW * SG_PFW;                                // whole rounds of PFW chunks per slice
@@ -1757,22 +1723,19 @@ int STRIPE_CAT(stripe_gemm_dispatch_b, STRIPE_BITS)(const StripeParams &p, void 
         if (p.gq_shift < 2) return GPTQ_E_VARIANT;   // group smaller than a row block
         grp_shift = p.gq_shift - 2;
     }
-    // round 5: K slices over several row tiles while the tiles cover at most half the chip (stripe_gemm_sliced_launch); GPTQ_SGS_MT=0: off (A/B)
+    const int spg = p.NS == 1 ? 8 : 4, ngroups = (p.N / 16 + spg - 1) / spg;
+    // K slices over several row tiles while the tiles cover at most half the chip (stripe_gemm_sliced_launch declines otherwise): profiles/r5e_gemm8_tile/
     if constexpr (SB != 2) {
-        static const int sgs_mt = [] { const char *e = getenv("GPTQ_SGS_MT"); return e ? atoi(e) : 1; }();
-        if (sgs_mt != 0 && p.NS == 1 && p.M > 128 && ws) {
+        if (p.NS == 1 && p.M > 128 && ws) {
             const int rc = stripe_gemm_sliced_launch<1>(p, grp_shift, ws, ws_bytes, -1, s);
             if (rc != GPTQ_E_VARIANT && rc != GPTQ_E_WORKSPACE) return rc;
         }
     }
-    // 128- or 256-row tiles: whichever needs less time in whole rounds of workgroups over the 256 CUs -- a 256-row tile costs 1.75 x a
-    // 128-row tile (profiles/r3g_mid_m/stripe_gemm_tile_rows.txt: 66-70 us against 36-40 us per round at K = 4096).  GPTQ_SG_RT=4|8 pins
-    // one (A-B runs).
-    static const int pin = [] { const char *e = getenv("GPTQ_SG_RT"); return e ? atoi(e) : 0; }();
-    const int spg = p.NS == 1 ? 8 : 4, ngroups = (p.N / 16 + spg - 1) / spg;
+    // 256-row tiles where they need less time in whole rounds of workgroups over the 256 CUs: a 256-row tile costs 1.75 x a 128-row tile
+    // (profiles/r3g_mid_m/stripe_gemm_tile_rows.txt: 66-70 us against 36-40 us per round at K = 4096)
     const int64_t r4 = ((int64_t)ngroups * ((p.M + 127) / 128) + 255) / 256, r8 = ((int64_t)ngroups * ((p.M + 255) / 256) + 255) / 256;
-    const bool big = pin ? pin == 8 : 7 * r8 < 4 * r4;
-    if (big) return p.NS == 2 ? stripe_gemm_launch<2, 8>(p, grp_shift, s) : stripe_gemm_launch<1, 8>(p, grp_shift, s);
+    if (7 * r8 < 4 * r4) return p.NS == 2 ? stripe_gemm_launch<2, 8>(p, grp_shift, s) : stripe_gemm_launch<1, 8>(p, grp_shift, s);
+    // 128-row tiles: everything else
     return p.NS == 2 ? stripe_gemm_launch<2, 4>(p, grp_shift, s) : stripe_gemm_launch<1, 4>(p, grp_shift, s);
 }
 
@@ -1789,164 +1752,79 @@ int STRIPE_CAT(stripe_mm_dispatch_b, STRIPE_BITS)(const StripeParams &p, void *w
         if (p.gq_shift < 2) ps = true;            // group smaller than a row block: prescale kernels
         else grp_shift = p.gq_shift - 2;          // BK = 4 LK
     }
-    const int tm = (p.M + 15) / 16;
-    // round 3: wave-private staging (stripe_mm3_kernel).  It re-reads x once per stripe, so it wins where ONE round of workgroups covers N and K
-    // is short (every workgroup pulls M K 2 bytes through its CU at ~75 GB/s): measured (profiles/r3g_mid_m/mm3_ab.txt, us, new vs round 2's
-    // schedules) 4096^2: M = 16 / 32 / 64 / 96 / 128: 5.4 / 7.2 / 9.8 / 12.3 / 14.7 vs 6.0 / 8.6 / 12.5 / 19.5 / 19.6; 4096 x 12288 (three rounds) and
-    // 11008 x 4096 (long K) lose except at 65..96 rows (34.6 / 32.1 vs 43.2 / 40.2).  GPTQ_MM3=0 restores round 2's schedules, GPTQ_MM3=2 forces
-    // the new kernel wherever it can run (A-B runs: tools/bench_stripe_mm.py).
-    static const int mm3_mode = [] { const char *e = getenv("GPTQ_MM3"); return e ? atoi(e) : 1; }();
-    // (8-bit: eight row blocks of packed words per wave and segment -- the instances beyond four row tiles / the pair beyond one would spill)
-    const bool mm3_can = !ps && forced_slices < 0 && (p.NS == 1 ? tm <= (SB == 8 ? 4 : 8) : tm <= (SB == 8 ? 1 : 2));
-    const bool mm3_pays = (p.N / 16 <= 256 && p.K <= 6144) || (p.NS == 1 && (tm == 5 || tm == 6) && SB != 8);
-    // round 5: K slices with TWO stripes per wave (stripe_mm_kernel<.., C = 2>) for two to four row tiles on shapes whose stripes need several
-    // rounds of workgroups, and on long K: every A fragment feeds two MFMAs, half the column groups, ONE round of workgroups (240 for
-    // 4096 x 12288).  BUILT, PARITY-GREEN, MEASURED, AND SLOWER -- so OFF by default (profiles/r5b_ksc/, us, this / round 4's schedules):
-    // 4096 x 12288 at 17 / 32 / 48 / 64 rows 16.4 / 16.3 / 19.9 / 23.1 against 11.8 / 12.1 / 16.2 / 19.9; 4096 x 11008 15.0 / 15.4 / 18.8 / 22.4
-    // against 10.9 / 11.4 / 14.9 / 19.4; 11008 x 4096 14.8 / 15.2 / 18.0 / 20.6 against 13.3 / 13.7 / 16.2 / 21.8 (the one cell it wins).  Under
-    // rocprofv3 the slice kernel alone runs 18.7 us at 64 rows (12.6 at 32) + 4.8 (4.6) for the reduce launch, where the matrix core needs 2.6 us
-    // and the weights 5: the slices do not remove what bounds these batches -- see DESIGN 3.3a, round 5.  GPTQ_MM_KSC=2 runs it wherever it can (A/B).
-    // A second form -- straight-line instances per slice length with EVERY row block of the slice and all of x requested up front, because the ISA of
-    // the loop starts each round of two steps with s_waitcnt vmcnt(0) -- changed nothing (18.9 us for the slice kernel, 24.1 in total at 64 rows:
-    // profiles/r5b_ksc/ksc_straight_line_ab.txt; the fifteen instances were removed again): the wait at the loop head is not what these launches spend
-    // their time on either.
-    static const int ksc_mode = [] { const char *e = getenv("GPTQ_MM_KSC"); return e ? atoi(e) : 0; }();
-    if constexpr (SB == 4 || SB == 3) {
-        const int cw = (p.N / 16 + 255) / 256;
-        const bool ksc_can = !ps && forced_slices < 0 && p.NS == 1 && tm >= 2 && tm <= 4;
-        if (ksc_can && (ksc_mode == 2 || (ksc_mode == 1 && (cw >= 2 || p.K > 6144)))) {
-            int rc;
-            switch (tm) {
-                case 2: rc = stripe_mm_launch<2, 1, false, 2>(p, grp_shift, ws, ws_bytes, -1, s); break;
-                case 3: rc = stripe_mm_launch<3, 1, false, 2>(p, grp_shift, ws, ws_bytes, -1, s); break;
-                default: rc = stripe_mm_launch<4, 1, false, 2>(p, grp_shift, ws, ws_bytes, -1, s); break;
-            }
-            if (rc != GPTQ_E_VARIANT && rc != GPTQ_E_WORKSPACE) return rc;
-        }
-    }
-    // round 6: loader / consumer split (stripe_mmr_kernel) for 17 .. 128 rows on shapes with 2-3 rounds of stripes (N = 8192, 11008, 12288) and K <= 8192.
-    // Measured (profiles/r6s_mmr/, r6x_mmr_tm7/, r6y_mmr_halves/, us per launch, this kernel / round 5's routes): 4096 x 12288 at 32 / 48 / 64 / 80 / 96 / 112 / 128
-    // rows 11.2 / 13.3 / 15.5 / 19.8 / 21.5 / 22.9 / 24.0 against 12.0 / 16.3 / 20.5 / 28.9 / 29.1 / 29.0 / 28.9, 4096 x 11008 10.7 / 12.7 / 14.4 / 18.6 / 20.3 / 21.6 / 22.4
-    // against 11.3 / 15.5 / 19.4 / 27.9 / 28.0 / 28.2 / 28.3, 4096 x 8192 at 80 .. 128 rows 17.6 / 18.9 / 19.8 / 19.4 against 20.2 / 21.9 / 24.8 / 24.5; at 16 rows 10.0 / 9.0
-    // against 10.35 / 9.2 (a tie: stays with the decode batch routes); on one-round shapes it LOSES (4096^2 at 64 rows 11.2 against 9.7, 11008 x 4096 24.4 against
-    // 23.2: one stripe per workgroup, x is re-read per 16 columns).  Loader waves 2 / 3 / 4 and 1 / 2 / 3 chunks in flight measure within 5 % of each other: what is
-    // left is NOT the loaders -- the slope is 1.65-2 us per 16 rows on every kernel built for these batches (rounds 4, 5, this one), which is x through the
-    // L2s: 16 rows x 4096 k x 2 B x 256 workgroups = 32 MB per row tile, ~20 TB/s of the L2s' 34.5 (the counters: DESIGN 3.3a, round 6; a padded row stride of x
-    // changes nothing: profiles/r6u_xpad/).  GPTQ_MMR=0: off; =2: wherever it can run (A/B).
-    static const int mmr_mode = [] { const char *e = getenv("GPTQ_MMR"); return e ? atoi(e) : 1; }();
+    // the facts the routes share.  An ordered list: the first route whose predicate holds (and whose launcher does not decline) runs.
+    // What each route was measured against, and the forms that were built and removed: DESIGN 3.3a.
+    const int tm = (p.M + 15) / 16;                    // row tiles of 16
+    const int cw = (p.N / 16 + 255) / 256;             // rounds of stripes over the 256 CUs = adjacent stripes per workgroup of the C-stripe kernels
+    const bool auto_slices = forced_slices < 0;        // the caller pins no slice count (gptq_set_split_k)
+    const bool x_aligned = p.K % BK == 0 && (uintptr_t)p.x % 16 == 0 && p.ldx % 8 == 0;      // LDS-DMA of whole 16-byte pieces of x
+    const bool one_round_short_k = p.N / 16 <= 256 && p.K <= 6144;
+    const bool c_stripes = !ps && auto_slices && p.K <= 6144 && (cw == 2 || cw == 3);         // what the C-stripes-per-workgroup routes share
+
     if constexpr (SB == 4) {
-        const int cw = (p.N / 16 + 255) / 256;
-        static const int mmr_tmax = [] { const char *e = getenv("GPTQ_MMR_TMAX"); return e ? atoi(e) : 0; }();      // (A/B: 4 = round 6's first form)
-        const int tmax = mmr_tmax > 0 ? mmr_tmax : 8;
-        const bool can = !ps && forced_slices < 0 && p.NS == 1 && tm <= 8 && cw >= 1 && cw <= 3 && p.K % BK == 0 && (uintptr_t)p.x % 16 == 0 && p.ldx % 8 == 0;
-        if (can && (mmr_mode == 2 || (mmr_mode == 1 && tm >= 2 && tm <= tmax && cw >= 2 && p.K <= (tm >= 6 ? 6144 : 8192)))) {     // (8192 x 8192 from 96 rows on: 34-37 us against 33-34)
-            static const int c1 = [] { const char *e = getenv("GPTQ_MMR_C1"); return e ? atoi(e) : 1; }();      // (A/B: stripes per workgroup on one-round shapes -- 2: half the CUs)
-            const int rc = cw == 1 ? (c1 == 2 ? stripe_mmr_dispatch<2>(tm, p, grp_shift, s) : stripe_mmr_dispatch<1>(tm, p, grp_shift, s))
-                                   : (cw == 2 ? stripe_mmr_dispatch<2>(tm, p, grp_shift, s) : stripe_mmr_dispatch<3>(tm, p, grp_shift, s));
-            if (rc != GPTQ_E_VARIANT) return rc;
-        }
-        // K slices on one-round shapes with a long K (LLaMA-7B down_proj 11008 x 4096: 256 stripes -> 64 groups of four stripes x four slices, a quarter of x per
-        // workgroup, the slices' fp32 rows added by mmr_combine_kernel).  Measured (profiles/r7g_mmr_kslices/, us, this / the routes before): 32 / 48 / 64 / 80 / 96 / 128
-        // rows 13.7 / 15.8 / 17.9 / 24.0 / 24.4 / 25.8 against 14.8 / 16.9 / 22.8 / 26.0 / 26.0 / 26.6; two stripes x two slices and 4 x 2 / 2 x 4 lose, and so does every
-        // form on 4096^2 (12.1 against 10.0 at 64 rows: the combine launch costs more than half of x saves).  GPTQ_MMR_KS=C*10+S pins (C stripes, S slices), 0 = off
-        static const int mmr_ks = [] { const char *e = getenv("GPTQ_MMR_KS"); return e ? atoi(e) : -1; }();
+        // loader / consumer split, 17 .. 128 rows on shapes with two or three rounds of stripes, K <= 8192 (8192 x 8192 from 96 rows on loses: 6144 there).
+        // profiles/r6s_mmr/, r6x_mmr_tm7/, r6y_mmr_halves/
+        if (!ps && auto_slices && x_aligned && p.NS == 1 && tm >= 2 && tm <= 8 && (cw == 2 || cw == 3) && p.K <= (tm >= 6 ? 6144 : 8192))
+            return cw == 2 ? stripe_mmr_dispatch<2>(tm, p, grp_shift, s) : stripe_mmr_dispatch<3>(tm, p, grp_shift, s);
+        // the same kernel in four K slices of four stripes: one round of stripes with a long K (LLaMA-7B down_proj, 11008 x 4096).  profiles/r7g_mmr_kslices/
         const int nst = p.N / 16;
-        const bool ks_auto = mmr_ks < 0 && mmr_mode == 1 && nst > 192 && nst <= 256 && p.K > 6144 && p.K <= 16384;
-        if ((mmr_ks > 0 || ks_auto) && !ps && forced_slices < 0 && p.NS == 1 && cw == 1 && tm >= (mmr_ks > 0 ? 1 : 2) && tm <= 8 && p.K % BK == 0 && (uintptr_t)p.x % 16 == 0 && p.ldx % 8 == 0 && ws) {
-            const int kc = mmr_ks > 0 ? mmr_ks / 10 : 4, ksl = mmr_ks > 0 ? mmr_ks % 10 : 4;
-            const int rc = kc == 4 ? stripe_mmr_sliced_dispatch<4>(tm, ksl, p, grp_shift, ws, ws_bytes, s) : stripe_mmr_sliced_dispatch<2>(tm, ksl, p, grp_shift, ws, ws_bytes, s);
+        if (!ps && auto_slices && x_aligned && p.NS == 1 && tm >= 2 && tm <= 8 && nst > 192 && nst <= 256 && p.K > 6144 && p.K <= 16384 && ws) {
+            const int rc = stripe_mmr_sliced_dispatch(tm, 4, p, grp_shift, ws, ws_bytes, s);
             if (rc != GPTQ_E_VARIANT && rc != GPTQ_E_WORKSPACE) return rc;
         }
-        // the gate | up pair (before: 20.9 / 35.7 / 35.9 / 54.6 / 70.0 us at 32 / 48 / 64 / 96 / 128 rows of 2 x 4096 x 11008, profiles/r6z_pair/); GPTQ_MMR_PAIR=0: off
-        static const int mmr_pair = [] { const char *e = getenv("GPTQ_MMR_PAIR"); return e ? atoi(e) : 1; }();
-        const bool canp = !ps && forced_slices < 0 && p.NS == 2 && tm <= 8 && cw >= 2 && cw <= 3 && p.K % BK == 0 && (uintptr_t)p.x % 16 == 0 && p.ldx % 8 == 0;
-        if (canp && mmr_pair != 0 && tm >= 2 && p.K <= 6144) {
-            // eight row tiles of three stripes spill (51 us): rows 0 .. 63 and 64 .. M - 1 as TWO launches of the four-tile instance (2 x 21.9 us; the second
-            // reads the weights out of the Infinity Cache); GPTQ_MMR_PAIR_C8=2: two stripes per workgroup in 1.3 rounds (48.9 us), =3: the spilling instance (A/B)
-            static const int c8 = [] { const char *e = getenv("GPTQ_MMR_PAIR_C8"); return e ? atoi(e) : 0; }();
-            if (tm == 8 && cw == 3 && c8 == 0) {
+        // the gate | up pair on the loader / consumer kernel, 17 .. 128 rows.  Eight row tiles of three stripes would spill: rows 0 .. 63 and 64 .. M - 1 as TWO
+        // launches of the four-tile instance (the second reads the weights out of the Infinity Cache).  profiles/r6z_pair/, r7e_pair_two_launches/
+        if (c_stripes && x_aligned && p.NS == 2 && tm >= 2 && tm <= 8) {
+            if (tm == 8 && cw == 3) {
                 StripeParams lo = p, hi = p;
                 lo.M = 64;
                 hi.M = p.M - 64; hi.x = p.x + 64 * p.ldx; hi.y = p.y + 64 * p.ldy;
                 if (p.bias && p.ldb) hi.bias = p.bias + 64 * p.ldb;
-                int rc = stripe_mmr_pair_dispatch<3>(4, lo, grp_shift, s);
-                if (rc == 0) rc = stripe_mmr_pair_dispatch<3>((hi.M + 15) / 16, hi, grp_shift, s);
-                if (rc != GPTQ_E_VARIANT) return rc;
+                const int rc = stripe_mmr_pair_dispatch<3>(4, lo, grp_shift, s);
+                return rc ? rc : stripe_mmr_pair_dispatch<3>((hi.M + 15) / 16, hi, grp_shift, s);
             }
-            const int rc = (cw == 2 || (tm == 8 && c8 == 2)) ? stripe_mmr_pair_dispatch<2>(tm, p, grp_shift, s) : stripe_mmr_pair_dispatch<3>(tm, p, grp_shift, s);
-            if (rc != GPTQ_E_VARIANT) return rc;
+            return cw == 2 ? stripe_mmr_pair_dispatch<2>(tm, p, grp_shift, s) : stripe_mmr_pair_dispatch<3>(tm, p, grp_shift, s);
         }
     }
-    // round 4: the four-wave instances of the wave-private kernel for 33..64 rows on shapes with 2-3 rounds of stripes, ..96 rows with two (GPTQ_MM3W4=0: off)
-    static const int w4_mode = [] { const char *e = getenv("GPTQ_MM3W4"); return e ? atoi(e) : 1; }();
     if constexpr (SB == 4 || SB == 3) {
-        const int cw = (p.N / 16 + 255) / 256;
-        if (w4_mode != 0 && !ps && forced_slices < 0 && p.NS == 1 && p.K <= 6144 && ((cw == 2 && tm >= 3 && tm <= 6) || (cw == 3 && (tm == 3 || tm == 4)))) {
-            const int rc = cw == 2 ? stripe_mm3w4_dispatch<2>(tm, p, grp_shift, s) : stripe_mm3w4_dispatch<3>(tm, p, grp_shift, s);
-            if (rc != GPTQ_E_VARIANT) return rc;
-        }
+        // four-wave instances of the wave-private kernel (512 registers per wave): 33 .. 64 rows on shapes with two or three rounds of stripes, .. 96 rows with two.
+        // profiles/r4l_w4/, r4n_w4pf/
+        if (c_stripes && p.NS == 1 && ((cw == 2 && tm >= 3 && tm <= 6) || (cw == 3 && (tm == 3 || tm == 4))))
+            return cw == 2 ? stripe_mm3w4_dispatch<2>(tm, p, grp_shift, s) : stripe_mm3w4_dispatch<3>(tm, p, grp_shift, s);
+        // cw adjacent stripes per workgroup on the same staged x, one and two row tiles.  profiles/r4f_mm3c/
+        if (c_stripes && p.NS == 1 && tm <= 2)
+            return cw == 2 ? stripe_mm3c_dispatch<2>(tm, p, grp_shift, s) : stripe_mm3c_dispatch<3>(tm, p, grp_shift, s);
     }
-    // round 4: C adjacent stripes per workgroup on the same staged x for shapes with 2..3 rounds of stripes (N = 8192, 11008, 12288) and short K,
-    // one and two row tiles: GPTQ_MM3C=0 restores the K-slice schedule (A/B runs), GPTQ_MM3C=2 / 3 pins C.
-    static const int mm3c_mode = [] { const char *e = getenv("GPTQ_MM3C"); return e ? atoi(e) : 1; }();
-    if constexpr (SB == 4 || SB == 3) {
-        const int nst = p.N / 16, cw = (nst + 255) / 256;
-        const int c = mm3c_mode >= 2 ? mm3c_mode : cw;
-        if (mm3c_mode != 0 && !ps && forced_slices < 0 && p.NS == 1 && p.K <= 6144 && (c == 2 || c == 3) && tm <= 2) {
-            const int rc = c == 2 ? stripe_mm3c_dispatch<2>(tm, p, grp_shift, s) : stripe_mm3c_dispatch<3>(tm, p, grp_shift, s);
-            if (rc != GPTQ_E_VARIANT) return rc;
-        }
-    }
-    // round 5: the gate | up pair at one row tile on shapes with 2..3 rounds of stripes (N = 11008: 688 stripes -> 230 workgroups of three):
-    // the single-launch pair kernel (stripe_mm1_kernel<1, 2, 4>) re-reads x per stripe and runs 19-21 us at 5..16 rows where four rows cost 11.7
-    // through the decode kernel.  Measured (gpurun_out r5d, us, 2 x 4096 x 11008 at 5 / 8 / 16 rows): 14.1 / 13.8 / 14.7 with one sub-slot of x in flight,
-    // 14.4 / 14.3 / 14.8 with two, 19.4 / 19.4 / 21.4 before.  GPTQ_MM3C_PAIR=0: off; GPTQ_MM3C_PAIR_PF=1|2: x sub-slots in flight.
-    static const int mm3c_pair = [] { const char *e = getenv("GPTQ_MM3C_PAIR"); return e ? atoi(e) : 1; }();
-    static const int mm3c_pair_pf = [] { const char *e = getenv("GPTQ_MM3C_PAIR_PF"); return e ? atoi(e) : 1; }();
     if constexpr (SB == 4) {
-        const int nst = p.N / 16, cw = (nst + 255) / 256;
-        if (mm3c_pair != 0 && !ps && forced_slices < 0 && p.NS == 2 && p.K <= 6144 && (cw == 2 || cw == 3) && tm == 1) {
-            int rc;
-            if (cw == 2) rc = mm3c_pair_pf == 1 ? stripe_mm3c_pair_dispatch<2, 1>(tm, p, grp_shift, s) : stripe_mm3c_pair_dispatch<2, 2>(tm, p, grp_shift, s);
-            else rc = mm3c_pair_pf == 1 ? stripe_mm3c_pair_dispatch<3, 1>(tm, p, grp_shift, s) : stripe_mm3c_pair_dispatch<3, 2>(tm, p, grp_shift, s);
-            if (rc != GPTQ_E_VARIANT) return rc;
-        }
+        // the gate | up pair at one row tile (5 .. 16 rows of a decode batch), cw stripes per workgroup: the single-launch pair kernel re-reads x per stripe.
+        // DESIGN 3.8
+        if (c_stripes && p.NS == 2 && tm == 1)
+            return cw == 2 ? stripe_mm3c_pair_dispatch<2>(tm, p, grp_shift, s) : stripe_mm3c_pair_dispatch<3>(tm, p, grp_shift, s);
     }
-    // round 4: K slices of the 128-row fused tile GEMM (stripe_gemm_sliced_launch) from 65 rows on where one round of stripes does not
-    // cover N or K is long.  Measured (profiles/r4g_sgs/sgs.txt, us, M = 96 / 128, this / before): 4096 x 12288 27 / 27 against 33 / 41,
-    // 4096 x 11008 27 / 27 against 32 / 39, 11008 x 4096 25 / 25 against 31 / 38; below 65 rows the 16-row-tile schedules stay ahead (24 us at
-    // 64 rows).  GPTQ_SGS=0: off; GPTQ_SGS=2: from one row tile on, a forced slice count is passed through (A/B runs).
-    static const int sgs_mode = [] { const char *e = getenv("GPTQ_SGS"); return e ? atoi(e) : 1; }();
     if constexpr (SB != 2) {
-        const bool one_round_short_k = p.N / 16 <= 256 && p.K <= 6144;     // stripe_mm3_kernel's home ground (4096 x 4096: 14.7 us at 128 rows)
-        if (sgs_mode != 0 && !ps && p.NS == 1 && forced_slices != 0 && (sgs_mode == 2 || (tm >= 5 && !one_round_short_k))) {
+        // K slices of the 128-row fused tile GEMM from 65 rows on, where one round of stripes does not cover N or K is long (4096 x 4096 stays with the
+        // wave-private kernel: 14.7 us at 128 rows); a forced slice count >= 1 is passed through.  profiles/r4g_sgs/
+        if (!ps && p.NS == 1 && forced_slices != 0 && tm >= 5 && !one_round_short_k) {
             const int rc = stripe_gemm_sliced_launch<1>(p, grp_shift, ws, ws_bytes, forced_slices, s);
             if (rc != GPTQ_E_VARIANT && rc != GPTQ_E_WORKSPACE) return rc;
         }
     }
-    if (mm3_can && (mm3_mode == 2 || (mm3_mode == 1 && mm3_pays))) {
+    // wave-private staging (stripe_mm3_kernel): it re-reads x once per stripe, so it runs where ONE round of workgroups covers N and K is short, and at
+    // 65 .. 96 rows elsewhere.  8-bit: the instances beyond four row tiles / the pair beyond one would spill.  profiles/r3g_mid_m/mm3_ab.txt
+    const bool mm3_can = !ps && auto_slices && (p.NS == 1 ? tm <= (SB == 8 ? 4 : 8) : tm <= (SB == 8 ? 1 : 2));
+    if (mm3_can && (one_round_short_k || (p.NS == 1 && (tm == 5 || tm == 6) && SB != 8)))
         return p.NS == 2 ? stripe_mm3_dispatch<2>(tm, p, grp_shift, s) : stripe_mm3_dispatch<1>(tm, p, grp_shift, s);
-    }
-    // One launch (a stripe x whole K per workgroup, x streamed through LDS) for up to 32 rows while that is one round of workgroups
-    // over the 256 CUs and K is short; otherwise K slices + the reduce kernel.  Measured (profiles/r2c_mm/slices.txt), us, one launch
-    // vs best slicing, M = 16 / 32 / 48 / 64: 4096^2 5.9 / 8.5 / 12.3 / 12.5 vs 7.9 / 9.5 / 11.1 / 12.4; 4096 x 12288 12.0 / 23.6 / 28 / 36
-    // vs 12.0 / 13.5 / 21.8 / 24.6; 11008 x 4096 12.8 / 17.9 / 30 / 30 vs 11.7 / 13.8 / 16.5 / 22.2.  forced_slices: 0 = one launch, S >= 1.
-    // (the single-launch kernels exist for 4 / 8 bits with groups of at least a row block; everything else slices K)
+    // one launch (a stripe x whole K per workgroup, x streamed through LDS) for up to 32 rows while that is one round of workgroups over the 256 CUs and K
+    // is short, or when the caller asks for it (forced_slices == 0); 4 / 8 bits with groups of at least a row block.  profiles/r2c_mm/slices.txt
     constexpr bool has_single = SB == 4 || SB == 8;
-    const bool single = has_single && !ps && (forced_slices == 0 || (forced_slices < 0 && p.K <= 6144 && ((tm == 1 && p.N / 16 <= 1024) || (tm == 2 && p.N / 16 <= 288))));
+    const bool single = has_single && !ps && (forced_slices == 0 || (auto_slices && p.K <= 6144 && ((tm == 1 && p.N / 16 <= 1024) || (tm == 2 && p.N / 16 <= 288))));
     if constexpr (has_single) {
         if (single) {
             int rc;
             if (p.NS == 2) {
                 switch (tm) {
-                    case 1: {
-                        // the pair instance with two workgroups per CU (PF = 2, 128 VGPRs) spills 208 B per lane
-                        // (profiles/r2d_final/kernel_resources.txt); PF = 4 runs one workgroup per CU without spills.
-                        // GPTQ_MM1_PAIR_PF=2|4 pins either for A/B runs (tools/bench_pair_mm1.py); default: see the measurement there
-                        static const int pair_pf = [] { const char *e = getenv("GPTQ_MM1_PAIR_PF"); return e ? atoi(e) : 4; }();
-                        rc = pair_pf == 2 ? stripe_mm1_launch<1, 2, 2>(p, grp_shift, s) : stripe_mm1_launch<1, 2, 4>(p, grp_shift, s);
-                        break;
-                    }
+                    // (PF = 4, one workgroup per CU: the pair instance with PF = 2 spilled 208 B per lane, profiles/r2d_final/kernel_resources.txt)
+                    case 1: rc = stripe_mm1_launch<1, 2, 4>(p, grp_shift, s); break;
                     case 2: rc = stripe_mm2_launch<2, 2>(p, grp_shift, s); break;
                     case 3: rc = stripe_mm2_launch<3, 2>(p, grp_shift, s); break;
                     default: rc = stripe_mm2_launch<4, 2>(p, grp_shift, s); break;
@@ -1962,6 +1840,7 @@ int STRIPE_CAT(stripe_mm_dispatch_b, STRIPE_BITS)(const StripeParams &p, void *w
             if (rc != GPTQ_E_VARIANT || forced_slices == 0) return rc;   // a table too large for the LDS-DMA stages: K slices instead
         }
     }
+    // everything else: K slices + the reduce kernel (forced_slices >= 1: that many)
     const int fs = forced_slices == 0 ? -1 : forced_slices;
 #define MM_SPLIT(TMV, NSV) (ps ? stripe_mm_launch<TMV, NSV, true>(p, grp_shift, ws, ws_bytes, fs, s) : stripe_mm_launch<TMV, NSV, false>(p, grp_shift, ws, ws_bytes, fs, s))
     if (p.NS == 2) {

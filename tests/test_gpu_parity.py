@@ -1146,8 +1146,8 @@ def test_stripe_mm_fused_mlp(bits, K, N, gs, M):
 def test_stripe_mm_loader_consumer_pair(K, N, gs, M):
     """the gate | up pair at 17 .. 128 rows on shapes with two or three rounds of column stripes: the loader / consumer kernel with the consumers
     split by SET (csrc/stripe_mm.inc stripe_mmr_kernel<.., NS = 2, SS = 1>, round 6) -- three k lanes per set, a chunk of x released when the
-    consumers of both sets are done with it, SiLU(gate) * up on the fp32 sums; 113 .. 128 rows of three-stripe shapes run two stripes per
-    workgroup (the eight-tile instance of three spills).  Against the oracle and the float64 result, bit-reproducible, rows bit-independent
+    consumers of both sets are done with it, SiLU(gate) * up on the fp32 sums; 113 .. 128 rows of three-stripe shapes run as two launches
+    of the four-tile instance, rows 0 .. 63 and 64 .. M - 1 (an eight-tile instance of three stripes would spill).  Against the oracle and the float64 result, bit-reproducible, rows bit-independent
     of their position, x as a strided view with NaN padding, the default dispatch takes the same launch"""
     A, B = make_random_layer(4, gs, K, N, seed=K + M), make_random_layer(4, gs, K, N, seed=K + M + 1)
     rng = np.random.default_rng(M)

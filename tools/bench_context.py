@@ -1,5 +1,5 @@
 """engine tokens/s at depth (round 6): DecodeEngine(batch = B) with ~ctx tokens of history per row, one engine per batch size.
-   python tools/bench_context.py [B ...]      env knobs: GPTQ_ATTN_RECORDS, GPTQ_ATTN_SPLITS, GPTQ_ATTN_TPS_REC, GPTQ_ATTN_TPS, GPTQ_ATTN_NW"""
+   python tools/bench_context.py [B ...]      env knob: GPTQ_ATTN_RECORDS"""
 import json
 import os
 import sys

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""17 .. 128 rows on the LLaMA-7B shapes through the drop-in matmul248 (hipGraph, cold weights) -- run once per GPTQ_MMR setting (the loader /
-consumer small-batch kernel, csrc/stripe_mm.inc stripe_mmr_kernel).   MS=16,32,48,64,128  python tools/bench_mmr.py"""
+"""17 .. 128 rows on the LLaMA-7B shapes through the drop-in matmul248 (hipGraph, cold weights): the routes of the loader /
+consumer small-batch kernel (csrc/stripe_mm.inc stripe_mmr_kernel).   MS=16,32,48,64,128  python tools/bench_mmr.py"""
 import json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, 'gptq-for-llama_amd')); sys.path.insert(0, ROOT)
@@ -11,7 +11,7 @@ dev = 'cuda:0'
 gen = torch.Generator(device=dev); gen.manual_seed(6)
 MS = [int(v) for v in os.environ.get('MS', '16,32,48,64,128').split(',')]
 XPAD = int(os.environ.get('XPAD', '0'))
-out = {'GPTQ_MMR': os.environ.get('GPTQ_MMR', ''), 'XPAD': XPAD}
+out = {'XPAD': XPAD}
 SHAPES = [(HIDDEN, 3 * HIDDEN), (HIDDEN, INTER)] if os.environ.get('SHAPES2') else [(HIDDEN, 3 * HIDDEN), (HIDDEN, INTER), (HIDDEN, HIDDEN), (INTER, HIDDEN)]
 if os.environ.get('SHAPES'):           # SHAPES=4096x8192,8192x8192
     SHAPES = [tuple(int(v) for v in sh.split('x')) for sh in os.environ['SHAPES'].split(',')]

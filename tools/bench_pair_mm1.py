@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
-"""the single-launch gate/up pair kernel for 5..16 rows (stripe_mm1_kernel<1, 2, PF>): PF = 2 (two workgroups per CU, 128 VGPRs, 208 B of
-scratch per lane) against PF = 4 (one workgroup per CU, no spills).  Run once per setting: GPTQ_MM1_PAIR_PF=2|4 python tools/bench_pair_mm1.py
-Round 6: MS=16,32,..,128 times 2 x 4096 x 11008 at those batches (17 .. 128 rows: the loader / consumer pair, GPTQ_MMR_PAIR=0 restores the routes before)."""
+"""the gate/up pair through gptq_stripe_matmul_f16, cold weights, hipGraph timing: 9 and 16 rows on 2 x 4096 x 11008 and 2 x 4096 x 4096 (the one-row-tile
+pair kernels), or MS=16,32,..,128 on 2 x 4096 x 11008 at those batches (17 .. 128 rows: the loader / consumer pair).   python tools/bench_pair_mm1.py"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, 'gptq-for-llama_amd')); sys.path.insert(0, ROOT)
@@ -40,6 +39,6 @@ for K, N in ([(4096, 11008)] if os.environ.get('MS') else [(4096, 11008), (4096,
             for _ in range(5): g.replay()
             e1.record(); torch.cuda.synchronize()
             best = min(best, e0.elapsed_time(e1) * 1e3 / (5 * nsets))
-        print('MMR_PAIR=%s PF=%s gate/up 2x%dx%d M=%-2d: %.2f us' % (os.environ.get('GPTQ_MMR_PAIR', 'default(1)'), os.environ.get('GPTQ_MM1_PAIR_PF', 'default(4)'), K, N, M, best), flush=True)
+        print('gate/up 2x%dx%d M=%-2d: %.2f us' % (K, N, M, best), flush=True)
     del imgs
     torch.cuda.empty_cache()

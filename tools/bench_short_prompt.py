@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """A short prompt through the drop-in model (eager module chain, one forward of [1, T] with a fresh cache): wall time per forward and the GPU time
-of the same forward replayed from a hipGraph (the kernels alone) -- run once per GPTQ_MMR* setting.   TS=32,64,128 python tools/bench_short_prompt.py"""
+of the same forward replayed from a hipGraph (the kernels alone).   TS=32,64,128 python tools/bench_short_prompt.py"""
 import json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, 'gptq-for-llama_amd')); sys.path.insert(0, ROOT)
@@ -10,7 +10,7 @@ from transformers.cache_utils import DynamicCache
 from quant import decode as D
 dev = 'cuda:0'
 model = D.build_random_llama(dev)
-out = {'GPTQ_MMR': os.environ.get('GPTQ_MMR', ''), 'GPTQ_MMR_PAIR': os.environ.get('GPTQ_MMR_PAIR', ''), 'GPTQ_MMR_KS': os.environ.get('GPTQ_MMR_KS', '')}
+out = {}
 for T in [int(v) for v in os.environ.get('TS', '32,64,128').split(',')]:
     ids = torch.randint(0, model.config.vocab_size, (1, T), device=dev)
     def fwd():

@@ -1,5 +1,5 @@
 """tests/test_gpu_model.py::test_tiny_llama_batched_decode_matches_dense_twin at one batch: the drop-in model's logits against the fp16 dense twin (the
-test's figure) AND against the twin run in fp32 (the truth both approximate), for A/B of a kernel route (env knobs, e.g. GPTQ_DECODE_MF8=0).
+test's figure) AND against the twin run in fp32 (the truth both approximate), for A/B of a kernel route (the Python-side switches, e.g. GPTQ_STRIPE=0).
    python tools/debug/twin_noise.py BATCH [SEED ...]"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
