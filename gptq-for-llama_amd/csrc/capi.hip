@@ -998,9 +998,9 @@ int gptq_decode_attn_splits(int batch, int heads, int head_dim, int t_max) {
 }
 
 /* a PROMPT chunk: `rows` consecutive tokens of one sequence at positions start .. start + rows - 1 (csrc/prompt_attn.hip).  start is a host value:
- * prefill is not graph-captured. */
+ * prefill is not graph-captured.  rows may exceed t_max: the packed rows of gptq_prompt_attn_batch_f16 are those of up to 16 sequences. */
 size_t gptq_prompt_attn_workspace_bytes(int rows, int heads, int head_dim, int t_max) {
-    if (rows <= 0 || heads <= 0 || head_dim != 128 || t_max <= 0 || rows > t_max) return 0;
+    if (rows <= 0 || heads <= 0 || head_dim != 128 || t_max <= 0) return 0;
     return prompt_attn_ws_bytes(rows, heads);
 }
 
@@ -1017,6 +1017,33 @@ int gptq_prompt_attn_f16(const void *qkv, int64_t ldq, int rows, int64_t start, 
     if (workspace_bytes < prompt_attn_ws_bytes(rows, heads)) return GPTQ_E_WORKSPACE;
     return prompt_attn_launch((const half_t *)qkv, ldq, rows, start, (half_t *)k_cache, (half_t *)v_cache, (half_t *)out, ldo, (half_t *)workspace, heads,
                               t_max, base, scale, rope_table, (hipStream_t)stream);
+}
+
+/* up to 16 such chunks -- different sequences, lengths and start positions -- of ONE packed qkv / out and one cache allocation, in the same two
+ * launches.  segs is a host array: validated here, then copied into the launch arguments. */
+int gptq_prompt_attn_batch_f16(const void *qkv, int64_t ldq, int total_rows, const gptq_prompt_seg_t *segs, int nseq, void *k_cache, void *v_cache,
+                               int64_t slot_stride, void *out, int64_t ldo, void *workspace, size_t workspace_bytes, int heads, int head_dim, int t_max,
+                               float base, float scale, const float *rope_table, gptq_stream_t stream) {
+    if (!qkv || !segs || !k_cache || !v_cache || !out || !workspace) return GPTQ_E_NULL;
+    if (nseq < 1 || nseq > GPTQ_PROMPT_ATTN_MAX_SEQS || total_rows <= 0 || heads <= 0 || heads > 65535 || head_dim != 128 || t_max <= 0 ||
+        slot_stride < (int64_t)t_max * heads * head_dim || ldq < 3 * (int64_t)heads * head_dim || ldo < (int64_t)heads * head_dim)
+        return GPTQ_E_SHAPE;
+    for (int i = 0; i < nseq; i++) {
+        const gptq_prompt_seg_t &a = segs[i];
+        if (a.rows <= 0 || a.start < 0 || (int64_t)a.start + a.rows > t_max || a.slot < 0 || a.row0 < 0 || (int64_t)a.row0 + a.rows > total_rows)
+            return GPTQ_E_SHAPE;
+        for (int j = 0; j < i; j++) {
+            const gptq_prompt_seg_t &b = segs[j];
+            if (a.slot == b.slot) return GPTQ_E_SHAPE;       // one would read cache rows the other writes in the same launch
+            if ((int64_t)a.row0 < (int64_t)b.row0 + b.rows && (int64_t)b.row0 < (int64_t)a.row0 + a.rows) return GPTQ_E_SHAPE;
+        }
+    }
+    if (!aligned(qkv, 16) || !aligned(k_cache, 16) || !aligned(v_cache, 16) || !aligned(workspace, 16) || (rope_table && !aligned(rope_table, 8)) ||
+        ldq % 8 != 0 || ldo % 8 != 0 || slot_stride % 8 != 0 || !aligned(out, 8))
+        return GPTQ_E_ALIGN;
+    if (workspace_bytes < prompt_attn_ws_bytes(total_rows, heads)) return GPTQ_E_WORKSPACE;
+    return prompt_attn_batch_launch((const half_t *)qkv, ldq, segs, nseq, (half_t *)k_cache, (half_t *)v_cache, slot_stride, (half_t *)out, ldo,
+                                    (half_t *)workspace, heads, base, scale, rope_table, (hipStream_t)stream);
 }
 
 // ---- stripe16: no-split-K decode GEMV on a load-time repacked copy (stripe*.hip) ----

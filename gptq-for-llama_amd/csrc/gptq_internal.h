@@ -259,5 +259,9 @@ int rope_table_launch(float *table, int t_max, int head_dim, float base, hipStre
 size_t prompt_attn_ws_bytes(int rows, int heads);
 int prompt_attn_launch(const half_t *qkv, int64_t ldq, int rows, int64_t start, half_t *kc, half_t *vc, half_t *out, int64_t ldo, half_t *ws,
                        int heads, int t_max, float base, float scale, const float *rope_table, hipStream_t s);
+// the same two launches for a table of nseq <= 16 segments (HOST array, copied into the launch arguments) of one packed qkv / out and one cache
+// allocation (slot s at s * slot_stride elements); ws = prompt_attn_ws_bytes(packed rows, heads)
+int prompt_attn_batch_launch(const half_t *qkv, int64_t ldq, const gptq_prompt_seg_t *segs, int nseq, half_t *kc, half_t *vc, int64_t slot_stride,
+                             half_t *out, int64_t ldo, half_t *ws, int heads, float base, float scale, const float *rope_table, hipStream_t s);
 
 }  // namespace gptq

@@ -2,11 +2,16 @@
 // F.scaled_dot_product_attention does for a prompt between the reference's Triton kernels (quant/fused_attn.py:126-158), with the
 // RoPE (triton_rotate_half_ :126) and the cache append (torch.cat :142-143) of all rows in front of it.
 //
-// `rows` consecutive tokens of one sequence at positions start .. start + rows - 1; two launches:
+// A SEGMENT is `rows` consecutive tokens of one sequence at positions start .. start + rows - 1; a call serves a table of up to 16 of them
+// (gptq_prompt_seg_t: packed rows row0 .. row0 + rows - 1 of one qkv / out matrix, cache slice `slot` of one allocation) in two launches,
+// however many segments there are -- the table travels BY VALUE in the launch arguments (256 bytes: nothing is allocated or copied, the
+// caller's array is free at once), and a workgroup finds its segment with a scan of scalars (blockIdx and the table: wave-uniform).
+// gptq_prompt_attn_f16 is the table of one segment: one kernel body, the same bits.
 //   1. prompt_rope_kv_kernel: the arithmetic of rope_kv_kernel (decode_attn.hip) per (row, head) -- rotated k and v go to cache rows
 //      start + r (bit-identical to a token-by-token feed: same instructions, same flags, see the Makefile), the rotated q to a
 //      workspace copy; qkv itself is never written.
-//   2. prompt_attn_kernel: flash-style attention, grid = (q tile, head), q tiles issued last (longest) first.  A workgroup is four
+//   2. prompt_attn_kernel: flash-style attention, grid = (q tiles of all segments, head); the host sorts the table by start + rows
+//      (longest key range first), within a segment the q tiles are issued last (longest) first.  A workgroup is four
 //      waves x 32 query rows; it walks the keys [0, last position of the tile] in tiles of 64 with an online softmax (log2 domain).
 //      Q fragments live in registers; the K / V tile is requested into registers BEFORE the current tile is computed and written to
 //      LDS behind the barrier that ends it.  Both LDS images are plain 256-byte rows with the chunk swizzle
@@ -30,11 +35,33 @@ constexpr int PA_NW = 4;      // waves per workgroup
 constexpr int PA_QT = 32 * PA_NW;   // query rows per workgroup (32 per wave: one 32x32 MFMA column block)
 constexpr int PA_KT = 64;     // keys per tile
 
-__global__ void __launch_bounds__(64) prompt_rope_kv_kernel(const half_t *__restrict__ qkv, int64_t ldq, int64_t start, half_t *__restrict__ kc,
-                                                            half_t *__restrict__ vc, half_t *__restrict__ qrot, int heads, float inv_base,
-                                                            const float2 *__restrict__ tab) {
-    const int r = blockIdx.x, h = blockIdx.y, c = threadIdx.x, half = PA_HD / 2;
-    const int64_t pos = start + r;
+struct PromptSegTable {      // by value in the launch arguments
+    gptq_prompt_seg_t seg[GPTQ_PROMPT_ATTN_MAX_SEQS];
+    int nseq;
+};
+
+// The segment that unit u of a launch falls into, a segment holding ceil(rows / UNIT) units (UNIT = 1: rows, PA_QT: q tiles); u becomes the
+// unit within the segment.  u < sum of the units (the grid): the last segment needs no test.  Scalars only.
+template <int UNIT>
+GPTQ_DEV int pa_find_seg(const PromptSegTable &t, int &u) {
+    int si = 0;
+    for (; si + 1 < t.nseq; si++) {
+        const int n = (t.seg[si].rows + UNIT - 1) / UNIT;
+        if (u < n) break;
+        u -= n;
+    }
+    return si;
+}
+
+__global__ void __launch_bounds__(64) prompt_rope_kv_kernel(const half_t *__restrict__ qkv, int64_t ldq, const PromptSegTable t,
+                                                            half_t *__restrict__ kc, half_t *__restrict__ vc, int64_t slot_stride,
+                                                            half_t *__restrict__ qrot, int heads, float inv_base, const float2 *__restrict__ tab) {
+    const int h = blockIdx.y, c = threadIdx.x, half = PA_HD / 2;
+    int r = blockIdx.x;                                    // r-th row of all segments -> row r of segment si
+    const gptq_prompt_seg_t sg = t.seg[pa_find_seg<1>(t, r)];
+    const int64_t pos = (int64_t)sg.start + r, row = (int64_t)sg.row0 + r;   // cache row, packed row
+    kc += (int64_t)sg.slot * slot_stride;
+    vc += (int64_t)sg.slot * slot_stride;
     float cs, sn;
     if (tab) {   // {cos, sin} of (pos, c) from the table rope_table_kernel filled with the SAME instructions
         const float2 e = tab[(size_t)pos * half + c];
@@ -46,11 +73,11 @@ __global__ void __launch_bounds__(64) prompt_rope_kv_kernel(const half_t *__rest
         sn = sinf(freq);
     }
     const int hd = heads * PA_HD;
-    const half_t *q = qkv + (size_t)r * ldq + (size_t)h * PA_HD + c;
+    const half_t *q = qkv + (size_t)row * ldq + (size_t)h * PA_HD + c;
     const half_t *k = q + hd;
     const half_t *v = q + 2 * hd;
     const float qx = (float)q[0], qy = (float)q[half];
-    half_t *qd = qrot + (size_t)r * hd + (size_t)h * PA_HD + c;
+    half_t *qd = qrot + (size_t)row * hd + (size_t)h * PA_HD + c;
     qd[0] = (half_t)(qx * cs - qy * sn);
     qd[half] = (half_t)(qx * sn + qy * cs);
     const float kx = (float)k[0], ky = (float)k[half];
@@ -86,37 +113,44 @@ GPTQ_DEV float pa_sum_halves(float v) {
 }
 
 struct PromptAttnArgs {
-    const half_t *q;             // rotated q [rows][heads * 128]
-    const half_t *kc, *vc;       // [t_max][heads * 128]; rows [0, start + rows) are read
+    const half_t *q;             // rotated q [total rows][heads * 128], packed as qkv
+    const half_t *kc, *vc;       // slot s: [t_max][heads * 128] at s * slot_stride; rows [0, start + rows) of a segment's slot are read
     half_t *out;
-    int rows, start, heads;
-    int64_t ldo;
+    int heads;
+    int64_t ldo, slot_stride;
     float scale2;                // softmax scale x log2(e)
+    PromptSegTable t;            // sorted by start + rows, longest first
 };
 
 __global__ void __launch_bounds__(PA_NW * 64) prompt_attn_kernel(const PromptAttnArgs a) {
     __shared__ __attribute__((aligned(16))) half_t ks[PA_KT * PA_HD];
     __shared__ __attribute__((aligned(16))) half_t vs[PA_KT * PA_HD];
-    const int qt = (int)gridDim.x - 1 - (int)blockIdx.x;   // the last q tile has the longest key range: first
+    int bid = blockIdx.x;                                  // bid-th q tile of all segments -> tile bid of segment sg
+    const gptq_prompt_seg_t sg = a.t.seg[pa_find_seg<PA_QT>(a.t, bid)];
+    const int rows = sg.rows, start = sg.start;
+    const int qt = (rows + PA_QT - 1) / PA_QT - 1 - bid;   // the last q tile has the longest key range: first
+    const half_t *const qs = a.q + (int64_t)sg.row0 * (a.heads * PA_HD);
+    const half_t *const kc = a.kc + (int64_t)sg.slot * a.slot_stride, *const vc = a.vc + (int64_t)sg.slot * a.slot_stride;
+    half_t *const out = a.out + (int64_t)sg.row0 * a.ldo;
     const int h = blockIdx.y;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, hi = lane >> 5;
     const int hd = a.heads * PA_HD;
     const int q0 = qt * PA_QT;
-    const int qrow = q0 + wave * 32 + l31;                 // this lane's query row of the chunk (its partner lane ^ 32 has the same)
-    const int qpos = a.start + qrow;
-    const int kv_end = a.start + min(q0 + PA_QT, a.rows);  // keys the workgroup reads: [0, kv_end)
+    const int qrow = q0 + wave * 32 + l31;                 // this lane's query row of the segment (its partner lane ^ 32 has the same)
+    const int qpos = start + qrow;
+    const int kv_end = start + min(q0 + PA_QT, rows);      // keys the workgroup reads: [0, kv_end)
     const int ntiles = (kv_end + PA_KT - 1) / PA_KT;
-    const int wq_min = a.start + q0 + wave * 32, wq_max = wq_min + 31;   // positions of the wave's rows
-    const bool wave_active = q0 + wave * 32 < a.rows;      // (wave-uniform) a wave of padding rows only stages tiles
+    const int wq_min = start + q0 + wave * 32, wq_max = wq_min + 31;   // positions of the wave's rows
+    const bool wave_active = q0 + wave * 32 < rows;        // (wave-uniform) a wave of padding rows only stages tiles
 
     // ---- Q^T fragments (B operand of K Q^T): lane = query, element j of k-step s = dim 16 s + 8 hi + j --------------------------
     half8_t qf[8];
 #pragma unroll
     for (int s = 0; s < 8; s++) {
         qf[s] = half8_t{0, 0, 0, 0, 0, 0, 0, 0};
-        if (qrow < a.rows) qf[s] = *(const half8_t *)(a.q + (size_t)qrow * hd + (size_t)h * PA_HD + 16 * s + 8 * hi);
+        if (qrow < rows) qf[s] = *(const half8_t *)(qs + (size_t)qrow * hd + (size_t)h * PA_HD + 16 * s + 8 * hi);
     }
 
     // ---- staging: 1024 16-byte chunks per image and tile, four per thread (16 lanes = one 256-byte head row) ----------------------
@@ -130,8 +164,8 @@ __global__ void __launch_bounds__(PA_NW * 64) prompt_attn_kernel(const PromptAtt
             vreg[i] = u32x4{0u, 0u, 0u, 0u};
             if (key < kv_end) {
                 const size_t g = (size_t)key * hd + (size_t)h * PA_HD + sch * 8;
-                kreg[i] = *(const u32x4 *)(a.kc + g);
-                vreg[i] = *(const u32x4 *)(a.vc + g);
+                kreg[i] = *(const u32x4 *)(kc + g);
+                vreg[i] = *(const u32x4 *)(vc + g);
             }
         }
     };
@@ -231,9 +265,9 @@ __global__ void __launch_bounds__(PA_NW * 64) prompt_attn_kernel(const PromptAtt
 
     // ---- out[query][32 d + 8 g + 4 hi + (0..3)] = O^T / l: four dims per register quad, one fp16 rounding ----------------------
     l = pa_sum_halves(l);
-    if (qrow < a.rows) {
+    if (qrow < rows) {
         const float inv = 1.0f / l;
-        half_t *o = a.out + (size_t)qrow * a.ldo + (size_t)h * PA_HD + 4 * hi;
+        half_t *o = out + (size_t)qrow * a.ldo + (size_t)h * PA_HD + 4 * hi;
 #pragma unroll
         for (int d = 0; d < 4; d++)
 #pragma unroll
@@ -248,17 +282,33 @@ __global__ void __launch_bounds__(PA_NW * 64) prompt_attn_kernel(const PromptAtt
 
 size_t prompt_attn_ws_bytes(int rows, int heads) { return ((size_t)rows * heads * PA_HD * sizeof(half_t) + 255) & ~(size_t)255; }
 
+int prompt_attn_batch_launch(const half_t *qkv, int64_t ldq, const gptq_prompt_seg_t *segs, int nseq, half_t *kc, half_t *vc, int64_t slot_stride,
+                             half_t *out, int64_t ldo, half_t *ws, int heads, float base, float scale, const float *rope_table, hipStream_t s) {
+    PromptAttnArgs a{};
+    std::copy(segs, segs + nseq, a.t.seg);
+    a.t.nseq = nseq;
+    // long key ranges first (stable: a table already in that order is launched as it came)
+    std::stable_sort(a.t.seg, a.t.seg + nseq,
+                     [](const gptq_prompt_seg_t &x, const gptq_prompt_seg_t &y) { return x.start + x.rows > y.start + y.rows; });
+    int rows = 0, tiles = 0;
+    for (int i = 0; i < nseq; i++) {
+        rows += segs[i].rows;
+        tiles += (segs[i].rows + PA_QT - 1) / PA_QT;
+    }
+    const float inv_base = -2.0f * logf(base) / (float)PA_HD;   // reference fused_attn.py:91
+    hipLaunchKernelGGL(prompt_rope_kv_kernel, dim3(rows, heads), dim3(PA_HD / 2), 0, s, qkv, ldq, a.t, kc, vc, slot_stride, ws, heads, inv_base,
+                       (const float2 *)rope_table);
+    a.q = ws; a.kc = kc; a.vc = vc; a.out = out;
+    a.heads = heads; a.ldo = ldo; a.slot_stride = slot_stride;
+    a.scale2 = scale * 1.44269504088896340736f;
+    hipLaunchKernelGGL(prompt_attn_kernel, dim3(tiles, heads), dim3(PA_NW * 64), 0, s, a);
+    return (int)hipGetLastError();
+}
+
 int prompt_attn_launch(const half_t *qkv, int64_t ldq, int rows, int64_t start, half_t *kc, half_t *vc, half_t *out, int64_t ldo, half_t *ws,
                        int heads, int t_max, float base, float scale, const float *rope_table, hipStream_t s) {
-    const float inv_base = -2.0f * logf(base) / (float)PA_HD;   // reference fused_attn.py:91
-    hipLaunchKernelGGL(prompt_rope_kv_kernel, dim3(rows, heads), dim3(PA_HD / 2), 0, s, qkv, ldq, start, kc, vc, ws, heads, inv_base,
-                       (const float2 *)rope_table);
-    PromptAttnArgs a{};
-    a.q = ws; a.kc = kc; a.vc = vc; a.out = out;
-    a.rows = rows; a.start = (int)start; a.heads = heads; a.ldo = ldo;
-    a.scale2 = scale * 1.44269504088896340736f;
-    hipLaunchKernelGGL(prompt_attn_kernel, dim3((rows + PA_QT - 1) / PA_QT, heads), dim3(PA_NW * 64), 0, s, a);
-    return (int)hipGetLastError();
+    const gptq_prompt_seg_t one{0, rows, (int32_t)start, 0};    // the table of one segment
+    return prompt_attn_batch_launch(qkv, ldq, &one, 1, kc, vc, 0, out, ldo, ws, heads, base, scale, rope_table, s);
 }
 
 }  // namespace gptq

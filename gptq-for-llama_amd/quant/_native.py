@@ -22,6 +22,14 @@ _lock = threading.Lock()
 c_void_p, c_int, c_int64, c_size_t, c_float = (ctypes.c_void_p, ctypes.c_int, ctypes.c_int64,
                                                 ctypes.c_size_t, ctypes.c_float)
 
+PROMPT_ATTN_MAX_SEQS = 16      # GPTQ_PROMPT_ATTN_MAX_SEQS
+
+
+class PromptSeg(ctypes.Structure):
+    """gptq_prompt_seg_t: `rows` tokens of one sequence at positions start .. start + rows - 1, packed rows row0 .. of qkv / out, cache slice `slot`"""
+    _fields_ = [('row0', ctypes.c_int32), ('rows', ctypes.c_int32), ('start', ctypes.c_int32), ('slot', ctypes.c_int32)]
+
+
 # name -> argtypes; mirrors include/gptq_mi355x.h one to one
 _SIGNATURES = {
     'gptq_query': [c_int],
@@ -147,6 +155,9 @@ _SIGNATURES = {
     'gptq_prompt_attn_workspace_bytes': [c_int, c_int, c_int, c_int],
     'gptq_prompt_attn_f16': [c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_size_t, c_int, c_int, c_int,
                              c_float, c_float, c_void_p, c_void_p],
+    # ... of up to 16 segments (a HOST array of PromptSeg) of one packed qkv / out and one cache allocation
+    'gptq_prompt_attn_batch_f16': [c_void_p, c_int64, c_int, ctypes.POINTER(PromptSeg), c_int, c_void_p, c_void_p, c_int64, c_void_p, c_int64,
+                                   c_void_p, c_size_t, c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p],
 }
 
 

@@ -736,6 +736,91 @@ class DecodeEngine:
             self.pos[row:row + 1].fill_(start + T)
         return self.logits[row]
 
+    def prefill_batch(self, prompts, rows=None, starts=None, max_rows=4096):
+        """Feed SEVERAL prompts at once: prompts[i] (1-D int64 ids, any length >= 1, 1 <= len(prompts) <= batch) goes into cache row rows[i]
+        (default 0 .. n - 1; distinct) at positions starts[i] .. starts[i] + T_i - 1 (default 0; a None entry continues at self.pos[row]).
+        Returns self.logits[rows]: the logits after each prompt's last token (the static buffer's rows, as prefill's).  All prompts are packed
+        into one [sum T, hidden] activation and every layer runs ONCE at M = sum T through the launches of prefill -- gptq_rmsnorm_f16, the
+        layer's PreparedLayer, gptq_add_rows_f16 -- with gptq_prompt_attn_batch_f16 (one segment per prompt, two launches) on kcb[li] / vcb[li];
+        the last row of each prompt is gathered and the LM head runs once for those rows.  Above max_rows packed rows the work is done in
+        passes of at most max_rows (the buffers grow to min(sum T, max_rows) rows and are shared with prefill); a prompt that straddles a pass
+        boundary continues in the next pass at its advanced position.  Cache rows and positions of engine rows not named stay as they are.
+        ValueError before anything is launched: an empty prompt, duplicate rows, a row outside the batch, positions beyond t_max.  Not
+        graph-captured; nothing of `transformers` is involved.  Measured against a loop of prefill: profiles/prefill_batch/README.md."""
+        n = len(prompts)
+        if not 1 <= n <= self.batch:
+            raise ValueError('DecodeEngine.prefill_batch: %d prompts for an engine of batch %d' % (n, self.batch))
+        if any((not torch.is_tensor(p)) or p.dim() != 1 or p.numel() == 0 for p in prompts):
+            raise ValueError('DecodeEngine.prefill_batch: every prompt must be a non-empty 1-D tensor of ids')
+        rows = list(range(n)) if rows is None else [int(r) for r in rows]
+        if len(rows) != n or len(set(rows)) != n or any(not 0 <= r < self.batch for r in rows):
+            raise ValueError('DecodeEngine.prefill_batch: rows %r must be %d distinct rows of the batch of %d' % (rows, n, self.batch))
+        starts = [0] * n if starts is None else list(starts)
+        if len(starts) != n:
+            raise ValueError('DecodeEngine.prefill_batch: %d starts for %d prompts' % (len(starts), n))
+        if any(st is None for st in starts):
+            pos = self.pos.tolist()
+            starts = [pos[r] if st is None else st for st, r in zip(starts, rows)]
+        starts = [int(st) for st in starts]
+        lens = [int(p.numel()) for p in prompts]
+        for st, T in zip(starts, lens):
+            if st < 0 or st + T > self.t_max:
+                raise ValueError('DecodeEngine.prefill_batch: positions %d .. %d do not fit the engine cache (%d)' % (st, st + T - 1, self.t_max))
+        max_rows = int(max_rows)
+        if max_rows < 1:
+            raise ValueError('DecodeEngine.prefill_batch: max_rows must be positive')
+        total = sum(lens)
+        offs = [sum(lens[:i]) for i in range(n)]                                    # first packed row of prompt i
+        lib, ptr, H = self.lib, self.native.ptr, self.hidden
+        scale = 1.0 / float(np.sqrt(self.head_dim))
+        with torch.no_grad(), torch.cuda.device(self.dev):
+            s = self.native.stream_ptr(self.dev)
+            pb = self._prefill_buffers(min(total, max_rows))
+            ids = torch.cat([p.to(device=self.dev, dtype=torch.int64) for p in prompts])
+            last = torch.empty((n, H), dtype=torch.float16, device=self.dev)        # the final hidden row of every prompt
+            slot_stride = self.kcb.stride(1)
+            for p0 in range(0, total, max_rows):
+                M = min(total, p0 + max_rows) - p0
+                # the part of every prompt inside packed rows [p0, p0 + M): ONE segment per prompt and pass (never two of the same cache row)
+                segs, ends = [], []
+                for i in range(n):
+                    lo, hi = max(offs[i], p0), min(offs[i] + lens[i], p0 + M)
+                    if lo < hi:
+                        segs.append(self.native.PromptSeg(lo - p0, hi - lo, starts[i] + lo - offs[i], rows[i]))
+                        if hi == offs[i] + lens[i]:
+                            ends.append((i, hi - 1 - p0))
+                table = (self.native.PromptSeg * len(segs))(*segs)
+                x, x2, h, qkv, ab, cb = (pb[k][:M] for k in ('x', 'x2', 'h', 'qkv', 'ab', 'cb'))
+                ws = pb['ws']
+                torch.index_select(self.embed, 0, ids[p0:p0 + M], out=x)
+
+                def add_rows(y, r):
+                    self.native.check(lib.gptq_add_rows_f16(y.data_ptr(), y.stride(0), r.data_ptr(), r.stride(0), M, H, s), 'gptq_add_rows_f16')
+                for li, L in enumerate(self.layers):
+                    self._norm_rows(x, L['ln1'], h, s)
+                    L['qkv']['_keep'].forward(h, qkv)                               # qkv = qkv_proj(rmsnorm(x))
+                    tab = self._rope_table(L['theta'], s)
+                    rc = lib.gptq_prompt_attn_batch_f16(qkv.data_ptr(), qkv.stride(0), M, table, len(segs), self.kcb[li].data_ptr(),
+                                                        self.vcb[li].data_ptr(), slot_stride, ab.data_ptr(), ab.stride(0), ws.data_ptr(), ws.numel(),
+                                                        self.heads, self.head_dim, self.t_max, L['theta'], scale, ptr(tab), s)
+                    self.native.check(rc, 'gptq_prompt_attn_batch_f16')
+                    L['o']['_keep'].forward(ab, x2)
+                    add_rows(x2, x)                                                 # x2 = x + o_proj(attn)
+                    self._norm_rows(x2, L['ln2'], h, s)
+                    L['gate']['_keep'].forward(h, cb)                               # c = silu(gate(h)) * up(h): the pair's PreparedLayer
+                    L['down']['_keep'].forward(cb, x)
+                    add_rows(x, x2)                                                 # x = x2 + down(c)
+                if ends:
+                    dst = torch.tensor([i for i, _ in ends], dtype=torch.int64, device=self.dev)
+                    src = torch.tensor([r for _, r in ends], dtype=torch.int64, device=self.dev)
+                    last.index_copy_(0, dst, x.index_select(0, src))
+            rows_t = torch.tensor(rows, dtype=torch.int64, device=self.dev)
+            logits = torch.empty((n, self.logits.shape[1]), dtype=torch.float16, device=self.dev)
+            lm_head_logits(self, last, logits, s)
+            self.logits.index_copy_(0, rows_t, logits)
+            self.pos.index_copy_(0, rows_t, torch.tensor([st + T for st, T in zip(starts, lens)], dtype=torch.int64, device=self.dev))
+        return self.logits[rows_t]
+
     def decode(self, token):
         """one token per row in ([batch] ids), logits [batch, vocab] out (the static buffer: clone it to keep it)."""
         if torch.is_tensor(token):
@@ -809,6 +894,51 @@ def engine_generate(model, input_ids, max_new_tokens, eos_token_id=None, engine=
             if hit.numel():
                 gen = gen[:int(hit[0]) + 1]
     return torch.cat([input_ids[0], gen.to(input_ids.dtype)]).unsqueeze(0)
+
+
+def engine_generate_batch(model, prompts, max_new_tokens, eos_token_id=None, engine=None, t_max=2048):
+    """Greedy generation for a LIST of prompts of different lengths (1-D id tensors): all prompts enter the engine through ONE
+    DecodeEngine.prefill_batch, and every further step is one replay of the capture_greedy_rows graph for all rows; the host looks at the
+    stream every 16 steps.  Returns a list of 1-D tensors, prompt + generated, each cut after its first eos_token_id.  engine.batch must
+    equal len(prompts) (without an engine, one of that batch is built); max(T) + max_new_tokens <= t_max.  Nothing of `transformers` is
+    involved."""
+    n = len(prompts)
+    if n < 1 or any((not torch.is_tensor(p)) or p.dim() != 1 or p.numel() == 0 for p in prompts):
+        raise ValueError('engine_generate_batch: prompts must be a non-empty list of non-empty 1-D id tensors')
+    max_new_tokens = int(max_new_tokens)
+    if max_new_tokens < 1:
+        raise ValueError('engine_generate_batch: max_new_tokens must be positive')
+    eng = engine if engine is not None else DecodeEngine(model, t_max=t_max, batch=n)
+    if eng.batch != n:
+        raise ValueError('engine_generate_batch: %d prompts for an engine of batch %d' % (n, eng.batch))
+    if max(int(p.numel()) for p in prompts) + max_new_tokens > eng.t_max:
+        raise ValueError('engine_generate_batch: prompt + max_new_tokens exceeds the engine cache (%d)' % eng.t_max)
+    with torch.no_grad():
+        if eng.greedy_rows_graph is None:
+            eng.pos.zero_()                                      # (the capture's warm-up step writes cache row pos of every row)
+            eng.capture_greedy_rows()
+        first = eng.prefill_batch(prompts, starts=[0] * n).argmax(dim=-1)
+        eng.ids.copy_(first)
+        eng.stepc.zero_()                                        # stream_rows[k] = the tokens chosen by replay k
+        done = 1
+        hit = (first == eos_token_id) if eos_token_id is not None else None
+        while done < max_new_tokens and not (hit is not None and bool(hit.all())):
+            burst = min(16, max_new_tokens - done)               # the host looks at the stream every 16 steps only
+            for _ in range(burst):
+                eng.greedy_rows_graph.replay()
+            if hit is not None:
+                hit = hit | (eng.stream_rows[done - 1:done - 1 + burst] == eos_token_id).any(dim=0)
+            done += burst
+        gen = torch.cat([first.unsqueeze(0), eng.stream_rows[:done - 1]]).t()      # [row][step]
+        out = []
+        for i, p in enumerate(prompts):
+            g = gen[i]
+            if eos_token_id is not None:
+                at = (g == eos_token_id).nonzero()
+                if at.numel():
+                    g = g[:int(at[0]) + 1]
+            out.append(torch.cat([p, g.to(device=p.device, dtype=p.dtype)]))
+    return out
 
 
 def benchmark_decode_engine(model, tokens=64, t_max=2048, seed=0, graph=True, fuse_norm=True, fuse_attn=True, start_pos=0, batch=1):

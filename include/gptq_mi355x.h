@@ -564,6 +564,25 @@ int gptq_prompt_attn_f16(const void *qkv, int64_t ldq, int rows, int64_t start, 
                          void *workspace, size_t workspace_bytes, int heads, int head_dim, int t_max, float base, float scale,
                          const float *rope_table, gptq_stream_t stream);
 
+/* The same for up to 16 SEGMENTS at once -- chunks of different sequences, of any lengths and start positions -- that share one packed qkv / out
+ * matrix and one cache allocation: what a batch of prompts needs to enter the decode engine in one pass over the weights.  Segment i is `rows`
+ * consecutive tokens of one sequence at positions start .. start + rows - 1; its projection rows are qkv + (row0 + r) ldq, its output rows
+ * out + (row0 + r) ldo, its cache slices k_cache / v_cache + slot * slot_stride ([t_max][heads 128] each, slot_stride in elements: the engine's
+ * [batch][t_max][heads 128] cache with slot_stride = t_max heads 128).  Per segment the contract -- and every bit of the output rows and the cache
+ * rows -- is that of the single-sequence entry on that segment alone: one kernel body serves both, in TWO launches however many segments there
+ * are.  The order of the table does not matter (the library issues long key ranges first).  Rows of qkv / out that no segment covers are neither
+ * read nor written, nor are cache slices that no segment names.  `segs` is a HOST array: it is validated, then passed to the kernels by value in
+ * the launch arguments (256 bytes) -- the library allocates nothing, copies nothing, never synchronises, and the caller may reuse the array at
+ * once.  total_rows = rows of qkv / out; the workspace is that of the single-sequence entry for total_rows, which may exceed t_max.
+ * GPTQ_E_SHAPE: nseq outside 1 .. 16, a segment with rows <= 0, start < 0, start + rows > t_max, slot < 0 or rows outside [0, total_rows); two
+ * segments whose row ranges overlap; two segments with the same slot (one would read cache rows the other writes in the same launch: feed a
+ * sequence's chunks in consecutive calls); slot_stride < t_max heads 128; ldq / ldo below the row width. */
+#define GPTQ_PROMPT_ATTN_MAX_SEQS 16
+typedef struct { int32_t row0, rows, start, slot; } gptq_prompt_seg_t;
+int gptq_prompt_attn_batch_f16(const void *qkv, int64_t ldq, int total_rows, const gptq_prompt_seg_t *segs, int nseq, void *k_cache,
+                               void *v_cache, int64_t slot_stride, void *out, int64_t ldo, void *workspace, size_t workspace_bytes, int heads,
+                               int head_dim, int t_max, float base, float scale, const float *rope_table, gptq_stream_t stream);
+
 /* ---- GPTQ solver (the caller that PRODUCES the weights; reference gptq.py:128-228) -------------------------------
  * One column block [i1, i1 + count), count <= 128, of the sequential quantise / error-feedback loop (gptq.py:177-199)
  * for all rows at once, in the reference's own fp32 arithmetic (IEEE division, round-half-even, no contraction).
