@@ -1046,6 +1046,26 @@ int gptq_prompt_attn_batch_f16(const void *qkv, int64_t ldq, int total_rows, con
                                     (half_t *)workspace, heads, base, scale, rope_table, (hipStream_t)stream);
 }
 
+/* scoring (csrc/gemm8.hip, cross-entropy epilogue): everything is checked here, before the first launch */
+size_t gptq_lm_head_nll_workspace_bytes(int M, int N) {
+    if (M <= 0 || N <= 0) return 0;
+    return lm_head_nll_ws_bytes(M, N);
+}
+
+int gptq_lm_head_nll_f16(const void *x, int64_t ldx, const void *weight, int64_t ldw, const void *bias, const int64_t *targets, float *nll, float *lse,
+                         int32_t *argmax, int M, int N, int K, void *workspace, size_t workspace_bytes, gptq_stream_t stream) {
+    if (!x || !weight || !targets || !nll || !workspace) return GPTQ_E_NULL;
+    if (M < 0 || N <= 0 || K <= 0 || ldx < K || ldw < K) return GPTQ_E_SHAPE;
+    if (!aligned(x, 16) || !aligned(weight, 16) || ldx % 8 != 0 || ldw % 8 != 0 || (bias && !aligned(bias, 8)) || !aligned(targets, 8) ||
+        !aligned(nll, 4) || (lse && !aligned(lse, 4)) || (argmax && !aligned(argmax, 4)) || !aligned(workspace, 16))
+        return GPTQ_E_ALIGN;
+    if (workspace_bytes < gptq_lm_head_nll_workspace_bytes(M, N)) return GPTQ_E_WORKSPACE;
+    if (K % 128 != 0) return GPTQ_E_VARIANT;
+    if (M == 0) return GPTQ_OK;
+    return lm_head_nll_launch((const half_t *)x, ldx, (const half_t *)weight, ldw, (const half_t *)bias, targets, nll, lse, argmax, M, N, K, workspace,
+                              (hipStream_t)stream);
+}
+
 // ---- stripe16: no-split-K decode GEMV on a load-time repacked copy (stripe*.hip) ----
 size_t gptq_stripe_bytes(int K, int N, int bits, int groupsize, int nsets) { return stripe_total_bytes(K, N, bits, groupsize, nsets); }
 

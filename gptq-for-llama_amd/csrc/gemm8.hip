@@ -68,6 +68,87 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define G8_VMCNT8() asm volatile("s_waitcnt vmcnt(8)" ::: "memory")
 #define G8_LGKM0() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
 
+// ---- the cross-entropy epilogue (gptq_lm_head_nll_f16): the logits of a tile leave the workgroup as ONE record per row, never as logits.
+// A record is what a softmax needs of a set of columns: {max z, sum exp(z - max), lowest index of a maximal z, z of the target column or ABSENT};
+// two records of disjoint column sets merge into the record of their union, and the merge is symmetric.
+struct Gemm8NllParams : Gemm8Params {   // c / ldc unused
+    const int64_t *targets;   // [M]
+    f32x4 *rec;               // [M][ntn] records {max, sumexp, arg (int bits), z_target}
+};
+struct NllRec {
+    float m, s;
+    int a;
+    float zt;
+};
+constexpr uint32_t NLL_ABSENT = 0xffffffffu;   // no fp16 value converts to these bits
+
+GPTQ_DEV void nll_merge(NllRec &x, const NllRec &y) {
+    const float m = fmaxf(x.m, y.m);
+    const float ms = m == -INFINITY ? 0.f : m;   // two empty sets: exp(-inf - 0) = 0, never inf - inf
+    x.s = x.s * __expf(x.m - ms) + y.s * __expf(y.m - ms);
+    x.a = (y.m > x.m || (y.m == x.m && y.a < x.a)) ? y.a : x.a;
+    x.m = m;
+    x.zt = __float_as_uint(x.zt) != NLL_ABSENT ? x.zt : y.zt;
+}
+
+// After the K loop (16x16x32, plain mode) lane l holds, per m rep i, 16 logits of row mloc + 16 i: columns n0 + 64 wc + 16 j + 4 (l / 16) + r.
+//  1. z = fp16(acc) (+ bias, rounded again): the bits gemm8_kernel would have stored; columns >= N count as -inf ONE BY ONE;
+//  2. the lane's record, then the record of the wave's 64 columns by a butterfly over the four 16-lane groups (lane ^ 16, lane ^ 32);
+//  3. the four wave columns meet in LDS (free once every wave's DMA has landed and its last fragment is read: vmcnt(0) + barrier);
+//  4. thread t < TM merges row t's four records in wave-column order and stores the tile's record with one 16-byte store.
+template <int AM, int AN, int XU, int TM>
+GPTQ_DEV void nll_epilogue(const Gemm8NllParams &p, const f32x4 (&acc)[AM][AN], char *smem, int tid, int lane, int wc, int m0, int mloc, int n0, int n4,
+                           int tn) {
+    static_assert(AN == 4, "16x16x32 plain mode: four n reps of 16 columns");
+    const int M = p.M, N = p.N;
+    __syncthreads();   // every wave is past its vmcnt(0) and its last LDS read
+    f32x4 *lrec = (f32x4 *)smem;   // [TM][4 wave columns]
+    const int nb = n0 + wc * 64 + n4;
+#pragma unroll
+    for (int i = 0; i < AM; i++) {
+        const int ml = mloc + i * 16;
+        const int64_t tgt = p.targets[min(m0 + ml, M - 1)];
+        NllRec a = {-INFINITY, 0.f, 0x7fffffff, __uint_as_float(NLL_ABSENT)};
+        float z[16];
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const int n = nb + j * 16 + r;
+                half_t h = (half_t)acc[i][j][r];
+                if (p.bias) h = (half_t)((float)h + (float)p.bias[min(n, N - 1)]);   // fp16(fp16(acc) + bias), as gemm8_kernel
+                const float v = n < N ? (float)h : -INFINITY;
+                z[j * 4 + r] = v;
+                if ((int64_t)n == tgt) a.zt = v;
+                if (v > a.m) { a.m = v; a.a = n; }   // ascending n, strict: the lowest index of a maximal z
+            }
+        const float ms = a.m == -INFINITY ? 0.f : a.m;
+#pragma unroll
+        for (int c = 0; c < 16; c++) a.s += __expf(z[c] - ms);
+#pragma unroll
+        for (int d = 16; d < 64; d <<= 1) {
+            NllRec b;
+            b.m = __shfl_xor(a.m, d);
+            b.s = __shfl_xor(a.s, d);
+            b.a = __shfl_xor(a.a, d);
+            b.zt = __shfl_xor(a.zt, d);
+            nll_merge(a, b);
+        }
+        if (lane < 16) lrec[ml * 4 + wc] = f32x4{a.m, a.s, __uint_as_float((uint32_t)a.a), a.zt};
+    }
+    __syncthreads();
+    if (tid < TM && m0 + tid < M) {
+        const f32x4 v0 = lrec[tid * 4];
+        NllRec a = {v0[0], v0[1], (int)__float_as_uint(v0[2]), v0[3]};
+#pragma unroll
+        for (int w = 1; w < 4; w++) {
+            const f32x4 v = lrec[tid * 4 + w];
+            nll_merge(a, NllRec{v[0], v[1], (int)__float_as_uint(v[2]), v[3]});
+        }
+        p.rec[(size_t)(m0 + tid) * p.ntn + tn] = f32x4{a.m, a.s, __uint_as_float((uint32_t)a.a), a.zt};
+    }
+}
+
 // MF32: v_mfma_f32_32x32x16_f16 instead of 16x16x32 (8 instead of 16 MFMAs per phase at the same LDS traffic; the larger shape reaches
 // the full 1024 flop / cycle / SIMD, the smaller one ~85-94 % of it) -- same units, phases and waits, other fragment maps.
 //
@@ -78,9 +159,14 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // and vmcnt bookkeeping: an X unit is 96 rows instead of 128, so the DMA instructions of waves 6 and 7 repeat those of waves 0 and 1 (same
 // bytes to the same LDS address -- benign, and every wave keeps the same number of loads in flight).  The K order of every accumulator is
 // unchanged: results are bit-identical to the 256-row tile.
-template <bool PAIR, bool MF32, int XH>
-__global__ void __launch_bounds__(512) gemm8_kernel(const Gemm8Params p) {
+//
+// NLL (the LM head of DecodeEngine.score, reference llama.py:241-258): the same schedule with a cross-entropy epilogue instead of the stores -- see
+// nll_epilogue above.  The mode is a template parameter with its own parameter block; its branch is an `if constexpr`, so the six instances with
+// NLL = false compile to the instructions they had before the mode existed (only their mangled names gained the parameter).
+template <bool PAIR, bool MF32, int XH, bool NLL = false>
+__global__ void __launch_bounds__(512) gemm8_kernel(const typename std::conditional<NLL, Gemm8NllParams, Gemm8Params>::type p) {
     static_assert(XH == 64 || (XH == 48 && !MF32), "X unit half: 64 rows, or 48 (16-row fragments only)");
+    static_assert(!NLL || (!PAIR && !MF32), "the cross-entropy epilogue is written for the plain 16x16x32 instance");
     constexpr int TM = 4 * XH, XU = 2 * XH;   // rows of the workgroup tile; rows of an X unit (both wave rows)
     extern __shared__ __attribute__((aligned(16))) char smem[];   // ALL of the kernel's LDS (one object: see the guide's .s traps)
     const int tid = threadIdx.x, lane = tid & 63;
@@ -245,6 +331,10 @@ __global__ void __launch_bounds__(512) gemm8_kernel(const Gemm8Params p) {
     constexpr int NG = MF32 ? 4 : 1;                  // groups of four consecutive n per accumulator tile
     const int mloc = wr * XU + frow;
     const int n4 = MF32 ? (lane >> 5) * 4 : (lane >> 4) * 4;
+    if constexpr (NLL) {
+        nll_epilogue<AM, AN, XU, TM>(p, acc, smem, tid, lane, wc, m0, mloc, n0, n4, tn);
+        return;
+    }
     auto acc4 = [&](const acc_t &a, int rg, int r) -> float {
         if constexpr (MF32) return a[4 * rg + r];
         else return a[r];
@@ -287,6 +377,40 @@ __global__ void __launch_bounds__(512) gemm8_kernel(const Gemm8Params p) {
             }
         }
     }
+}
+
+// One wave per row: the row's ntn records merged -- lane l folds records l, l + 64, ... in that order, then a butterfly over the lanes (nll_merge is
+// symmetric in its operands, so every lane ends with the same bits) -- and turned into lse = max + log(sum), nll = lse - z_target, argmax.
+__global__ void __launch_bounds__(256) lm_head_nll_merge_kernel(const f32x4 *rec, const int64_t *targets, float *nll, float *lse, int32_t *argmax,
+                                                                int M, int N, int ntn) {
+    const int lane = threadIdx.x & 63;
+    const int m = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (m >= M) return;
+    const f32x4 *row = rec + (size_t)m * ntn;
+    NllRec a = {-INFINITY, 0.f, 0x7fffffff, __uint_as_float(NLL_ABSENT)};
+    for (int t = lane; t < ntn; t += 64) {
+        const f32x4 v = row[t];
+        nll_merge(a, NllRec{v[0], v[1], (int)__float_as_uint(v[2]), v[3]});
+    }
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        NllRec b;
+        b.m = __shfl_xor(a.m, d);
+        b.s = __shfl_xor(a.s, d);
+        b.a = __shfl_xor(a.a, d);
+        b.zt = __shfl_xor(a.zt, d);
+        nll_merge(a, b);
+    }
+    if (lane != 0) return;
+    const float l = a.m + (float)log((double)a.s);   // one per row: the accurate log costs nothing here
+    const int64_t tgt = targets[m];
+    float v;
+    if (tgt < 0) v = 0.f;
+    else if (tgt >= N || __float_as_uint(a.zt) == NLL_ABSENT) v = __uint_as_float(0x7fc00000u);
+    else v = l - a.zt;
+    nll[m] = v;
+    if (lse) lse[m] = l;
+    if (argmax) argmax[m] = min(a.a, N - 1);
 }
 
 template <bool PAIR, bool MF32, int XH>
@@ -338,6 +462,32 @@ int gemm8_dense_f16(const half_t *x, int64_t ldx, const half_t *wt, int64_t ldw,
     if (mf32) return pair ? gemm8_launch<true, true, 64>(p, s) : gemm8_launch<false, true, 64>(p, s);
     if (rows == 192) return pair ? gemm8_launch<true, false, 48>(p, s) : gemm8_launch<false, false, 48>(p, s);
     return pair ? gemm8_launch<true, false, 64>(p, s) : gemm8_launch<false, false, 64>(p, s);
+}
+
+// nll[m] = logsumexp_n z[m, n] - z[m, targets[m]] with z = fp16(x . wt^T) (+ bias): the tile GEMM above with the cross-entropy epilogue (one record per
+// row and n-tile into ws), then the merge launch.  The arguments were validated by the caller (capi.hip); K % 128 == 0.  Always the 256-row tile: the
+// K order of an accumulator, and with it every bit of a row's result, does not depend on the tile or on the row's place in it.
+size_t lm_head_nll_ws_bytes(int M, int N) { return (size_t)max(M, 0) * (size_t)((max(N, 1) + 255) / 256) * sizeof(f32x4); }
+
+int lm_head_nll_launch(const half_t *x, int64_t ldx, const half_t *wt, int64_t ldw, const half_t *bias, const int64_t *targets, float *nll, float *lse,
+                       int32_t *argmax, int M, int N, int K, void *ws, hipStream_t s) {
+    Gemm8NllParams p;
+    p.x = x; p.wt = wt; p.bias = bias; p.c = nullptr;
+    p.ldx = ldx; p.ldw = ldw; p.ldc = 0;
+    p.M = M; p.K = K; p.N = N;
+    p.ntn = (N + 255) / 256;
+    p.ntm = (M + 255) / 256;
+    p.per = (p.ntm * p.ntn + 7) / 8;
+    p.targets = targets;
+    p.rec = (f32x4 *)ws;
+    auto kern = gemm8_kernel<false, false, 64, true>;
+    constexpr int lds = 2 * BUF_BYTES;
+    static LdsOptIn opt_in;
+    if (int rc = opt_in.ensure((const void *)kern, lds)) return rc;
+    hipLaunchKernelGGL(kern, dim3(8 * p.per), dim3(512), lds, s, p);
+    if (int rc = (int)hipGetLastError()) return rc;
+    hipLaunchKernelGGL(lm_head_nll_merge_kernel, dim3((M + 3) / 4), dim3(256), 0, s, (const f32x4 *)ws, targets, nll, lse, argmax, M, N, p.ntn);
+    return (int)hipGetLastError();
 }
 
 int gemm8_set_mfma(int shape) { return (shape == 16 || shape == 32) ? g_gemm8_mfma.exchange(shape) : GPTQ_E_VARIANT; }

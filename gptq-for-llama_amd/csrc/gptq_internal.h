@@ -176,6 +176,11 @@ int gemm8_set_tile(int rows);   // 0 (per launch), 192, 256; returns the previou
 int gemm8_set_mfma(int shape);   // 16 (16x16x32) or 32 (32x32x16); returns the previous value
 int gemm8_dense_f16(const half_t *x, int64_t ldx, const half_t *wt, int64_t ldw, const half_t *bias, half_t *c, int64_t ldc, int M, int K, int N,
                     bool pair, hipStream_t s);
+// gemm8.hip: the LM head for many rows that never writes the logits: nll[m] = logsumexp(z[m, :]) - z[m, targets[m]], z = fp16(x . wt^T) (+ bias);
+// ws = lm_head_nll_ws_bytes(M, N) bytes of records; arguments validated by the caller, K % 128 == 0
+size_t lm_head_nll_ws_bytes(int M, int N);
+int lm_head_nll_launch(const half_t *x, int64_t ldx, const half_t *wt, int64_t ldw, const half_t *bias, const int64_t *targets, float *nll, float *lse,
+                       int32_t *argmax, int M, int N, int K, void *ws, hipStream_t s);
 // dense_gemm.hip: y = x . W (+ bias) through hipBLASLt (dlopen'ed), plans cached per shape
 bool dense_gemm_available();
 int dense_gemm_plan_count();   // plans currently cached (bounded LRU)

@@ -7,6 +7,7 @@ performs (llama_inference.py:27-72): ``make_quant_linear`` on every decoder line
 fp16, :46-48), then ``make_quant_attn``, ``make_quant_norm``, ``make_fused_mlp``.  The packed
 buffers are filled with the synthetic distribution of SURVEY 8(d) directly on the GPU.
 """
+import math
 import time
 
 import numpy as np
@@ -821,6 +822,151 @@ class DecodeEngine:
             self.pos.index_copy_(0, rows_t, torch.tensor([st + T for st, T in zip(starts, lens)], dtype=torch.int64, device=self.dev))
         return self.logits[rows_t]
 
+    # -- scoring: how likely was the prompt?  The launches of prefill / prefill_batch, then the LM head of EVERY row with the cross-entropy inside ---
+    def _nll_rows(self, h, targets, nll, s):
+        """nll[m] = -log softmax(lm_head(h[m]))[targets[m]] for the already normalised rows h; a negative target gives 0.  gptq_lm_head_nll_f16
+        (csrc/gemm8.hip: the tile GEMM with a cross-entropy epilogue -- the [M, vocab] logits never exist); a head the kernel declines (rc -6:
+        hidden % 128 != 0; non-fp16, non-unit stride, misaligned) goes through torch.matmul + log_softmax in row chunks whose temporaries
+        (fp16 logits + their fp32 log-softmax) stay under 64 MiB."""
+        W, bias = self.lm_head, self.lm_head_bias
+        M, N = h.shape[0], W.shape[0]
+        ok = (W.dtype == torch.float16 and W.dim() == 2 and W.stride(1) == 1 and W.stride(0) % 8 == 0 and W.shape[1] == h.shape[1] and
+              W.data_ptr() % 16 == 0 and (bias is None or (bias.dtype == torch.float16 and bias.is_contiguous() and bias.data_ptr() % 8 == 0)))
+        if ok:
+            need = self.lib.gptq_lm_head_nll_workspace_bytes(M, N)
+            ws = self.__dict__.get('_nll_ws')
+            if ws is None or ws.numel() < need:
+                ws = self._nll_ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.dev)
+            rc = self.lib.gptq_lm_head_nll_f16(h.data_ptr(), h.stride(0), W.data_ptr(), W.stride(0), self.native.ptr(bias), targets.data_ptr(),
+                                               nll.data_ptr(), None, None, M, N, W.shape[1], ws.data_ptr(), ws.numel(), s)
+            if rc != -6:
+                self.native.check(rc, 'gptq_lm_head_nll_f16')
+                return
+        chunk = max(1, (64 << 20) // (6 * N))
+        for r0 in range(0, M, chunk):
+            hc, tc = h[r0:r0 + chunk].to(W.dtype), targets[r0:r0 + chunk]
+            z = torch.matmul(hc, W.t()) if bias is None else torch.addmm(bias, hc, W.t())
+            picked = torch.log_softmax(z.float(), dim=-1).gather(1, tc.clamp(min=0)[:, None])[:, 0]
+            nll[r0:r0 + chunk] = torch.where(tc < 0, torch.zeros_like(picked), -picked)
+
+    def _score_packed(self, what, prompts, rows, starts, max_rows):
+        """The packed layer loop of prefill_batch with the LM head of every row behind it: prompts[i] enters cache row rows[i] at starts[i] ..,
+        in passes of at most max_rows packed rows.  Returns (nll [sum T] float32 -- row t of a prompt holds -log p(its token t + 1 | tokens <= t),
+        the last row of every prompt 0 --, last [n, hidden]: the final hidden row of every prompt, for the caller's LM-head launch).  The
+        targets are the packed ids shifted by one, so the last row of a pass is scored against the first token of the next.  Validates
+        everything (ValueError) before the first launch; does not touch self.pos / self.logits."""
+        n = len(prompts)
+        rows = [int(r) for r in rows]
+        if len(rows) != n or len(set(rows)) != n or any(not 0 <= r < self.batch for r in rows):
+            raise ValueError('DecodeEngine.%s: rows %r must be %d distinct rows of the batch of %d' % (what, rows, n, self.batch))
+        max_rows = int(max_rows)
+        if max_rows < 1:
+            raise ValueError('DecodeEngine.%s: max_rows must be positive' % what)
+        if any(st is None for st in starts):
+            pos = self.pos.tolist()
+            starts = [pos[r] if st is None else st for st, r in zip(starts, rows)]
+        starts = [int(st) for st in starts]
+        lens = [int(p.numel()) for p in prompts]
+        for st, T in zip(starts, lens):
+            if st < 0 or st + T > self.t_max:
+                raise ValueError('DecodeEngine.%s: positions %d .. %d do not fit the engine cache (%d)' % (what, st, st + T - 1, self.t_max))
+        vocab = min(self.embed.shape[0], self.lm_head.shape[0])
+        host = torch.cat([p.detach().reshape(-1).to(device='cpu', dtype=torch.int64) for p in prompts])      # a copy, not a launch
+        if int(host.min()) < 0 or int(host.max()) >= vocab:
+            raise ValueError('DecodeEngine.%s: token ids must lie in [0, %d)' % (what, vocab))
+        total = sum(lens)
+        offs = [sum(lens[:i]) for i in range(n)]                                    # first packed row of prompt i
+        shifted = torch.full((total,), -100, dtype=torch.int64)                     # target of packed row r: the next id of the SAME prompt
+        for o, T in zip(offs, lens):
+            shifted[o:o + T - 1] = host[o + 1:o + T]
+        lib, ptr, H = self.lib, self.native.ptr, self.hidden
+        scale = 1.0 / float(np.sqrt(self.head_dim))
+        with torch.no_grad(), torch.cuda.device(self.dev):
+            s = self.native.stream_ptr(self.dev)
+            pb = self._prefill_buffers(min(total, max_rows))
+            ids = host.to(self.dev)
+            targets = shifted.to(self.dev)
+            nll = torch.empty(total, dtype=torch.float32, device=self.dev)
+            last = torch.empty((n, H), dtype=torch.float16, device=self.dev)
+            slot_stride = self.kcb.stride(1)
+            for p0 in range(0, total, max_rows):
+                M = min(total, p0 + max_rows) - p0
+                segs, ends = [], []
+                for i in range(n):                                                  # ONE segment per prompt and pass, as prefill_batch
+                    lo, hi = max(offs[i], p0), min(offs[i] + lens[i], p0 + M)
+                    if lo < hi:
+                        segs.append(self.native.PromptSeg(lo - p0, hi - lo, starts[i] + lo - offs[i], rows[i]))
+                        if hi == offs[i] + lens[i]:
+                            ends.append((i, hi - 1 - p0))
+                table = (self.native.PromptSeg * len(segs))(*segs)
+                x, x2, h, qkv, ab, cb = (pb[k][:M] for k in ('x', 'x2', 'h', 'qkv', 'ab', 'cb'))
+                ws = pb['ws']
+                torch.index_select(self.embed, 0, ids[p0:p0 + M], out=x)
+
+                def add_rows(y, r):
+                    self.native.check(lib.gptq_add_rows_f16(y.data_ptr(), y.stride(0), r.data_ptr(), r.stride(0), M, H, s), 'gptq_add_rows_f16')
+                for li, L in enumerate(self.layers):
+                    self._norm_rows(x, L['ln1'], h, s)
+                    L['qkv']['_keep'].forward(h, qkv)
+                    tab = self._rope_table(L['theta'], s)
+                    rc = lib.gptq_prompt_attn_batch_f16(qkv.data_ptr(), qkv.stride(0), M, table, len(segs), self.kcb[li].data_ptr(),
+                                                        self.vcb[li].data_ptr(), slot_stride, ab.data_ptr(), ab.stride(0), ws.data_ptr(), ws.numel(),
+                                                        self.heads, self.head_dim, self.t_max, L['theta'], scale, ptr(tab), s)
+                    self.native.check(rc, 'gptq_prompt_attn_batch_f16')
+                    L['o']['_keep'].forward(ab, x2)
+                    add_rows(x2, x)
+                    self._norm_rows(x2, L['ln2'], h, s)
+                    L['gate']['_keep'].forward(h, cb)
+                    L['down']['_keep'].forward(cb, x)
+                    add_rows(x, x2)
+                if ends:
+                    dst = torch.tensor([i for i, _ in ends], dtype=torch.int64, device=self.dev)
+                    src = torch.tensor([r for _, r in ends], dtype=torch.int64, device=self.dev)
+                    last.index_copy_(0, dst, x.index_select(0, src))
+                self._norm_rows(x, self.final_norm, h, s)                           # all rows: the model's final norm in front of the head
+                self._nll_rows(h, targets[p0:p0 + M], nll[p0:p0 + M], s)
+        return nll, last, starts, lens, offs
+
+    def score(self, input_ids, row=0, start=0, max_rows=4096):
+        """nll [T - 1] (float32, on the device): nll[t] = -log p(input_ids[t + 1] | input_ids[: t + 1]) -- what the reference's evaluation sums
+        (llama.py:241-258: lm_head over all rows, shifted labels, CrossEntropyLoss), as the fp32 cross-entropy of the fp16 logits.  Runs the
+        launches of prefill on cache row `row` from position `start` (None: continue at self.pos[row]), then the final norm and
+        gptq_lm_head_nll_f16 over all rows; sequences longer than max_rows go in passes.  Afterwards the engine is in exactly the state
+        prefill(input_ids, row, start) leaves -- cache rows, pos[row], logits[row] after the last token -- so a caller can score a prompt and go
+        on generating.  T == 1 returns an empty tensor.  ValueError before anything is launched: an id outside [0, vocab), and every case
+        prefill refuses."""
+        ids = input_ids.reshape(-1) if (torch.is_tensor(input_ids) and (input_ids.dim() == 1 or (input_ids.dim() == 2 and input_ids.shape[0] == 1))) else None
+        if ids is None or ids.numel() == 0:
+            raise ValueError('DecodeEngine.score: input_ids must be a non-empty 1-D or [1, T] tensor')
+        if not 0 <= int(row) < self.batch:
+            raise ValueError('DecodeEngine.score: row %d outside the batch of %d' % (int(row), self.batch))
+        nll, last, starts, lens, _ = self._score_packed('score', [ids], [row], [start], max_rows)
+        with torch.no_grad(), torch.cuda.device(self.dev):
+            row = int(row)
+            lm_head_logits(self, last, self.logits[row:row + 1], self.native.stream_ptr(self.dev))          # the launch prefill ends with
+            self.pos[row:row + 1].fill_(starts[0] + lens[0])
+        return nll[:lens[0] - 1]
+
+    def score_batch(self, prompts, rows=None, max_rows=4096):
+        """score for SEVERAL prompts at once, with the packing of prefill_batch: one activation, one segment per prompt, every prompt from
+        position 0 of its cache row (rows[i], default 0 .. n - 1), ONE gptq_lm_head_nll_f16 call per pass over all packed rows.  Returns a list
+        of [T_i - 1] float32 tensors (views of one buffer) and leaves the state prefill_batch(prompts, rows) leaves.  ValueError as
+        prefill_batch, and for an id outside [0, vocab)."""
+        n = len(prompts)
+        if not 1 <= n <= self.batch:
+            raise ValueError('DecodeEngine.score_batch: %d prompts for an engine of batch %d' % (n, self.batch))
+        if any((not torch.is_tensor(p)) or p.dim() != 1 or p.numel() == 0 for p in prompts):
+            raise ValueError('DecodeEngine.score_batch: every prompt must be a non-empty 1-D tensor of ids')
+        rows = list(range(n)) if rows is None else list(rows)
+        nll, last, starts, lens, offs = self._score_packed('score_batch', prompts, rows, [0] * n, max_rows)
+        with torch.no_grad(), torch.cuda.device(self.dev):
+            rows_t = torch.tensor([int(r) for r in rows], dtype=torch.int64, device=self.dev)
+            logits = torch.empty((n, self.logits.shape[1]), dtype=torch.float16, device=self.dev)
+            lm_head_logits(self, last, logits, self.native.stream_ptr(self.dev))                            # as prefill_batch ends
+            self.logits.index_copy_(0, rows_t, logits)
+            self.pos.index_copy_(0, rows_t, torch.tensor([st + T for st, T in zip(starts, lens)], dtype=torch.int64, device=self.dev))
+        return [nll[o:o + T - 1] for o, T in zip(offs, lens)]
+
     def decode(self, token):
         """one token per row in ([batch] ids), logits [batch, vocab] out (the static buffer: clone it to keep it)."""
         if torch.is_tensor(token):
@@ -833,6 +979,38 @@ class DecodeEngine:
             else:
                 self._step()
         return self.logits
+
+
+def perplexity(model, input_ids, seqlen=2048, engine=None, batch=1):
+    """The reference's quality gate (llama_eval, llama.py:173-261) on the engine: input_ids (any shape; the caller brings the ids -- no dataset,
+    tokenizer or network here) is cut into numel // seqlen segments of seqlen tokens (llama.py:178), every segment is scored from position 0
+    (DecodeEngine.score; batch > 1: score_batch, `batch` segments per call) and the results are
+        nll_sum, tokens   sum and number of the per-token negative log-likelihoods (seqlen - 1 targets per segment),
+        ppl               exp(nll_sum / tokens),
+        ppl_reference     the reference's own figure: per segment the MEAN over its seqlen - 1 targets (CrossEntropyLoss, llama.py:254-255)
+                          times seqlen (llama.py:256), summed and divided by nsamples * seqlen before the exp (llama.py:258) -- it weighs
+                          every segment's mean as if the segment had seqlen targets.
+    engine=None builds a DecodeEngine(model, t_max=seqlen, batch=batch)."""
+    ids = input_ids.reshape(-1)
+    seqlen, batch = int(seqlen), int(batch)
+    nsamples = ids.numel() // seqlen
+    if seqlen < 2 or nsamples < 1:
+        raise ValueError('perplexity: needs seqlen >= 2 and at least seqlen ids')
+    if engine is None:
+        engine = DecodeEngine(model, t_max=seqlen, batch=batch)
+    if batch < 1 or batch > engine.batch:
+        raise ValueError('perplexity: batch %d for an engine of batch %d' % (batch, engine.batch))
+    segments = [ids[i * seqlen:(i + 1) * seqlen] for i in range(nsamples)]
+    sums = []
+    for i in range(0, nsamples, batch):
+        group = segments[i:i + batch]
+        nlls = [engine.score(group[0], row=0, start=0)] if batch == 1 else engine.score_batch(group)
+        sums.extend(v.double().sum() for v in nlls)
+    sums = torch.stack(sums).cpu()                                     # [nsamples] float64
+    tokens = nsamples * (seqlen - 1)
+    nll_sum = float(sums.sum())
+    reference = float((sums / (seqlen - 1) * seqlen).sum() / (nsamples * seqlen))
+    return dict(nll_sum=nll_sum, tokens=tokens, ppl=math.exp(nll_sum / tokens), ppl_reference=math.exp(reference))
 
 
 def _cache_layer_kv(cache, li):

@@ -583,6 +583,25 @@ int gptq_prompt_attn_batch_f16(const void *qkv, int64_t ldq, int total_rows, con
                                void *v_cache, int64_t slot_stride, void *out, int64_t ldo, void *workspace, size_t workspace_bytes, int heads,
                                int head_dim, int t_max, float base, float scale, const float *rope_table, gptq_stream_t stream);
 
+/* ---- scoring: the LM head of MANY rows with the cross-entropy inside (reference llama.py:241-258: lm_head over all rows of a segment, shifted
+ * labels, CrossEntropyLoss) -- the [M, N] logits never exist in memory.
+ *   x [M, K] (ldx)       fp16, the already normalised hidden rows
+ *   weight [N, K] (ldw)  fp16, k contiguous: lm_head.weight as stored; bias fp16 [N] or NULL
+ *   targets [M]          device int64; a negative target marks an ignored row
+ *   nll [M]              out, fp32; lse / argmax [M]: optional outputs (either may be NULL)
+ * The logit of column n is z_n = fp16(acc_n), with a bias fp16(fp16(acc_n) + bias_n), acc in fp32 on v_mfma_f32_16x16x32_f16: the bits the tile GEMM
+ * would have stored, so the results are the fp32 cross-entropy of the fp16 logits.  lse = max z + log sum exp(z - max); nll = lse - z_target;
+ * argmax = the lowest index among the maximal z.  target < 0: nll = 0 (lse and argmax are still written); target >= N: nll = NaN, nothing is read
+ * out of bounds.  Any N >= 1 (columns >= N are masked one by one).  Two launches, no atomics: bit-identical from run to run, and a row's results do
+ * not depend on M or on the row's position.  The workspace (gptq_lm_head_nll_workspace_bytes(M, N): M ceil(N / 256) records of 16 bytes, 16-byte
+ * aligned) is pure scratch: no initialisation, no state between launches.
+ * Validated before anything is launched: GPTQ_E_NULL (x, weight, targets, nll, workspace), GPTQ_E_SHAPE (M < 0, N <= 0, K <= 0, ldx < K, ldw < K),
+ * GPTQ_E_ALIGN (x / weight 16 bytes, ldx / ldw multiples of 8, bias 8 bytes, targets 8 bytes, nll / lse / argmax 4 bytes, workspace 16 bytes),
+ * GPTQ_E_WORKSPACE, GPTQ_E_VARIANT (K % 128 != 0: the caller falls back); M == 0 then returns GPTQ_OK. */
+size_t gptq_lm_head_nll_workspace_bytes(int M, int N);
+int gptq_lm_head_nll_f16(const void *x, int64_t ldx, const void *weight, int64_t ldw, const void *bias, const int64_t *targets, float *nll,
+                         float *lse, int32_t *argmax, int M, int N, int K, void *workspace, size_t workspace_bytes, gptq_stream_t stream);
+
 /* ---- GPTQ solver (the caller that PRODUCES the weights; reference gptq.py:128-228) -------------------------------
  * One column block [i1, i1 + count), count <= 128, of the sequential quantise / error-feedback loop (gptq.py:177-199)
  * for all rows at once, in the reference's own fp32 arithmetic (IEEE division, round-half-even, no contraction).
