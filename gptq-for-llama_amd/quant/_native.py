@@ -162,6 +162,8 @@ _SIGNATURES = {
     'gptq_lm_head_nll_workspace_bytes': [c_int, c_int],
     'gptq_lm_head_nll_f16': [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
                              c_size_t, c_void_p],
+    # sampling: one token per row of fp16 logits, temperature / top-k / top-p per row in device memory (csrc/sample.hip)
+    'gptq_sample_rows_f16': [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
 }
 
 

@@ -263,6 +263,12 @@ class DecodeEngine:
         self.stream_out = torch.zeros(self.t_max + 1, dtype=torch.int64, device=dev)   # greedy mode (batch 1): token chosen after position p
         self.greedy_graph = None
         self.greedy_rows_graph, self.stream_rows, self.stepc, self.sample_graphs = None, None, None, {}
+        # gptq_sample_rows_f16: the uniforms and every row's (temperature, top_k, top_p), read by the kernel at every replay (set_sampling)
+        self.u = torch.zeros(B, dtype=torch.float32, device=dev)
+        self.temperature = torch.ones(B, dtype=torch.float32, device=dev)
+        self.top_k = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.top_p = torch.ones(B, dtype=torch.float32, device=dev)
+        self.sample_native_graph = None
         nl = len(self.layers)
         self.kcb = torch.zeros((nl, B, self.t_max, H), **f16)          # [layer][row][t][heads * head_dim]
         self.vcb = torch.zeros((nl, B, self.t_max, H), **f16)
@@ -663,6 +669,90 @@ class DecodeEngine:
             self.sample_graphs = {key: g}          # (one setting at a time: a graph holds the temporaries of a vocabulary-sized sort per row)
         return g
 
+    # -- sampling of the engine's own: gptq_sample_rows_f16 (csrc/sample.hip) with every row's setting in device memory --------------------
+    def set_sampling(self, temperature=1.0, top_k=0, top_p=1.0):
+        """the rows' sampling settings: a scalar for all rows or one value per row.  temperature 0 makes a row greedy, top_k 0 and top_p 1 switch
+        the filter off.  Only the static device buffers change: a captured graph (capture_sample_native) serves the new setting at its next
+        replay.  ValueError for a temperature that is negative or not finite, a negative top_k, a top_p outside (0, 1]."""
+        B = self.batch
+
+        def per_row(name, v, ok):
+            vals = [v] * B if not isinstance(v, (list, tuple)) and not torch.is_tensor(v) else [x for x in (v.tolist() if torch.is_tensor(v) else v)]
+            if len(vals) != B:
+                raise ValueError('DecodeEngine.set_sampling: %s has %d values for a batch of %d' % (name, len(vals), B))
+            for x in vals:
+                if isinstance(x, bool) or not isinstance(x, (int, float)) or not ok(x):
+                    raise ValueError('DecodeEngine.set_sampling: %s = %r' % (name, x))
+            return vals
+        t = per_row('temperature', temperature, lambda x: math.isfinite(x) and x >= 0)
+        k = per_row('top_k', top_k, lambda x: float(x).is_integer() and 0 <= x < 2 ** 31)
+        p = per_row('top_p', top_p, lambda x: 0 < x <= 1)
+        with torch.no_grad():
+            self.temperature.copy_(torch.tensor(t, dtype=torch.float32))
+            self.top_k.copy_(torch.tensor([int(x) for x in k], dtype=torch.int32))
+            self.top_p.copy_(torch.tensor(p, dtype=torch.float32))
+        return self
+
+    def sample_logits(self, logits, out=None, u=None):
+        """one token id per row of `logits` ([n, vocab] or [vocab] fp16 on the engine's device, unit column stride, n <= batch) drawn by
+        gptq_sample_rows_f16 under the settings of rows 0 .. n - 1 (set_sampling).  u: n float32 uniforms in [0, 1) on the device -- with a
+        given u nothing random happens; None draws them from torch's CUDA generator.  out: int64 [n] on the device (default: a new tensor)."""
+        if logits.dim() == 1:
+            logits = logits.unsqueeze(0)
+        n = logits.shape[0] if logits.dim() == 2 else 0
+        if not 1 <= n <= self.batch or logits.dtype != torch.float16 or logits.device != self.ids.device or logits.stride(1) != 1 or logits.shape[1] < 1:
+            raise ValueError('DecodeEngine.sample_logits: logits must be fp16 [n <= %d, vocab] with unit column stride on %s' % (self.batch, self.dev))
+        if u is None:
+            u = torch.rand(n, dtype=torch.float32, device=self.ids.device)
+        if out is None:
+            out = torch.empty(n, dtype=torch.int64, device=self.ids.device)
+        for name, t, dt in (('u', u, torch.float32), ('out', out, torch.int64)):
+            if t.dtype != dt or t.device != self.ids.device or t.shape != (n,) or not t.is_contiguous():
+                raise ValueError('DecodeEngine.sample_logits: %s must be a contiguous %s [%d] on %s' % (name, dt, n, self.dev))
+        with self.native.on_device(self.dev):
+            rc = self.lib.gptq_sample_rows_f16(logits.data_ptr(), logits.stride(0) if n > 1 else logits.shape[1], n, logits.shape[1], u.data_ptr(),
+                                               self.temperature.data_ptr(), self.top_k.data_ptr(), self.top_p.data_ptr(), out.data_ptr(),
+                                               self.native.stream_ptr(self.dev))
+        self.native.check(rc, 'gptq_sample_rows_f16')
+        return out
+
+    def _stream_buffers(self):
+        """stream_rows / stepc of the self-feeding steps, allocated on first use"""
+        if self.stream_rows is None:
+            self.stream_rows = torch.zeros((self.t_max + 1, self.batch), dtype=torch.int64, device=self.dev)
+            self.stepc = torch.zeros(1, dtype=torch.int64, device=self.dev)
+
+    def _sample_native_step(self):
+        """the self-feeding sampling step of the engine's own, for ANY batch: one decode step, fresh uniforms from torch's CUDA generator (inside a
+        graph its Philox offset advances per replay exactly as per eager call), ONE launch that draws every row's next token under that row's
+        setting, and the bookkeeping of _greedy_rows_step."""
+        self._stream_buffers()
+        self._step()
+        self.u.uniform_()
+        self.sample_logits(self.logits, out=self.ids, u=self.u)
+        self.stream_rows.index_copy_(0, self.stepc, self.ids.unsqueeze(0))
+        self.stepc.add_(1)
+
+    def capture_sample_native(self):
+        """capture _sample_native_step ONCE: the settings are device buffers the kernel reads at every replay, so set_sampling never re-captures.
+        The generator's state is put back behind the warm-up run, as capture_sample_rows does."""
+        with torch.no_grad():
+            self._stream_buffers()
+            rng = torch.cuda.get_rng_state(self.dev)
+            pos0, ids0 = self.pos.clone(), self.ids.clone()
+            self.stepc.zero_()
+            self._sample_native_step()
+            torch.cuda.synchronize(self.dev)
+            self.pos.copy_(pos0); self.ids.copy_(ids0); self.stepc.zero_()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                self._sample_native_step()
+            self.pos.copy_(pos0); self.ids.copy_(ids0); self.stepc.zero_()
+            torch.cuda.synchronize(self.dev)
+            torch.cuda.set_rng_state(rng, self.dev)
+            self.sample_native_graph = g
+        return g
+
     def capture(self):
         """warm up once (module loads, workspace), then capture one decode step into a hipGraph."""
         with torch.no_grad():
@@ -1022,7 +1112,17 @@ def _cache_layer_kv(cache, li):
     return kv[0], kv[1]
 
 
-def engine_generate(model, input_ids, max_new_tokens, eos_token_id=None, engine=None, t_max=2048, prefill='hf'):
+def _sampling_settings(what, sample):
+    """the `sample` argument of engine_generate / engine_generate_batch as keywords of DecodeEngine.set_sampling (which validates the values)"""
+    if not isinstance(sample, dict):
+        raise ValueError('%s: sample must be None or a dict with the keys temperature, top_k, top_p' % what)
+    unknown = sorted(set(sample) - {'temperature', 'top_k', 'top_p'})
+    if unknown:
+        raise ValueError('%s: unknown sampling keys %r' % (what, unknown))
+    return dict(sample)
+
+
+def engine_generate(model, input_ids, max_new_tokens, eos_token_id=None, engine=None, t_max=2048, prefill='hf', sample=None):
     """Greedy generation: the prompt goes through the HF model once (the drop-in modules' prefill path: MFMA GEMMs,
     fused MLP epilogue), its KV cache is copied into the engine's static cache, and every further token is ONE hipGraph
     replay (DecodeEngine).  Returns the full sequence [1, prompt + generated].  Batch 1; the reference equivalent is
@@ -1030,9 +1130,14 @@ def engine_generate(model, input_ids, max_new_tokens, eos_token_id=None, engine=
     prefill='engine': the prompt goes through DecodeEngine.prefill instead (the engine's own launches with the hand-written causal
     attention kernel straight into its cache: no HF module chain, no DynamicCache, no copy); 'hf' (the default) is the route above.
     Measured on the 7B shape (profiles/prompt_attn/README.md): 'engine' reaches the first token sooner at 16, 128, 512 and 2047 tokens
-    (2.1 / 4.2 / 9.5 / 29.0 ms against 7.9 / 8.3 / 12.2 / 38.1) -- at no measured length is it slower than 'hf'."""
+    (2.1 / 4.2 / 9.5 / 29.0 ms against 7.9 / 8.3 / 12.2 / 38.1) -- at no measured length is it slower than 'hf'.
+    sample=dict(temperature=..., top_k=..., top_p=...) (every key optional: DecodeEngine.set_sampling) SAMPLES instead, as the reference's script does
+    (llama_inference.py:119-127): the first token is drawn from the prompt's logits by DecodeEngine.sample_logits, every further one by a replay of
+    the capture_sample_native graph; the draws follow torch.manual_seed.  temperature 0 gives the greedy tokens.  The settings STAY in the engine's
+    buffers afterwards: a later eng.sample_logits(...) or a replay of the native graph uses them until set_sampling is called again."""
     if prefill not in ('hf', 'engine'):
         raise ValueError("engine_generate: prefill must be 'hf' or 'engine', not %r" % (prefill,))
+    settings = None if sample is None else _sampling_settings('engine_generate', sample)
     if input_ids.dim() != 2 or input_ids.shape[0] != 1:
         raise ValueError('engine_generate: batch 1 only')
     dev = input_ids.device
@@ -1040,6 +1145,11 @@ def engine_generate(model, input_ids, max_new_tokens, eos_token_id=None, engine=
     eng = engine if engine is not None else DecodeEngine(model, t_max=t_max).capture()
     if T + max_new_tokens > eng.t_max:
         raise ValueError('engine_generate: prompt + max_new_tokens exceeds the engine cache (%d)' % eng.t_max)
+    if settings is not None:
+        if eng.batch != 1:
+            raise ValueError('engine_generate: sampling needs an engine of batch 1')
+        eng.set_sampling(**settings)
+        return _engine_generate_sampled(model, input_ids, max_new_tokens, eos_token_id, eng, prefill)
     with torch.no_grad():
         if prefill == 'engine':
             first = eng.prefill(input_ids[0], start=0).argmax().reshape(1)
@@ -1074,12 +1184,58 @@ def engine_generate(model, input_ids, max_new_tokens, eos_token_id=None, engine=
     return torch.cat([input_ids[0], gen.to(input_ids.dtype)]).unsqueeze(0)
 
 
-def engine_generate_batch(model, prompts, max_new_tokens, eos_token_id=None, engine=None, t_max=2048):
+def _engine_generate_sampled(model, input_ids, max_new_tokens, eos_token_id, eng, prefill):
+    """engine_generate with sampling (the settings are already in the engine): the greedy loop with sample_logits for the first token and the
+    capture_sample_native graph -- whose choices land in stream_rows -- for the others"""
+    T = input_ids.shape[1]
+    with torch.no_grad():
+        if eng.sample_native_graph is None:
+            eng.pos.zero_()                                      # (the capture's warm-up step writes cache row pos -- and the logits buffer)
+            eng.capture_sample_native()
+        if prefill == 'engine':
+            logits = eng.prefill(input_ids[0], start=0)
+        else:
+            from transformers.cache_utils import DynamicCache
+            cache = DynamicCache(config=model.config)
+            out = model(input_ids, past_key_values=cache, use_cache=True)
+            for li in range(len(eng.layers)):
+                k, v = _cache_layer_kv(cache, li)
+                eng.kc[li, :T].copy_(k[0].transpose(0, 1).reshape(T, -1))
+                eng.vc[li, :T].copy_(v[0].transpose(0, 1).reshape(T, -1))
+            eng.pos.fill_(T)
+            logits = out.logits[0, -1].to(torch.float16).contiguous()
+            del out, cache
+        first = eng.sample_logits(logits)
+        eng.ids.copy_(first)
+        eng.stepc.zero_()                                        # stream_rows[k] = the token chosen by replay k
+        done = 1
+        hit = eos_token_id is not None and int(first[0]) == eos_token_id
+        while done < max_new_tokens and not hit:
+            burst = min(16, max_new_tokens - done)               # the host looks at the stream every 16 tokens only
+            for _ in range(burst):
+                eng.sample_native_graph.replay()
+            if eos_token_id is not None:
+                hit = bool((eng.stream_rows[done - 1:done - 1 + burst, 0] == eos_token_id).any())
+            done += burst
+        gen = torch.cat([first, eng.stream_rows[:done - 1, 0]])
+        if eos_token_id is not None:
+            at = (gen == eos_token_id).nonzero()
+            if at.numel():
+                gen = gen[:int(at[0]) + 1]
+    return torch.cat([input_ids[0], gen.to(input_ids.dtype)]).unsqueeze(0)
+
+
+def engine_generate_batch(model, prompts, max_new_tokens, eos_token_id=None, engine=None, t_max=2048, sample=None):
     """Greedy generation for a LIST of prompts of different lengths (1-D id tensors): all prompts enter the engine through ONE
     DecodeEngine.prefill_batch, and every further step is one replay of the capture_greedy_rows graph for all rows; the host looks at the
     stream every 16 steps.  Returns a list of 1-D tensors, prompt + generated, each cut after its first eos_token_id.  engine.batch must
     equal len(prompts) (without an engine, one of that batch is built); max(T) + max_new_tokens <= t_max.  Nothing of `transformers` is
-    involved."""
+    involved.
+    sample=dict(temperature=..., top_k=..., top_p=...) SAMPLES instead: every key optional, a scalar for all rows or one value per prompt
+    (DecodeEngine.set_sampling; a row with temperature 0 stays greedy).  The first tokens are drawn from the prompts' logits by
+    DecodeEngine.sample_logits, every further step is a replay of the capture_sample_native graph; the draws follow torch.manual_seed.  The
+    settings STAY in the engine's buffers afterwards, until set_sampling is called again."""
+    settings = None if sample is None else _sampling_settings('engine_generate_batch', sample)
     n = len(prompts)
     if n < 1 or any((not torch.is_tensor(p)) or p.dim() != 1 or p.numel() == 0 for p in prompts):
         raise ValueError('engine_generate_batch: prompts must be a non-empty list of non-empty 1-D id tensors')
@@ -1091,11 +1247,21 @@ def engine_generate_batch(model, prompts, max_new_tokens, eos_token_id=None, eng
         raise ValueError('engine_generate_batch: %d prompts for an engine of batch %d' % (n, eng.batch))
     if max(int(p.numel()) for p in prompts) + max_new_tokens > eng.t_max:
         raise ValueError('engine_generate_batch: prompt + max_new_tokens exceeds the engine cache (%d)' % eng.t_max)
+    if settings is not None:
+        eng.set_sampling(**settings)
     with torch.no_grad():
-        if eng.greedy_rows_graph is None:
-            eng.pos.zero_()                                      # (the capture's warm-up step writes cache row pos of every row)
-            eng.capture_greedy_rows()
-        first = eng.prefill_batch(prompts, starts=[0] * n).argmax(dim=-1)
+        if settings is not None:
+            if eng.sample_native_graph is None:
+                eng.pos.zero_()
+                eng.capture_sample_native()
+            graph = eng.sample_native_graph
+            first = eng.sample_logits(eng.prefill_batch(prompts, starts=[0] * n))
+        else:
+            if eng.greedy_rows_graph is None:
+                eng.pos.zero_()                                  # (the capture's warm-up step writes cache row pos of every row)
+                eng.capture_greedy_rows()
+            graph = eng.greedy_rows_graph
+            first = eng.prefill_batch(prompts, starts=[0] * n).argmax(dim=-1)
         eng.ids.copy_(first)
         eng.stepc.zero_()                                        # stream_rows[k] = the tokens chosen by replay k
         done = 1
@@ -1103,7 +1269,7 @@ def engine_generate_batch(model, prompts, max_new_tokens, eos_token_id=None, eng
         while done < max_new_tokens and not (hit is not None and bool(hit.all())):
             burst = min(16, max_new_tokens - done)               # the host looks at the stream every 16 steps only
             for _ in range(burst):
-                eng.greedy_rows_graph.replay()
+                graph.replay()
             if hit is not None:
                 hit = hit | (eng.stream_rows[done - 1:done - 1 + burst] == eos_token_id).any(dim=0)
             done += burst

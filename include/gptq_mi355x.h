@@ -602,6 +602,28 @@ size_t gptq_lm_head_nll_workspace_bytes(int M, int N);
 int gptq_lm_head_nll_f16(const void *x, int64_t ldx, const void *weight, int64_t ldw, const void *bias, const int64_t *targets, float *nll,
                          float *lse, int32_t *argmax, int M, int N, int K, void *workspace, size_t workspace_bytes, gptq_stream_t stream);
 
+/* ---- sampling: one token per row of fp16 logits (reference llama_inference.py:119-127: do_sample=True, top_p=0.95, temperature=0.8) in ONE
+ * launch (csrc/sample.hip), one workgroup per row, no workspace, no atomics on global memory.
+ *   logits [rows, vocab] (ld)  fp16, row r at logits + r ld, ld >= vocab; rows need 2-byte alignment only (a [B, 32001] buffer is fine)
+ *   u, temperature, top_p      device float [rows]; top_k device int32 [rows]: every row has its own setting, and a captured graph serves any
+ *   ids_out                    device int64 [rows]
+ * Per row, with l_i the logits and T, k, p, u the row's parameters:
+ *   sanitising   T not finite or <= 0: greedy -- the index of the first maximal logit.  k <= 0 or k >= vocab: top-k off.  p NaN or >= 1: top-p
+ *                off; p <= 0: only the top class survives.  u is clamped into [0, 1 - 2^-24], NaN becomes 0.
+ *   classes      two tokens are tied iff their fp16 logits compare equal (-0 == +0); a class is kept or dropped whole
+ *   weights      w_i = exp((l_i - l_max) / T); -inf weighs 0 and is never drawn
+ *   top-k        keeps every token whose logit is >= the k-th largest logit: ALL ties stay, so more than k tokens can survive
+ *   top-p        on what top-k kept, of mass Z: token i stays iff the mass of the kept tokens with a strictly larger logit is < p Z
+ *   draw         W = the mass of the final kept set, c_j its running sum in ascending token id: the first kept id with c_j > u W
+ *   non-finite   a row that holds a NaN or +inf: the index of the first such element, nothing else happens
+ * The id written is in [0, vocab) whatever the input.  Weights are the accurate fp32 expf of an IEEE division and are summed as integer
+ * multiples of 2^-40 (of 2^-(62 - ceil(log2 vocab)) above 2^22 tokens) of the top class's weight: every mass is within vocab 2^-41 of the exact
+ * sum of the fp32 weights, and the same inputs give the same id on every call.
+ * Validated before the launch: GPTQ_E_NULL (any pointer, reported first), GPTQ_E_SHAPE (rows < 1, vocab < 1, ld < vocab), GPTQ_E_ALIGN (logits 2
+ * bytes, u / temperature / top_k / top_p 4 bytes, ids_out 8 bytes). */
+int gptq_sample_rows_f16(const void *logits, int64_t ld, int rows, int vocab, const float *u, const float *temperature, const int32_t *top_k,
+                         const float *top_p, int64_t *ids_out, gptq_stream_t stream);
+
 /* ---- GPTQ solver (the caller that PRODUCES the weights; reference gptq.py:128-228) -------------------------------
  * One column block [i1, i1 + count), count <= 128, of the sequential quantise / error-feedback loop (gptq.py:177-199)
  * for all rows at once, in the reference's own fp32 arithmetic (IEEE division, round-half-even, no contraction).
