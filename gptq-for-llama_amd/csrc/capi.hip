@@ -1046,6 +1046,33 @@ int gptq_prompt_attn_batch_f16(const void *qkv, int64_t ldq, int total_rows, con
                                     (half_t *)workspace, heads, base, scale, rope_table, (hipStream_t)stream);
 }
 
+/* a CHUNK of a decoding sequence: `rows` (1 .. 16) consecutive tokens at positions *position .. *position + rows - 1, the position in device memory
+ * (csrc/chunk_attn.hip): the verify step of speculative decoding, graph-captured once and replayed at any position */
+size_t gptq_decode_attn_chunk_workspace_bytes(int rows, int heads, int head_dim, int t_max) {
+    if (rows < 1 || rows > 16 || heads <= 0 || heads > 65535 || head_dim != 128 || t_max <= 0) return 0;
+    return chunk_attn_ws_bytes(rows, heads, t_max);
+}
+
+int gptq_decode_attn_chunk_splits(int heads, int head_dim, int t_max, int len) {
+    if (heads <= 0 || heads > 65535 || head_dim != 128 || t_max <= 0 || len < 1 || len > t_max) return GPTQ_E_SHAPE;
+    return chunk_attn_active_splits(heads, t_max, len);
+}
+
+int gptq_decode_attn_chunk_f16(const void *qkv, int64_t ldq, int rows, const int64_t *position, void *k_cache, void *v_cache, void *out, int64_t ldo,
+                               void *workspace, size_t workspace_bytes, int heads, int head_dim, int t_max, float base, float scale,
+                               const float *rope_table, gptq_stream_t stream) {
+    if (!qkv || !position || !k_cache || !v_cache || !out || !workspace) return GPTQ_E_NULL;
+    if (rows < 1 || rows > 16 || heads <= 0 || heads > 65535 || head_dim != 128 || t_max <= 0 || ldq < 3 * (int64_t)heads * head_dim ||
+        ldo < (int64_t)heads * head_dim)
+        return GPTQ_E_SHAPE;
+    if (!aligned(qkv, 16) || !aligned(position, 8) || !aligned(k_cache, 16) || !aligned(v_cache, 16) || !aligned(workspace, 16) ||
+        (rope_table && !aligned(rope_table, 8)) || ldq % 8 != 0 || ldo % 8 != 0 || !aligned(out, 16))
+        return GPTQ_E_ALIGN;
+    if (workspace_bytes < chunk_attn_ws_bytes(rows, heads, t_max)) return GPTQ_E_SHAPE;   /* (this entry reports it with the shapes) */
+    return chunk_attn_launch((const half_t *)qkv, ldq, rows, position, (half_t *)k_cache, (half_t *)v_cache, (half_t *)out, ldo, workspace, heads,
+                             t_max, base, scale, rope_table, (hipStream_t)stream);
+}
+
 /* scoring (csrc/gemm8.hip, cross-entropy epilogue): everything is checked here, before the first launch */
 size_t gptq_lm_head_nll_workspace_bytes(int M, int N) {
     if (M <= 0 || N <= 0) return 0;

@@ -1,0 +1,369 @@
+// chunk_attn.hip -- attention of a handful of CONSECUTIVE tokens of one sequence over a long history, with the position in device memory: the
+// verify step of speculative decoding (the last accepted token and its drafts go through the model together, one pass over the weights).
+// Reference: what HF generate's one-token loop does R times behind llama_inference.py:109-115 -- triton_rotate_half_, torch.cat onto the past and
+// F.scaled_dot_product_attention (quant/fused_attn.py:126-158) -- for R rows at once.
+//
+// rows (1..16, a host value: it shapes the grid) tokens sit at positions p .. p + rows - 1, p = *position read on the device, so a captured graph
+// replays the call at any position.  Two launches:
+//   1. chunk_rope_kv_kernel, grid (rows, heads): the arithmetic of rope_kv_kernel (decode_attn.hip) / prompt_rope_kv_kernel (prompt_attn.hip) per
+//      (row, head) -- same instructions, same flags (see the Makefile), so cache rows p + r get the bits a token-by-token feed writes; the rotated q
+//      goes to the workspace, qkv is never written.  It also clears the arrival tickets of launch 2 (no state is asked of the caller's workspace).
+//      The kernel boundary orders the append against every read of launch 2.
+//   2. chunk_attn_kernel, grid (heads, S): the key range [0, p + rows) is cut into splits by attn_split() from its length at run time, as the decode
+//      attention does (attn_split.h; CA_TPS tokens per split at least, at most S <= ATT_MAX_SPLITS) -- ONE cut for all rows: a split streams its
+//      keys and values once and serves every row with them.  A split is a workgroup of four waves; a wave walks tiles of 32 keys with an online
+//      softmax (log2 domain) per query row, the query rows padded to 16:
+//        S^T[key][query] = K Q^T   v_mfma_f32_16x16x32_f16, K straight from global memory in the A layout (lane = key, 64 contiguous bytes per
+//                                  lane), Q^T fragments in registers for the whole walk;
+//        O^T[dim][query] += V^T P^T  the accumulator layout of the first product is the B operand of the second (P rounded to fp16 in registers);
+//                                  V^T comes through ds_read_b64_tr_b16 from the wave's own LDS image of the V tile (256-byte rows with the
+//                                  chunk swizzle of prompt_attn.hip; the key order of a 16-key block is permuted so that the two 4-row blocks a
+//                                  32-lane half reads lie 8 rows apart: conflict-free).
+//      The next tile's K / V are requested into registers before the current one is computed.  No workgroup barrier inside the walk: the LDS image
+//      is private to the wave.  The four waves meet once (LDS), giving the split's {M, den, o = num / den in fp16} per row.  One active split: that
+//      IS the output row.  Several: records go out with system-scope stores, an arrival ticket per head elects the last split, which merges the
+//      records in split order with the shared attn_merge_* helpers -- the ticket decides who merges, never what is computed: same inputs, same bits.
+// Bounds: keys at and beyond min(p + rows, t_max) are never loaded (their slots of a tile are zeros); for row r everything above p + r is masked by a
+// select before the maximum.  p < 0 or p >= t_max: nothing is read or written.  A row whose position is >= t_max is skipped.
+#include <algorithm>
+
+#include "attn_split.h"
+#include "gptq_device.h"
+#include "gptq_internal.h"
+
+namespace gptq {
+
+constexpr int CA_HD = 128;     // head_dim served
+constexpr int CA_NW = 4;       // waves per workgroup
+constexpr int CA_KT = 32;      // keys per wave tile (two 16-key MFMA blocks)
+constexpr int CA_QR = 16;      // query rows of the MFMA (rows padded to it)
+constexpr int CA_TPS = 256;    // tokens a split owns at least: 8 splits from 1793 tokens on (32 heads x 8 = one workgroup per CU at 2047)
+
+__global__ void __launch_bounds__(64) chunk_rope_kv_kernel(const half_t *__restrict__ qkv, int64_t ldq, const int64_t *__restrict__ pos_ptr,
+                                                           half_t *__restrict__ kc, half_t *__restrict__ vc, half_t *__restrict__ qrot,
+                                                           unsigned *__restrict__ tickets, int heads, int t_max, float inv_base,
+                                                           const float2 *__restrict__ tab) {
+    const int h = blockIdx.y, c = threadIdx.x, half = CA_HD / 2;
+    const int r = blockIdx.x;
+    if (r == 0 && c == 0) tickets[h] = 0u;
+    const int64_t p = pos_ptr[0];
+    if (p < 0) return;
+    const int64_t pos = p + r;
+    if (pos >= t_max) return;
+    float cs, sn;
+    if (tab) {   // {cos, sin} of (pos, c) from the table rope_table_kernel filled with the SAME instructions
+        const float2 e = tab[(size_t)pos * half + c];
+        cs = e.x;
+        sn = e.y;
+    } else {
+        const float freq = expf((float)c * inv_base) * (float)pos;
+        cs = cosf(freq);
+        sn = sinf(freq);
+    }
+    const int hd = heads * CA_HD;
+    const half_t *q = qkv + (size_t)r * ldq + (size_t)h * CA_HD + c;
+    const half_t *k = q + hd;
+    const half_t *v = q + 2 * hd;
+    const float qx = (float)q[0], qy = (float)q[half];
+    half_t *qd = qrot + (size_t)r * hd + (size_t)h * CA_HD + c;
+    qd[0] = (half_t)(qx * cs - qy * sn);
+    qd[half] = (half_t)(qx * sn + qy * cs);
+    const float kx = (float)k[0], ky = (float)k[half];
+    half_t *kd = kc + (size_t)pos * hd + (size_t)h * CA_HD + c;
+    kd[0] = (half_t)(kx * cs - ky * sn);
+    kd[half] = (half_t)(kx * sn + ky * cs);
+    half_t *vd = vc + (size_t)pos * hd + (size_t)h * CA_HD + c;
+    vd[0] = v[0];
+    vd[half] = v[half];
+}
+
+// byte offset of 16-byte chunk ch (0..15) of row `row` in a [rows][128 fp16] LDS image (the swizzle of prompt_attn.hip)
+GPTQ_DEV int ca_off(int row, int ch) { return 256 * row + 16 * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3))); }
+
+typedef short ca_short4 __attribute__((__vector_size__(4 * sizeof(short))));
+#define CA_LDS __attribute__((address_space(3)))
+
+// ds_read_b64_tr_b16: per 16-lane group a block of 4 rows x 16 columns, lane i receives column i (row q in element q).  Every lane supplies an
+// address (EXEC must be full: only ever called under wave-uniform control flow).
+GPTQ_DEV half4_t ca_tr_read(const half_t *img, int off) {
+    return __builtin_bit_cast(half4_t, __builtin_amdgcn_ds_read_tr16_b64_v4i16((CA_LDS ca_short4 *)((CA_LDS char *)img + off)));
+}
+// over the wave's four 16-lane rows (xor 16, 32): every lane of a column ends with the column's value
+GPTQ_DEV float ca_rows_max(float v) {
+    const uint32_t u = __builtin_bit_cast(uint32_t, v);
+    auto a = __builtin_amdgcn_permlane16_swap(u, u, false, false);
+    const float m16 = fmaxf(__builtin_bit_cast(float, (uint32_t)a[0]), __builtin_bit_cast(float, (uint32_t)a[1]));
+    const uint32_t u2 = __builtin_bit_cast(uint32_t, m16);
+    auto b = __builtin_amdgcn_permlane32_swap(u2, u2, false, false);
+    return fmaxf(__builtin_bit_cast(float, (uint32_t)b[0]), __builtin_bit_cast(float, (uint32_t)b[1]));
+}
+GPTQ_DEV float ca_rows_sum(float v) {
+    const uint32_t u = __builtin_bit_cast(uint32_t, v);
+    auto a = __builtin_amdgcn_permlane16_swap(u, u, false, false);
+    const float s16 = __builtin_bit_cast(float, (uint32_t)a[0]) + __builtin_bit_cast(float, (uint32_t)a[1]);
+    const uint32_t u2 = __builtin_bit_cast(uint32_t, s16);
+    auto b = __builtin_amdgcn_permlane32_swap(u2, u2, false, false);
+    return __builtin_bit_cast(float, (uint32_t)b[0]) + __builtin_bit_cast(float, (uint32_t)b[1]);
+}
+
+struct ChunkAttnArgs {
+    const half_t *q;             // rotated q [rows][heads * 128]
+    const int64_t *pos;
+    const half_t *kc, *vc;       // [t_max][heads * 128]
+    half_t *out;
+    uint32_t *o16;               // records: [S][rows][heads * 128] fp16 partial outputs (as pairs)
+    float *md;                   //          [S][heads][rows] {M, den}
+    unsigned *tickets;           //          [heads]
+    int heads, rows, t_max;
+    int64_t ldo;
+    float scale2;                // softmax scale x log2(e)
+};
+
+__global__ void __launch_bounds__(CA_NW * 64) chunk_attn_kernel(const ChunkAttnArgs a) {
+    // the waves' V tiles [32 keys][128] fp16; at the end the waves' O [16 rows][128] fp32 (the same 8 KB each)
+    __shared__ __attribute__((aligned(16))) half_t vs[CA_NW][CA_KT * CA_HD];
+    __shared__ float mw[CA_NW][CA_QR], lw[CA_NW][CA_QR];
+    __shared__ int last_flag;
+    const int h = blockIdx.x, s = blockIdx.y, S = gridDim.y;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int g = lane >> 4, qi = lane & 15;               // 16-lane row of the wave, column (= query row of the MFMA)
+    const int hd = a.heads * CA_HD;
+    const int64_t p64 = ((const __attribute__((address_space(4))) int64_t *)a.pos)[0];
+    if (p64 < 0 || p64 >= a.t_max) return;
+    const int p = (int)p64;
+    const int nr = min(a.rows, a.t_max - p);               // rows that fit the cache
+    const int len = p + nr;                                // keys of the launch: [0, len)
+    const AttnSplit sp = attn_split(len, S, CA_TPS);
+    if (s >= sp.nsp) return;
+    const int t0 = s * sp.chunk;
+    const int t_end = min(t0 + sp.chunk, len);             // this split attends to keys [t0, t_end)
+    const int ntiles = (t_end - t0 + CA_KT - 1) / CA_KT;   // >= 1
+    const half_t *const kc = a.kc + (size_t)h * CA_HD, *const vc = a.vc + (size_t)h * CA_HD;
+
+    // ---- Q^T fragments (B operand of K Q^T): lane = query, element j of k-step ks = dim 32 g + 8 ks + j (K's fragments use the same map) ----
+    half8_t qf[4];
+#pragma unroll
+    for (int ks = 0; ks < 4; ks++) {
+        qf[ks] = half8_t{0, 0, 0, 0, 0, 0, 0, 0};
+        if (qi < nr) qf[ks] = *(const half8_t *)(a.q + (size_t)qi * hd + (size_t)h * CA_HD + 32 * g + 8 * ks);
+    }
+    // A row m of a 16-key block is key ca_key(m) of the block: accumulator register r of lane row g holds key 8 (g & 1) + 4 (g >> 1) + r
+    const int krow = 8 * ((qi >> 2) & 1) + 4 * (qi >> 3) + (qi & 3);
+    const int kreg0 = 8 * (g & 1) + 4 * (g >> 1);
+    const int vrow = lane >> 4, vch = lane & 15;           // V staging: chunk vch of tile rows vrow + 4 i
+
+    u32x4 kA[2][4], vA[8], kB[2][4], vB[8];
+    auto request = [&](u32x4 (&K)[2][4], u32x4 (&V)[8], int tb) {
+#pragma unroll
+        for (int b = 0; b < 2; b++) {
+            const int key = tb + 16 * b + krow;
+#pragma unroll
+            for (int ks = 0; ks < 4; ks++) {
+                K[b][ks] = u32x4{0u, 0u, 0u, 0u};
+                if (key < t_end) K[b][ks] = *(const u32x4 *)(kc + (size_t)key * hd + 32 * g + 8 * ks);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            const int key = tb + vrow + 4 * i;
+            V[i] = u32x4{0u, 0u, 0u, 0u};
+            if (key < t_end) V[i] = *(const u32x4 *)(vc + (size_t)key * hd + vch * 8);
+        }
+    };
+    half_t *const img = vs[wave];
+
+    // ---- running state of the lane's query row: M (log2 domain, the same in the four lanes of a column), l (this lane's keys), O^T[dim][query] ----
+    float M = ATT_M_FLOOR, l = 0.f;
+    float4_t acc[8];
+#pragma unroll
+    for (int d = 0; d < 8; d++) acc[d] = float4_t{0.f, 0.f, 0.f, 0.f};
+    const int qpos = p + qi;                               // the last key this lane's query row sees
+
+    auto tile = [&](const u32x4 (&K)[2][4], const u32x4 (&V)[8], int tb) {
+#pragma unroll
+        for (int i = 0; i < 8; i++) *(CA_LDS u32x4 *)((CA_LDS char *)img + ca_off(vrow + 4 * i, vch)) = V[i];
+        float4_t sc[2];
+#pragma unroll
+        for (int b = 0; b < 2; b++) {
+            sc[b] = float4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ks = 0; ks < 4; ks++)
+                sc[b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8_t, K[b][ks]), qf[ks], sc[b], 0, 0, 0);
+        }
+        float mt = -INFINITY;
+#pragma unroll
+        for (int b = 0; b < 2; b++)
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const int key = tb + 16 * b + kreg0 + r;
+                float v = sc[b][r] * a.scale2;
+                if (key > qpos || key >= t_end) v = -INFINITY;
+                sc[b][r] = v;
+                mt = fmaxf(mt, v);
+            }
+        mt = ca_rows_max(mt);
+        const float Mn = fmaxf(M, mt);                     // finite: M starts at the floor
+        const float alpha = __builtin_amdgcn_exp2f(M - Mn);
+        M = Mn;
+        float ps = 0.f;
+        half8_t pf;
+#pragma unroll
+        for (int b = 0; b < 2; b++)
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const float e = __builtin_amdgcn_exp2f(sc[b][r] - Mn);   // masked slots hold -inf: 0
+                ps += e;
+                pf[4 * b + r] = (half_t)e;
+            }
+        l = __builtin_fmaf(l, alpha, ps);
+#pragma unroll
+        for (int d = 0; d < 8; d++) acc[d] *= alpha;
+        // O^T[dim][query] += V^T P^T: element j of lane row g is key 16 (j >> 2) + kreg0 + (j & 3) -- what pf holds -- so V^T comes as two transposed
+        // 4-key blocks, 16 keys apart; lane 4 q + pp of a 16-lane group supplies row q, columns 4 pp .. 4 pp + 3 of the block
+#pragma unroll
+        for (int d = 0; d < 8; d++) {
+            const int r0 = kreg0 + (qi >> 2), ch = 2 * d + ((qi & 3) >> 1), sub = 8 * (qi & 1);
+            const half4_t lo = ca_tr_read(img, ca_off(r0, ch) + sub);
+            const half4_t up = ca_tr_read(img, ca_off(r0 + 16, ch) + sub);
+            const half8_t vf = half8_t{lo[0], lo[1], lo[2], lo[3], up[0], up[1], up[2], up[3]};
+            acc[d] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf, pf, acc[d], 0, 0, 0);
+        }
+    };
+
+    // the wave's tiles: wave, wave + 4, ... (wave-uniform control flow: EXEC is full at every transposed read)
+    if (wave < ntiles) {
+        request(kA, vA, t0 + wave * CA_KT);
+        for (int i = wave; i < ntiles; i += 2 * CA_NW) {
+            const bool more = i + CA_NW < ntiles;
+            if (more) request(kB, vB, t0 + (i + CA_NW) * CA_KT);
+            tile(kA, vA, t0 + i * CA_KT);
+            if (more) {
+                if (i + 2 * CA_NW < ntiles) request(kA, vA, t0 + (i + 2 * CA_NW) * CA_KT);
+                tile(kB, vB, t0 + (i + CA_NW) * CA_KT);
+            }
+        }
+    }
+
+    // ---- the lane rows of a column -> one, the waves -> one (LDS): {Mx, den, num} of the split per query row ----
+    l = ca_rows_sum(l);
+    float *const ow = (float *)img;                        // [16 queries][128 dims] fp32: the wave is done with its own V image
+#pragma unroll
+    for (int d = 0; d < 8; d++) *(CA_LDS float4_t *)((CA_LDS float *)ow + qi * CA_HD + 16 * d + 4 * g) = acc[d];
+    if (g == 0) {
+        mw[wave][qi] = M;
+        lw[wave][qi] = l;
+    }
+    __syncthreads();
+    const int qq = tid >> 4, d0 = (tid & 15) * 8;          // this thread's query row and its eight dims
+    float Mx = mw[0][qq];
+#pragma unroll
+    for (int w = 1; w < CA_NW; w++) Mx = fmaxf(Mx, mw[w][qq]);
+    float num[8], den = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; j++) num[j] = 0.f;
+#pragma unroll
+    for (int w = 0; w < CA_NW; w++) {
+        const float e = __builtin_amdgcn_exp2f(mw[w][qq] - Mx);
+        den = __builtin_fmaf(e, lw[w][qq], den);
+        const float *src = (const float *)vs[w] + qq * CA_HD + d0;
+#pragma unroll
+        for (int j = 0; j < 8; j++) num[j] = __builtin_fmaf(e, src[j], num[j]);
+    }
+    // the split's normalised output; a row that saw no key of this split (den = 0: its keys end below t0) leaves zeros, which merge with weight 0
+    const float rden = den > 0.f ? __builtin_amdgcn_rcpf(den) : 0.f;
+    half8_t o;
+#pragma unroll
+    for (int j = 0; j < 8; j++) o[j] = attn_round_f16(num[j] * rden);
+    half_t *const orow = a.out + (size_t)qq * a.ldo + (size_t)h * CA_HD + d0;
+    if (sp.nsp == 1) {       // this workgroup is the whole head
+        if (qq < nr) *(half8_t *)orow = o;
+        return;
+    }
+    // ---- several splits: system-scope records, arrival ticket, the last split merges them in split order ----
+    const size_t rstride = (size_t)a.rows * hd / 2;        // uint32 words per split
+    uint32_t *const ro = a.o16 + ((size_t)qq * hd + (size_t)h * CA_HD + d0) / 2;
+    float *const rmd = a.md + ((size_t)h * a.rows + qq) * 2;
+    const size_t mstride = (size_t)a.heads * a.rows * 2;
+    if (qq < nr) {
+        const u32x4 ow4 = __builtin_bit_cast(u32x4, o);
+#pragma unroll
+        for (int j = 0; j < 4; j++) __hip_atomic_store(ro + (size_t)s * rstride + j, ow4[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        if ((tid & 15) == 0) {
+            __hip_atomic_store(rmd + (size_t)s * mstride, Mx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            __hip_atomic_store(rmd + (size_t)s * mstride + 1, den, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (tid == 0) {
+        unsigned *ticket = a.tickets + h;
+        const unsigned t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int last = (t == (unsigned)(sp.nsp - 1));
+        if (last) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        last_flag = last;
+    }
+    __syncthreads();
+    if (!last_flag || qq >= nr) return;
+    float mi[ATT_MAX_SPLITS], di[ATT_MAX_SPLITS];
+    u32x4 oi[ATT_MAX_SPLITS];
+#pragma unroll
+    for (int i = 0; i < ATT_MAX_SPLITS; i++) {
+        const int ii = min(i, sp.nsp - 1);
+        mi[i] = __hip_atomic_load(rmd + (size_t)ii * mstride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        di[i] = __hip_atomic_load(rmd + (size_t)ii * mstride + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+#pragma unroll
+        for (int j = 0; j < 4; j++) oi[i][j] = __hip_atomic_load(ro + (size_t)ii * rstride + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+    float c[ATT_MAX_SPLITS];
+    attn_merge_coeffs(mi, di, sp.nsp, c);
+    half8_t res;
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+        half_t oj[ATT_MAX_SPLITS];
+#pragma unroll
+        for (int i = 0; i < ATT_MAX_SPLITS; i++) oj[i] = __builtin_bit_cast(half8_t, oi[i])[j];
+        res[j] = attn_round_f16(attn_merge_value(oj, c));
+    }
+    *(half8_t *)orow = res;
+}
+
+// S of the launch's grid: as the decode attention of one row (heads x S <= 256 workgroups, at most ATT_MAX_SPLITS, one split per tile of tokens)
+int chunk_attn_grid_splits(int heads, int t_max) { return decode_attn_grid_splits(heads, t_max, 1); }
+
+// active splits of a call whose rows end at token `len` (= p + rows, capped at t_max): what attn_split() gives the kernel
+int chunk_attn_active_splits(int heads, int t_max, int len) { return attn_split(len, chunk_attn_grid_splits(heads, t_max), CA_TPS).nsp; }
+
+static size_t ca_align(size_t n) { return (n + 255) & ~(size_t)255; }
+
+// rotated q [rows][hd] fp16 | records [S][rows][hd] fp16 | {M, den} [S][heads][rows] fp32 x 2 | tickets [heads]
+size_t chunk_attn_ws_bytes(int rows, int heads, int t_max) {
+    const size_t S = (size_t)chunk_attn_grid_splits(heads, t_max), hd = (size_t)heads * CA_HD;
+    return ca_align(rows * hd * sizeof(half_t)) + ca_align(S * rows * hd * sizeof(half_t)) + ca_align(S * heads * rows * 2 * sizeof(float)) +
+           ca_align(heads * sizeof(unsigned));
+}
+
+int chunk_attn_launch(const half_t *qkv, int64_t ldq, int rows, const int64_t *pos, half_t *kc, half_t *vc, half_t *out, int64_t ldo, void *ws,
+                      int heads, int t_max, float base, float scale, const float *rope_table, hipStream_t s) {
+    const int S = chunk_attn_grid_splits(heads, t_max);
+    const size_t hd = (size_t)heads * CA_HD;
+    char *w = (char *)ws;
+    half_t *qrot = (half_t *)w;
+    w += ca_align(rows * hd * sizeof(half_t));
+    ChunkAttnArgs a{};
+    a.o16 = (uint32_t *)w;
+    w += ca_align((size_t)S * rows * hd * sizeof(half_t));
+    a.md = (float *)w;
+    w += ca_align((size_t)S * heads * rows * 2 * sizeof(float));
+    a.tickets = (unsigned *)w;
+    const float inv_base = -2.0f * logf(base) / (float)CA_HD;   // reference fused_attn.py:91
+    hipLaunchKernelGGL(chunk_rope_kv_kernel, dim3(rows, heads), dim3(CA_HD / 2), 0, s, qkv, ldq, pos, kc, vc, qrot, a.tickets, heads, t_max, inv_base,
+                       (const float2 *)rope_table);
+    a.q = qrot; a.pos = pos; a.kc = kc; a.vc = vc; a.out = out;
+    a.heads = heads; a.rows = rows; a.t_max = t_max; a.ldo = ldo;
+    a.scale2 = scale * 1.44269504088896340736f;
+    hipLaunchKernelGGL(chunk_attn_kernel, dim3(heads, S), dim3(CA_NW * 64), 0, s, a);
+    return (int)hipGetLastError();
+}
+
+}  // namespace gptq

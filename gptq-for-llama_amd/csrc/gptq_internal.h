@@ -269,4 +269,12 @@ int prompt_attn_launch(const half_t *qkv, int64_t ldq, int rows, int64_t start, 
 int prompt_attn_batch_launch(const half_t *qkv, int64_t ldq, const gptq_prompt_seg_t *segs, int nseq, half_t *kc, half_t *vc, int64_t slot_stride,
                              half_t *out, int64_t ldo, half_t *ws, int heads, float base, float scale, const float *rope_table, hipStream_t s);
 
+// chunk_attn.hip: RoPE + cache append + causal attention of `rows` (1..16) consecutive tokens at positions *pos .. *pos + rows - 1 (pos in DEVICE
+// memory) over cache rows [0, *pos + rows), the key range cut into splits at run time; ws = chunk_attn_ws_bytes(rows, heads, t_max), no state
+size_t chunk_attn_ws_bytes(int rows, int heads, int t_max);
+int chunk_attn_grid_splits(int heads, int t_max);                  // S of the launch grid
+int chunk_attn_active_splits(int heads, int t_max, int len);      // splits a call whose last row sits at token len - 1 uses
+int chunk_attn_launch(const half_t *qkv, int64_t ldq, int rows, const int64_t *pos, half_t *kc, half_t *vc, half_t *out, int64_t ldo, void *ws,
+                      int heads, int t_max, float base, float scale, const float *rope_table, hipStream_t s);
+
 }  // namespace gptq

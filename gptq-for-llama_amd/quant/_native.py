@@ -158,6 +158,11 @@ _SIGNATURES = {
     # ... of up to 16 segments (a HOST array of PromptSeg) of one packed qkv / out and one cache allocation
     'gptq_prompt_attn_batch_f16': [c_void_p, c_int64, c_int, ctypes.POINTER(PromptSeg), c_int, c_void_p, c_void_p, c_int64, c_void_p, c_int64,
                                    c_void_p, c_size_t, c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p],
+    # speculative decoding: a chunk of consecutive tokens of one sequence, the position in device memory (csrc/chunk_attn.hip)
+    'gptq_decode_attn_chunk_workspace_bytes': [c_int, c_int, c_int, c_int],
+    'gptq_decode_attn_chunk_splits': [c_int, c_int, c_int, c_int],
+    'gptq_decode_attn_chunk_f16': [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_size_t, c_int, c_int, c_int,
+                                   c_float, c_float, c_void_p, c_void_p],
     # scoring: the LM head of many rows with the cross-entropy in the tile GEMM's epilogue (csrc/gemm8.hip); the logits are never written
     'gptq_lm_head_nll_workspace_bytes': [c_int, c_int],
     'gptq_lm_head_nll_f16': [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
@@ -203,6 +208,7 @@ def lib():
             L.gptq_decode_attn_batch_workspace_bytes.restype = c_size_t
             L.gptq_prompt_attn_workspace_bytes.restype = c_size_t
             L.gptq_lm_head_nll_workspace_bytes.restype = c_size_t
+            L.gptq_decode_attn_chunk_workspace_bytes.restype = c_size_t
             L.gptq_layer_destroy.restype = None
             L.gptq_strerror.argtypes = [c_int]
             L.gptq_strerror.restype = ctypes.c_char_p

@@ -207,8 +207,12 @@ def lm_head_logits(eng, x, logits, s):
 
 class DecodeEngine:
 
-    def __init__(self, model, t_max=2048, fuse_norm=True, fuse_attn=True, batch=1):
-        """batch (round 5): rows of a decode BATCH -- B sequences advance by one token per step, every row with its own position and its
+    def __init__(self, model, t_max=2048, fuse_norm=True, fuse_attn=True, batch=1, chunk=0):
+        """chunk = R in 2 .. 16 (batch 1 only) adds the VERIFY step of speculative decoding: R consecutive tokens of the one sequence -- the last
+        accepted token and R - 1 drafts -- go through every layer at M = R in one pass over the weights (verify / accept / capture_verify_greedy,
+        engine_generate(speculate=...)); attention by gptq_decode_attn_chunk_f16 on the engine's own cache.  chunk=0 (the default) allocates
+        nothing and changes nothing.
+        batch (round 5): rows of a decode BATCH -- B sequences advance by one token per step, every row with its own position and its
         own slice of the K/V cache (the reference's one kernel serves any batch, quant_linear.py:263-269; HF generate drives it with
         [B, 1] steps).  The linears run at M = B through gptq_layer_decode_f16 (norm and residual inside the decode kernel's launch up to
         four rows, 16-row MFMA tiles above), attention through gptq_decode_attn_batch_f16, the LM head through gptq_dense_matmat_f16:
@@ -220,6 +224,9 @@ class DecodeEngine:
         self.batch = int(batch)
         if not 1 <= self.batch <= MAX_BATCH:
             raise NotImplementedError('DecodeEngine: batch must be 1 .. %d' % MAX_BATCH)
+        self.chunk = int(chunk)
+        if self.chunk != 0 and (not 2 <= self.chunk <= MAX_BATCH or self.batch != 1):
+            raise ValueError('DecodeEngine: chunk must be 0 or 2 .. %d, and needs batch 1' % MAX_BATCH)
         self.fuse_norm, self.fuse_attn = bool(fuse_norm), bool(fuse_attn)
         self.native = _native
         self.lib = _native.lib()
@@ -292,6 +299,9 @@ class DecodeEngine:
                         raise NotImplementedError('DecodeEngine(batch=%d): a layer has no stripe16 route for %d rows (route %d)' % (B, B, route))
                     need = max(need, self.lib.gptq_layer_decode_scratch_bytes(pl.handle, B))
             self.scratch = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+        self.verify_graph, self.spec_stats = None, None
+        if self.chunk:
+            self._chunk_buffers()
 
     # -- weights: the engine reads the SAME derived copy as the modules -------------------------------------------------------
     # Every linear is taken from quant/layer.py prepared() with exactly the arguments the module's own forward uses, so the eager
@@ -1057,6 +1067,145 @@ class DecodeEngine:
             self.pos.index_copy_(0, rows_t, torch.tensor([st + T for st, T in zip(starts, lens)], dtype=torch.int64, device=self.dev))
         return [nll[o:o + T - 1] for o, T in zip(offs, lens)]
 
+    # -- speculative decoding: R consecutive tokens of the ONE sequence per step (chunk = R) ---------------------------------------------------
+    def _chunk_buffers(self):
+        """[R, .] activations, chunk_ids / chunk_logits, the attention workspace and the decode kernels' scratch for M = R; every layer must have
+        the route the batch > 1 constructor path asks for"""
+        R, H, dev = self.chunk, self.hidden, self.dev
+        need = 0
+        for L in self.layers:
+            for w in (L['qkv'], L['o'], L['gate'], L['down']):
+                pl = w['_keep']
+                route = self.lib.gptq_layer_route_for(pl.handle, R)
+                if route not in (1, 2) and not (pl.kind == 1 and route > 0):     # stripe decode kernel / 16-row tiles on the image
+                    raise NotImplementedError('DecodeEngine(chunk=%d): a layer has no stripe16 route for %d rows (route %d)' % (R, R, route))
+                need = max(need, self.lib.gptq_layer_decode_scratch_bytes(pl.handle, R), self.lib.gptq_layer_decode_scratch_bytes(pl.handle, 1))
+        f16 = dict(dtype=torch.float16, device=dev)
+        self.chunk_ids = torch.zeros(R, dtype=torch.int64, device=dev)
+        self.chunk_logits = torch.zeros((R, self.lm_head.shape[0]), **f16)
+        self.chunk_bufs = dict(x=torch.zeros((R, H), **f16), x2=torch.zeros((R, H), **f16), h=torch.zeros((R, H), **f16),
+                               qkv=torch.zeros((R, 3 * H), **f16), ab=torch.zeros((R, H), **f16), cb=torch.zeros((R, self.cb.shape[1]), **f16))
+        self.chunk_attn_ws = torch.zeros(self.lib.gptq_decode_attn_chunk_workspace_bytes(R, self.heads, self.head_dim, self.t_max),
+                                         dtype=torch.uint8, device=dev)
+        self.scratch = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)      # of gptq_layer_decode_f16 at M = R (and at M = 1: _gemv)
+        # the verify-greedy graph's result, read by the host in ONE copy per step: [a, am[0 .. R - 1]]
+        self.verify_out = torch.zeros(R + 1, dtype=torch.int64, device=dev)
+
+    def _step_chunk(self):
+        """_step_batch at M = R for R consecutive tokens of the one sequence (chunk_ids at positions pos .. pos + R - 1): the same _lin /
+        _lin_next_norm launches, gptq_decode_attn_chunk_f16 on kc[li] / vc[li] with pos[0:1] as the DEVICE position, the LM head for R rows into
+        chunk_logits.  Does not advance pos."""
+        lib = self.lib
+        s = self.native.stream_ptr(self.dev)
+        lws = self.native.layer_workspace(self.dev, s)
+        b = self.chunk_bufs
+        x, x2, h, qkvb, ab, cb = b['x'], b['x2'], b['h'], b['qkv'], b['ab'], b['cb']
+        R = self.chunk
+        torch.index_select(self.embed, 0, self.chunk_ids, out=x)
+        scale = 1.0 / float(np.sqrt(self.head_dim))
+        normed = False
+        for li, L in enumerate(self.layers):
+            if normed:
+                self._lin(L['qkv'], h, qkvb, s, lws)
+            elif self.fuse_norm:
+                self._lin(L['qkv'], x, qkvb, s, lws, norm=L['ln1'])                             # qkv = qkv_proj(rmsnorm(x))
+            else:
+                self._norm_rows(x, L['ln1'], h, s)
+                self._lin(L['qkv'], h, qkvb, s, lws)
+            tab = self._rope_table(L['theta'], s)
+            rc = lib.gptq_decode_attn_chunk_f16(qkvb.data_ptr(), qkvb.stride(0), R, self.pos.data_ptr(), self.kc[li].data_ptr(),
+                                                self.vc[li].data_ptr(), ab.data_ptr(), ab.stride(0), self.chunk_attn_ws.data_ptr(),
+                                                self.chunk_attn_ws.numel(), self.heads, self.head_dim, self.t_max, L['theta'], scale,
+                                                self.native.ptr(tab), s)
+            self.native.check(rc, 'gptq_decode_attn_chunk_f16')
+            self._lin(L['o'], ab, x2, s, lws, residual=x)                                       # x2 = x + o_proj(attn)
+            if self.fuse_norm:
+                self._lin(L['gate'], x2, cb, s, lws, norm=L['ln2'])                             # c = silu(gate(h)) * up(h), h = rmsnorm(x2)
+            else:
+                self._norm_rows(x2, L['ln2'], h, s)
+                self._lin(L['gate'], h, cb, s, lws)
+            if self.fuse_norm and li + 1 < len(self.layers):                                    # x = x2 + down(c) (+ the next block's input norm)
+                normed = self._lin_next_norm(L['down'], cb, x, s, lws, x2, self.layers[li + 1]['ln1'], h)
+            else:
+                self._lin(L['down'], cb, x, s, lws, residual=x2)
+                normed = False
+        saved, self.h = self.h, h                                          # (lm_head_logits norms into self.h when it cannot fuse: R rows)
+        try:
+            lm_head_logits(self, x, self.chunk_logits, s)
+        finally:
+            self.h = saved
+
+    def _need_chunk(self, what):
+        if not self.chunk:
+            raise ValueError('DecodeEngine.%s: the engine was built without chunk=R' % what)
+
+    def verify(self, tokens):
+        """tokens: 1-D, 1 .. R ids -- the last accepted token followed by the drafts -- fed at positions pos .. pos + n - 1.  Returns
+        chunk_logits[:n] (the static buffer: clone it to keep it): row i is the distribution after tokens[:i + 1].  Fewer than R tokens are padded
+        with copies of the last one (their rows are computed and dropped).  pos is unchanged: accept(n) advances it.  Cache rows pos .. pos + R - 1
+        are written; what lies beyond the accepted ones is stale by contract and overwritten by the next step."""
+        self._need_chunk('verify')
+        R = self.chunk
+        t = torch.as_tensor(tokens).reshape(-1) if not (torch.is_tensor(tokens) and tokens.dim() == 1) else tokens
+        n = int(t.numel())
+        if not 1 <= n <= R:
+            raise ValueError('DecodeEngine.verify: 1 .. %d tokens, not %d' % (R, n))
+        pos = int(self.pos[0])
+        if pos + R > self.t_max:
+            raise ValueError('DecodeEngine.verify: positions %d .. %d do not fit the engine cache (%d)' % (pos, pos + R - 1, self.t_max))
+        with torch.no_grad(), torch.cuda.device(self.dev):
+            t = t.to(device=self.dev, dtype=torch.int64)
+            self.chunk_ids[:n].copy_(t)
+            if n < R:
+                self.chunk_ids[n:].copy_(t[n - 1:n].expand(R - n))
+            self._step_chunk()
+        return self.chunk_logits[:n]
+
+    def accept(self, n):
+        """pos += n (1 .. R): the first n tokens of the last verify stay in the cache, the rest is stale"""
+        self._need_chunk('accept')
+        n = int(n)
+        if not 1 <= n <= self.chunk:
+            raise ValueError('DecodeEngine.accept: n must be 1 .. %d, not %d' % (self.chunk, n))
+        pos = int(self.pos[0])
+        if pos + n > self.t_max:
+            raise ValueError('DecodeEngine.accept: position %d beyond the engine cache (%d)' % (pos + n, self.t_max))
+        self.pos.add_(n)
+        return self
+
+    def _verify_greedy_step(self):
+        """_step_chunk and the greedy accept rule, entirely on the device: am = argmax of every row, a = the length of the longest prefix of drafts
+        with am[i] == chunk_ids[i + 1], pos += a + 1; verify_out = [a, am[0 .. R - 1]] (the tokens a step emits are am[0 .. a])"""
+        self._step_chunk()
+        am = torch.argmax(self.chunk_logits, dim=-1)
+        ok = (am[:-1] == self.chunk_ids[1:]).to(torch.int64)
+        a = torch.cumprod(ok, dim=0).sum()
+        self.verify_out[0:1].copy_(a.reshape(1))
+        self.verify_out[1:].copy_(am)
+        self.pos.add_(a + 1)
+
+    def capture_verify_greedy(self):
+        """capture _verify_greedy_step into ONE hipGraph: a replay verifies chunk_ids at the device position and advances it by what was accepted.
+        The capture runs the step once for real at the current position: cache rows pos .. pos + R - 1 of every layer are overwritten (rows at and
+        beyond pos are stale by contract, so the history below pos is intact) and pos, chunk_ids are put back.  ValueError when pos + R > t_max:
+        capture earlier in the sequence, or before the prompt (engine_generate captures at pos = 0, in front of the prefill)."""
+        self._need_chunk('capture_verify_greedy')
+        pos = int(self.pos[0])
+        if pos + self.chunk > self.t_max:
+            raise ValueError('DecodeEngine.capture_verify_greedy: the warm-up step at positions %d .. %d does not fit the engine cache (%d)' % (
+                pos, pos + self.chunk - 1, self.t_max))
+        with torch.no_grad(), torch.cuda.device(self.dev):
+            pos0, ids0 = self.pos.clone(), self.chunk_ids.clone()
+            self._verify_greedy_step()
+            torch.cuda.synchronize(self.dev)
+            self.pos.copy_(pos0); self.chunk_ids.copy_(ids0)
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                self._verify_greedy_step()
+            self.verify_graph = g
+            self.pos.copy_(pos0); self.chunk_ids.copy_(ids0)
+        return self
+
     def decode(self, token):
         """one token per row in ([batch] ids), logits [batch, vocab] out (the static buffer: clone it to keep it)."""
         if torch.is_tensor(token):
@@ -1112,6 +1261,23 @@ def _cache_layer_kv(cache, li):
     return kv[0], kv[1]
 
 
+def _prompt_into_engine(model, input_ids, eng, prefill):
+    """the prompt of engine_generate ([1, T] ids) into the engine's cache, pos = T; returns the logits after its last token.  'engine':
+    DecodeEngine.prefill; 'hf': once through the HF model (the drop-in modules' prefill path), its KV cache copied into the engine's"""
+    T = input_ids.shape[1]
+    if prefill == 'engine':
+        return eng.prefill(input_ids[0], start=0)
+    from transformers.cache_utils import DynamicCache
+    cache = DynamicCache(config=model.config)
+    out = model(input_ids, past_key_values=cache, use_cache=True)
+    for li in range(len(eng.layers)):
+        k, v = _cache_layer_kv(cache, li)
+        eng.kc[li, :T].copy_(k[0].transpose(0, 1).reshape(T, -1))
+        eng.vc[li, :T].copy_(v[0].transpose(0, 1).reshape(T, -1))
+    eng.pos.fill_(T)
+    return out.logits[0, -1]
+
+
 def _sampling_settings(what, sample):
     """the `sample` argument of engine_generate / engine_generate_batch as keywords of DecodeEngine.set_sampling (which validates the values)"""
     if not isinstance(sample, dict):
@@ -1122,7 +1288,57 @@ def _sampling_settings(what, sample):
     return dict(sample)
 
 
-def engine_generate(model, input_ids, max_new_tokens, eos_token_id=None, engine=None, t_max=2048, prefill='hf', sample=None):
+def prompt_lookup_draft(tokens, k, max_ngram=3):
+    """Draft k tokens for speculative decoding from the sequence itself (prompt lookup): find the MOST RECENT earlier occurrence of the last n
+    tokens, trying n = max_ngram down to 1, and propose the tokens that followed it; when that run ends before k tokens (the match sits near the
+    end) the lookup continues from the sequence extended by the proposal; without any match the last token is repeated.  Pure host code:
+    tokens is a list or a numpy array of ids, the result a list of exactly k ints."""
+    seq = list(tokens) if isinstance(tokens, list) else [int(t) for t in (tokens.tolist() if hasattr(tokens, 'tolist') else tokens)]
+    k, max_ngram = int(k), int(max_ngram)
+    if not seq or k < 0 or max_ngram < 1:
+        raise ValueError('prompt_lookup_draft: needs a non-empty sequence, k >= 0 and max_ngram >= 1')
+    out = []
+    while len(out) < k:
+        L = len(seq)
+        rev = seq[::-1]                                          # rev[j] = seq[L - 1 - j]: list.index walks it at C speed
+        last, nmax = rev[0], min(max_ngram, L - 1)
+        # ONE pass over the earlier occurrences of the last token, most recent first: at each, how many tokens in front of it agree with the
+        # tail; the first occurrence that reaches n tokens is the most recent match of the n-gram.  It ends at the first full-length match.
+        best_n, best_j, j = 0, 0, 0
+        while best_n < nmax:
+            try:
+                j = rev.index(last, j + 1)
+            except ValueError:
+                break
+            n = 1
+            while n < nmax and j + n < L and rev[j + n] == rev[n]:
+                n += 1
+            if n > best_n:
+                best_n, best_j = n, j
+        run = seq[L - best_j:L - best_j + (k - len(out))] if best_n else [last]
+        out.extend(run)
+        seq.extend(run)
+    return out
+
+
+def _speculate_settings(speculate):
+    """the `speculate` argument of engine_generate: (k, max_ngram, draft) -- every key optional"""
+    if not isinstance(speculate, dict):
+        raise ValueError('engine_generate: speculate must be None or a dict with the keys k, max_ngram, draft')
+    unknown = sorted(set(speculate) - {'k', 'max_ngram', 'draft'})
+    if unknown:
+        raise ValueError('engine_generate: unknown speculation keys %r' % (unknown,))
+    k, max_ngram, draft = speculate.get('k', 4), speculate.get('max_ngram', 3), speculate.get('draft')
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= MAX_BATCH - 1:
+        raise ValueError('engine_generate: speculate k must be 1 .. %d, not %r' % (MAX_BATCH - 1, k))
+    if isinstance(max_ngram, bool) or not isinstance(max_ngram, int) or max_ngram < 1:
+        raise ValueError('engine_generate: speculate max_ngram must be a positive int, not %r' % (max_ngram,))
+    if draft is not None and not callable(draft):
+        raise ValueError('engine_generate: speculate draft must be a callable (tokens_so_far, k) -> k ids')
+    return k, max_ngram, draft
+
+
+def engine_generate(model, input_ids, max_new_tokens, eos_token_id=None, engine=None, t_max=2048, prefill='hf', sample=None, speculate=None):
     """Greedy generation: the prompt goes through the HF model once (the drop-in modules' prefill path: MFMA GEMMs,
     fused MLP epilogue), its KV cache is copied into the engine's static cache, and every further token is ONE hipGraph
     replay (DecodeEngine).  Returns the full sequence [1, prompt + generated].  Batch 1; the reference equivalent is
@@ -1134,36 +1350,47 @@ def engine_generate(model, input_ids, max_new_tokens, eos_token_id=None, engine=
     sample=dict(temperature=..., top_k=..., top_p=...) (every key optional: DecodeEngine.set_sampling) SAMPLES instead, as the reference's script does
     (llama_inference.py:119-127): the first token is drawn from the prompt's logits by DecodeEngine.sample_logits, every further one by a replay of
     the capture_sample_native graph; the draws follow torch.manual_seed.  temperature 0 gives the greedy tokens.  The settings STAY in the engine's
-    buffers afterwards: a later eng.sample_logits(...) or a replay of the native graph uses them until set_sampling is called again."""
+    buffers afterwards: a later eng.sample_logits(...) or a replay of the native graph uses them until set_sampling is called again.
+    speculate=dict(k=4, max_ngram=3, draft=None) (every key optional) decodes SPECULATIVELY, greedy: per step a draft of k tokens -- from
+    draft(tokens_so_far: list[int], k) -> k ids, by default prompt_lookup_draft -- goes through the model together with the last token as ONE
+    replay of the capture_verify_greedy graph (a DecodeEngine with chunk = k + 1: one pass over the weights), which accepts the longest prefix the
+    greedy rule agrees with and emits one token more; the host reads (accepted, tokens) in one copy per step.  Where fewer than 2 tokens remain or
+    the chunk no longer fits the cache, the single-step greedy graph finishes.  Same return value and eos semantics as the greedy path (the tokens
+    are the greedy ones up to the near ties that any change of the arithmetic's row count moves); eng.spec_stats = dict(steps, emitted,
+    accepted=[per step]) describes the last run.  ValueError: together with sample; k outside 1 .. 15; an engine passed in whose chunk is not
+    k + 1 or whose batch is not 1."""
     if prefill not in ('hf', 'engine'):
         raise ValueError("engine_generate: prefill must be 'hf' or 'engine', not %r" % (prefill,))
     settings = None if sample is None else _sampling_settings('engine_generate', sample)
+    spec = None
+    if speculate is not None:
+        if sample is not None:
+            raise ValueError('engine_generate: speculate and sample exclude each other (greedy speculation only)')
+        spec = _speculate_settings(speculate)
+        if engine is not None and (engine.batch != 1 or engine.chunk != spec[0] + 1):
+            raise ValueError('engine_generate: speculate k = %d needs an engine of batch 1 with chunk = %d (this one: batch %d, chunk %d)' % (
+                spec[0], spec[0] + 1, engine.batch, engine.chunk))
     if input_ids.dim() != 2 or input_ids.shape[0] != 1:
         raise ValueError('engine_generate: batch 1 only')
     dev = input_ids.device
     T = input_ids.shape[1]
-    eng = engine if engine is not None else DecodeEngine(model, t_max=t_max).capture()
+    if engine is not None:
+        eng = engine
+    elif spec is not None:
+        eng = DecodeEngine(model, t_max=t_max, chunk=spec[0] + 1)
+    else:
+        eng = DecodeEngine(model, t_max=t_max).capture()
     if T + max_new_tokens > eng.t_max:
         raise ValueError('engine_generate: prompt + max_new_tokens exceeds the engine cache (%d)' % eng.t_max)
+    if spec is not None:
+        return _engine_generate_speculative(model, input_ids, max_new_tokens, eos_token_id, eng, prefill, *spec)
     if settings is not None:
         if eng.batch != 1:
             raise ValueError('engine_generate: sampling needs an engine of batch 1')
         eng.set_sampling(**settings)
         return _engine_generate_sampled(model, input_ids, max_new_tokens, eos_token_id, eng, prefill)
     with torch.no_grad():
-        if prefill == 'engine':
-            first = eng.prefill(input_ids[0], start=0).argmax().reshape(1)
-        else:
-            from transformers.cache_utils import DynamicCache
-            cache = DynamicCache(config=model.config)
-            out = model(input_ids, past_key_values=cache, use_cache=True)
-            for li in range(len(eng.layers)):
-                k, v = _cache_layer_kv(cache, li)
-                eng.kc[li, :T].copy_(k[0].transpose(0, 1).reshape(T, -1))
-                eng.vc[li, :T].copy_(v[0].transpose(0, 1).reshape(T, -1))
-            eng.pos.fill_(T)
-            first = out.logits[0, -1].argmax().reshape(1)
-            del out, cache
+        first = _prompt_into_engine(model, input_ids, eng, prefill).argmax().reshape(1)
         if eng.greedy_graph is None:
             eng.capture_greedy()
         eng.ids.copy_(first)
@@ -1184,6 +1411,57 @@ def engine_generate(model, input_ids, max_new_tokens, eos_token_id=None, engine=
     return torch.cat([input_ids[0], gen.to(input_ids.dtype)]).unsqueeze(0)
 
 
+def _engine_generate_speculative(model, input_ids, max_new_tokens, eos_token_id, eng, prefill, k, max_ngram, draft):
+    """engine_generate with speculation: prefill as the greedy path -> first token -> (draft; upload chunk_ids; replay the verify-greedy graph; read
+    (a, am); append am[0 .. a]; eos / length cut) until done; the single-step greedy graph where the chunk no longer fits or one token remains"""
+    T, R = input_ids.shape[1], k + 1
+    if draft is None:
+        draft = lambda toks, n: prompt_lookup_draft(toks, n, max_ngram)
+    with torch.no_grad():
+        if eng.verify_graph is None:
+            eng.pos.zero_()                                      # (the capture's warm-up step writes cache rows pos .. pos + R - 1)
+            eng.capture_verify_greedy()
+        first = int(_prompt_into_engine(model, input_ids, eng, prefill).argmax())
+        seq = [int(t) for t in input_ids[0].tolist()] + [first]  # every token so far; the last one is not in the cache yet: pos = len(seq) - 1
+        gen = [first]
+        accepted = []
+        emitted_total = 0
+        hit = eos_token_id is not None and first == eos_token_id
+        while len(gen) < max_new_tokens and not hit:
+            left = max_new_tokens - len(gen)
+            if len(seq) - 1 + R > eng.t_max or left < 2:
+                break
+            d = [int(t) for t in draft(seq, k)]                  # (the draft reads the list, it must not change it)
+            if len(d) != k:
+                raise ValueError('engine_generate: the draft returned %d ids for k = %d' % (len(d), k))
+            eng.chunk_ids.copy_(torch.tensor([seq[-1]] + d, dtype=torch.int64))
+            eng.verify_graph.replay()
+            res = eng.verify_out.tolist()                        # one copy per step: [a, am[0 .. R - 1]]
+            a = res[0]
+            new = res[1:a + 2][:left]                            # the accepted drafts (= am[0 .. a - 1]) and the token after them
+            if eos_token_id is not None and eos_token_id in new:
+                new = new[:new.index(eos_token_id) + 1]
+                hit = True
+            accepted.append(a)
+            emitted_total += len(new)
+            gen.extend(new)
+            seq.extend(new)
+        eng.spec_stats = dict(steps=len(accepted), emitted=emitted_total, accepted=accepted)
+        eng.pos.fill_(len(seq) - 1)                              # (a step cut by the length or an eos advanced the device position further)
+        if not hit and len(gen) < max_new_tokens:                # the tail: single-step greedy replays
+            if eng.greedy_graph is None:
+                eng.capture_greedy()
+            p0, n = len(seq) - 1, max_new_tokens - len(gen)
+            eng.ids.fill_(seq[-1])
+            for _ in range(n):
+                eng.greedy_graph.replay()
+            tail = eng.stream_out[p0 + 1:p0 + 1 + n].tolist()    # stream_out[p] = token generated after p consumed tokens
+            if eos_token_id is not None and eos_token_id in tail:
+                tail = tail[:tail.index(eos_token_id) + 1]
+            gen.extend(tail)
+    return torch.cat([input_ids[0], torch.tensor(gen, dtype=input_ids.dtype, device=input_ids.device)]).unsqueeze(0)
+
+
 def _engine_generate_sampled(model, input_ids, max_new_tokens, eos_token_id, eng, prefill):
     """engine_generate with sampling (the settings are already in the engine): the greedy loop with sample_logits for the first token and the
     capture_sample_native graph -- whose choices land in stream_rows -- for the others"""
@@ -1192,19 +1470,7 @@ def _engine_generate_sampled(model, input_ids, max_new_tokens, eos_token_id, eng
         if eng.sample_native_graph is None:
             eng.pos.zero_()                                      # (the capture's warm-up step writes cache row pos -- and the logits buffer)
             eng.capture_sample_native()
-        if prefill == 'engine':
-            logits = eng.prefill(input_ids[0], start=0)
-        else:
-            from transformers.cache_utils import DynamicCache
-            cache = DynamicCache(config=model.config)
-            out = model(input_ids, past_key_values=cache, use_cache=True)
-            for li in range(len(eng.layers)):
-                k, v = _cache_layer_kv(cache, li)
-                eng.kc[li, :T].copy_(k[0].transpose(0, 1).reshape(T, -1))
-                eng.vc[li, :T].copy_(v[0].transpose(0, 1).reshape(T, -1))
-            eng.pos.fill_(T)
-            logits = out.logits[0, -1].to(torch.float16).contiguous()
-            del out, cache
+        logits = _prompt_into_engine(model, input_ids, eng, prefill).to(torch.float16).contiguous()
         first = eng.sample_logits(logits)
         eng.ids.copy_(first)
         eng.stepc.zero_()                                        # stream_rows[k] = the token chosen by replay k

@@ -583,6 +583,31 @@ int gptq_prompt_attn_batch_f16(const void *qkv, int64_t ldq, int total_rows, con
                                void *v_cache, int64_t slot_stride, void *out, int64_t ldo, void *workspace, size_t workspace_bytes, int heads,
                                int head_dim, int t_max, float base, float scale, const float *rope_table, gptq_stream_t stream);
 
+/* ---- speculative decoding: attention of a CHUNK of a decoding sequence with the position in device memory (csrc/chunk_attn.hip) ----------------
+ * Replaces what HF generate's one-token loop (llama_inference.py:109-115) does R times between qkv_proj and o_proj: `rows` (1 .. 16, a host value: it
+ * shapes the grid) consecutive tokens of ONE sequence -- the last accepted token and its drafts -- sit at positions p .. p + rows - 1 with
+ * p = *position read on the DEVICE, so a captured graph replays the call at any position.  qkv [rows][3 heads 128] (q | k | v, rows ldq apart) is
+ * left untouched; k_cache / v_cache are one slot [t_max][heads 128].  The rotated k and the v of row r go to cache row p + r, bit-identical to what
+ * gptq_decode_rope_kv_f16 and gptq_prompt_attn_f16 write for that row and position (rope_table = NULL computes the trig in the kernel, bit-identical
+ * to the table of gptq_rope_table_f32); out[r] = softmax(scale q_r . K[0 .. p + r]) V[0 .. p + r], causal inside the chunk, fp32 accumulation on
+ * v_mfma_f32_16x16x32_f16, rows ldo apart.  The history [0, p) is streamed ONCE per head for all rows: the key range [0, p + rows) is cut into
+ * gptq_decode_attn_chunk_splits(heads, 128, t_max, p + rows) splits of at least 256 tokens (attn_split.h, at most 8 and at most 256 / heads), each
+ * a workgroup; one split stores the rows itself (one fp16 rounding), several leave {M, den, fp16 o} records in the workspace and the last to arrive
+ * (an arrival ticket, the only atomic) merges them in split order: the same inputs give the same bits on every call.
+ * Cache rows at and beyond p + rows are never loaded and, for row r, nothing above p + r reaches the result: stale or NaN rows behind the chunk
+ * (rejected drafts) are harmless.  p < 0 marks an idle call: no cache row and no output row is read or written.  A row whose position would be
+ * >= t_max is skipped (no cache write, its out row untouched); the rows that fit are served.  No access outside the slot for any *position.
+ * Two launches.  The workspace (gptq_decode_attn_chunk_workspace_bytes; 0 for unsupported shapes) is pure scratch: no initialisation, no state
+ * between calls -- but two calls that may overlap must not share it.
+ * Validated before anything is launched: GPTQ_E_NULL (qkv, position, k_cache, v_cache, out, workspace); GPTQ_E_SHAPE (rows outside 1 .. 16,
+ * heads < 1, head_dim != 128, t_max < 1, ldq < 3 heads 128, ldo < heads 128, workspace_bytes too small); GPTQ_E_ALIGN (qkv / caches / workspace /
+ * out 16 bytes, position and rope_table 8 bytes, ldq / ldo multiples of 8). */
+size_t gptq_decode_attn_chunk_workspace_bytes(int rows, int heads, int head_dim, int t_max);
+int gptq_decode_attn_chunk_splits(int heads, int head_dim, int t_max, int len);   /* active splits of a call with p + rows = len */
+int gptq_decode_attn_chunk_f16(const void *qkv, int64_t ldq, int rows, const int64_t *position, void *k_cache, void *v_cache, void *out, int64_t ldo,
+                               void *workspace, size_t workspace_bytes, int heads, int head_dim, int t_max, float base, float scale,
+                               const float *rope_table, gptq_stream_t stream);
+
 /* ---- scoring: the LM head of MANY rows with the cross-entropy inside (reference llama.py:241-258: lm_head over all rows of a segment, shifted
  * labels, CrossEntropyLoss) -- the [M, N] logits never exist in memory.
  *   x [M, K] (ldx)       fp16, the already normalised hidden rows
