@@ -179,10 +179,12 @@ LM_HEAD_KERNEL = os.environ.get('GPTQ_LM_HEAD_KERNEL', '1') != '0'   # 0: final 
 MAX_BATCH = 16         # rows of a decode batch one engine serves (the LM head kernel and the decode kernel's row groups end there)
 
 
-def lm_head_logits(eng, x, logits, s):
+def lm_head_logits(eng, x, logits, s, h=None):
     """shared by DecodeEngine and TPDecodeEngine: logits[B, rows] = lm_head(rmsnorm(x[B, hidden])) (+ lm_head.bias).  The hand-written
     launch needs an fp16 [rows, hidden] weight with unit column stride whose shape matches the logits buffer (a resized head would write
-    past it: ADVICE r4) -- anything else, or GPTQ_LM_HEAD_KERNEL=0, takes the stand-alone norm + torch.matmul."""
+    past it: ADVICE r4) -- anything else, or GPTQ_LM_HEAD_KERNEL=0, takes the stand-alone norm + torch.matmul.
+    h: the [B, hidden] scratch of the stand-alone norm (default eng.h)."""
+    h = eng.h if h is None else h
     W = eng.lm_head
     bias = getattr(eng, 'lm_head_bias', None)
     B = x.shape[0]
@@ -191,18 +193,18 @@ def lm_head_logits(eng, x, logits, s):
     if ok:
         nw = eng.final_norm if eng.fuse_norm else None
         if nw is None:
-            eng._norm_rows(x, eng.final_norm, eng.h, s)
-        src = x if nw is not None else eng.h
+            eng._norm_rows(x, eng.final_norm, h, s)
+        src = x if nw is not None else h
         rc = eng.lib.gptq_dense_matmat_f16(src.data_ptr(), src.stride(0), W.data_ptr(), W.stride(0), eng.native.ptr(bias), logits.data_ptr(),
                                            logits.stride(0), B, W.shape[0], W.shape[1], eng.native.ptr(nw), eng.eps, s)
         if rc != -6:
             eng.native.check(rc, 'gptq_dense_matmat_f16')
             return
-    eng._norm_rows(x, eng.final_norm, eng.h, s)
+    eng._norm_rows(x, eng.final_norm, h, s)
     if bias is not None:
-        torch.addmm(bias, eng.h, W.t(), out=logits)
+        torch.addmm(bias, h, W.t(), out=logits)
     else:
-        torch.matmul(eng.h, W.t(), out=logits)
+        torch.matmul(h, W.t(), out=logits)
 
 
 class DecodeEngine:
@@ -238,6 +240,7 @@ class DecodeEngine:
         self.hidden = cfg.hidden_size
         self.heads = cfg.num_attention_heads
         self.head_dim = self.hidden // self.heads
+        self.scale = 1.0 / float(np.sqrt(self.head_dim))
         self.eps = float(cfg.rms_norm_eps)
         if self.head_dim != 128:
             raise NotImplementedError('DecodeEngine: head_dim must be 128')
@@ -285,20 +288,13 @@ class DecodeEngine:
         self.ws = _native.workspace(dev)
         self.graph = None
         self.scratch = None
+        self._rope_tabs, self._prefill_bufs, self._nll_ws = {}, None, None      # filled on first use: _rope_table, _prefill_buffers, _nll_rows
         # batch 1: the attention's splits are merged by o_proj's decode kernel when every o_proj can (trivial g_idx, an image, no bias next to the residual)
         self.attn_records = bool(ATTN_RECORDS and self.fuse_attn and B == 1 and all(
             L['o']['st'] is not None and L['o']['bias'] is None and
             self.lib.gptq_layer_decode_attn_supported(L['o']['_keep'].handle, 1, self.heads, self.head_dim) == 1 for L in self.layers))
         if B > 1:
-            need = 0
-            for L in self.layers:
-                for w in (L['qkv'], L['o'], L['gate'], L['down']):
-                    pl = w['_keep']
-                    route = self.lib.gptq_layer_route_for(pl.handle, B)
-                    if route not in (1, 2) and not (pl.kind == 1 and route > 0):     # stripe decode kernel / 16-row tiles on the image
-                        raise NotImplementedError('DecodeEngine(batch=%d): a layer has no stripe16 route for %d rows (route %d)' % (B, B, route))
-                    need = max(need, self.lib.gptq_layer_decode_scratch_bytes(pl.handle, B))
-            self.scratch = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+            self.scratch = self._rows_scratch('batch', (B,))
         self.verify_graph, self.spec_stats = None, None
         if self.chunk:
             self._chunk_buffers()
@@ -359,6 +355,19 @@ class DecodeEngine:
             g['pair_sorted'] = g['srt'] is not None and u['srt'] is not None and bool(torch.equal(g['srt'][1], u['srt'][1]))
         return g, u
 
+    def _rows_scratch(self, what, rows):
+        """the scratch of gptq_layer_decode_f16 for every row count in `rows`; NotImplementedError unless every layer has a stripe16 route for
+        rows[0] (what: 'batch' or 'chunk', for the message)"""
+        M, need = rows[0], 256
+        for L in self.layers:
+            for w in (L['qkv'], L['o'], L['gate'], L['down']):
+                pl = w['_keep']
+                route = self.lib.gptq_layer_route_for(pl.handle, M)
+                if route not in (1, 2) and not (pl.kind == 1 and route > 0):     # stripe decode kernel / 16-row tiles on the image
+                    raise NotImplementedError('DecodeEngine(%s=%d): a layer has no stripe16 route for %d rows (route %d)' % (what, M, M, route))
+                need = max([need] + [self.lib.gptq_layer_decode_scratch_bytes(pl.handle, m) for m in rows])
+        return torch.empty(need, dtype=torch.uint8, device=self.dev)
+
     # -- launches ------------------------------------------------------------------------------
     def _gemv(self, x, w, y, s, residual=None, x_sorted=False):
         """x_sorted: x was written in this layer's group-sorted order by its producer -- no gather (the image IS the sorted rows)"""
@@ -384,8 +393,8 @@ class DecodeEngine:
                                          self.ws.numel(), s)
         self.native.check(rc, 'gptq_matmul248_f16')
 
-    def _norm(self, x, w, y, s):
-        rc = self.lib.gptq_rmsnorm_f16(x.data_ptr(), self.hidden, w.data_ptr(), y.data_ptr(), self.hidden, 1, self.hidden, self.eps, s)
+    def _norm_rows(self, x, w, y, s):
+        rc = self.lib.gptq_rmsnorm_f16(x.data_ptr(), x.stride(0), w.data_ptr(), y.data_ptr(), y.stride(0), x.shape[0], self.hidden, self.eps, s)
         self.native.check(rc, 'gptq_rmsnorm_f16')
 
     def _norm_gemv(self, x, nw, w, y, s):
@@ -409,7 +418,7 @@ class DecodeEngine:
             if rc != -6:   # GPTQ_E_VARIANT: shape needs the generic kernels
                 self.native.check(rc, 'gptq_rmsnorm_matmul248_f16')
                 return
-        self._norm(x, nw, self.h, s)
+        self._norm_rows(x, nw, self.h, s)
         self._gemv(self.h, w, y, s)
 
     def _norm_mlp(self, x, nw, g, u, c, s, out_perm=None):
@@ -420,7 +429,7 @@ class DecodeEngine:
             if self.fuse_norm:
                 quant_linear.stripe_matvec(x, g['st2'], c, g['K'], g['N'], g['bits'], g['gs'], nsets=2, norm_weight=nw, eps=self.eps, perm=perm, out_perm=out_perm)
             else:
-                self._norm(x, nw, self.h, s)
+                self._norm_rows(x, nw, self.h, s)
                 quant_linear.stripe_matvec(self.h, g['st2'], c, g['K'], g['N'], g['bits'], g['gs'], nsets=2, perm=perm, out_perm=out_perm)
             return
         assert out_perm is None
@@ -434,7 +443,7 @@ class DecodeEngine:
                 return
         if g.get('pair_sorted'):
             # act-order MLP: gate and up share the permutation of their common input -> sorted fused kernel
-            self._norm(x, nw, self.h, s)
+            self._norm_rows(x, nw, self.h, s)
             rc = self.lib.gptq_fused_mlp_sorted_f16(self.h.data_ptr(), g['K'], g['srt'][1].data_ptr(), g['srt'][0].data_ptr(),
                                                     g['sc'].data_ptr(), g['qz'].data_ptr(), u['srt'][0].data_ptr(), u['sc'].data_ptr(),
                                                     u['qz'].data_ptr(), c.data_ptr(), g['N'], 1, g['K'], g['N'], g['bits'], g['gs'],
@@ -450,7 +459,7 @@ class DecodeEngine:
             if rc != -6:
                 self.native.check(rc, 'gptq_rmsnorm_fused_mlp_f16')
                 return
-        self._norm(x, nw, self.h, s)
+        self._norm_rows(x, nw, self.h, s)
         rc = self.lib.gptq_fused_mlp_f16(self.h.data_ptr(), g['K'], g['qw'].data_ptr(), g['sc'].data_ptr(), g['qz'].data_ptr(), ptr(g['gi']),
                                          u['qw'].data_ptr(), u['sc'].data_ptr(), u['qz'].data_ptr(), ptr(u['gi']), c.data_ptr(), g['N'], 1,
                                          g['K'], g['N'], g['bits'], g['gs'], self.ws.data_ptr(), self.ws.numel(), s)
@@ -461,7 +470,7 @@ class DecodeEngine:
         evaluate them per token and head.  GPTQ_ROPE_TABLE=0: compute in the attention kernel (A/B runs)."""
         if not ROPE_TABLE:
             return None
-        tabs = self.__dict__.setdefault('_rope_tabs', {})
+        tabs = self._rope_tabs
         t = tabs.get(float(theta))
         if t is None:
             t = torch.empty((self.t_max, self.head_dim // 2, 2), dtype=torch.float32, device=self.dev)
@@ -490,54 +499,54 @@ class DecodeEngine:
         self.native.check(rc, 'gptq_layer_decode_next_norm_f16')
         return bool(done.value)
 
-    def _step_batch(self):
-        lib = self.lib
+    def _step_rows(self, bufs, ids, attn, logits):
+        """one decode step at M = len(ids) rows on the [M, .] activations `bufs` (x, x2, h, qkv, ab, cb): every linear is ONE _lin /
+        _lin_next_norm launch, attention is the caller's attn(li, L, qkv, ab, tab, s), the LM head writes `logits`.  Does not advance pos."""
         s = self.native.stream_ptr(self.dev)
         lws = self.native.layer_workspace(self.dev, s)
-        B, H = self.batch, self.hidden
-        torch.index_select(self.embed, 0, self.ids, out=self.x)
-        scale = 1.0 / float(np.sqrt(self.head_dim))
-        normed = False          # self.h holds rmsnorm(x) * ln1 of this block already (written by the previous block's down_proj: round 6)
+        x, x2, h, qkvb, ab, cb = (bufs[k] for k in ('x', 'x2', 'h', 'qkv', 'ab', 'cb'))
+        torch.index_select(self.embed, 0, ids, out=x)
+        normed = False          # h holds rmsnorm(x) * ln1 of this block already (written by the previous block's down_proj: round 6)
         for li, L in enumerate(self.layers):
             if normed:
-                self._lin(L['qkv'], self.h, self.qkvb, s, lws)
+                self._lin(L['qkv'], h, qkvb, s, lws)
             elif self.fuse_norm:
-                self._lin(L['qkv'], self.x, self.qkvb, s, lws, norm=L['ln1'])                   # qkv = qkv_proj(rmsnorm(x))
+                self._lin(L['qkv'], x, qkvb, s, lws, norm=L['ln1'])                             # qkv = qkv_proj(rmsnorm(x))
             else:
-                self._norm_rows(self.x, L['ln1'], self.h, s)
-                self._lin(L['qkv'], self.h, self.qkvb, s, lws)
-            tab = self._rope_table(L['theta'], s)
-            rc = lib.gptq_decode_attn_batch_f16(self.qkvb.data_ptr(), self.qkvb.stride(0), self.pos.data_ptr(), self.kcb[li].data_ptr(),
-                                                self.vcb[li].data_ptr(), self.ab.data_ptr(), self.ab.stride(0), self.attn_ws.data_ptr(),
-                                                self.attn_ws.numel(), B, self.heads, self.head_dim, self.t_max, L['theta'], scale,
-                                                self.native.ptr(tab), None, s)
-            self.native.check(rc, 'gptq_decode_attn_batch_f16')
-            self._lin(L['o'], self.ab, self.x2, s, lws, residual=self.x)                       # x2 = x + o_proj(attn)
+                self._norm_rows(x, L['ln1'], h, s)
+                self._lin(L['qkv'], h, qkvb, s, lws)
+            attn(li, L, qkvb, ab, self._rope_table(L['theta'], s), s)
+            self._lin(L['o'], ab, x2, s, lws, residual=x)                                       # x2 = x + o_proj(attn)
             if self.fuse_norm:
-                self._lin(L['gate'], self.x2, self.cb, s, lws, norm=L['ln2'])                   # c = silu(gate(h)) * up(h), h = rmsnorm(x2)
+                self._lin(L['gate'], x2, cb, s, lws, norm=L['ln2'])                             # c = silu(gate(h)) * up(h), h = rmsnorm(x2)
             else:
-                self._norm_rows(self.x2, L['ln2'], self.h, s)
-                self._lin(L['gate'], self.h, self.cb, s, lws)
-            if self.fuse_norm and li + 1 < len(self.layers):                                   # x = x2 + down(c) (+ the next block's input norm)
-                normed = self._lin_next_norm(L['down'], self.cb, self.x, s, lws, self.x2, self.layers[li + 1]['ln1'], self.h)
+                self._norm_rows(x2, L['ln2'], h, s)
+                self._lin(L['gate'], h, cb, s, lws)
+            if self.fuse_norm and li + 1 < len(self.layers):                                    # x = x2 + down(c) (+ the next block's input norm)
+                normed = self._lin_next_norm(L['down'], cb, x, s, lws, x2, self.layers[li + 1]['ln1'], h)
             else:
-                self._lin(L['down'], self.cb, self.x, s, lws, residual=self.x2)
+                self._lin(L['down'], cb, x, s, lws, residual=x2)
                 normed = False
-        self._lm_head(s)
-        self.pos.add_(1)
+        lm_head_logits(self, x, logits, s, h)
 
-    def _norm_rows(self, x, w, y, s):
-        rc = self.lib.gptq_rmsnorm_f16(x.data_ptr(), x.stride(0), w.data_ptr(), y.data_ptr(), y.stride(0), x.shape[0], self.hidden, self.eps, s)
-        self.native.check(rc, 'gptq_rmsnorm_f16')
+    def _step_batch(self):
+        """a decode batch: _step_rows at M = batch, gptq_decode_attn_batch_f16 on every row's own cache slice and position"""
+        def attn(li, L, qkvb, ab, tab, s):
+            rc = self.lib.gptq_decode_attn_batch_f16(qkvb.data_ptr(), qkvb.stride(0), self.pos.data_ptr(), self.kcb[li].data_ptr(),
+                                                     self.vcb[li].data_ptr(), ab.data_ptr(), ab.stride(0), self.attn_ws.data_ptr(),
+                                                     self.attn_ws.numel(), self.batch, self.heads, self.head_dim, self.t_max, L['theta'],
+                                                     self.scale, self.native.ptr(tab), None, s)
+            self.native.check(rc, 'gptq_decode_attn_batch_f16')
+        self._step_rows(dict(x=self.x, x2=self.x2, h=self.h, qkv=self.qkvb, ab=self.ab, cb=self.cb), self.ids, attn, self.logits)
+        self.pos.add_(1)
 
     def _step(self):
         if self.batch > 1:
             return self._step_batch()
         lib, ptr = self.lib, self.native.ptr
         s = torch.cuda.current_stream(self.dev).cuda_stream
-        H = self.hidden
         torch.index_select(self.embed, 0, self.ids, out=self.x)
-        scale = 1.0 / float(np.sqrt(self.head_dim))
+        scale = self.scale
         for li, L in enumerate(self.layers):
             self._norm_gemv(self.x, L['ln1'], L['qkv'], self.qkvb, s)       # qkv = qkv_proj(rmsnorm(x))
             # producer-side permutation: o_proj / down_proj of an act-order checkpoint read x in their sorted order -- written that way by the attention /
@@ -556,10 +565,7 @@ class DecodeEngine:
                                                     self.heads, self.head_dim, self.t_max, 0, self.x2.data_ptr(), self.x2.stride(0), self.x.data_ptr(),
                                                     self.x.stride(0), s)                                   # x2 = x + o_proj(merge(records))
                 self.native.check(rc, 'gptq_layer_decode_attn_f16')
-                self._norm_mlp(self.x2, L['ln2'], L['gate'], L['up'], self.cb, s, out_perm=d_inv)
-                self._gemv(self.cb, L['down'], self.x, s, residual=self.x2, x_sorted=d_inv is not None)
-                continue
-            if self.fuse_attn:
+            elif self.fuse_attn:
                 tab = self._rope_table(L['theta'], s)
                 if o_inv is not None:
                     rc = lib.gptq_decode_attn_batch_f16(self.qkvb.data_ptr(), self.qkvb.stride(0), self.pos.data_ptr(), self.kc[li].data_ptr(),
@@ -584,7 +590,8 @@ class DecodeEngine:
                                               self.ab.data_ptr(), self.attn_ws.data_ptr(), self.attn_ws.numel(), self.heads,
                                               self.head_dim, self.t_max, scale, s)
                 self.native.check(rc, 'gptq_decode_attn_f16')
-            self._gemv(self.ab, L['o'], self.x2, s, residual=self.x, x_sorted=o_inv is not None)        # x2 = x + o_proj(attn)
+            if not self.attn_records:
+                self._gemv(self.ab, L['o'], self.x2, s, residual=self.x, x_sorted=o_inv is not None)    # x2 = x + o_proj(attn)
             self._norm_mlp(self.x2, L['ln2'], L['gate'], L['up'], self.cb, s, out_perm=d_inv)
             self._gemv(self.cb, L['down'], self.x, s, residual=self.x2, x_sorted=d_inv is not None)     # x = x2 + down(silu(gate) * up)
         self._lm_head(s)
@@ -606,19 +613,45 @@ class DecodeEngine:
         torch.argmax(self.logits, dim=-1, out=self.ids)
         self.stream_out.index_copy_(0, self.pos, self.ids)
 
-    def capture_greedy(self):
-        """capture the self-feeding greedy step (engine_generate): a replay needs no host input at all."""
-        with torch.no_grad():
-            pos0, ids0 = self.pos.clone(), self.ids.clone()
-            self._greedy_step()
+    def _capture(self, step, state, keep_rng=False):
+        """warm up once (module loads, workspaces), then capture step() into ONE hipGraph and return it.  The tensors of `state` -- what the step
+        advances -- get their present values back behind the warm-up run and behind the capture; keep_rng: torch's CUDA generator, which a
+        sampling step draws from, is put back where it was as well"""
+        with torch.no_grad(), torch.cuda.device(self.dev):
+            rng = torch.cuda.get_rng_state(self.dev) if keep_rng else None
+            saved = [t.clone() for t in state]
+
+            def restore():
+                for t, t0 in zip(state, saved):
+                    t.copy_(t0)
+            step()
             torch.cuda.synchronize(self.dev)
-            self.pos.copy_(pos0); self.ids.copy_(ids0)
+            restore()
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
-                self._greedy_step()
-            self.greedy_graph = g
-            self.pos.copy_(pos0); self.ids.copy_(ids0)
+                step()
+            restore()
+            if keep_rng:
+                torch.cuda.synchronize(self.dev)
+                torch.cuda.set_rng_state(rng, self.dev)
+        return g
+
+    def capture_greedy(self):
+        """capture the self-feeding greedy step (engine_generate): a replay needs no host input at all."""
+        self.greedy_graph = self._capture(self._greedy_step, (self.pos, self.ids))
         return self
+
+    def _stream_buffers(self):
+        """stream_rows / stepc of the self-feeding steps, allocated on first use"""
+        if self.stream_rows is None:
+            self.stream_rows = torch.zeros((self.t_max + 1, self.batch), dtype=torch.int64, device=self.dev)
+            self.stepc = torch.zeros(1, dtype=torch.int64, device=self.dev)
+
+    def _capture_rows(self, step, keep_rng=False):
+        """_capture for the steps that append to stream_rows: the step counter starts at 0, and is 0 again afterwards"""
+        self._stream_buffers()
+        self.stepc.zero_()
+        return self._capture(step, (self.pos, self.ids, self.stepc), keep_rng)
 
     def _greedy_rows_step(self):
         """the self-feeding greedy step for ANY batch: every row's argmax becomes its next input token, and the choices of step n are row n of
@@ -630,20 +663,7 @@ class DecodeEngine:
 
     def capture_greedy_rows(self):
         """capture _greedy_rows_step (quant/engine_hook.py _greedy_fast: greedy model.generate without a host round trip per token)"""
-        with torch.no_grad():
-            if getattr(self, 'stream_rows', None) is None:
-                self.stream_rows = torch.zeros((self.t_max + 1, self.batch), dtype=torch.int64, device=self.dev)
-                self.stepc = torch.zeros(1, dtype=torch.int64, device=self.dev)
-            pos0, ids0 = self.pos.clone(), self.ids.clone()
-            self.stepc.zero_()
-            self._greedy_rows_step()
-            torch.cuda.synchronize(self.dev)
-            self.pos.copy_(pos0); self.ids.copy_(ids0); self.stepc.zero_()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self._greedy_rows_step()
-            self.greedy_rows_graph = g
-            self.pos.copy_(pos0); self.ids.copy_(ids0); self.stepc.zero_()
+        self.greedy_rows_graph = self._capture_rows(self._greedy_rows_step)
         return self
 
     def _sample_rows_step(self, warpers):
@@ -660,23 +680,8 @@ class DecodeEngine:
 
     def capture_sample_rows(self, key, warpers):
         """capture _sample_rows_step for one (temperature, top_k, top_p) setting; the generator's state is put back behind the warm-up run"""
-        with torch.no_grad():
-            if getattr(self, 'stream_rows', None) is None:
-                self.stream_rows = torch.zeros((self.t_max + 1, self.batch), dtype=torch.int64, device=self.dev)
-                self.stepc = torch.zeros(1, dtype=torch.int64, device=self.dev)
-            rng = torch.cuda.get_rng_state(self.dev)
-            pos0, ids0 = self.pos.clone(), self.ids.clone()
-            self.stepc.zero_()
-            self._sample_rows_step(warpers)
-            torch.cuda.synchronize(self.dev)
-            self.pos.copy_(pos0); self.ids.copy_(ids0); self.stepc.zero_()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self._sample_rows_step(warpers)
-            self.pos.copy_(pos0); self.ids.copy_(ids0); self.stepc.zero_()
-            torch.cuda.synchronize(self.dev)
-            torch.cuda.set_rng_state(rng, self.dev)
-            self.sample_graphs = {key: g}          # (one setting at a time: a graph holds the temporaries of a vocabulary-sized sort per row)
+        g = self._capture_rows(lambda: self._sample_rows_step(warpers), keep_rng=True)
+        self.sample_graphs = {key: g}              # (one setting at a time: a graph holds the temporaries of a vocabulary-sized sort per row)
         return g
 
     # -- sampling of the engine's own: gptq_sample_rows_f16 (csrc/sample.hip) with every row's setting in device memory --------------------
@@ -726,12 +731,6 @@ class DecodeEngine:
         self.native.check(rc, 'gptq_sample_rows_f16')
         return out
 
-    def _stream_buffers(self):
-        """stream_rows / stepc of the self-feeding steps, allocated on first use"""
-        if self.stream_rows is None:
-            self.stream_rows = torch.zeros((self.t_max + 1, self.batch), dtype=torch.int64, device=self.dev)
-            self.stepc = torch.zeros(1, dtype=torch.int64, device=self.dev)
-
     def _sample_native_step(self):
         """the self-feeding sampling step of the engine's own, for ANY batch: one decode step, fresh uniforms from torch's CUDA generator (inside a
         graph its Philox offset advances per replay exactly as per eager call), ONE launch that draws every row's next token under that row's
@@ -746,41 +745,19 @@ class DecodeEngine:
     def capture_sample_native(self):
         """capture _sample_native_step ONCE: the settings are device buffers the kernel reads at every replay, so set_sampling never re-captures.
         The generator's state is put back behind the warm-up run, as capture_sample_rows does."""
-        with torch.no_grad():
-            self._stream_buffers()
-            rng = torch.cuda.get_rng_state(self.dev)
-            pos0, ids0 = self.pos.clone(), self.ids.clone()
-            self.stepc.zero_()
-            self._sample_native_step()
-            torch.cuda.synchronize(self.dev)
-            self.pos.copy_(pos0); self.ids.copy_(ids0); self.stepc.zero_()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self._sample_native_step()
-            self.pos.copy_(pos0); self.ids.copy_(ids0); self.stepc.zero_()
-            torch.cuda.synchronize(self.dev)
-            torch.cuda.set_rng_state(rng, self.dev)
-            self.sample_native_graph = g
-        return g
+        self.sample_native_graph = self._capture_rows(self._sample_native_step, keep_rng=True)
+        return self.sample_native_graph
 
     def capture(self):
         """warm up once (module loads, workspace), then capture one decode step into a hipGraph."""
-        with torch.no_grad():
-            self.reset()
-            self._step()
-            torch.cuda.synchronize(self.dev)
-            self.reset()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self._step()
-            self.graph = g
-            self.reset()
+        self.reset()
+        self.graph = self._capture(self._step, (self.pos,))
         return self
 
     # -- a prompt: T tokens of ONE row at M = T, attention by gptq_prompt_attn_f16 on the row's own cache slice -----------------------
     def _prefill_buffers(self, T):
         """activation buffers for M = T rows: allocated on first use, grown when a longer prompt arrives, kept"""
-        pb = self.__dict__.get('_prefill_bufs')
+        pb = self._prefill_bufs
         if pb is None or pb['x'].shape[0] < T:
             H, I = self.hidden, self.cb.shape[1]
             f16 = dict(dtype=torch.float16, device=self.dev)
@@ -790,6 +767,42 @@ class DecodeEngine:
                                      dtype=torch.uint8, device=self.dev))
             self._prefill_bufs = pb
         return pb
+
+    def _prompt_layers(self, ids, attn, s):
+        """every layer at M = len(ids) packed rows on the first M rows of the prefill buffers (_prefill_buffers has been called): embedding,
+        then per layer norm -> qkv -> the caller's attn(li, L, qkv, ab, ws, tab) (RoPE + cache append + causal attention) -> o_proj -> add ->
+        norm -> gate/up -> down -> add.  Returns (x, h): the last block's output and an [M, hidden] scratch."""
+        pb, M = self._prefill_bufs, int(ids.numel())
+        x, x2, h, qkv, ab, cb = (pb[k][:M] for k in ('x', 'x2', 'h', 'qkv', 'ab', 'cb'))
+        torch.index_select(self.embed, 0, ids, out=x)
+
+        def add_rows(y, r):
+            self.native.check(self.lib.gptq_add_rows_f16(y.data_ptr(), y.stride(0), r.data_ptr(), r.stride(0), M, self.hidden, s), 'gptq_add_rows_f16')
+        for li, L in enumerate(self.layers):
+            self._norm_rows(x, L['ln1'], h, s)
+            L['qkv']['_keep'].forward(h, qkv)                                       # qkv = qkv_proj(rmsnorm(x))
+            attn(li, L, qkv, ab, pb['ws'], self._rope_table(L['theta'], s))
+            L['o']['_keep'].forward(ab, x2)
+            add_rows(x2, x)                                                         # x2 = x + o_proj(attn)
+            self._norm_rows(x2, L['ln2'], h, s)
+            L['gate']['_keep'].forward(h, cb)                                       # c = silu(gate(h)) * up(h): the pair's PreparedLayer
+            L['down']['_keep'].forward(cb, x)
+            add_rows(x, x2)                                                         # x = x2 + down(c)
+        return x, h
+
+    def _head_rows(self, last, rows, pos, s):
+        """the end of every prompt call: logits[rows] = lm_head(rmsnorm(last)) and pos[rows] = pos; returns those rows of the static logits buffer.
+        rows an int (prefill, score): the one row is written in place; a list: one LM head launch for all of them, then scattered."""
+        if isinstance(rows, int):
+            lm_head_logits(self, last, self.logits[rows:rows + 1], s)
+            self.pos[rows:rows + 1].fill_(pos)
+            return self.logits[rows]
+        rows_t = torch.tensor(rows, dtype=torch.int64, device=self.dev)
+        logits = torch.empty((len(rows), self.logits.shape[1]), dtype=torch.float16, device=self.dev)
+        lm_head_logits(self, last, logits, s)
+        self.logits.index_copy_(0, rows_t, logits)
+        self.pos.index_copy_(0, rows_t, torch.tensor(pos, dtype=torch.int64, device=self.dev))
+        return self.logits[rows_t]
 
     def prefill(self, input_ids, row=0, start=None):
         """Feed T tokens of ONE sequence (input_ids: int64, 1-D or [1, T]) into cache row `row` at positions start .. start + T - 1 and return
@@ -808,57 +821,36 @@ class DecodeEngine:
         start = int(self.pos[row]) if start is None else int(start)
         if start < 0 or start + T > self.t_max:
             raise ValueError('DecodeEngine.prefill: positions %d .. %d do not fit the engine cache (%d)' % (start, start + T - 1, self.t_max))
-        lib, ptr = self.lib, self.native.ptr
-        scale = 1.0 / float(np.sqrt(self.head_dim))
         with torch.no_grad(), torch.cuda.device(self.dev):
             s = self.native.stream_ptr(self.dev)
-            pb = self._prefill_buffers(T)
-            x, x2, h, qkv, ab, cb = (pb[k][:T] for k in ('x', 'x2', 'h', 'qkv', 'ab', 'cb'))
-            ws = pb['ws']
-            torch.index_select(self.embed, 0, ids.to(device=self.dev, dtype=torch.int64), out=x)
+            self._prefill_buffers(T)
 
-            def add_rows(y, r):
-                self.native.check(lib.gptq_add_rows_f16(y.data_ptr(), y.stride(0), r.data_ptr(), r.stride(0), T, self.hidden, s), 'gptq_add_rows_f16')
-            for li, L in enumerate(self.layers):
-                self._norm_rows(x, L['ln1'], h, s)
-                L['qkv']['_keep'].forward(h, qkv)                                   # qkv = qkv_proj(rmsnorm(x))
-                tab = self._rope_table(L['theta'], s)
-                rc = lib.gptq_prompt_attn_f16(qkv.data_ptr(), qkv.stride(0), T, start, self.kcb[li, row].data_ptr(), self.vcb[li, row].data_ptr(),
-                                              ab.data_ptr(), ab.stride(0), ws.data_ptr(), ws.numel(), self.heads, self.head_dim, self.t_max,
-                                              L['theta'], scale, ptr(tab), s)
+            def attn(li, L, qkv, ab, ws, tab):
+                rc = self.lib.gptq_prompt_attn_f16(qkv.data_ptr(), qkv.stride(0), T, start, self.kcb[li, row].data_ptr(), self.vcb[li, row].data_ptr(),
+                                                   ab.data_ptr(), ab.stride(0), ws.data_ptr(), ws.numel(), self.heads, self.head_dim, self.t_max,
+                                                   L['theta'], self.scale, self.native.ptr(tab), s)
                 self.native.check(rc, 'gptq_prompt_attn_f16')
-                L['o']['_keep'].forward(ab, x2)
-                add_rows(x2, x)                                                     # x2 = x + o_proj(attn)
-                self._norm_rows(x2, L['ln2'], h, s)
-                L['gate']['_keep'].forward(h, cb)                                   # c = silu(gate(h)) * up(h): the pair's PreparedLayer
-                L['down']['_keep'].forward(cb, x)
-                add_rows(x, x2)                                                     # x = x2 + down(c)
-            lm_head_logits(self, x[T - 1:T], self.logits[row:row + 1], s)
-            self.pos[row:row + 1].fill_(start + T)
-        return self.logits[row]
+            x, _ = self._prompt_layers(ids.to(device=self.dev, dtype=torch.int64), attn, s)
+            return self._head_rows(x[T - 1:T], row, start + T, s)
 
-    def prefill_batch(self, prompts, rows=None, starts=None, max_rows=4096):
-        """Feed SEVERAL prompts at once: prompts[i] (1-D int64 ids, any length >= 1, 1 <= len(prompts) <= batch) goes into cache row rows[i]
-        (default 0 .. n - 1; distinct) at positions starts[i] .. starts[i] + T_i - 1 (default 0; a None entry continues at self.pos[row]).
-        Returns self.logits[rows]: the logits after each prompt's last token (the static buffer's rows, as prefill's).  All prompts are packed
-        into one [sum T, hidden] activation and every layer runs ONCE at M = sum T through the launches of prefill -- gptq_rmsnorm_f16, the
-        layer's PreparedLayer, gptq_add_rows_f16 -- with gptq_prompt_attn_batch_f16 (one segment per prompt, two launches) on kcb[li] / vcb[li];
-        the last row of each prompt is gathered and the LM head runs once for those rows.  Above max_rows packed rows the work is done in
-        passes of at most max_rows (the buffers grow to min(sum T, max_rows) rows and are shared with prefill); a prompt that straddles a pass
-        boundary continues in the next pass at its advanced position.  Cache rows and positions of engine rows not named stay as they are.
-        ValueError before anything is launched: an empty prompt, duplicate rows, a row outside the batch, positions beyond t_max.  Not
-        graph-captured; nothing of `transformers` is involved.  Measured against a loop of prefill: profiles/prefill_batch/README.md."""
+    def _packed(self, what, prompts, rows, starts, max_rows, score=False, one_row=False):
+        """prefill_batch (`what`: the public method, for the messages), score and score_batch: prompts[i] enters cache row rows[i] at starts[i] ..,
+        all prompts packed into one activation, in passes of at most max_rows packed rows with ONE segment per prompt and pass; the last row
+        of every prompt goes through _head_rows (one_row: the in-place form of prefill).  score: the ids are range-checked on the host, and
+        behind every pass the final norm and _nll_rows run over all its rows -- the targets are the packed ids shifted by one, so the last row
+        of a pass is scored against the first token of the next, and the last row of every prompt gives 0.  Validates everything (ValueError)
+        before the first launch.  Returns (logits[rows], nll [sum T] float32 or None, offs, lens)."""
         n = len(prompts)
         if not 1 <= n <= self.batch:
-            raise ValueError('DecodeEngine.prefill_batch: %d prompts for an engine of batch %d' % (n, self.batch))
+            raise ValueError('DecodeEngine.%s: %d prompts for an engine of batch %d' % (what, n, self.batch))
         if any((not torch.is_tensor(p)) or p.dim() != 1 or p.numel() == 0 for p in prompts):
-            raise ValueError('DecodeEngine.prefill_batch: every prompt must be a non-empty 1-D tensor of ids')
+            raise ValueError('DecodeEngine.%s: every prompt must be a non-empty 1-D tensor of ids' % what)
         rows = list(range(n)) if rows is None else [int(r) for r in rows]
         if len(rows) != n or len(set(rows)) != n or any(not 0 <= r < self.batch for r in rows):
-            raise ValueError('DecodeEngine.prefill_batch: rows %r must be %d distinct rows of the batch of %d' % (rows, n, self.batch))
+            raise ValueError('DecodeEngine.%s: rows %r must be %d distinct rows of the batch of %d' % (what, rows, n, self.batch))
         starts = [0] * n if starts is None else list(starts)
         if len(starts) != n:
-            raise ValueError('DecodeEngine.prefill_batch: %d starts for %d prompts' % (len(starts), n))
+            raise ValueError('DecodeEngine.%s: %d starts for %d prompts' % (what, len(starts), n))
         if any(st is None for st in starts):
             pos = self.pos.tolist()
             starts = [pos[r] if st is None else st for st, r in zip(starts, rows)]
@@ -866,19 +858,30 @@ class DecodeEngine:
         lens = [int(p.numel()) for p in prompts]
         for st, T in zip(starts, lens):
             if st < 0 or st + T > self.t_max:
-                raise ValueError('DecodeEngine.prefill_batch: positions %d .. %d do not fit the engine cache (%d)' % (st, st + T - 1, self.t_max))
+                raise ValueError('DecodeEngine.%s: positions %d .. %d do not fit the engine cache (%d)' % (what, st, st + T - 1, self.t_max))
         max_rows = int(max_rows)
         if max_rows < 1:
-            raise ValueError('DecodeEngine.prefill_batch: max_rows must be positive')
+            raise ValueError('DecodeEngine.%s: max_rows must be positive' % what)
         total = sum(lens)
         offs = [sum(lens[:i]) for i in range(n)]                                    # first packed row of prompt i
-        lib, ptr, H = self.lib, self.native.ptr, self.hidden
-        scale = 1.0 / float(np.sqrt(self.head_dim))
+        if score:
+            vocab = min(self.embed.shape[0], self.lm_head.shape[0])
+            host = torch.cat([p.detach().reshape(-1).to(device='cpu', dtype=torch.int64) for p in prompts])      # a copy, not a launch
+            if int(host.min()) < 0 or int(host.max()) >= vocab:
+                raise ValueError('DecodeEngine.%s: token ids must lie in [0, %d)' % (what, vocab))
+            shifted = torch.full((total,), -100, dtype=torch.int64)                 # target of packed row r: the next id of the SAME prompt
+            for o, T in zip(offs, lens):
+                shifted[o:o + T - 1] = host[o + 1:o + T]
         with torch.no_grad(), torch.cuda.device(self.dev):
             s = self.native.stream_ptr(self.dev)
-            pb = self._prefill_buffers(min(total, max_rows))
-            ids = torch.cat([p.to(device=self.dev, dtype=torch.int64) for p in prompts])
-            last = torch.empty((n, H), dtype=torch.float16, device=self.dev)        # the final hidden row of every prompt
+            self._prefill_buffers(min(total, max_rows))
+            nll = None
+            if score:
+                ids, targets = host.to(self.dev), shifted.to(self.dev)
+                nll = torch.empty(total, dtype=torch.float32, device=self.dev)
+            else:
+                ids = torch.cat([p.to(device=self.dev, dtype=torch.int64) for p in prompts])
+            last = torch.empty((n, self.hidden), dtype=torch.float16, device=self.dev)      # the final hidden row of every prompt
             slot_stride = self.kcb.stride(1)
             for p0 in range(0, total, max_rows):
                 M = min(total, p0 + max_rows) - p0
@@ -891,36 +894,37 @@ class DecodeEngine:
                         if hi == offs[i] + lens[i]:
                             ends.append((i, hi - 1 - p0))
                 table = (self.native.PromptSeg * len(segs))(*segs)
-                x, x2, h, qkv, ab, cb = (pb[k][:M] for k in ('x', 'x2', 'h', 'qkv', 'ab', 'cb'))
-                ws = pb['ws']
-                torch.index_select(self.embed, 0, ids[p0:p0 + M], out=x)
 
-                def add_rows(y, r):
-                    self.native.check(lib.gptq_add_rows_f16(y.data_ptr(), y.stride(0), r.data_ptr(), r.stride(0), M, H, s), 'gptq_add_rows_f16')
-                for li, L in enumerate(self.layers):
-                    self._norm_rows(x, L['ln1'], h, s)
-                    L['qkv']['_keep'].forward(h, qkv)                               # qkv = qkv_proj(rmsnorm(x))
-                    tab = self._rope_table(L['theta'], s)
-                    rc = lib.gptq_prompt_attn_batch_f16(qkv.data_ptr(), qkv.stride(0), M, table, len(segs), self.kcb[li].data_ptr(),
-                                                        self.vcb[li].data_ptr(), slot_stride, ab.data_ptr(), ab.stride(0), ws.data_ptr(), ws.numel(),
-                                                        self.heads, self.head_dim, self.t_max, L['theta'], scale, ptr(tab), s)
+                def attn(li, L, qkv, ab, ws, tab):
+                    rc = self.lib.gptq_prompt_attn_batch_f16(qkv.data_ptr(), qkv.stride(0), M, table, len(segs), self.kcb[li].data_ptr(),
+                                                             self.vcb[li].data_ptr(), slot_stride, ab.data_ptr(), ab.stride(0), ws.data_ptr(),
+                                                             ws.numel(), self.heads, self.head_dim, self.t_max, L['theta'], self.scale,
+                                                             self.native.ptr(tab), s)
                     self.native.check(rc, 'gptq_prompt_attn_batch_f16')
-                    L['o']['_keep'].forward(ab, x2)
-                    add_rows(x2, x)                                                 # x2 = x + o_proj(attn)
-                    self._norm_rows(x2, L['ln2'], h, s)
-                    L['gate']['_keep'].forward(h, cb)                               # c = silu(gate(h)) * up(h): the pair's PreparedLayer
-                    L['down']['_keep'].forward(cb, x)
-                    add_rows(x, x2)                                                 # x = x2 + down(c)
+                x, h = self._prompt_layers(ids[p0:p0 + M], attn, s)
                 if ends:
                     dst = torch.tensor([i for i, _ in ends], dtype=torch.int64, device=self.dev)
                     src = torch.tensor([r for _, r in ends], dtype=torch.int64, device=self.dev)
                     last.index_copy_(0, dst, x.index_select(0, src))
-            rows_t = torch.tensor(rows, dtype=torch.int64, device=self.dev)
-            logits = torch.empty((n, self.logits.shape[1]), dtype=torch.float16, device=self.dev)
-            lm_head_logits(self, last, logits, s)
-            self.logits.index_copy_(0, rows_t, logits)
-            self.pos.index_copy_(0, rows_t, torch.tensor([st + T for st, T in zip(starts, lens)], dtype=torch.int64, device=self.dev))
-        return self.logits[rows_t]
+                if score:
+                    self._norm_rows(x, self.final_norm, h, s)                       # all rows: the model's final norm in front of the head
+                    self._nll_rows(h, targets[p0:p0 + M], nll[p0:p0 + M], s)
+            new_pos = [st + T for st, T in zip(starts, lens)]
+            logits = self._head_rows(last, rows[0], new_pos[0], s) if one_row else self._head_rows(last, rows, new_pos, s)
+        return logits, nll, offs, lens
+
+    def prefill_batch(self, prompts, rows=None, starts=None, max_rows=4096):
+        """Feed SEVERAL prompts at once: prompts[i] (1-D int64 ids, any length >= 1, 1 <= len(prompts) <= batch) goes into cache row rows[i]
+        (default 0 .. n - 1; distinct) at positions starts[i] .. starts[i] + T_i - 1 (default 0; a None entry continues at self.pos[row]).
+        Returns self.logits[rows]: the logits after each prompt's last token (the static buffer's rows, as prefill's).  All prompts are packed
+        into one [sum T, hidden] activation and every layer runs ONCE at M = sum T through the launches of prefill -- gptq_rmsnorm_f16, the
+        layer's PreparedLayer, gptq_add_rows_f16 -- with gptq_prompt_attn_batch_f16 (one segment per prompt, two launches) on kcb[li] / vcb[li];
+        the last row of each prompt is gathered and the LM head runs once for those rows.  Above max_rows packed rows the work is done in
+        passes of at most max_rows (the buffers grow to min(sum T, max_rows) rows and are shared with prefill); a prompt that straddles a pass
+        boundary continues in the next pass at its advanced position.  Cache rows and positions of engine rows not named stay as they are.
+        ValueError before anything is launched: an empty prompt, duplicate rows, a row outside the batch, positions beyond t_max.  Not
+        graph-captured; nothing of `transformers` is involved.  Measured against a loop of prefill: profiles/prefill_batch/README.md."""
+        return self._packed('prefill_batch', prompts, rows, starts, max_rows)[0]
 
     # -- scoring: how likely was the prompt?  The launches of prefill / prefill_batch, then the LM head of EVERY row with the cross-entropy inside ---
     def _nll_rows(self, h, targets, nll, s):
@@ -934,7 +938,7 @@ class DecodeEngine:
               W.data_ptr() % 16 == 0 and (bias is None or (bias.dtype == torch.float16 and bias.is_contiguous() and bias.data_ptr() % 8 == 0)))
         if ok:
             need = self.lib.gptq_lm_head_nll_workspace_bytes(M, N)
-            ws = self.__dict__.get('_nll_ws')
+            ws = self._nll_ws
             if ws is None or ws.numel() < need:
                 ws = self._nll_ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.dev)
             rc = self.lib.gptq_lm_head_nll_f16(h.data_ptr(), h.stride(0), W.data_ptr(), W.stride(0), self.native.ptr(bias), targets.data_ptr(),
@@ -949,84 +953,6 @@ class DecodeEngine:
             picked = torch.log_softmax(z.float(), dim=-1).gather(1, tc.clamp(min=0)[:, None])[:, 0]
             nll[r0:r0 + chunk] = torch.where(tc < 0, torch.zeros_like(picked), -picked)
 
-    def _score_packed(self, what, prompts, rows, starts, max_rows):
-        """The packed layer loop of prefill_batch with the LM head of every row behind it: prompts[i] enters cache row rows[i] at starts[i] ..,
-        in passes of at most max_rows packed rows.  Returns (nll [sum T] float32 -- row t of a prompt holds -log p(its token t + 1 | tokens <= t),
-        the last row of every prompt 0 --, last [n, hidden]: the final hidden row of every prompt, for the caller's LM-head launch).  The
-        targets are the packed ids shifted by one, so the last row of a pass is scored against the first token of the next.  Validates
-        everything (ValueError) before the first launch; does not touch self.pos / self.logits."""
-        n = len(prompts)
-        rows = [int(r) for r in rows]
-        if len(rows) != n or len(set(rows)) != n or any(not 0 <= r < self.batch for r in rows):
-            raise ValueError('DecodeEngine.%s: rows %r must be %d distinct rows of the batch of %d' % (what, rows, n, self.batch))
-        max_rows = int(max_rows)
-        if max_rows < 1:
-            raise ValueError('DecodeEngine.%s: max_rows must be positive' % what)
-        if any(st is None for st in starts):
-            pos = self.pos.tolist()
-            starts = [pos[r] if st is None else st for st, r in zip(starts, rows)]
-        starts = [int(st) for st in starts]
-        lens = [int(p.numel()) for p in prompts]
-        for st, T in zip(starts, lens):
-            if st < 0 or st + T > self.t_max:
-                raise ValueError('DecodeEngine.%s: positions %d .. %d do not fit the engine cache (%d)' % (what, st, st + T - 1, self.t_max))
-        vocab = min(self.embed.shape[0], self.lm_head.shape[0])
-        host = torch.cat([p.detach().reshape(-1).to(device='cpu', dtype=torch.int64) for p in prompts])      # a copy, not a launch
-        if int(host.min()) < 0 or int(host.max()) >= vocab:
-            raise ValueError('DecodeEngine.%s: token ids must lie in [0, %d)' % (what, vocab))
-        total = sum(lens)
-        offs = [sum(lens[:i]) for i in range(n)]                                    # first packed row of prompt i
-        shifted = torch.full((total,), -100, dtype=torch.int64)                     # target of packed row r: the next id of the SAME prompt
-        for o, T in zip(offs, lens):
-            shifted[o:o + T - 1] = host[o + 1:o + T]
-        lib, ptr, H = self.lib, self.native.ptr, self.hidden
-        scale = 1.0 / float(np.sqrt(self.head_dim))
-        with torch.no_grad(), torch.cuda.device(self.dev):
-            s = self.native.stream_ptr(self.dev)
-            pb = self._prefill_buffers(min(total, max_rows))
-            ids = host.to(self.dev)
-            targets = shifted.to(self.dev)
-            nll = torch.empty(total, dtype=torch.float32, device=self.dev)
-            last = torch.empty((n, H), dtype=torch.float16, device=self.dev)
-            slot_stride = self.kcb.stride(1)
-            for p0 in range(0, total, max_rows):
-                M = min(total, p0 + max_rows) - p0
-                segs, ends = [], []
-                for i in range(n):                                                  # ONE segment per prompt and pass, as prefill_batch
-                    lo, hi = max(offs[i], p0), min(offs[i] + lens[i], p0 + M)
-                    if lo < hi:
-                        segs.append(self.native.PromptSeg(lo - p0, hi - lo, starts[i] + lo - offs[i], rows[i]))
-                        if hi == offs[i] + lens[i]:
-                            ends.append((i, hi - 1 - p0))
-                table = (self.native.PromptSeg * len(segs))(*segs)
-                x, x2, h, qkv, ab, cb = (pb[k][:M] for k in ('x', 'x2', 'h', 'qkv', 'ab', 'cb'))
-                ws = pb['ws']
-                torch.index_select(self.embed, 0, ids[p0:p0 + M], out=x)
-
-                def add_rows(y, r):
-                    self.native.check(lib.gptq_add_rows_f16(y.data_ptr(), y.stride(0), r.data_ptr(), r.stride(0), M, H, s), 'gptq_add_rows_f16')
-                for li, L in enumerate(self.layers):
-                    self._norm_rows(x, L['ln1'], h, s)
-                    L['qkv']['_keep'].forward(h, qkv)
-                    tab = self._rope_table(L['theta'], s)
-                    rc = lib.gptq_prompt_attn_batch_f16(qkv.data_ptr(), qkv.stride(0), M, table, len(segs), self.kcb[li].data_ptr(),
-                                                        self.vcb[li].data_ptr(), slot_stride, ab.data_ptr(), ab.stride(0), ws.data_ptr(), ws.numel(),
-                                                        self.heads, self.head_dim, self.t_max, L['theta'], scale, ptr(tab), s)
-                    self.native.check(rc, 'gptq_prompt_attn_batch_f16')
-                    L['o']['_keep'].forward(ab, x2)
-                    add_rows(x2, x)
-                    self._norm_rows(x2, L['ln2'], h, s)
-                    L['gate']['_keep'].forward(h, cb)
-                    L['down']['_keep'].forward(cb, x)
-                    add_rows(x, x2)
-                if ends:
-                    dst = torch.tensor([i for i, _ in ends], dtype=torch.int64, device=self.dev)
-                    src = torch.tensor([r for _, r in ends], dtype=torch.int64, device=self.dev)
-                    last.index_copy_(0, dst, x.index_select(0, src))
-                self._norm_rows(x, self.final_norm, h, s)                           # all rows: the model's final norm in front of the head
-                self._nll_rows(h, targets[p0:p0 + M], nll[p0:p0 + M], s)
-        return nll, last, starts, lens, offs
-
     def score(self, input_ids, row=0, start=0, max_rows=4096):
         """nll [T - 1] (float32, on the device): nll[t] = -log p(input_ids[t + 1] | input_ids[: t + 1]) -- what the reference's evaluation sums
         (llama.py:241-258: lm_head over all rows, shifted labels, CrossEntropyLoss), as the fp32 cross-entropy of the fp16 logits.  Runs the
@@ -1040,11 +966,7 @@ class DecodeEngine:
             raise ValueError('DecodeEngine.score: input_ids must be a non-empty 1-D or [1, T] tensor')
         if not 0 <= int(row) < self.batch:
             raise ValueError('DecodeEngine.score: row %d outside the batch of %d' % (int(row), self.batch))
-        nll, last, starts, lens, _ = self._score_packed('score', [ids], [row], [start], max_rows)
-        with torch.no_grad(), torch.cuda.device(self.dev):
-            row = int(row)
-            lm_head_logits(self, last, self.logits[row:row + 1], self.native.stream_ptr(self.dev))          # the launch prefill ends with
-            self.pos[row:row + 1].fill_(starts[0] + lens[0])
+        _, nll, _, lens = self._packed('score', [ids], [row], [start], max_rows, score=True, one_row=True)
         return nll[:lens[0] - 1]
 
     def score_batch(self, prompts, rows=None, max_rows=4096):
@@ -1052,19 +974,7 @@ class DecodeEngine:
         position 0 of its cache row (rows[i], default 0 .. n - 1), ONE gptq_lm_head_nll_f16 call per pass over all packed rows.  Returns a list
         of [T_i - 1] float32 tensors (views of one buffer) and leaves the state prefill_batch(prompts, rows) leaves.  ValueError as
         prefill_batch, and for an id outside [0, vocab)."""
-        n = len(prompts)
-        if not 1 <= n <= self.batch:
-            raise ValueError('DecodeEngine.score_batch: %d prompts for an engine of batch %d' % (n, self.batch))
-        if any((not torch.is_tensor(p)) or p.dim() != 1 or p.numel() == 0 for p in prompts):
-            raise ValueError('DecodeEngine.score_batch: every prompt must be a non-empty 1-D tensor of ids')
-        rows = list(range(n)) if rows is None else list(rows)
-        nll, last, starts, lens, offs = self._score_packed('score_batch', prompts, rows, [0] * n, max_rows)
-        with torch.no_grad(), torch.cuda.device(self.dev):
-            rows_t = torch.tensor([int(r) for r in rows], dtype=torch.int64, device=self.dev)
-            logits = torch.empty((n, self.logits.shape[1]), dtype=torch.float16, device=self.dev)
-            lm_head_logits(self, last, logits, self.native.stream_ptr(self.dev))                            # as prefill_batch ends
-            self.logits.index_copy_(0, rows_t, logits)
-            self.pos.index_copy_(0, rows_t, torch.tensor([st + T for st, T in zip(starts, lens)], dtype=torch.int64, device=self.dev))
+        _, nll, offs, lens = self._packed('score_batch', prompts, rows, None, max_rows, score=True)
         return [nll[o:o + T - 1] for o, T in zip(offs, lens)]
 
     # -- speculative decoding: R consecutive tokens of the ONE sequence per step (chunk = R) ---------------------------------------------------
@@ -1072,14 +982,7 @@ class DecodeEngine:
         """[R, .] activations, chunk_ids / chunk_logits, the attention workspace and the decode kernels' scratch for M = R; every layer must have
         the route the batch > 1 constructor path asks for"""
         R, H, dev = self.chunk, self.hidden, self.dev
-        need = 0
-        for L in self.layers:
-            for w in (L['qkv'], L['o'], L['gate'], L['down']):
-                pl = w['_keep']
-                route = self.lib.gptq_layer_route_for(pl.handle, R)
-                if route not in (1, 2) and not (pl.kind == 1 and route > 0):     # stripe decode kernel / 16-row tiles on the image
-                    raise NotImplementedError('DecodeEngine(chunk=%d): a layer has no stripe16 route for %d rows (route %d)' % (R, R, route))
-                need = max(need, self.lib.gptq_layer_decode_scratch_bytes(pl.handle, R), self.lib.gptq_layer_decode_scratch_bytes(pl.handle, 1))
+        self.scratch = self._rows_scratch('chunk', (R, 1))                 # of gptq_layer_decode_f16 at M = R (and at M = 1: _gemv)
         f16 = dict(dtype=torch.float16, device=dev)
         self.chunk_ids = torch.zeros(R, dtype=torch.int64, device=dev)
         self.chunk_logits = torch.zeros((R, self.lm_head.shape[0]), **f16)
@@ -1087,53 +990,19 @@ class DecodeEngine:
                                qkv=torch.zeros((R, 3 * H), **f16), ab=torch.zeros((R, H), **f16), cb=torch.zeros((R, self.cb.shape[1]), **f16))
         self.chunk_attn_ws = torch.zeros(self.lib.gptq_decode_attn_chunk_workspace_bytes(R, self.heads, self.head_dim, self.t_max),
                                          dtype=torch.uint8, device=dev)
-        self.scratch = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)      # of gptq_layer_decode_f16 at M = R (and at M = 1: _gemv)
         # the verify-greedy graph's result, read by the host in ONE copy per step: [a, am[0 .. R - 1]]
         self.verify_out = torch.zeros(R + 1, dtype=torch.int64, device=dev)
 
     def _step_chunk(self):
-        """_step_batch at M = R for R consecutive tokens of the one sequence (chunk_ids at positions pos .. pos + R - 1): the same _lin /
-        _lin_next_norm launches, gptq_decode_attn_chunk_f16 on kc[li] / vc[li] with pos[0:1] as the DEVICE position, the LM head for R rows into
-        chunk_logits.  Does not advance pos."""
-        lib = self.lib
-        s = self.native.stream_ptr(self.dev)
-        lws = self.native.layer_workspace(self.dev, s)
-        b = self.chunk_bufs
-        x, x2, h, qkvb, ab, cb = b['x'], b['x2'], b['h'], b['qkv'], b['ab'], b['cb']
-        R = self.chunk
-        torch.index_select(self.embed, 0, self.chunk_ids, out=x)
-        scale = 1.0 / float(np.sqrt(self.head_dim))
-        normed = False
-        for li, L in enumerate(self.layers):
-            if normed:
-                self._lin(L['qkv'], h, qkvb, s, lws)
-            elif self.fuse_norm:
-                self._lin(L['qkv'], x, qkvb, s, lws, norm=L['ln1'])                             # qkv = qkv_proj(rmsnorm(x))
-            else:
-                self._norm_rows(x, L['ln1'], h, s)
-                self._lin(L['qkv'], h, qkvb, s, lws)
-            tab = self._rope_table(L['theta'], s)
-            rc = lib.gptq_decode_attn_chunk_f16(qkvb.data_ptr(), qkvb.stride(0), R, self.pos.data_ptr(), self.kc[li].data_ptr(),
-                                                self.vc[li].data_ptr(), ab.data_ptr(), ab.stride(0), self.chunk_attn_ws.data_ptr(),
-                                                self.chunk_attn_ws.numel(), self.heads, self.head_dim, self.t_max, L['theta'], scale,
-                                                self.native.ptr(tab), s)
+        """_step_rows at M = R for R consecutive tokens of the one sequence (chunk_ids at positions pos .. pos + R - 1): gptq_decode_attn_chunk_f16
+        on kc[li] / vc[li] with pos[0:1] as the DEVICE position, the LM head for R rows into chunk_logits.  Does not advance pos."""
+        def attn(li, L, qkvb, ab, tab, s):
+            rc = self.lib.gptq_decode_attn_chunk_f16(qkvb.data_ptr(), qkvb.stride(0), self.chunk, self.pos.data_ptr(), self.kc[li].data_ptr(),
+                                                     self.vc[li].data_ptr(), ab.data_ptr(), ab.stride(0), self.chunk_attn_ws.data_ptr(),
+                                                     self.chunk_attn_ws.numel(), self.heads, self.head_dim, self.t_max, L['theta'], self.scale,
+                                                     self.native.ptr(tab), s)
             self.native.check(rc, 'gptq_decode_attn_chunk_f16')
-            self._lin(L['o'], ab, x2, s, lws, residual=x)                                       # x2 = x + o_proj(attn)
-            if self.fuse_norm:
-                self._lin(L['gate'], x2, cb, s, lws, norm=L['ln2'])                             # c = silu(gate(h)) * up(h), h = rmsnorm(x2)
-            else:
-                self._norm_rows(x2, L['ln2'], h, s)
-                self._lin(L['gate'], h, cb, s, lws)
-            if self.fuse_norm and li + 1 < len(self.layers):                                    # x = x2 + down(c) (+ the next block's input norm)
-                normed = self._lin_next_norm(L['down'], cb, x, s, lws, x2, self.layers[li + 1]['ln1'], h)
-            else:
-                self._lin(L['down'], cb, x, s, lws, residual=x2)
-                normed = False
-        saved, self.h = self.h, h                                          # (lm_head_logits norms into self.h when it cannot fuse: R rows)
-        try:
-            lm_head_logits(self, x, self.chunk_logits, s)
-        finally:
-            self.h = saved
+        self._step_rows(self.chunk_bufs, self.chunk_ids, attn, self.chunk_logits)
 
     def _need_chunk(self, what):
         if not self.chunk:
@@ -1194,16 +1063,7 @@ class DecodeEngine:
         if pos + self.chunk > self.t_max:
             raise ValueError('DecodeEngine.capture_verify_greedy: the warm-up step at positions %d .. %d does not fit the engine cache (%d)' % (
                 pos, pos + self.chunk - 1, self.t_max))
-        with torch.no_grad(), torch.cuda.device(self.dev):
-            pos0, ids0 = self.pos.clone(), self.chunk_ids.clone()
-            self._verify_greedy_step()
-            torch.cuda.synchronize(self.dev)
-            self.pos.copy_(pos0); self.chunk_ids.copy_(ids0)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self._verify_greedy_step()
-            self.verify_graph = g
-            self.pos.copy_(pos0); self.chunk_ids.copy_(ids0)
+        self.verify_graph = self._capture(self._verify_greedy_step, (self.pos, self.chunk_ids))
         return self
 
     def decode(self, token):
@@ -1276,6 +1136,15 @@ def _prompt_into_engine(model, input_ids, eng, prefill):
         eng.vc[li, :T].copy_(v[0].transpose(0, 1).reshape(T, -1))
     eng.pos.fill_(T)
     return out.logits[0, -1]
+
+
+def _cut_after_eos(gen, eos_token_id):
+    """the 1-D id tensor gen up to and including its first eos_token_id (None, or not there: all of it)"""
+    if eos_token_id is not None:
+        at = (gen == eos_token_id).nonzero()
+        if at.numel():
+            return gen[:int(at[0]) + 1]
+    return gen
 
 
 def _sampling_settings(what, sample):
@@ -1403,11 +1272,7 @@ def engine_generate(model, input_ids, max_new_tokens, eos_token_id=None, engine=
             done += burst
             if eos_token_id is not None and bool((eng.stream_out[T:T + done] == eos_token_id).any()):
                 break
-        gen = eng.stream_out[T:T + done].clone()
-        if eos_token_id is not None:
-            hit = (gen == eos_token_id).nonzero()
-            if hit.numel():
-                gen = gen[:int(hit[0]) + 1]
+        gen = _cut_after_eos(eng.stream_out[T:T + done].clone(), eos_token_id)
     return torch.cat([input_ids[0], gen.to(input_ids.dtype)]).unsqueeze(0)
 
 
@@ -1483,11 +1348,7 @@ def _engine_generate_sampled(model, input_ids, max_new_tokens, eos_token_id, eng
             if eos_token_id is not None:
                 hit = bool((eng.stream_rows[done - 1:done - 1 + burst, 0] == eos_token_id).any())
             done += burst
-        gen = torch.cat([first, eng.stream_rows[:done - 1, 0]])
-        if eos_token_id is not None:
-            at = (gen == eos_token_id).nonzero()
-            if at.numel():
-                gen = gen[:int(at[0]) + 1]
+        gen = _cut_after_eos(torch.cat([first, eng.stream_rows[:done - 1, 0]]), eos_token_id)
     return torch.cat([input_ids[0], gen.to(input_ids.dtype)]).unsqueeze(0)
 
 
@@ -1542,11 +1403,7 @@ def engine_generate_batch(model, prompts, max_new_tokens, eos_token_id=None, eng
         gen = torch.cat([first.unsqueeze(0), eng.stream_rows[:done - 1]]).t()      # [row][step]
         out = []
         for i, p in enumerate(prompts):
-            g = gen[i]
-            if eos_token_id is not None:
-                at = (g == eos_token_id).nonzero()
-                if at.numel():
-                    g = g[:int(at[0]) + 1]
+            g = _cut_after_eos(gen[i], eos_token_id)
             out.append(torch.cat([p, g.to(device=p.device, dtype=p.dtype)]))
     return out
 

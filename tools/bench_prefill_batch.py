@@ -109,11 +109,11 @@ def step_ttft(lens, model, eng):
         return eng.logits[:B].argmax(dim=-1)
 
     res = dict(step='ttft', lens=lens)
-    eng.__dict__.pop('_prefill_bufs', None)              # every cell pays for its own buffers: the peaks are those of this cell
+    eng._prefill_bufs = None                             # every cell pays for its own buffers: the peaks are those of this cell
     torch.cuda.empty_cache()
     base = torch.cuda.memory_allocated(dev)
     for name, f in (('loop', loop), ('packed', packed)):             # (the loop first: its buffers are the smaller ones)
-        eng.__dict__.pop('_prefill_bufs', None)
+        eng._prefill_bufs = None
         torch.cuda.empty_cache()
         f()
         torch.cuda.synchronize()
