@@ -156,6 +156,55 @@ def test_layer_decode_leaves_the_next_norm_behind(bits, K, N, gs, M):
                                                ws.data_ptr(), ws.numel(), scratch.data_ptr(), scratch.numel(), s) == 0 and done.value == 0
 
 
+@pytest.mark.parametrize('M', [9, 16])
+@pytest.mark.parametrize('K,N', [(11008, 4096), (11008, 256)])
+def test_layer_decode_next_norm_takes_its_own_eps_and_each_rows_rstd(K, N, M):
+    """the combine + next-norm launch on rows whose scales are decades apart (row m of x and of the residual times 2^j, j cycling over
+    -10, -5, 0, 3) with a next-norm weight that is not ~1 and a next-norm eps (1e-5) that differs from the first (1e-6): y the bits of
+    gptq_layer_decode_f16, h the bits of gptq_rmsnorm_f16(y, next weight, 1e-5) -- and NOT those of the same call with 1e-6 (on the 2^-10
+    rows var(y) ~ 2e-5: the two eps values move h by ~20 % there; on unit rows they would round to the same fp16 bits almost everywhere)"""
+    import norm_cases as NC
+    bits, gs = 4, 128
+    Ls = [make_random_layer(bits, gs, K, N, seed=900 + bits)]
+    pl, _keep = _prepared(Ls, gs, K, N, bits)
+    lib = _native.lib()
+    s = _native.stream_ptr(torch.device(DEV))
+    ws = _native.layer_workspace(torch.device(DEV), s)
+    rng = np.random.default_rng(K + N + M)
+    scale = (2.0 ** np.array([-10, -5, 0, 3]))[np.arange(M) % 4][:, None]
+    x = dev((rng.standard_normal((M, K)) * scale).astype(np.float16))
+    res = dev((rng.standard_normal((M, N)) * scale).astype(np.float16))
+    nw = dev(NC.norm_weight(N, rng))
+    scratch = torch.empty(max(lib.gptq_layer_decode_scratch_bytes(pl.handle, M), 256), dtype=torch.uint8, device=DEV)
+    y0 = torch.full((M, N), float('nan'), dtype=torch.float16, device=DEV)
+    rc = lib.gptq_layer_decode_f16(pl.handle, x.data_ptr(), K, y0.data_ptr(), N, M, None, 1e-6, res.data_ptr(), N, ws.data_ptr(), ws.numel(), scratch.data_ptr(),
+                                   scratch.numel(), s)
+    assert rc == 0, rc
+    torch.cuda.synchronize()
+    rms = y0.double().pow(2).mean(1).sqrt().cpu().numpy()
+    assert rms[0::4].max() < 2.0 ** -6 and rms[3::4].min() > 2, rms                # the rows of y span the scales
+    want = {}
+    for eps in (1e-5, 1e-6):
+        want[eps] = torch.empty_like(y0)
+        assert lib.gptq_rmsnorm_f16(y0.data_ptr(), N, nw.data_ptr(), want[eps].data_ptr(), N, M, N, eps, s) == 0
+    got = {}
+    for eps in (1e-5, 1e-6):
+        y = torch.full((M, N), float('nan'), dtype=torch.float16, device=DEV)
+        h = torch.full((M, N), 7.0, dtype=torch.float16, device=DEV)
+        done = ctypes.c_int(-1)
+        rc = lib.gptq_layer_decode_next_norm_f16(pl.handle, x.data_ptr(), K, y.data_ptr(), N, M, None, 1e-6, res.data_ptr(), N, nw.data_ptr(), eps,
+                                                 h.data_ptr(), N, ctypes.byref(done), ws.data_ptr(), ws.numel(), scratch.data_ptr(), scratch.numel(), s)
+        assert rc == 0, rc
+        torch.cuda.synchronize()
+        assert done.value == 1                                                  # LLaMA-7B's down_proj K at 9 .. 16 rows: the combine launch
+        assert torch.equal(y, y0)
+        got[eps] = h
+    assert torch.equal(got[1e-5], want[1e-5])
+    assert torch.equal(got[1e-6], want[1e-6])
+    assert not torch.equal(got[1e-5], got[1e-6])
+    assert not torch.equal(got[1e-5][0::4], got[1e-6][0::4])                    # (the 2^-10 rows are where they differ most)
+
+
 @pytest.mark.parametrize('M', [1, 2, 3, 4, 5, 8, 9, 13, 16])          # 9 .. 16 (round 6): sixteen A rows of the 16x16x16 inner product, one deferred epilogue
 @pytest.mark.parametrize('bits,K,N,gs,NS', [(4, 4096, 12288, 128, 1),      # qkv of LLaMA-7B: 768 stripes = 256 workgroups x 3
                                             (4, 512, 8224, 128, 1),        # 514 stripes: the last workgroup owns ONE stripe
