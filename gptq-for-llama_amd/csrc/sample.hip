@@ -13,117 +13,12 @@
 // C level-2 histogram of top-k's bin (top-k on), D level-2 histogram of top-p's bin (top-p on and another bin than C's), E the draw: a block-wide
 // running sum of the kept weights in ascending token id that stops in the round where it passes u W.
 // Rows need 2-byte alignment only: up to 7 leading and 7 trailing elements are read one by one, everything between as 16-byte vectors.
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdint.h>
-
+// The key, the row scan, the weigher and the wave's select live in sample_common.h, shared with spec_sample.hip.  That header also holds a COPY of
+// the passes A .. E below as functions (select_row, draw_row): an edit to either must be mirrored in the other.
 #include "../../include/gptq_mi355x.h"
-#include "gptq_device.h"
+#include "sample_common.h"
 
 namespace {
-
-typedef unsigned long long u64;
-constexpr int SM_NT = 1024, SM_NW = SM_NT / 64;
-
-// -0 == +0; then negative values in reversed order below the positive ones: a larger logit has a larger key (NaN rows never get this far)
-GPTQ_DEV uint32_t key_of(uint32_t b) {
-    b = (b == 0x8000u) ? 0u : b;
-    return (b & 0x8000u) ? (~b & 0xFFFFu) : (b | 0x8000u);
-}
-GPTQ_DEV float logit_of_key(uint32_t key) {
-    const uint16_t b = (uint16_t)((key & 0x8000u) ? (key & 0x7FFFu) : (~key & 0xFFFFu));
-    return (float)__builtin_bit_cast(half_t, b);
-}
-GPTQ_DEV bool not_finite_above(uint32_t b) { return (b & 0x7FFFu) > 0x7C00u || b == 0x7C00u; }   // NaN or +inf
-
-// f(token id, fp16 bits) for every element of the row, thread `tid` of SM_NT; a thread sees its ids in ascending order
-template <class F>
-GPTQ_DEV void scan_row(const uint16_t *row, int vocab, int tid, F f) {
-    const int head = min(vocab, (int)(((16u - (uint32_t)((uintptr_t)row & 15u)) & 15u) >> 1));
-    if (tid < head) f(tid, (uint32_t)row[tid]);
-    const int nvec = (vocab - head) >> 3;
-    const u32x4 *v = (const u32x4 *)(row + head);
-    for (int i = tid; i < nvec; i += SM_NT) {
-        const u32x4 q = v[i];
-        const int base = head + i * 8;
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            f(base + 2 * j, q[j] & 0xFFFFu);
-            f(base + 2 * j + 1, q[j] >> 16);
-        }
-    }
-    const int t = head + nvec * 8 + tid;
-    if (t < vocab) f(t, (uint32_t)row[t]);
-}
-
-struct Weigher {
-    float lmax, T;
-    double scale;
-    // the token's mass as an integer multiple of 1 / scale; -inf gives exp(-inf) = 0
-    __device__ __forceinline__ u64 operator()(uint32_t key) const {
-        const float w = expf((logit_of_key(key) - lmax) / T);
-        return (u64)((double)w * scale + 0.5);
-    }
-};
-
-// what wave 0 reads off a 256-bin histogram {count, mass}; bins above a bin = the larger keys
-struct Select {
-    int kbin;          // top-k: the bin that holds the k-th largest element
-    uint32_t kcnt;     //   elements above that bin (base included)
-    u64 kabove, kge;   //   mass above that bin / of that bin and above (base included)
-    int pbin;          // top-p: the lowest bin whose top has less than thr above it
-    u64 pabove, pge;
-    u64 total;
-};
-
-// wave 0 only (lane = tid < 64, four bins per lane).  k > 0: the bin with baseC + count above < k <= baseC + count above + own count.
-// thr > 0: the bin with baseM + mass above < thr that is bin 0 or whose own mass brings it to thr.
-GPTQ_DEV void wave_select(const uint32_t *hc, const u64 *hm, uint32_t baseC, u64 baseM, uint32_t k, u64 thr, Select *out, int lane) {
-    uint32_t c[4], ca[4];
-    u64 m[4], ma[4];
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        c[j] = hc[4 * lane + j];
-        m[j] = hm[4 * lane + j];
-    }
-    const uint32_t cs = c[0] + c[1] + c[2] + c[3];
-    const u64 ms = m[0] + m[1] + m[2] + m[3];
-    uint32_t ci = cs;
-    u64 mi = ms;
-    for (int d = 1; d < 64; d <<= 1) {           // inclusive suffix sums over the lanes
-        const uint32_t cn = __shfl_down(ci, d, 64);
-        const u64 mn = __shfl_down(mi, d, 64);
-        if (lane + d < 64) {
-            ci += cn;
-            mi += mn;
-        }
-    }
-    uint32_t cr = baseC + ci - cs;
-    u64 mr = baseM + mi - ms;
-#pragma unroll
-    for (int j = 3; j >= 0; j--) {
-        ca[j] = cr;
-        ma[j] = mr;
-        cr += c[j];
-        mr += m[j];
-    }
-    if (lane == 0) out->total = mr;
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        const int b = 4 * lane + j;
-        if (k > 0 && ca[j] < k && ca[j] + c[j] >= k) {
-            out->kbin = b;
-            out->kcnt = ca[j];
-            out->kabove = ma[j];
-            out->kge = ma[j] + m[j];
-        }
-        if (thr > 0 && ma[j] < thr && (b == 0 || ma[j] + m[j] >= thr)) {
-            out->pbin = b;
-            out->pabove = ma[j];
-            out->pge = ma[j] + m[j];
-        }
-    }
-}
 
 __global__ __launch_bounds__(SM_NT) void sample_rows_kernel(const uint16_t *logits, int64_t ld, int vocab, const float *u, const float *temperature,
                                                             const int32_t *top_k, const float *top_p, int64_t *ids_out) {

@@ -169,6 +169,10 @@ _SIGNATURES = {
                              c_size_t, c_void_p],
     # sampling: one token per row of fp16 logits, temperature / top-k / top-p per row in device memory (csrc/sample.hip)
     'gptq_sample_rows_f16': [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    # speculative sampling: accept / resample for the R rows of one verify step, prefix + pos in the same launch (csrc/spec_sample.hip)
+    'gptq_spec_sample_workspace_bytes': [c_int],
+    'gptq_spec_sample_rows_f16': [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_void_p, c_void_p, c_void_p, c_size_t, c_void_p],
 }
 
 
@@ -209,6 +213,7 @@ def lib():
             L.gptq_prompt_attn_workspace_bytes.restype = c_size_t
             L.gptq_lm_head_nll_workspace_bytes.restype = c_size_t
             L.gptq_decode_attn_chunk_workspace_bytes.restype = c_size_t
+            L.gptq_spec_sample_workspace_bytes.restype = c_size_t
             L.gptq_layer_destroy.restype = None
             L.gptq_strerror.argtypes = [c_int]
             L.gptq_strerror.restype = ctypes.c_char_p

@@ -295,7 +295,8 @@ class DecodeEngine:
             self.lib.gptq_layer_decode_attn_supported(L['o']['_keep'].handle, 1, self.heads, self.head_dim) == 1 for L in self.layers))
         if B > 1:
             self.scratch = self._rows_scratch('batch', (B,))
-        self.verify_graph, self.spec_stats = None, None
+        self.verify_graph, self.verify_sample_graphs, self.spec_stats = None, {}, None
+        self.draft_graph, self._draft_engine = None, None          # capture_draft_step (a draft engine) / (draft model, its engine) of a target engine
         if self.chunk:
             self._chunk_buffers()
 
@@ -688,7 +689,9 @@ class DecodeEngine:
     def set_sampling(self, temperature=1.0, top_k=0, top_p=1.0):
         """the rows' sampling settings: a scalar for all rows or one value per row.  temperature 0 makes a row greedy, top_k 0 and top_p 1 switch
         the filter off.  Only the static device buffers change: a captured graph (capture_sample_native) serves the new setting at its next
-        replay.  ValueError for a temperature that is negative or not finite, a negative top_k, a top_p outside (0, 1]."""
+        replay.  An engine with chunk=R also gets row 0's setting in all R rows of its verify step (capture_verify_sample: the rows are
+        consecutive tokens of the one sequence).  ValueError for a temperature that is negative or not finite, a negative top_k, a top_p outside
+        (0, 1]."""
         B = self.batch
 
         def per_row(name, v, ok):
@@ -706,6 +709,10 @@ class DecodeEngine:
             self.temperature.copy_(torch.tensor(t, dtype=torch.float32))
             self.top_k.copy_(torch.tensor([int(x) for x in k], dtype=torch.int32))
             self.top_p.copy_(torch.tensor(p, dtype=torch.float32))
+            if self.chunk:                           # every row of a verify step decodes the one sequence: row 0's setting
+                self.chunk_temperature.fill_(t[0])
+                self.chunk_top_k.fill_(int(k[0]))
+                self.chunk_top_p.fill_(p[0])
         return self
 
     def sample_logits(self, logits, out=None, u=None):
@@ -992,6 +999,14 @@ class DecodeEngine:
                                          dtype=torch.uint8, device=dev)
         # the verify-greedy graph's result, read by the host in ONE copy per step: [a, am[0 .. R - 1]]
         self.verify_out = torch.zeros(R + 1, dtype=torch.int64, device=dev)
+        # speculative sampling (gptq_spec_sample_rows_f16): the R rows' setting (set_sampling fills them from row 0), their uniforms, the draft
+        # model's logits rows, and the kernel's workspace [ticket, R records] -- zero once, the ticket puts itself back
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.chunk_temperature, self.chunk_top_p = torch.ones(R, **f32), torch.ones(R, **f32)
+        self.chunk_top_k = torch.zeros(R, dtype=torch.int32, device=dev)
+        self.chunk_u_accept, self.chunk_u_draw = torch.zeros(R, **f32), torch.zeros(R, **f32)
+        self.chunk_draft_logits = torch.zeros((R - 1, self.lm_head.shape[0]), **f16)
+        self.spec_ws = torch.zeros(self.lib.gptq_spec_sample_workspace_bytes(R) // 8, dtype=torch.int64, device=dev)
 
     def _step_chunk(self):
         """_step_rows at M = R for R consecutive tokens of the one sequence (chunk_ids at positions pos .. pos + R - 1): gptq_decode_attn_chunk_f16
@@ -1065,6 +1080,103 @@ class DecodeEngine:
                 pos, pos + self.chunk - 1, self.t_max))
         self.verify_graph = self._capture(self._verify_greedy_step, (self.pos, self.chunk_ids))
         return self
+
+    # -- speculative SAMPLING: the verify step followed by the accept / resample rule of gptq_spec_sample_rows_f16 (csrc/spec_sample.hip) -------
+    def _spec_sample_rows(self, draft_logits):
+        """the kernel on chunk_logits / chunk_ids under the chunk rows' setting and the uniforms in chunk_u_accept / chunk_u_draw: verify_out =
+        [a, d_0 .. d_{a-1}, t_a, ..] and pos += a + 1, in one launch"""
+        dl = self.chunk_draft_logits if draft_logits else None
+        with self.native.on_device(self.dev):
+            rc = self.lib.gptq_spec_sample_rows_f16(self.chunk_logits.data_ptr(), self.chunk_logits.stride(0), dl.data_ptr() if draft_logits else None,
+                                                    dl.stride(0) if draft_logits else 0, self.chunk, self.chunk_logits.shape[1],
+                                                    self.chunk_ids.data_ptr(), self.chunk_temperature.data_ptr(), self.chunk_top_k.data_ptr(),
+                                                    self.chunk_top_p.data_ptr(), self.chunk_u_accept.data_ptr(), self.chunk_u_draw.data_ptr(),
+                                                    self.pos.data_ptr(), self.verify_out.data_ptr(), self.spec_ws.data_ptr(),
+                                                    self.spec_ws.numel() * 8, self.native.stream_ptr(self.dev))
+        self.native.check(rc, 'gptq_spec_sample_rows_f16')
+
+    def _verify_sample_step(self, draft_logits=False):
+        """_step_chunk, fresh uniforms from torch's CUDA generator (inside a graph its Philox offset advances per replay as per eager call), the
+        accept / resample launch"""
+        self._step_chunk()
+        self.chunk_u_accept.uniform_()
+        self.chunk_u_draw.uniform_()
+        self._spec_sample_rows(draft_logits)
+
+    def verify_sample(self, tokens, draft_logits=None, u_accept=None, u_draw=None):
+        """Speculative sampling of one step, eagerly.  tokens: 1-D, 2 .. R ids -- the last accepted token followed by the drafts, fed at positions
+        pos .. pos + n - 1 and padded as verify pads (a step of fewer than R tokens runs as R rows; the copies of the last draft behind it can only
+        be accepted after it, and what they emit is dropped).  draft_logits: [n - 1, vocab] fp16 rows the drafts were drawn from under the engine's
+        setting (set_sampling), None: every draft is a point mass.  u_accept / u_draw: float32 [R] on the device; None draws them from torch's CUDA
+        generator.  Returns (a, tokens): a accepted drafts and the a + 1 ids the step emits (a list of ints); pos has advanced by a + 1."""
+        self._need_chunk('verify_sample')
+        R = self.chunk
+        t = torch.as_tensor(tokens).reshape(-1)
+        n = int(t.numel())
+        if not 2 <= n <= R:
+            raise ValueError('DecodeEngine.verify_sample: 2 .. %d tokens, not %d' % (R, n))
+        if draft_logits is not None and (draft_logits.shape != (n - 1, self.chunk_logits.shape[1]) or draft_logits.dtype != torch.float16):
+            raise ValueError('DecodeEngine.verify_sample: draft_logits must be fp16 [%d, %d]' % (n - 1, self.chunk_logits.shape[1]))
+        for name, u in (('u_accept', u_accept), ('u_draw', u_draw)):
+            if u is not None and (u.dtype != torch.float32 or u.shape != (R,)):
+                raise ValueError('DecodeEngine.verify_sample: %s must be float32 [%d]' % (name, R))
+        pos = int(self.pos[0])
+        if pos + R > self.t_max:
+            raise ValueError('DecodeEngine.verify_sample: positions %d .. %d do not fit the engine cache (%d)' % (pos, pos + R - 1, self.t_max))
+        with torch.no_grad(), torch.cuda.device(self.dev):
+            t = t.to(device=self.dev, dtype=torch.int64)
+            self.chunk_ids[:n].copy_(t)
+            if n < R:
+                self.chunk_ids[n:].copy_(t[n - 1:n].expand(R - n))
+            if draft_logits is not None:
+                self.chunk_draft_logits[:n - 1].copy_(draft_logits)
+                if n < R:                                        # a padding row's draft is a point mass: -inf everywhere but at the token
+                    self.chunk_draft_logits[n - 1:].fill_(float('-inf'))
+                    self.chunk_draft_logits[n - 1:].index_fill_(1, t[n - 1:n], 0.0)
+            self._step_chunk()
+            for buf, u in ((self.chunk_u_accept, u_accept), (self.chunk_u_draw, u_draw)):
+                if u is None:
+                    buf.uniform_()
+                else:
+                    buf.copy_(u)
+            self._spec_sample_rows(draft_logits is not None)
+            res = self.verify_out.tolist()
+        a = min(res[0], n - 1)                                   # (padding rows do not count; their tokens are dropped)
+        if a < res[0]:
+            self.pos.fill_(pos + a + 1)
+        return a, res[1:a + 2]
+
+    def capture_verify_sample(self, draft_logits=False):
+        """capture _verify_sample_step into ONE hipGraph: a replay verifies chunk_ids (and, draft_logits=True, reads the static chunk_draft_logits)
+        at the device position, draws fresh uniforms, and leaves [a, tokens] in verify_out with pos advanced.  One capture serves every setting
+        (set_sampling).  The generator's state is put back behind the warm-up run, as capture_sample_native does; the cache contract and the
+        ValueError are capture_verify_greedy's."""
+        self._need_chunk('capture_verify_sample')
+        pos = int(self.pos[0])
+        if pos + self.chunk > self.t_max:
+            raise ValueError('DecodeEngine.capture_verify_sample: the warm-up step at positions %d .. %d does not fit the engine cache (%d)' % (
+                pos, pos + self.chunk - 1, self.t_max))
+        g = self._capture(lambda: self._verify_sample_step(bool(draft_logits)), (self.pos, self.chunk_ids), keep_rng=True)
+        self.verify_sample_graphs[bool(draft_logits)] = g
+        return g
+
+    def _draft_step(self, target):
+        """the self-feeding sampling step of a DRAFT engine (batch 1) in front of `target` (a chunk engine of the same vocabulary): as
+        _sample_native_step, and the step's logits row -- what the token was drawn from -- goes into row stepc of target.chunk_draft_logits"""
+        self._step()
+        target.chunk_draft_logits.index_copy_(0, self.stepc, self.logits)
+        self.u.uniform_()
+        self.sample_logits(self.logits, out=self.ids, u=self.u)
+        self.stream_rows.index_copy_(0, self.stepc, self.ids.unsqueeze(0))
+        self.stepc.add_(1)
+
+    def capture_draft_step(self, target):
+        """capture _draft_step once for `target`: at most target.chunk - 1 replays between two resets of stepc.  ValueError for a batch other than
+        1, a target without chunk rows, or another vocabulary."""
+        if self.batch != 1 or not target.chunk or target.chunk_draft_logits.shape[1] != self.logits.shape[1] or target.dev != self.dev:
+            raise ValueError('DecodeEngine.capture_draft_step: needs a batch-1 engine and a chunk engine of the same vocabulary on one device')
+        self.draft_graph = self._capture_rows(lambda: self._draft_step(target), keep_rng=True)
+        return self.draft_graph
 
     def decode(self, token):
         """one token per row in ([batch] ids), logits [batch, vocab] out (the static buffer: clone it to keep it)."""
@@ -1194,7 +1306,7 @@ def _speculate_settings(speculate):
     """the `speculate` argument of engine_generate: (k, max_ngram, draft) -- every key optional"""
     if not isinstance(speculate, dict):
         raise ValueError('engine_generate: speculate must be None or a dict with the keys k, max_ngram, draft')
-    unknown = sorted(set(speculate) - {'k', 'max_ngram', 'draft'})
+    unknown = sorted(set(speculate) - {'k', 'max_ngram', 'draft', 'sample', 'draft_model'})
     if unknown:
         raise ValueError('engine_generate: unknown speculation keys %r' % (unknown,))
     k, max_ngram, draft = speculate.get('k', 4), speculate.get('max_ngram', 3), speculate.get('draft')
@@ -1205,6 +1317,19 @@ def _speculate_settings(speculate):
     if draft is not None and not callable(draft):
         raise ValueError('engine_generate: speculate draft must be a callable (tokens_so_far, k) -> k ids')
     return k, max_ngram, draft
+
+
+def _speculate_sampling(speculate, model):
+    """the keys of `speculate` that ask for speculative SAMPLING and for a draft MODEL: (sampling settings or None, draft model or None)"""
+    sample, draft_model = speculate.get('sample'), speculate.get('draft_model')
+    settings = None if sample is None else _sampling_settings('engine_generate', sample)
+    if draft_model is not None:
+        if speculate.get('draft') is not None:
+            raise ValueError('engine_generate: speculate takes draft or draft_model, not both')
+        dv, tv = getattr(getattr(draft_model, 'config', None), 'vocab_size', None), model.config.vocab_size
+        if dv != tv:
+            raise ValueError('engine_generate: the draft model has a vocabulary of %r tokens, the model one of %d' % (dv, tv))
+    return settings, draft_model
 
 
 def engine_generate(model, input_ids, max_new_tokens, eos_token_id=None, engine=None, t_max=2048, prefill='hf', sample=None, speculate=None):
@@ -1226,8 +1351,15 @@ def engine_generate(model, input_ids, max_new_tokens, eos_token_id=None, engine=
     greedy rule agrees with and emits one token more; the host reads (accepted, tokens) in one copy per step.  Where fewer than 2 tokens remain or
     the chunk no longer fits the cache, the single-step greedy graph finishes.  Same return value and eos semantics as the greedy path (the tokens
     are the greedy ones up to the near ties that any change of the arithmetic's row count moves); eng.spec_stats = dict(steps, emitted,
-    accepted=[per step]) describes the last run.  ValueError: together with sample; k outside 1 .. 15; an engine passed in whose chunk is not
-    k + 1 or whose batch is not 1."""
+    accepted=[per step]) describes the last run.
+    speculate=dict(..., sample=dict(temperature, top_k, top_p)) SAMPLES speculatively: the capture_verify_sample graph applies the accept /
+    resample rule of gptq_spec_sample_rows_f16 on the device, so the emitted tokens are distributed exactly as engine_generate(sample=...) draws
+    them, whatever the draft; drafts from prompt lookup or `draft` count as point masses; first token by sample_logits, tail by the
+    capture_sample_native graph.  speculate=dict(..., draft_model=<fused model of the same vocabulary>) drafts with a MODEL instead: a batch-1
+    DecodeEngine of its own (kept on the engine) draws the k tokens under the same setting and hands its logits rows to the verify step; without
+    `sample` it drafts greedily and the verify-greedy graph checks it.
+    ValueError: speculate together with the sample ARGUMENT; k outside 1 .. 15; an engine passed in whose chunk is not k + 1 or whose batch is
+    not 1; unknown keys; draft together with draft_model; a draft model of another vocabulary size."""
     if prefill not in ('hf', 'engine'):
         raise ValueError("engine_generate: prefill must be 'hf' or 'engine', not %r" % (prefill,))
     settings = None if sample is None else _sampling_settings('engine_generate', sample)
@@ -1235,7 +1367,7 @@ def engine_generate(model, input_ids, max_new_tokens, eos_token_id=None, engine=
     if speculate is not None:
         if sample is not None:
             raise ValueError('engine_generate: speculate and sample exclude each other (greedy speculation only)')
-        spec = _speculate_settings(speculate)
+        spec = _speculate_settings(speculate) + _speculate_sampling(speculate, model)
         if engine is not None and (engine.batch != 1 or engine.chunk != spec[0] + 1):
             raise ValueError('engine_generate: speculate k = %d needs an engine of batch 1 with chunk = %d (this one: batch %d, chunk %d)' % (
                 spec[0], spec[0] + 1, engine.batch, engine.chunk))
@@ -1276,18 +1408,49 @@ def engine_generate(model, input_ids, max_new_tokens, eos_token_id=None, engine=
     return torch.cat([input_ids[0], gen.to(input_ids.dtype)]).unsqueeze(0)
 
 
-def _engine_generate_speculative(model, input_ids, max_new_tokens, eos_token_id, eng, prefill, k, max_ngram, draft):
-    """engine_generate with speculation: prefill as the greedy path -> first token -> (draft; upload chunk_ids; replay the verify-greedy graph; read
-    (a, am); append am[0 .. a]; eos / length cut) until done; the single-step greedy graph where the chunk no longer fits or one token remains"""
+def _draft_model_engine(eng, draft_model, settings):
+    """the batch-1 engine of the draft model that belongs to the target engine `eng`: built and captured once (plain step, draft step), kept on eng"""
+    kept = eng._draft_engine
+    if kept is None or kept[0] is not draft_model:
+        deng = DecodeEngine(draft_model, t_max=eng.t_max).capture()
+        deng.capture_draft_step(eng)
+        kept = eng._draft_engine = (draft_model, deng)
+    deng = kept[1]
+    deng.set_sampling(**(settings if settings is not None else dict(temperature=0)))
+    return deng
+
+
+def _engine_generate_speculative(model, input_ids, max_new_tokens, eos_token_id, eng, prefill, k, max_ngram, draft, settings=None, draft_model=None):
+    """engine_generate with speculation: prefill as the greedy path -> first token -> (draft; upload chunk_ids; replay the verify graph; read
+    (a, tokens); append the a + 1 tokens; eos / length cut) until done; the single-step graph where the chunk no longer fits or one token remains.
+    settings None: the verify-greedy graph and the greedy tail.  settings: the verify-sample graph -- with the draft model's logits rows when a draft
+    model is given, point-mass drafts otherwise --, the first token by sample_logits, the tail by the capture_sample_native graph.
+    draft_model: a batch-1 DecodeEngine of its own drafts k tokens per step under the same setting (greedily without one): it first consumes the
+    tokens it has not seen (one after a rejection, two after a full accept), its captured step leaves every step's logits row in
+    eng.chunk_draft_logits, and its position is set back behind a rejection."""
     T, R = input_ids.shape[1], k + 1
     if draft is None:
         draft = lambda toks, n: prompt_lookup_draft(toks, n, max_ngram)
     with torch.no_grad():
-        if eng.verify_graph is None:
-            eng.pos.zero_()                                      # (the capture's warm-up step writes cache rows pos .. pos + R - 1)
-            eng.capture_verify_greedy()
-        first = int(_prompt_into_engine(model, input_ids, eng, prefill).argmax())
+        if settings is None:
+            if eng.verify_graph is None:
+                eng.pos.zero_()                                  # (the capture's warm-up step writes cache rows pos .. pos + R - 1)
+                eng.capture_verify_greedy()
+            graph = eng.verify_graph
+        else:
+            eng.set_sampling(**settings)
+            with_q = draft_model is not None
+            if eng.verify_sample_graphs.get(with_q) is None:
+                eng.pos.zero_()
+                eng.capture_verify_sample(draft_logits=with_q)
+            graph = eng.verify_sample_graphs[with_q]
+        deng = None if draft_model is None else _draft_model_engine(eng, draft_model, settings)
+        logits = _prompt_into_engine(model, input_ids, eng, prefill)
+        first = int(logits.argmax()) if settings is None else int(eng.sample_logits(logits.to(torch.float16).contiguous())[0])
         seq = [int(t) for t in input_ids[0].tolist()] + [first]  # every token so far; the last one is not in the cache yet: pos = len(seq) - 1
+        if deng is not None:
+            deng.prefill(input_ids[0], start=0)
+            seen = T                                             # tokens of seq the draft engine has consumed (its position)
         gen = [first]
         accepted = []
         emitted_total = 0
@@ -1296,14 +1459,28 @@ def _engine_generate_speculative(model, input_ids, max_new_tokens, eos_token_id,
             left = max_new_tokens - len(gen)
             if len(seq) - 1 + R > eng.t_max or left < 2:
                 break
-            d = [int(t) for t in draft(seq, k)]                  # (the draft reads the list, it must not change it)
-            if len(d) != k:
-                raise ValueError('engine_generate: the draft returned %d ids for k = %d' % (len(d), k))
-            eng.chunk_ids.copy_(torch.tensor([seq[-1]] + d, dtype=torch.int64))
-            eng.verify_graph.replay()
-            res = eng.verify_out.tolist()                        # one copy per step: [a, am[0 .. R - 1]]
+            if deng is None:
+                d = [int(t) for t in draft(seq, k)]              # (the draft reads the list, it must not change it)
+                if len(d) != k:
+                    raise ValueError('engine_generate: the draft returned %d ids for k = %d' % (len(d), k))
+                eng.chunk_ids.copy_(torch.tensor([seq[-1]] + d, dtype=torch.int64))
+            else:
+                L = len(seq)
+                deng.pos.fill_(seen)
+                for t in seq[seen:L - 1]:                        # what it has not seen yet, but for the last token: plain steps
+                    deng.decode(t)
+                deng.ids.fill_(seq[-1])
+                deng.stepc.zero_()
+                for _ in range(k):                               # consumes seq[-1], d_1 .. d_{k-1}; draws d_1 .. d_k
+                    deng.draft_graph.replay()
+                eng.chunk_ids[0:1].fill_(seq[-1])
+                eng.chunk_ids[1:].copy_(deng.stream_rows[:k, 0])
+            graph.replay()
+            res = eng.verify_out.tolist()                        # one copy per step: [a, the a + 1 tokens of the step, ...]
             a = res[0]
-            new = res[1:a + 2][:left]                            # the accepted drafts (= am[0 .. a - 1]) and the token after them
+            if deng is not None:
+                seen = len(seq) - 1 + min(a + 1, k)              # behind a rejection its later rows are stale
+            new = res[1:a + 2][:left]                            # the accepted drafts and the token after them
             if eos_token_id is not None and eos_token_id in new:
                 new = new[:new.index(eos_token_id) + 1]
                 hit = True
@@ -1313,14 +1490,23 @@ def _engine_generate_speculative(model, input_ids, max_new_tokens, eos_token_id,
             seq.extend(new)
         eng.spec_stats = dict(steps=len(accepted), emitted=emitted_total, accepted=accepted)
         eng.pos.fill_(len(seq) - 1)                              # (a step cut by the length or an eos advanced the device position further)
-        if not hit and len(gen) < max_new_tokens:                # the tail: single-step greedy replays
-            if eng.greedy_graph is None:
-                eng.capture_greedy()
+        if not hit and len(gen) < max_new_tokens:                # the tail: single-step replays
             p0, n = len(seq) - 1, max_new_tokens - len(gen)
-            eng.ids.fill_(seq[-1])
-            for _ in range(n):
-                eng.greedy_graph.replay()
-            tail = eng.stream_out[p0 + 1:p0 + 1 + n].tolist()    # stream_out[p] = token generated after p consumed tokens
+            if settings is None:
+                if eng.greedy_graph is None:
+                    eng.capture_greedy()
+                eng.ids.fill_(seq[-1])
+                for _ in range(n):
+                    eng.greedy_graph.replay()
+                tail = eng.stream_out[p0 + 1:p0 + 1 + n].tolist()    # stream_out[p] = token generated after p consumed tokens
+            else:
+                if eng.sample_native_graph is None:
+                    eng.capture_sample_native()                  # (its warm-up step writes cache row pos, which the tail overwrites first)
+                eng.ids.fill_(seq[-1])
+                eng.stepc.zero_()
+                for _ in range(n):
+                    eng.sample_native_graph.replay()
+                tail = eng.stream_rows[:n, 0].tolist()
             if eos_token_id is not None and eos_token_id in tail:
                 tail = tail[:tail.index(eos_token_id) + 1]
             gen.extend(tail)

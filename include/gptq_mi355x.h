@@ -649,6 +649,42 @@ int gptq_lm_head_nll_f16(const void *x, int64_t ldx, const void *weight, int64_t
 int gptq_sample_rows_f16(const void *logits, int64_t ld, int rows, int vocab, const float *u, const float *temperature, const int32_t *top_k,
                          const float *top_p, int64_t *ids_out, gptq_stream_t stream);
 
+/* ---- speculative sampling: the accept / resample rule for one verify step of `rows` = R >= 2 rows in ONE launch (csrc/spec_sample.hip), one
+ * workgroup per row.  The emitted tokens are distributed exactly as the target's, whatever the draft.
+ *   logits [R, vocab] (ld)           fp16 target logits: row i is the distribution after ids[0 .. i]; 2-byte alignment, ld >= vocab
+ *   draft_logits [R - 1, vocab]      fp16 (ld_draft >= vocab): row i is what ids[i + 1] was drawn from.  NULL: every draft is a point mass
+ *   ids                              device int64 [R]: ids[0] the last accepted token, ids[1 .. R - 1] the drafts
+ *   temperature, top_p, top_k        device float / float / int32 [R], sanitised as gptq_sample_rows_f16 does
+ *   u_accept, u_draw                 device float [R], clamped as u there (u_accept[R - 1] is not used)
+ *   pos                              device int64 [1], advanced by the launch
+ *   out                              device int64 [R + 1]
+ *   workspace                        gptq_spec_sample_workspace_bytes(R) bytes, 8-byte aligned: int64 [R + 1].  Word 0 is the arrival ticket: ZERO
+ *                                    before the first launch, it puts itself back to zero (a captured graph replays).  Word 1 + i is row i's
+ *                                    record, left there for inspection: bit 32 = the row accepted, the low 32 bits = its token (below)
+ * Row i, with p the target row's probabilities under the row's setting -- gptq_sample_rows_f16's classes, all ties kept, top-p on what top-k kept
+ * -- d = ids[i + 1], and q the same of draft row i under the SAME setting, or one-hot at d without draft logits:
+ *   accept    (i < R - 1) iff u_accept[i] q(d) < p(d): a draft outside p's kept set (or outside [0, vocab)) never survives, one with
+ *             p(d) >= q(d) always does.  The row's token is d.
+ *   reject    the row's token is the first id, ascending, whose running sum of r = max(p - q, 0) exceeds u_draw[i] sum(r); if sum(r) is 0
+ *             (impossible in exact arithmetic) the first maximal target logit
+ *   bonus     row R - 1 never accepts; its token is gptq_sample_rows_f16's for that row with u = u_draw[R - 1], to the bit
+ *   greedy    a greedy row (temperature 0 or not finite) accepts iff d is the first maximal target logit, and that index is its token
+ *   non-finite  a target or draft row with a NaN or +inf -- or a draft row of -inf only -- rejects; the token is what gptq_sample_rows_f16 gives
+ *             for the target row with u = u_draw[i]
+ * Result: a = the number of leading accepting rows among 0 .. R - 2; out = [a, d_0 .. d_{a-1}, t_a, then copies of t_a]; pos[0] += a + 1.  Every
+ * id written is in [0, vocab).  The prefix, out and pos are written in the same launch by the workgroup that arrives last.
+ * Arithmetic: p and q are the integer masses of gptq_sample_rows_f16 (same kept set, same bits).  A token's mass goes onto a scale common to both
+ * rows by the row's factor c_p = 2^S / W_p (one IEEE double division per row): P(x) = floor(m_p(x) c_p + 1/2), one double multiplication per
+ * token, S = 40 (62 - ceil(log2 vocab) above 2^22 tokens), Q likewise (2^S for
+ * a point mass); the test is u Q(d) < P(d) in doubles, r = max(P - Q, 0) in integers, the draw gptq_sample_rows_f16's on r.  All sums are integer
+ * sums: the same inputs give the same bits on every call.
+ * Validated before the launch: GPTQ_E_NULL (any pointer but draft_logits, reported first), GPTQ_E_SHAPE (rows < 2, vocab < 1, ld < vocab,
+ * ld_draft < vocab with draft logits), GPTQ_E_WORKSPACE, GPTQ_E_ALIGN (logits 2 bytes, float / int32 arrays 4, int64 arrays and workspace 8). */
+size_t gptq_spec_sample_workspace_bytes(int rows);
+int gptq_spec_sample_rows_f16(const void *logits, int64_t ld, const void *draft_logits, int64_t ld_draft, int rows, int vocab, const int64_t *ids,
+                              const float *temperature, const int32_t *top_k, const float *top_p, const float *u_accept, const float *u_draw,
+                              int64_t *pos, int64_t *out, void *workspace, size_t workspace_bytes, gptq_stream_t stream);
+
 /* ---- GPTQ solver (the caller that PRODUCES the weights; reference gptq.py:128-228) -------------------------------
  * One column block [i1, i1 + count), count <= 128, of the sequential quantise / error-feedback loop (gptq.py:177-199)
  * for all rows at once, in the reference's own fp32 arithmetic (IEEE division, round-half-even, no contraction).
