@@ -1073,6 +1073,28 @@ int gptq_decode_attn_chunk_f16(const void *qkv, int64_t ldq, int rows, const int
                              t_max, base, scale, rope_table, (hipStream_t)stream);
 }
 
+/* the same for `seqs` (1 .. 16) decoding sequences in the same two launches: sequence b owns packed rows b rows .. b rows + rows - 1 of qkv / out, cache
+ * slot b (slot_stride elements apart) and positions[b], read on the device -- the verify step of batched speculative decoding */
+size_t gptq_decode_attn_chunk_batch_workspace_bytes(int seqs, int rows, int heads, int head_dim, int t_max) {
+    if (seqs < 1 || seqs > 16 || rows < 1 || rows > 16 || seqs * rows > 128 || heads <= 0 || heads > 65535 || head_dim != 128 || t_max <= 0) return 0;
+    return chunk_attn_batch_ws_bytes(seqs, rows, heads, t_max);
+}
+
+int gptq_decode_attn_chunk_batch_f16(const void *qkv, int64_t ldq, int seqs, int rows, const int64_t *positions, void *k_cache, void *v_cache,
+                                     int64_t slot_stride, void *out, int64_t ldo, void *workspace, size_t workspace_bytes, int heads, int head_dim,
+                                     int t_max, float base, float scale, const float *rope_table, gptq_stream_t stream) {
+    if (!qkv || !positions || !k_cache || !v_cache || !out || !workspace) return GPTQ_E_NULL;
+    if (seqs < 1 || seqs > 16 || rows < 1 || rows > 16 || seqs * rows > 128 || heads <= 0 || heads > 65535 || head_dim != 128 || t_max <= 0 ||
+        ldq < 3 * (int64_t)heads * head_dim || ldo < (int64_t)heads * head_dim || slot_stride < (int64_t)t_max * heads * head_dim)
+        return GPTQ_E_SHAPE;
+    if (!aligned(qkv, 16) || !aligned(positions, 8) || !aligned(k_cache, 16) || !aligned(v_cache, 16) || !aligned(workspace, 16) ||
+        (rope_table && !aligned(rope_table, 8)) || ldq % 8 != 0 || ldo % 8 != 0 || slot_stride % 8 != 0 || !aligned(out, 16))
+        return GPTQ_E_ALIGN;
+    if (workspace_bytes < chunk_attn_batch_ws_bytes(seqs, rows, heads, t_max)) return GPTQ_E_SHAPE;   /* (with the shapes, as the chunk entry) */
+    return chunk_attn_batch_launch((const half_t *)qkv, ldq, seqs, rows, positions, (half_t *)k_cache, (half_t *)v_cache, slot_stride, (half_t *)out, ldo,
+                                   workspace, heads, t_max, base, scale, rope_table, (hipStream_t)stream);
+}
+
 /* scoring (csrc/gemm8.hip, cross-entropy epilogue): everything is checked here, before the first launch */
 size_t gptq_lm_head_nll_workspace_bytes(int M, int N) {
     if (M <= 0 || N <= 0) return 0;

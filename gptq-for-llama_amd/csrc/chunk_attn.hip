@@ -25,6 +25,9 @@
 //      records in split order with the shared attn_merge_* helpers -- the ticket decides who merges, never what is computed: same inputs, same bits.
 // Bounds: keys at and beyond min(p + rows, t_max) are never loaded (their slots of a tile are zeros); for row r everything above p + r is masked by a
 // select before the maximum.  p < 0 or p >= t_max: nothing is read or written.  A row whose position is >= t_max is skipped.
+// Several sequences (batched speculative decoding): both grids get the sequence b as blockIdx.z -- its packed rows b rows .. of qkv / out, its cache
+// slot, its position pos[b], its part of the workspace, its tickets -- and nothing else changes: per sequence the same instructions on the same
+// values as a single-sequence call (which is the seqs = 1 case), hence the same bits; still two launches for any number of sequences.
 #include <algorithm>
 
 #include "attn_split.h"
@@ -40,14 +43,14 @@ constexpr int CA_QR = 16;      // query rows of the MFMA (rows padded to it)
 constexpr int CA_TPS = 256;    // tokens a split owns at least: 8 splits from 1793 tokens on (32 heads x 8 = one workgroup per CU at 2047)
 
 __global__ void __launch_bounds__(64) chunk_rope_kv_kernel(const half_t *__restrict__ qkv, int64_t ldq, const int64_t *__restrict__ pos_ptr,
-                                                           half_t *__restrict__ kc, half_t *__restrict__ vc, half_t *__restrict__ qrot,
-                                                           unsigned *__restrict__ tickets, int heads, int t_max, float inv_base,
-                                                           const float2 *__restrict__ tab) {
+                                                           half_t *__restrict__ kc, half_t *__restrict__ vc, int64_t slot_stride,
+                                                           half_t *__restrict__ qrot, unsigned *__restrict__ tickets, int heads, int t_max,
+                                                           float inv_base, const float2 *__restrict__ tab) {
     const int h = blockIdx.y, c = threadIdx.x, half = CA_HD / 2;
-    const int r = blockIdx.x;
-    if (r == 0 && c == 0) tickets[h] = 0u;
-    const int64_t p = pos_ptr[0];
-    if (p < 0) return;
+    const int r = blockIdx.x, b = blockIdx.z, rows = gridDim.x;      // sequence b: packed rows b rows .., cache slot b, position pos_ptr[b]
+    if (r == 0 && c == 0) tickets[(size_t)b * heads + h] = 0u;
+    const int64_t p = pos_ptr[b];
+    if (p < 0 || p >= t_max) return;                              // (before the sum: p + r cannot wrap for any position value)
     const int64_t pos = p + r;
     if (pos >= t_max) return;
     float cs, sn;
@@ -61,18 +64,18 @@ __global__ void __launch_bounds__(64) chunk_rope_kv_kernel(const half_t *__restr
         sn = sinf(freq);
     }
     const int hd = heads * CA_HD;
-    const half_t *q = qkv + (size_t)r * ldq + (size_t)h * CA_HD + c;
+    const half_t *q = qkv + ((size_t)b * rows + r) * ldq + (size_t)h * CA_HD + c;
     const half_t *k = q + hd;
     const half_t *v = q + 2 * hd;
     const float qx = (float)q[0], qy = (float)q[half];
-    half_t *qd = qrot + (size_t)r * hd + (size_t)h * CA_HD + c;
+    half_t *qd = qrot + ((size_t)b * rows + r) * hd + (size_t)h * CA_HD + c;
     qd[0] = (half_t)(qx * cs - qy * sn);
     qd[half] = (half_t)(qx * sn + qy * cs);
     const float kx = (float)k[0], ky = (float)k[half];
-    half_t *kd = kc + (size_t)pos * hd + (size_t)h * CA_HD + c;
+    half_t *kd = kc + (size_t)b * slot_stride + (size_t)pos * hd + (size_t)h * CA_HD + c;
     kd[0] = (half_t)(kx * cs - ky * sn);
     kd[half] = (half_t)(kx * sn + ky * cs);
-    half_t *vd = vc + (size_t)pos * hd + (size_t)h * CA_HD + c;
+    half_t *vd = vc + (size_t)b * slot_stride + (size_t)pos * hd + (size_t)h * CA_HD + c;
     vd[0] = v[0];
     vd[half] = v[half];
 }
@@ -107,15 +110,15 @@ GPTQ_DEV float ca_rows_sum(float v) {
 }
 
 struct ChunkAttnArgs {
-    const half_t *q;             // rotated q [rows][heads * 128]
-    const int64_t *pos;
-    const half_t *kc, *vc;       // [t_max][heads * 128]
-    half_t *out;
-    uint32_t *o16;               // records: [S][rows][heads * 128] fp16 partial outputs (as pairs)
-    float *md;                   //          [S][heads][rows] {M, den}
-    unsigned *tickets;           //          [heads]
+    const half_t *q;             // rotated q [seqs][rows][heads * 128]
+    const int64_t *pos;          // [seqs]
+    const half_t *kc, *vc;       // [seqs] slots [t_max][heads * 128], slot_stride elements apart
+    half_t *out;                 // [seqs * rows] rows, ldo apart
+    uint32_t *o16;               // records: [seqs][S][rows][heads * 128] fp16 partial outputs (as pairs)
+    float *md;                   //          [seqs][S][heads][rows] {M, den}
+    unsigned *tickets;           //          [seqs][heads]
     int heads, rows, t_max;
-    int64_t ldo;
+    int64_t ldo, slot_stride;
     float scale2;                // softmax scale x log2(e)
 };
 
@@ -124,12 +127,12 @@ __global__ void __launch_bounds__(CA_NW * 64) chunk_attn_kernel(const ChunkAttnA
     __shared__ __attribute__((aligned(16))) half_t vs[CA_NW][CA_KT * CA_HD];
     __shared__ float mw[CA_NW][CA_QR], lw[CA_NW][CA_QR];
     __shared__ int last_flag;
-    const int h = blockIdx.x, s = blockIdx.y, S = gridDim.y;
+    const int h = blockIdx.x, s = blockIdx.y, S = gridDim.y, b = blockIdx.z;   // head, split, splits of the grid, sequence
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int g = lane >> 4, qi = lane & 15;               // 16-lane row of the wave, column (= query row of the MFMA)
     const int hd = a.heads * CA_HD;
-    const int64_t p64 = ((const __attribute__((address_space(4))) int64_t *)a.pos)[0];
+    const int64_t p64 = ((const __attribute__((address_space(4))) int64_t *)a.pos)[b];
     if (p64 < 0 || p64 >= a.t_max) return;
     const int p = (int)p64;
     const int nr = min(a.rows, a.t_max - p);               // rows that fit the cache
@@ -139,14 +142,15 @@ __global__ void __launch_bounds__(CA_NW * 64) chunk_attn_kernel(const ChunkAttnA
     const int t0 = s * sp.chunk;
     const int t_end = min(t0 + sp.chunk, len);             // this split attends to keys [t0, t_end)
     const int ntiles = (t_end - t0 + CA_KT - 1) / CA_KT;   // >= 1
-    const half_t *const kc = a.kc + (size_t)h * CA_HD, *const vc = a.vc + (size_t)h * CA_HD;
+    const half_t *const kc = a.kc + (size_t)b * a.slot_stride + (size_t)h * CA_HD, *const vc = a.vc + (size_t)b * a.slot_stride + (size_t)h * CA_HD;
+    const half_t *const qb = a.q + (size_t)b * a.rows * hd;           // this sequence's rotated q rows
 
     // ---- Q^T fragments (B operand of K Q^T): lane = query, element j of k-step ks = dim 32 g + 8 ks + j (K's fragments use the same map) ----
     half8_t qf[4];
 #pragma unroll
     for (int ks = 0; ks < 4; ks++) {
         qf[ks] = half8_t{0, 0, 0, 0, 0, 0, 0, 0};
-        if (qi < nr) qf[ks] = *(const half8_t *)(a.q + (size_t)qi * hd + (size_t)h * CA_HD + 32 * g + 8 * ks);
+        if (qi < nr) qf[ks] = *(const half8_t *)(qb + (size_t)qi * hd + (size_t)h * CA_HD + 32 * g + 8 * ks);
     }
     // A row m of a 16-key block is key ca_key(m) of the block: accumulator register r of lane row g holds key 8 (g & 1) + 4 (g >> 1) + r
     const int krow = 8 * ((qi >> 2) & 1) + 4 * (qi >> 3) + (qi & 3);
@@ -275,16 +279,16 @@ __global__ void __launch_bounds__(CA_NW * 64) chunk_attn_kernel(const ChunkAttnA
     half8_t o;
 #pragma unroll
     for (int j = 0; j < 8; j++) o[j] = attn_round_f16(num[j] * rden);
-    half_t *const orow = a.out + (size_t)qq * a.ldo + (size_t)h * CA_HD + d0;
+    half_t *const orow = a.out + ((size_t)b * a.rows + qq) * a.ldo + (size_t)h * CA_HD + d0;
     if (sp.nsp == 1) {       // this workgroup is the whole head
         if (qq < nr) *(half8_t *)orow = o;
         return;
     }
     // ---- several splits: system-scope records, arrival ticket, the last split merges them in split order ----
     const size_t rstride = (size_t)a.rows * hd / 2;        // uint32 words per split
-    uint32_t *const ro = a.o16 + ((size_t)qq * hd + (size_t)h * CA_HD + d0) / 2;
-    float *const rmd = a.md + ((size_t)h * a.rows + qq) * 2;
     const size_t mstride = (size_t)a.heads * a.rows * 2;
+    uint32_t *const ro = a.o16 + (size_t)b * S * rstride + ((size_t)qq * hd + (size_t)h * CA_HD + d0) / 2;
+    float *const rmd = a.md + (size_t)b * S * mstride + ((size_t)h * a.rows + qq) * 2;
     if (qq < nr) {
         const u32x4 ow4 = __builtin_bit_cast(u32x4, o);
 #pragma unroll
@@ -297,7 +301,7 @@ __global__ void __launch_bounds__(CA_NW * 64) chunk_attn_kernel(const ChunkAttnA
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (tid == 0) {
-        unsigned *ticket = a.tickets + h;
+        unsigned *ticket = a.tickets + (size_t)b * a.heads + h;
         const unsigned t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         const int last = (t == (unsigned)(sp.nsp - 1));
         if (last) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -336,34 +340,46 @@ int chunk_attn_active_splits(int heads, int t_max, int len) { return attn_split(
 
 static size_t ca_align(size_t n) { return (n + 255) & ~(size_t)255; }
 
-// rotated q [rows][hd] fp16 | records [S][rows][hd] fp16 | {M, den} [S][heads][rows] fp32 x 2 | tickets [heads]
-size_t chunk_attn_ws_bytes(int rows, int heads, int t_max) {
-    const size_t S = (size_t)chunk_attn_grid_splits(heads, t_max), hd = (size_t)heads * CA_HD;
-    return ca_align(rows * hd * sizeof(half_t)) + ca_align(S * rows * hd * sizeof(half_t)) + ca_align(S * heads * rows * 2 * sizeof(float)) +
-           ca_align(heads * sizeof(unsigned));
+// rotated q [seqs][rows][hd] fp16 | records [seqs][S][rows][hd] fp16 | {M, den} [seqs][S][heads][rows] fp32 x 2 | tickets [seqs][heads]
+// (seqs = 1: the layout and the size of the single-sequence entry)
+size_t chunk_attn_batch_ws_bytes(int seqs, int rows, int heads, int t_max) {
+    const size_t S = (size_t)chunk_attn_grid_splits(heads, t_max), hd = (size_t)heads * CA_HD, n = (size_t)seqs;
+    return ca_align(n * rows * hd * sizeof(half_t)) + ca_align(n * S * rows * hd * sizeof(half_t)) + ca_align(n * S * heads * rows * 2 * sizeof(float)) +
+           ca_align(n * heads * sizeof(unsigned));
+}
+
+size_t chunk_attn_ws_bytes(int rows, int heads, int t_max) { return chunk_attn_batch_ws_bytes(1, rows, heads, t_max); }
+
+// seqs sequences of `rows` rows each -- packed rows b rows .. b rows + rows - 1 of qkv / out, cache slot b (slot_stride elements apart), position
+// pos[b] on the device -- in the same two launches: the sequence is blockIdx.z of both kernels, everything else is per sequence what it is for one
+// (the same attn_split() cut from the same grid split count S, tickets per (sequence, head))
+int chunk_attn_batch_launch(const half_t *qkv, int64_t ldq, int seqs, int rows, const int64_t *pos, half_t *kc, half_t *vc, int64_t slot_stride,
+                            half_t *out, int64_t ldo, void *ws, int heads, int t_max, float base, float scale, const float *rope_table,
+                            hipStream_t s) {
+    const int S = chunk_attn_grid_splits(heads, t_max);
+    const size_t hd = (size_t)heads * CA_HD, n = (size_t)seqs;
+    char *w = (char *)ws;
+    half_t *qrot = (half_t *)w;
+    w += ca_align(n * rows * hd * sizeof(half_t));
+    ChunkAttnArgs a{};
+    a.o16 = (uint32_t *)w;
+    w += ca_align(n * S * rows * hd * sizeof(half_t));
+    a.md = (float *)w;
+    w += ca_align(n * S * heads * rows * 2 * sizeof(float));
+    a.tickets = (unsigned *)w;
+    const float inv_base = -2.0f * logf(base) / (float)CA_HD;   // reference fused_attn.py:91
+    hipLaunchKernelGGL(chunk_rope_kv_kernel, dim3(rows, heads, seqs), dim3(CA_HD / 2), 0, s, qkv, ldq, pos, kc, vc, slot_stride, qrot, a.tickets, heads,
+                       t_max, inv_base, (const float2 *)rope_table);
+    a.q = qrot; a.pos = pos; a.kc = kc; a.vc = vc; a.out = out;
+    a.heads = heads; a.rows = rows; a.t_max = t_max; a.ldo = ldo; a.slot_stride = slot_stride;
+    a.scale2 = scale * 1.44269504088896340736f;
+    hipLaunchKernelGGL(chunk_attn_kernel, dim3(heads, S, seqs), dim3(CA_NW * 64), 0, s, a);
+    return (int)hipGetLastError();
 }
 
 int chunk_attn_launch(const half_t *qkv, int64_t ldq, int rows, const int64_t *pos, half_t *kc, half_t *vc, half_t *out, int64_t ldo, void *ws,
                       int heads, int t_max, float base, float scale, const float *rope_table, hipStream_t s) {
-    const int S = chunk_attn_grid_splits(heads, t_max);
-    const size_t hd = (size_t)heads * CA_HD;
-    char *w = (char *)ws;
-    half_t *qrot = (half_t *)w;
-    w += ca_align(rows * hd * sizeof(half_t));
-    ChunkAttnArgs a{};
-    a.o16 = (uint32_t *)w;
-    w += ca_align((size_t)S * rows * hd * sizeof(half_t));
-    a.md = (float *)w;
-    w += ca_align((size_t)S * heads * rows * 2 * sizeof(float));
-    a.tickets = (unsigned *)w;
-    const float inv_base = -2.0f * logf(base) / (float)CA_HD;   // reference fused_attn.py:91
-    hipLaunchKernelGGL(chunk_rope_kv_kernel, dim3(rows, heads), dim3(CA_HD / 2), 0, s, qkv, ldq, pos, kc, vc, qrot, a.tickets, heads, t_max, inv_base,
-                       (const float2 *)rope_table);
-    a.q = qrot; a.pos = pos; a.kc = kc; a.vc = vc; a.out = out;
-    a.heads = heads; a.rows = rows; a.t_max = t_max; a.ldo = ldo;
-    a.scale2 = scale * 1.44269504088896340736f;
-    hipLaunchKernelGGL(chunk_attn_kernel, dim3(heads, S), dim3(CA_NW * 64), 0, s, a);
-    return (int)hipGetLastError();
+    return chunk_attn_batch_launch(qkv, ldq, 1, rows, pos, kc, vc, 0, out, ldo, ws, heads, t_max, base, scale, rope_table, s);
 }
 
 }  // namespace gptq

@@ -276,5 +276,11 @@ int chunk_attn_grid_splits(int heads, int t_max);                  // S of the l
 int chunk_attn_active_splits(int heads, int t_max, int len);      // splits a call whose last row sits at token len - 1 uses
 int chunk_attn_launch(const half_t *qkv, int64_t ldq, int rows, const int64_t *pos, half_t *kc, half_t *vc, half_t *out, int64_t ldo, void *ws,
                       int heads, int t_max, float base, float scale, const float *rope_table, hipStream_t s);
+// ... of `seqs` (1..16) sequences at once, still two launches: sequence b owns packed rows b * rows .. of qkv / out, cache slot b (slot_stride
+// elements apart) and pos[b]; ws = chunk_attn_batch_ws_bytes(seqs, rows, heads, t_max) (seqs = 1: the single-sequence layout)
+size_t chunk_attn_batch_ws_bytes(int seqs, int rows, int heads, int t_max);
+int chunk_attn_batch_launch(const half_t *qkv, int64_t ldq, int seqs, int rows, const int64_t *pos, half_t *kc, half_t *vc, int64_t slot_stride,
+                            half_t *out, int64_t ldo, void *ws, int heads, int t_max, float base, float scale, const float *rope_table,
+                            hipStream_t s);
 
 }  // namespace gptq

@@ -163,6 +163,10 @@ _SIGNATURES = {
     'gptq_decode_attn_chunk_splits': [c_int, c_int, c_int, c_int],
     'gptq_decode_attn_chunk_f16': [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_size_t, c_int, c_int, c_int,
                                    c_float, c_float, c_void_p, c_void_p],
+    # ... of up to 16 sequences in the same two launches: packed rows, one cache slot and one device position per sequence
+    'gptq_decode_attn_chunk_batch_workspace_bytes': [c_int, c_int, c_int, c_int, c_int],
+    'gptq_decode_attn_chunk_batch_f16': [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_size_t,
+                                         c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p],
     # scoring: the LM head of many rows with the cross-entropy in the tile GEMM's epilogue (csrc/gemm8.hip); the logits are never written
     'gptq_lm_head_nll_workspace_bytes': [c_int, c_int],
     'gptq_lm_head_nll_f16': [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
@@ -213,6 +217,7 @@ def lib():
             L.gptq_prompt_attn_workspace_bytes.restype = c_size_t
             L.gptq_lm_head_nll_workspace_bytes.restype = c_size_t
             L.gptq_decode_attn_chunk_workspace_bytes.restype = c_size_t
+            L.gptq_decode_attn_chunk_batch_workspace_bytes.restype = c_size_t
             L.gptq_spec_sample_workspace_bytes.restype = c_size_t
             L.gptq_layer_destroy.restype = None
             L.gptq_strerror.argtypes = [c_int]

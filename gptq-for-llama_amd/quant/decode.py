@@ -177,6 +177,7 @@ LM_HEAD_KERNEL = os.environ.get('GPTQ_LM_HEAD_KERNEL', '1') != '0'   # 0: final 
 
 
 MAX_BATCH = 16         # rows of a decode batch one engine serves (the LM head kernel and the decode kernel's row groups end there)
+MAX_CHUNK_ROWS = 128   # rows of a batched verify step (batch x batch_chunk): what gptq_layer_decode_f16 and the batched chunk attention take
 
 
 def lm_head_logits(eng, x, logits, s, h=None):
@@ -209,11 +210,16 @@ def lm_head_logits(eng, x, logits, s, h=None):
 
 class DecodeEngine:
 
-    def __init__(self, model, t_max=2048, fuse_norm=True, fuse_attn=True, batch=1, chunk=0):
+    def __init__(self, model, t_max=2048, fuse_norm=True, fuse_attn=True, batch=1, chunk=0, batch_chunk=0):
         """chunk = R in 2 .. 16 (batch 1 only) adds the VERIFY step of speculative decoding: R consecutive tokens of the one sequence -- the last
         accepted token and R - 1 drafts -- go through every layer at M = R in one pass over the weights (verify / accept / capture_verify_greedy,
         engine_generate(speculate=...)); attention by gptq_decode_attn_chunk_f16 on the engine's own cache.  chunk=0 (the default) allocates
         nothing and changes nothing.
+        batch_chunk = R in 2 .. 16 (batch B >= 2, B R <= 128) adds the verify step of BATCHED speculative decoding: R consecutive tokens of each
+        of the B sequences go through every layer at M = B R in one pass over the weights (verify_batch / accept_batch /
+        capture_verify_greedy_batch, engine_generate_batch(speculate=...)); attention by gptq_decode_attn_chunk_batch_f16 -- two launches for all
+        sequences -- on every row's own cache slice and position.  batch_chunk=0 (the default) allocates nothing and changes nothing;
+        NotImplementedError when a layer has no decode route for B R rows.
         batch (round 5): rows of a decode BATCH -- B sequences advance by one token per step, every row with its own position and its
         own slice of the K/V cache (the reference's one kernel serves any batch, quant_linear.py:263-269; HF generate drives it with
         [B, 1] steps).  The linears run at M = B through gptq_layer_decode_f16 (norm and residual inside the decode kernel's launch up to
@@ -229,6 +235,10 @@ class DecodeEngine:
         self.chunk = int(chunk)
         if self.chunk != 0 and (not 2 <= self.chunk <= MAX_BATCH or self.batch != 1):
             raise ValueError('DecodeEngine: chunk must be 0 or 2 .. %d, and needs batch 1' % MAX_BATCH)
+        self.batch_chunk = int(batch_chunk)
+        if self.batch_chunk != 0 and (self.batch < 2 or not 2 <= self.batch_chunk <= MAX_BATCH or self.batch * self.batch_chunk > MAX_CHUNK_ROWS):
+            raise ValueError('DecodeEngine: batch_chunk must be 0 or 2 .. %d, and needs batch >= 2 with batch x batch_chunk <= %d' % (
+                MAX_BATCH, MAX_CHUNK_ROWS))
         self.fuse_norm, self.fuse_attn = bool(fuse_norm), bool(fuse_attn)
         self.native = _native
         self.lib = _native.lib()
@@ -299,6 +309,9 @@ class DecodeEngine:
         self.draft_graph, self._draft_engine = None, None          # capture_draft_step (a draft engine) / (draft model, its engine) of a target engine
         if self.chunk:
             self._chunk_buffers()
+        self.verify_batch_graph = None
+        if self.batch_chunk:
+            self._chunk_batch_buffers()
 
     # -- weights: the engine reads the SAME derived copy as the modules -------------------------------------------------------
     # Every linear is taken from quant/layer.py prepared() with exactly the arguments the module's own forward uses, so the eager
@@ -1081,6 +1094,117 @@ class DecodeEngine:
         self.verify_graph = self._capture(self._verify_greedy_step, (self.pos, self.chunk_ids))
         return self
 
+    # -- batched speculative decoding: R consecutive tokens of EACH of the B sequences per step (batch = B, batch_chunk = R) ------------------------
+    def _chunk_batch_buffers(self):
+        """[B R, .] activations, chunk_ids [B, R], chunk_logits [B R, vocab], the attention workspace, verify_out [B, R + 1] and the decode
+        kernels' scratch for M = B R (and M = B: the plain batch step shares it); every layer must have a route for B R rows"""
+        B, R, H, dev = self.batch, self.batch_chunk, self.hidden, self.dev
+        M = B * R
+        self.scratch = self._rows_scratch('batch_chunk', (M, B))
+        f16 = dict(dtype=torch.float16, device=dev)
+        self.chunk_ids = torch.zeros((B, R), dtype=torch.int64, device=dev)
+        self.chunk_logits = torch.zeros((M, self.lm_head.shape[0]), **f16)
+        self.chunk_bufs = dict(x=torch.zeros((M, H), **f16), x2=torch.zeros((M, H), **f16), h=torch.zeros((M, H), **f16),
+                               qkv=torch.zeros((M, 3 * H), **f16), ab=torch.zeros((M, H), **f16), cb=torch.zeros((M, self.cb.shape[1]), **f16))
+        self.chunk_attn_ws = torch.zeros(self.lib.gptq_decode_attn_chunk_batch_workspace_bytes(B, R, self.heads, self.head_dim, self.t_max),
+                                         dtype=torch.uint8, device=dev)
+        # the verify-greedy-batch graph's result, read by the host in ONE copy per step: row b = [a_b, am_b[0 .. R - 1]]
+        self.verify_out = torch.zeros((B, R + 1), dtype=torch.int64, device=dev)
+
+    def _step_chunk_batch(self):
+        """_step_rows at M = B R: row b R + r is token r of sequence b (chunk_ids[b, r] at position pos[b] + r); gptq_decode_attn_chunk_batch_f16 on
+        kcb[li] / vcb[li] with pos as the DEVICE positions (pos[b] < 0: sequence b idles), the LM head for B R rows into chunk_logits (above 16
+        rows: the stand-alone norm + the library matmul of lm_head_logits).  Does not advance pos."""
+        slot_stride = self.kcb.stride(1)
+
+        def attn(li, L, qkvb, ab, tab, s):
+            rc = self.lib.gptq_decode_attn_chunk_batch_f16(qkvb.data_ptr(), qkvb.stride(0), self.batch, self.batch_chunk, self.pos.data_ptr(),
+                                                           self.kcb[li].data_ptr(), self.vcb[li].data_ptr(), slot_stride, ab.data_ptr(), ab.stride(0),
+                                                           self.chunk_attn_ws.data_ptr(), self.chunk_attn_ws.numel(), self.heads, self.head_dim,
+                                                           self.t_max, L['theta'], self.scale, self.native.ptr(tab), s)
+            self.native.check(rc, 'gptq_decode_attn_chunk_batch_f16')
+        self._step_rows(self.chunk_bufs, self.chunk_ids.view(-1), attn, self.chunk_logits)
+
+    def _need_batch_chunk(self, what):
+        if not self.batch_chunk:
+            raise ValueError('DecodeEngine.%s: the engine was built without batch_chunk=R' % what)
+
+    def verify_batch(self, tokens):
+        """tokens: a list of B entries, entry b the 1 .. R ids of sequence b -- its last accepted token followed by its drafts -- fed at positions
+        pos[b] .. pos[b] + n_b - 1, or None for a sequence that idles (nothing of its cache slot is read or written).  Returns chunk_logits viewed
+        [B, R, vocab] (the static buffer: clone it to keep it): row [b, i] is the distribution after entry b's first i + 1 tokens; rows behind a
+        short entry (padded with copies of its last id) and the rows of an idle sequence mean nothing.  pos is unchanged: accept_batch advances
+        it.  ValueError, with nothing launched, when an active sequence's chunk does not fit the cache."""
+        self._need_batch_chunk('verify_batch')
+        B, R = self.batch, self.batch_chunk
+        if not isinstance(tokens, (list, tuple)) or len(tokens) != B:
+            raise ValueError('DecodeEngine.verify_batch: tokens must be a list of %d entries (ids or None)' % B)
+        rows = []
+        for t in tokens:
+            if t is None:
+                rows.append(None)
+                continue
+            t = [int(x) for x in (t.reshape(-1).tolist() if torch.is_tensor(t) else list(t))]
+            if not 1 <= len(t) <= R:
+                raise ValueError('DecodeEngine.verify_batch: 1 .. %d tokens per sequence, not %d' % (R, len(t)))
+            rows.append(t + [t[-1]] * (R - len(t)))
+        pos = self.pos.tolist()
+        for b, t in enumerate(rows):
+            if t is not None and not 0 <= pos[b] <= self.t_max - R:
+                raise ValueError('DecodeEngine.verify_batch: positions %d .. %d of sequence %d do not fit the engine cache (%d)' % (
+                    pos[b], pos[b] + R - 1, b, self.t_max))
+        with torch.no_grad(), torch.cuda.device(self.dev):
+            self.chunk_ids.copy_(torch.tensor([t if t is not None else [0] * R for t in rows], dtype=torch.int64))
+            idle = any(t is None for t in rows)
+            if idle:                                             # the kernel's idle mark for the step; the positions come back behind it
+                self.pos.copy_(torch.tensor([p if t is not None else -1 for p, t in zip(pos, rows)], dtype=torch.int64))
+            self._step_chunk_batch()
+            if idle:
+                self.pos.copy_(torch.tensor(pos, dtype=torch.int64))
+        return self.chunk_logits.view(B, R, -1)
+
+    def accept_batch(self, ns):
+        """pos[b] += ns[b]: the first ns[b] (1 .. R) tokens of sequence b's last verify stay in its cache, the rest is stale; 0 for a sequence
+        that idled"""
+        self._need_batch_chunk('accept_batch')
+        ns = [int(n) for n in ns] if isinstance(ns, (list, tuple)) else None
+        if ns is None or len(ns) != self.batch or any(not 0 <= n <= self.batch_chunk for n in ns):
+            raise ValueError('DecodeEngine.accept_batch: needs %d counts in 0 .. %d' % (self.batch, self.batch_chunk))
+        pos = self.pos.tolist()
+        for b, n in enumerate(ns):
+            if n and pos[b] + n > self.t_max:
+                raise ValueError('DecodeEngine.accept_batch: position %d of sequence %d beyond the engine cache (%d)' % (pos[b] + n, b, self.t_max))
+        self.pos.add_(torch.tensor(ns, dtype=torch.int64).to(self.dev))
+        return self
+
+    def _verify_greedy_batch_step(self):
+        """_step_chunk_batch and the greedy accept rule per sequence, entirely on the device: am = argmax of every row, a_b = the length of the
+        longest prefix of sequence b's drafts with am[b, i] == chunk_ids[b, i + 1]; verify_out[b] = [a_b, am[b, 0 .. R - 1]]; pos[b] += a_b + 1
+        for the active sequences (0 <= pos[b] < t_max) only: an idle position stays as it is"""
+        B, R = self.batch, self.batch_chunk
+        self._step_chunk_batch()
+        am = torch.argmax(self.chunk_logits, dim=-1).view(B, R)
+        ok = (am[:, :-1] == self.chunk_ids[:, 1:]).to(torch.int64)
+        a = torch.cumprod(ok, dim=1).sum(dim=1)
+        self.verify_out[:, 0].copy_(a)
+        self.verify_out[:, 1:].copy_(am)
+        active = ((self.pos >= 0) & (self.pos < self.t_max)).to(torch.int64)
+        self.pos.add_((a + 1) * active)
+
+    def capture_verify_greedy_batch(self):
+        """capture _verify_greedy_batch_step into ONE hipGraph: a replay verifies chunk_ids [B, R] at the device positions and advances every
+        active sequence by what it accepted; the host uploads chunk_ids and downloads verify_out once per step.  The capture runs the step once
+        for real at the current positions (cache rows pos[b] .. pos[b] + R - 1 of every active slot are overwritten -- stale by contract) and
+        puts pos, chunk_ids back.  ValueError when an active sequence's warm-up chunk does not fit the cache: capture earlier, or before the
+        prompts (engine_generate_batch captures at pos = 0, in front of the prefill)."""
+        self._need_batch_chunk('capture_verify_greedy_batch')
+        for b, p in enumerate(self.pos.tolist()):
+            if 0 <= p < self.t_max and p + self.batch_chunk > self.t_max:
+                raise ValueError('DecodeEngine.capture_verify_greedy_batch: the warm-up step of sequence %d at positions %d .. %d does not fit the '
+                                 'engine cache (%d)' % (b, p, p + self.batch_chunk - 1, self.t_max))
+        self.verify_batch_graph = self._capture(self._verify_greedy_batch_step, (self.pos, self.chunk_ids))
+        return self
+
     # -- speculative SAMPLING: the verify step followed by the accept / resample rule of gptq_spec_sample_rows_f16 (csrc/spec_sample.hip) -------
     def _spec_sample_rows(self, draft_logits):
         """the kernel on chunk_logits / chunk_ids under the chunk rows' setting and the uniforms in chunk_u_accept / chunk_u_draw: verify_out =
@@ -1538,7 +1662,80 @@ def _engine_generate_sampled(model, input_ids, max_new_tokens, eos_token_id, eng
     return torch.cat([input_ids[0], gen.to(input_ids.dtype)]).unsqueeze(0)
 
 
-def engine_generate_batch(model, prompts, max_new_tokens, eos_token_id=None, engine=None, t_max=2048, sample=None):
+def _engine_generate_batch_speculative(prompts, max_new_tokens, eos_token_id, eng, k, max_ngram, draft):
+    """engine_generate_batch with speculation: prefill_batch -> first tokens by argmax -> (a draft per active sequence; ONE upload of chunk_ids;
+    replay the verify-greedy-batch graph; ONE download of verify_out; append every active sequence's a_b + 1 tokens; eos / length cut, after which
+    the sequence idles: position -1) until no active sequence has two tokens left or an active chunk no longer fits the cache; then the
+    capture_greedy_rows graph for what remains, the finished rows idling far below position 0."""
+    n, R = len(prompts), k + 1
+    if draft is None:
+        draft = lambda toks, m: prompt_lookup_draft(toks, m, max_ngram)
+    with torch.no_grad():
+        if eng.verify_batch_graph is None:
+            eng.pos.zero_()                                      # (the capture's warm-up step writes cache rows pos .. pos + R - 1 of every slot)
+            eng.capture_verify_greedy_batch()
+        if eng.greedy_rows_graph is None:
+            eng.pos.zero_()
+            eng.capture_greedy_rows()
+        first = eng.prefill_batch(prompts, starts=[0] * n).argmax(dim=-1).tolist()
+        seqs = [[int(t) for t in p.tolist()] + [f] for p, f in zip(prompts, first)]     # every token so far; the last one is not in the cache yet
+        gens = [[f] for f in first]
+        done = [(eos_token_id is not None and f == eos_token_id) or max_new_tokens == 1 for f in first]
+        accepted = [[] for _ in range(n)]
+        steps = 0
+        marked = [False] * n                                     # sequences whose device position holds the idle mark
+        while True:
+            active = [b for b in range(n) if not done[b]]
+            if not active or all(max_new_tokens - len(gens[b]) < 2 for b in active) or any(len(seqs[b]) - 1 + R > eng.t_max for b in active):
+                break
+            for b in range(n):
+                if done[b] and not marked[b]:
+                    eng.pos[b:b + 1].fill_(-1)
+                    marked[b] = True
+            ids = []
+            for b in range(n):
+                if done[b]:
+                    ids.append([0] * R)
+                    continue
+                d = [int(t) for t in draft(seqs[b], k)]          # (the draft reads the list, it must not change it)
+                if len(d) != k:
+                    raise ValueError('engine_generate_batch: the draft returned %d ids for k = %d' % (len(d), k))
+                ids.append([seqs[b][-1]] + d)
+            eng.chunk_ids.copy_(torch.tensor(ids, dtype=torch.int64))
+            eng.verify_batch_graph.replay()
+            res = eng.verify_out.tolist()                        # one copy per step: row b = [a_b, the a_b + 1 tokens of its step, ...]
+            steps += 1
+            for b in active:
+                a = res[b][0]
+                new = res[b][1:a + 2][:max_new_tokens - len(gens[b])]
+                if eos_token_id is not None and eos_token_id in new:
+                    new = new[:new.index(eos_token_id) + 1]
+                    done[b] = True
+                accepted[b].append(a)
+                gens[b].extend(new)
+                seqs[b].extend(new)
+                done[b] = done[b] or len(gens[b]) >= max_new_tokens
+        eng.spec_stats = dict(steps=steps, emitted=[len(g) - 1 for g in gens], accepted=accepted)
+        left = [0 if done[b] else max_new_tokens - len(gens[b]) for b in range(n)]
+        if max(left) > 0:                                        # the tail: single-step replays for all rows, the finished ones idle
+            far = -(eng.t_max + 1)                               # (a step adds 1 to every position: still negative after the tail)
+            eng.pos.copy_(torch.tensor([far if done[b] else len(seqs[b]) - 1 for b in range(n)], dtype=torch.int64))
+            eng.ids.copy_(torch.tensor([0 if done[b] else seqs[b][-1] for b in range(n)], dtype=torch.int64))
+            eng.stepc.zero_()
+            for _ in range(max(left)):
+                eng.greedy_rows_graph.replay()
+            tail = eng.stream_rows[:max(left)].t().tolist()      # [row][step]
+            for b in range(n):
+                new = tail[b][:left[b]]
+                if eos_token_id is not None and eos_token_id in new:
+                    new = new[:new.index(eos_token_id) + 1]
+                gens[b].extend(new)
+                seqs[b].extend(new)
+        eng.pos.copy_(torch.tensor([len(s) - 1 for s in seqs], dtype=torch.int64))     # every row: its last token is the one not consumed yet
+        return [torch.cat([p, torch.tensor(g, dtype=p.dtype, device=p.device)]) for p, g in zip(prompts, gens)]
+
+
+def engine_generate_batch(model, prompts, max_new_tokens, eos_token_id=None, engine=None, t_max=2048, sample=None, speculate=None):
     """Greedy generation for a LIST of prompts of different lengths (1-D id tensors): all prompts enter the engine through ONE
     DecodeEngine.prefill_batch, and every further step is one replay of the capture_greedy_rows graph for all rows; the host looks at the
     stream every 16 steps.  Returns a list of 1-D tensors, prompt + generated, each cut after its first eos_token_id.  engine.batch must
@@ -1547,19 +1744,46 @@ def engine_generate_batch(model, prompts, max_new_tokens, eos_token_id=None, eng
     sample=dict(temperature=..., top_k=..., top_p=...) SAMPLES instead: every key optional, a scalar for all rows or one value per prompt
     (DecodeEngine.set_sampling; a row with temperature 0 stays greedy).  The first tokens are drawn from the prompts' logits by
     DecodeEngine.sample_logits, every further step is a replay of the capture_sample_native graph; the draws follow torch.manual_seed.  The
-    settings STAY in the engine's buffers afterwards, until set_sampling is called again."""
+    settings STAY in the engine's buffers afterwards, until set_sampling is called again.
+    speculate=dict(k=4, max_ngram=3, draft=None) (every key optional, validated as engine_generate's) decodes SPECULATIVELY, greedy, at least two
+    prompts: per step every active sequence gets a draft of k tokens -- draft(tokens_so_far: list[int], k) -> k ids, by default
+    prompt_lookup_draft -- and all sequences' chunks go through the model as ONE replay of the capture_verify_greedy_batch graph (a DecodeEngine
+    with batch = len(prompts), batch_chunk = k + 1: one pass over the weights at M = batch x (k + 1)), which accepts per sequence the longest
+    prefix the greedy rule agrees with and emits one token more; the host uploads the chunks and reads (accepted, tokens) of all sequences in one
+    copy each per step.  A sequence that has hit its eos or its length idles; where no active sequence has two tokens left, or an active chunk no
+    longer fits the cache, the capture_greedy_rows graph finishes.  Same return value and eos semantics as the greedy path;
+    eng.spec_stats = dict(steps, emitted=[per sequence], accepted=[per sequence: per step]) describes the last run.
+    ValueError: speculate together with sample, or with the keys sample / draft_model (sampled batched verification is not built); k outside
+    1 .. 15; an engine passed in whose batch is not len(prompts) or whose batch_chunk is not k + 1; fewer than two prompts; unknown keys."""
     settings = None if sample is None else _sampling_settings('engine_generate_batch', sample)
+    spec = None
+    if speculate is not None:
+        if sample is not None:
+            raise ValueError('engine_generate_batch: speculate and sample exclude each other (greedy speculation only)')
+        spec = _speculate_settings(speculate)
+        if speculate.get('sample') is not None or speculate.get('draft_model') is not None:
+            raise ValueError('engine_generate_batch: speculate takes k, max_ngram and draft only (greedy, host drafts)')
     n = len(prompts)
     if n < 1 or any((not torch.is_tensor(p)) or p.dim() != 1 or p.numel() == 0 for p in prompts):
         raise ValueError('engine_generate_batch: prompts must be a non-empty list of non-empty 1-D id tensors')
     max_new_tokens = int(max_new_tokens)
     if max_new_tokens < 1:
         raise ValueError('engine_generate_batch: max_new_tokens must be positive')
-    eng = engine if engine is not None else DecodeEngine(model, t_max=t_max, batch=n)
+    if spec is not None and engine is not None and (engine.batch != n or engine.batch_chunk != spec[0] + 1):
+        raise ValueError('engine_generate_batch: speculate k = %d for %d prompts needs an engine of batch %d with batch_chunk = %d (this one: batch '
+                         '%d, batch_chunk %d)' % (spec[0], n, n, spec[0] + 1, engine.batch, engine.batch_chunk))
+    if engine is not None:
+        eng = engine
+    elif spec is not None:
+        eng = DecodeEngine(model, t_max=t_max, batch=n, batch_chunk=spec[0] + 1)
+    else:
+        eng = DecodeEngine(model, t_max=t_max, batch=n)
     if eng.batch != n:
         raise ValueError('engine_generate_batch: %d prompts for an engine of batch %d' % (n, eng.batch))
     if max(int(p.numel()) for p in prompts) + max_new_tokens > eng.t_max:
         raise ValueError('engine_generate_batch: prompt + max_new_tokens exceeds the engine cache (%d)' % eng.t_max)
+    if spec is not None:
+        return _engine_generate_batch_speculative(prompts, max_new_tokens, eos_token_id, eng, *spec)
     if settings is not None:
         eng.set_sampling(**settings)
     with torch.no_grad():

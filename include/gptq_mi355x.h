@@ -608,6 +608,28 @@ int gptq_decode_attn_chunk_f16(const void *qkv, int64_t ldq, int rows, const int
                                void *workspace, size_t workspace_bytes, int heads, int head_dim, int t_max, float base, float scale,
                                const float *rope_table, gptq_stream_t stream);
 
+/* The same for `seqs` (1 .. 16) decoding SEQUENCES at once, `rows` (1 .. 16) consecutive tokens each, seqs rows <= 128 -- the verify step of batched
+ * speculative decoding -- still in TWO launches for any seqs (the sequence is a grid dimension of both kernels).  Both counts are host values: they
+ * shape the grid.  Row r of sequence b is qkv + (b rows + r) ldq, its output row out + (b rows + r) ldo; cache slot b is k_cache / v_cache +
+ * b slot_stride elements ([t_max][heads 128] each; slot_stride >= t_max heads 128 and a multiple of 8: the engine's [batch][t_max][hidden] layer
+ * slice has slot_stride = t_max hidden); positions[b] is read on the DEVICE, so a captured graph replays the call at any positions.
+ * Every sequence gets exactly the contract of gptq_decode_attn_chunk_f16 -- RoPE + append at cache rows p_b .. p_b + rows - 1 of its slot, attention
+ * causal inside its chunk, its history streamed once per head for all its rows, the same attn_split() cut with the same grid split count, the same
+ * record / ticket merge with one ticket per (sequence, head) -- and the same bits: cache rows and output rows are bit-identical to a call of the
+ * single-sequence entry on that slot, whatever the other sequences hold.
+ * positions[b] < 0 or >= t_max marks an IDLE sequence: nothing of its slot or its output rows is read or written.  A row whose position would be
+ * >= t_max is skipped; the rows that fit are served.  No access outside a slot for any position value.
+ * The workspace (gptq_decode_attn_chunk_batch_workspace_bytes; 0 for unsupported shapes; for seqs = 1 the size of the single-sequence entry) is pure
+ * scratch: no initialisation, no state between calls -- but two calls that may overlap must not share it.
+ * Validated before anything is launched: GPTQ_E_NULL (qkv, positions, k_cache, v_cache, out, workspace); GPTQ_E_SHAPE (seqs or rows outside
+ * 1 .. 16, seqs rows > 128, heads < 1, head_dim != 128, t_max < 1, ldq < 3 heads 128, ldo < heads 128, slot_stride < t_max heads 128,
+ * workspace_bytes too small); GPTQ_E_ALIGN (qkv / caches / workspace / out 16 bytes, positions and rope_table 8 bytes, ldq / ldo / slot_stride
+ * multiples of 8). */
+size_t gptq_decode_attn_chunk_batch_workspace_bytes(int seqs, int rows, int heads, int head_dim, int t_max);
+int gptq_decode_attn_chunk_batch_f16(const void *qkv, int64_t ldq, int seqs, int rows, const int64_t *positions, void *k_cache, void *v_cache,
+                                     int64_t slot_stride, void *out, int64_t ldo, void *workspace, size_t workspace_bytes, int heads, int head_dim,
+                                     int t_max, float base, float scale, const float *rope_table, gptq_stream_t stream);
+
 /* ---- scoring: the LM head of MANY rows with the cross-entropy inside (reference llama.py:241-258: lm_head over all rows of a segment, shifted
  * labels, CrossEntropyLoss) -- the [M, N] logits never exist in memory.
  *   x [M, K] (ldx)       fp16, the already normalised hidden rows
