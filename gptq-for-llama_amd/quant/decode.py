@@ -211,15 +211,15 @@ def lm_head_logits(eng, x, logits, s, h=None):
 class DecodeEngine:
 
     def __init__(self, model, t_max=2048, fuse_norm=True, fuse_attn=True, batch=1, chunk=0, batch_chunk=0):
-        """chunk = R in 2 .. 16 (batch 1 only) adds the VERIFY step of speculative decoding: R consecutive tokens of the one sequence -- the last
-        accepted token and R - 1 drafts -- go through every layer at M = R in one pass over the weights (verify / accept / capture_verify_greedy,
-        engine_generate(speculate=...)); attention by gptq_decode_attn_chunk_f16 on the engine's own cache.  chunk=0 (the default) allocates
-        nothing and changes nothing.
-        batch_chunk = R in 2 .. 16 (batch B >= 2, B R <= 128) adds the verify step of BATCHED speculative decoding: R consecutive tokens of each
-        of the B sequences go through every layer at M = B R in one pass over the weights (verify_batch / accept_batch /
-        capture_verify_greedy_batch, engine_generate_batch(speculate=...)); attention by gptq_decode_attn_chunk_batch_f16 -- two launches for all
-        sequences -- on every row's own cache slice and position.  batch_chunk=0 (the default) allocates nothing and changes nothing;
-        NotImplementedError when a layer has no decode route for B R rows.
+        """chunk = R or batch_chunk = R (2 .. 16) adds the VERIFY step of speculative decoding: R consecutive tokens of each of the B = batch
+        sequences -- the last accepted token and R - 1 drafts -- go through every layer at M = B R in one pass over the weights; attention by
+        gptq_decode_attn_chunk_batch_f16 -- two launches for all sequences -- on every sequence's own cache slice and position.  It is ONE
+        mechanism (_chunk_buffers, _step_chunk, _verify_greedy_step, one graph) with two entry points that differ in the shapes they show:
+        chunk = R needs batch 1: verify / accept / capture_verify_greedy / verify_sample, engine_generate(speculate=...); chunk_ids [R] and
+        verify_out [R + 1] are row 0 of the [1, .] buffers.
+        batch_chunk = R needs batch B >= 2 with B R <= 128: verify_batch / accept_batch / capture_verify_greedy_batch,
+        engine_generate_batch(speculate=...); chunk_ids [B, R], verify_out [B, R + 1].
+        0 for both (the default) allocates nothing and changes nothing; NotImplementedError when a layer has no decode route for B R rows.
         batch (round 5): rows of a decode BATCH -- B sequences advance by one token per step, every row with its own position and its
         own slice of the K/V cache (the reference's one kernel serves any batch, quant_linear.py:263-269; HF generate drives it with
         [B, 1] steps).  The linears run at M = B through gptq_layer_decode_f16 (norm and residual inside the decode kernel's launch up to
@@ -307,11 +307,11 @@ class DecodeEngine:
             self.scratch = self._rows_scratch('batch', (B,))
         self.verify_graph, self.verify_sample_graphs, self.spec_stats = None, {}, None
         self.draft_graph, self._draft_engine = None, None          # capture_draft_step (a draft engine) / (draft model, its engine) of a target engine
-        if self.chunk:
+        self.chunk_rows = self.chunk or self.batch_chunk           # R of the verify step, whichever argument asked for it (0: none)
+        if self.chunk_rows:
             self._chunk_buffers()
-        self.verify_batch_graph = None
-        if self.batch_chunk:
-            self._chunk_batch_buffers()
+
+    verify_batch_graph = property(lambda self: self.verify_graph, doc='the ONE verify-greedy graph under the name capture_verify_greedy_batch stores it')
 
     # -- weights: the engine reads the SAME derived copy as the modules -------------------------------------------------------
     # Every linear is taken from quant/layer.py prepared() with exactly the arguments the module's own forward uses, so the eager
@@ -997,23 +997,27 @@ class DecodeEngine:
         _, nll, offs, lens = self._packed('score_batch', prompts, rows, None, max_rows, score=True)
         return [nll[o:o + T - 1] for o, T in zip(offs, lens)]
 
-    # -- speculative decoding: R consecutive tokens of the ONE sequence per step (chunk = R) ---------------------------------------------------
+    # -- speculative decoding: R consecutive tokens of EACH of the B sequences per step.  ONE mechanism: chunk = R is its B = 1 case (chunk_ids [R],
+    # -- verify_out [R + 1]: row 0), batch_chunk = R the B >= 2 one (chunk_ids [B, R], verify_out [B, R + 1]); the public pairs differ in shapes only
     def _chunk_buffers(self):
-        """[R, .] activations, chunk_ids / chunk_logits, the attention workspace and the decode kernels' scratch for M = R; every layer must have
-        the route the batch > 1 constructor path asks for"""
-        R, H, dev = self.chunk, self.hidden, self.dev
-        self.scratch = self._rows_scratch('chunk', (R, 1))                 # of gptq_layer_decode_f16 at M = R (and at M = 1: _gemv)
+        """[B R, .] activations, chunk_ids, chunk_logits [B R, vocab], the attention workspace, verify_out and the decode kernels' scratch for
+        M = B R (and M = B: the plain step shares it); every layer must have a route for B R rows"""
+        B, R, H, dev = self.batch, self.chunk_rows, self.hidden, self.dev
+        M = B * R
+        self.scratch = self._rows_scratch('chunk' if self.chunk else 'batch_chunk', (M, B))
         f16 = dict(dtype=torch.float16, device=dev)
-        self.chunk_ids = torch.zeros(R, dtype=torch.int64, device=dev)
-        self.chunk_logits = torch.zeros((R, self.lm_head.shape[0]), **f16)
-        self.chunk_bufs = dict(x=torch.zeros((R, H), **f16), x2=torch.zeros((R, H), **f16), h=torch.zeros((R, H), **f16),
-                               qkv=torch.zeros((R, 3 * H), **f16), ab=torch.zeros((R, H), **f16), cb=torch.zeros((R, self.cb.shape[1]), **f16))
-        self.chunk_attn_ws = torch.zeros(self.lib.gptq_decode_attn_chunk_workspace_bytes(R, self.heads, self.head_dim, self.t_max),
+        self.chunk_logits = torch.zeros((M, self.lm_head.shape[0]), **f16)
+        self.chunk_bufs = dict(x=torch.zeros((M, H), **f16), x2=torch.zeros((M, H), **f16), h=torch.zeros((M, H), **f16),
+                               qkv=torch.zeros((M, 3 * H), **f16), ab=torch.zeros((M, H), **f16), cb=torch.zeros((M, self.cb.shape[1]), **f16))
+        self.chunk_attn_ws = torch.zeros(self.lib.gptq_decode_attn_chunk_batch_workspace_bytes(B, R, self.heads, self.head_dim, self.t_max),
                                          dtype=torch.uint8, device=dev)
-        # the verify-greedy graph's result, read by the host in ONE copy per step: [a, am[0 .. R - 1]]
-        self.verify_out = torch.zeros(R + 1, dtype=torch.int64, device=dev)
-        # speculative sampling (gptq_spec_sample_rows_f16): the R rows' setting (set_sampling fills them from row 0), their uniforms, the draft
-        # model's logits rows, and the kernel's workspace [ticket, R records] -- zero once, the ticket puts itself back
+        # the verify-greedy graph's result, read by the host in ONE copy per step: row b = [a_b, am_b[0 .. R - 1]]
+        ids, out = torch.zeros((B, R), dtype=torch.int64, device=dev), torch.zeros((B, R + 1), dtype=torch.int64, device=dev)
+        self.chunk_ids, self.verify_out = (ids[0], out[0]) if self.chunk else (ids, out)
+        if not self.chunk:
+            return
+        # speculative sampling (gptq_spec_sample_rows_f16; B = 1 only): the R rows' setting (set_sampling fills them from row 0), their uniforms,
+        # the draft model's logits rows, and the kernel's workspace [ticket, R records] -- zero once, the ticket puts itself back
         f32 = dict(dtype=torch.float32, device=dev)
         self.chunk_temperature, self.chunk_top_p = torch.ones(R, **f32), torch.ones(R, **f32)
         self.chunk_top_k = torch.zeros(R, dtype=torch.int32, device=dev)
@@ -1022,187 +1026,138 @@ class DecodeEngine:
         self.spec_ws = torch.zeros(self.lib.gptq_spec_sample_workspace_bytes(R) // 8, dtype=torch.int64, device=dev)
 
     def _step_chunk(self):
-        """_step_rows at M = R for R consecutive tokens of the one sequence (chunk_ids at positions pos .. pos + R - 1): gptq_decode_attn_chunk_f16
-        on kc[li] / vc[li] with pos[0:1] as the DEVICE position, the LM head for R rows into chunk_logits.  Does not advance pos."""
-        def attn(li, L, qkvb, ab, tab, s):
-            rc = self.lib.gptq_decode_attn_chunk_f16(qkvb.data_ptr(), qkvb.stride(0), self.chunk, self.pos.data_ptr(), self.kc[li].data_ptr(),
-                                                     self.vc[li].data_ptr(), ab.data_ptr(), ab.stride(0), self.chunk_attn_ws.data_ptr(),
-                                                     self.chunk_attn_ws.numel(), self.heads, self.head_dim, self.t_max, L['theta'], self.scale,
-                                                     self.native.ptr(tab), s)
-            self.native.check(rc, 'gptq_decode_attn_chunk_f16')
-        self._step_rows(self.chunk_bufs, self.chunk_ids, attn, self.chunk_logits)
-
-    def _need_chunk(self, what):
-        if not self.chunk:
-            raise ValueError('DecodeEngine.%s: the engine was built without chunk=R' % what)
-
-    def verify(self, tokens):
-        """tokens: 1-D, 1 .. R ids -- the last accepted token followed by the drafts -- fed at positions pos .. pos + n - 1.  Returns
-        chunk_logits[:n] (the static buffer: clone it to keep it): row i is the distribution after tokens[:i + 1].  Fewer than R tokens are padded
-        with copies of the last one (their rows are computed and dropped).  pos is unchanged: accept(n) advances it.  Cache rows pos .. pos + R - 1
-        are written; what lies beyond the accepted ones is stale by contract and overwritten by the next step."""
-        self._need_chunk('verify')
-        R = self.chunk
-        t = torch.as_tensor(tokens).reshape(-1) if not (torch.is_tensor(tokens) and tokens.dim() == 1) else tokens
-        n = int(t.numel())
-        if not 1 <= n <= R:
-            raise ValueError('DecodeEngine.verify: 1 .. %d tokens, not %d' % (R, n))
-        pos = int(self.pos[0])
-        if pos + R > self.t_max:
-            raise ValueError('DecodeEngine.verify: positions %d .. %d do not fit the engine cache (%d)' % (pos, pos + R - 1, self.t_max))
-        with torch.no_grad(), torch.cuda.device(self.dev):
-            t = t.to(device=self.dev, dtype=torch.int64)
-            self.chunk_ids[:n].copy_(t)
-            if n < R:
-                self.chunk_ids[n:].copy_(t[n - 1:n].expand(R - n))
-            self._step_chunk()
-        return self.chunk_logits[:n]
-
-    def accept(self, n):
-        """pos += n (1 .. R): the first n tokens of the last verify stay in the cache, the rest is stale"""
-        self._need_chunk('accept')
-        n = int(n)
-        if not 1 <= n <= self.chunk:
-            raise ValueError('DecodeEngine.accept: n must be 1 .. %d, not %d' % (self.chunk, n))
-        pos = int(self.pos[0])
-        if pos + n > self.t_max:
-            raise ValueError('DecodeEngine.accept: position %d beyond the engine cache (%d)' % (pos + n, self.t_max))
-        self.pos.add_(n)
-        return self
-
-    def _verify_greedy_step(self):
-        """_step_chunk and the greedy accept rule, entirely on the device: am = argmax of every row, a = the length of the longest prefix of drafts
-        with am[i] == chunk_ids[i + 1], pos += a + 1; verify_out = [a, am[0 .. R - 1]] (the tokens a step emits are am[0 .. a])"""
-        self._step_chunk()
-        am = torch.argmax(self.chunk_logits, dim=-1)
-        ok = (am[:-1] == self.chunk_ids[1:]).to(torch.int64)
-        a = torch.cumprod(ok, dim=0).sum()
-        self.verify_out[0:1].copy_(a.reshape(1))
-        self.verify_out[1:].copy_(am)
-        self.pos.add_(a + 1)
-
-    def capture_verify_greedy(self):
-        """capture _verify_greedy_step into ONE hipGraph: a replay verifies chunk_ids at the device position and advances it by what was accepted.
-        The capture runs the step once for real at the current position: cache rows pos .. pos + R - 1 of every layer are overwritten (rows at and
-        beyond pos are stale by contract, so the history below pos is intact) and pos, chunk_ids are put back.  ValueError when pos + R > t_max:
-        capture earlier in the sequence, or before the prompt (engine_generate captures at pos = 0, in front of the prefill)."""
-        self._need_chunk('capture_verify_greedy')
-        pos = int(self.pos[0])
-        if pos + self.chunk > self.t_max:
-            raise ValueError('DecodeEngine.capture_verify_greedy: the warm-up step at positions %d .. %d does not fit the engine cache (%d)' % (
-                pos, pos + self.chunk - 1, self.t_max))
-        self.verify_graph = self._capture(self._verify_greedy_step, (self.pos, self.chunk_ids))
-        return self
-
-    # -- batched speculative decoding: R consecutive tokens of EACH of the B sequences per step (batch = B, batch_chunk = R) ------------------------
-    def _chunk_batch_buffers(self):
-        """[B R, .] activations, chunk_ids [B, R], chunk_logits [B R, vocab], the attention workspace, verify_out [B, R + 1] and the decode
-        kernels' scratch for M = B R (and M = B: the plain batch step shares it); every layer must have a route for B R rows"""
-        B, R, H, dev = self.batch, self.batch_chunk, self.hidden, self.dev
-        M = B * R
-        self.scratch = self._rows_scratch('batch_chunk', (M, B))
-        f16 = dict(dtype=torch.float16, device=dev)
-        self.chunk_ids = torch.zeros((B, R), dtype=torch.int64, device=dev)
-        self.chunk_logits = torch.zeros((M, self.lm_head.shape[0]), **f16)
-        self.chunk_bufs = dict(x=torch.zeros((M, H), **f16), x2=torch.zeros((M, H), **f16), h=torch.zeros((M, H), **f16),
-                               qkv=torch.zeros((M, 3 * H), **f16), ab=torch.zeros((M, H), **f16), cb=torch.zeros((M, self.cb.shape[1]), **f16))
-        self.chunk_attn_ws = torch.zeros(self.lib.gptq_decode_attn_chunk_batch_workspace_bytes(B, R, self.heads, self.head_dim, self.t_max),
-                                         dtype=torch.uint8, device=dev)
-        # the verify-greedy-batch graph's result, read by the host in ONE copy per step: row b = [a_b, am_b[0 .. R - 1]]
-        self.verify_out = torch.zeros((B, R + 1), dtype=torch.int64, device=dev)
-
-    def _step_chunk_batch(self):
         """_step_rows at M = B R: row b R + r is token r of sequence b (chunk_ids[b, r] at position pos[b] + r); gptq_decode_attn_chunk_batch_f16 on
         kcb[li] / vcb[li] with pos as the DEVICE positions (pos[b] < 0: sequence b idles), the LM head for B R rows into chunk_logits (above 16
         rows: the stand-alone norm + the library matmul of lm_head_logits).  Does not advance pos."""
         slot_stride = self.kcb.stride(1)
 
         def attn(li, L, qkvb, ab, tab, s):
-            rc = self.lib.gptq_decode_attn_chunk_batch_f16(qkvb.data_ptr(), qkvb.stride(0), self.batch, self.batch_chunk, self.pos.data_ptr(),
+            rc = self.lib.gptq_decode_attn_chunk_batch_f16(qkvb.data_ptr(), qkvb.stride(0), self.batch, self.chunk_rows, self.pos.data_ptr(),
                                                            self.kcb[li].data_ptr(), self.vcb[li].data_ptr(), slot_stride, ab.data_ptr(), ab.stride(0),
                                                            self.chunk_attn_ws.data_ptr(), self.chunk_attn_ws.numel(), self.heads, self.head_dim,
                                                            self.t_max, L['theta'], self.scale, self.native.ptr(tab), s)
             self.native.check(rc, 'gptq_decode_attn_chunk_batch_f16')
         self._step_rows(self.chunk_bufs, self.chunk_ids.view(-1), attn, self.chunk_logits)
 
-    def _need_batch_chunk(self, what):
-        if not self.batch_chunk:
-            raise ValueError('DecodeEngine.%s: the engine was built without batch_chunk=R' % what)
+    def _need_chunk(self, what, batched=False):
+        if not (self.batch_chunk if batched else self.chunk):
+            raise ValueError('DecodeEngine.%s: the engine was built without %s=R' % (what, 'batch_chunk' if batched else 'chunk'))
 
-    def verify_batch(self, tokens):
-        """tokens: a list of B entries, entry b the 1 .. R ids of sequence b -- its last accepted token followed by its drafts -- fed at positions
-        pos[b] .. pos[b] + n_b - 1, or None for a sequence that idles (nothing of its cache slot is read or written).  Returns chunk_logits viewed
-        [B, R, vocab] (the static buffer: clone it to keep it): row [b, i] is the distribution after entry b's first i + 1 tokens; rows behind a
-        short entry (padded with copies of its last id) and the rows of an idle sequence mean nothing.  pos is unchanged: accept_batch advances
-        it.  ValueError, with nothing launched, when an active sequence's chunk does not fit the cache."""
-        self._need_batch_chunk('verify_batch')
-        B, R = self.batch, self.batch_chunk
+    def _chunks_fit(self, what, active=None):
+        """ValueError unless positions pos[b] .. pos[b] + R - 1 fit the cache for every sequence b -- of `active` (a list of B flags) when given,
+        which exempts the others, wherever their positions are"""
+        R = self.chunk_rows
+        for b, p in enumerate(self.pos.tolist()):
+            if (active is None or active[b]) and not 0 <= p <= self.t_max - R:
+                raise ValueError('DecodeEngine.%s: positions %d .. %d of sequence %d do not fit the engine cache (%d)' % (what, p, p + R - 1, b, self.t_max))
+
+    def _verify_rows(self, what, tokens):
+        """verify and verify_batch: tokens is a list of B entries, entry b the 1 .. R ids of sequence b -- short ones are padded with copies of
+        their last id -- or None for a sequence that idles: its position holds the kernel's idle mark (-1) during the step and comes back behind
+        it.  Everything is checked (ValueError) before the upload of chunk_ids and the step."""
+        B, R = self.batch, self.chunk_rows
         if not isinstance(tokens, (list, tuple)) or len(tokens) != B:
-            raise ValueError('DecodeEngine.verify_batch: tokens must be a list of %d entries (ids or None)' % B)
+            raise ValueError('DecodeEngine.%s: tokens must be a list of %d entries (ids or None)' % (what, B))
         rows = []
         for t in tokens:
-            if t is None:
-                rows.append(None)
-                continue
-            t = [int(x) for x in (t.reshape(-1).tolist() if torch.is_tensor(t) else list(t))]
-            if not 1 <= len(t) <= R:
-                raise ValueError('DecodeEngine.verify_batch: 1 .. %d tokens per sequence, not %d' % (R, len(t)))
-            rows.append(t + [t[-1]] * (R - len(t)))
-        pos = self.pos.tolist()
-        for b, t in enumerate(rows):
-            if t is not None and not 0 <= pos[b] <= self.t_max - R:
-                raise ValueError('DecodeEngine.verify_batch: positions %d .. %d of sequence %d do not fit the engine cache (%d)' % (
-                    pos[b], pos[b] + R - 1, b, self.t_max))
+            if t is not None:
+                t = [int(x) for x in (t.reshape(-1).tolist() if torch.is_tensor(t) else list(t))]
+                if not 1 <= len(t) <= R:
+                    raise ValueError('DecodeEngine.%s: 1 .. %d tokens per sequence, not %d' % (what, R, len(t)))
+                t = t + [t[-1]] * (R - len(t))
+            rows.append(t)
+        self._chunks_fit(what, [t is not None for t in rows])
         with torch.no_grad(), torch.cuda.device(self.dev):
-            self.chunk_ids.copy_(torch.tensor([t if t is not None else [0] * R for t in rows], dtype=torch.int64))
+            self.chunk_ids.view(B, R).copy_(torch.tensor([t if t is not None else [0] * R for t in rows], dtype=torch.int64))
             idle = any(t is None for t in rows)
-            if idle:                                             # the kernel's idle mark for the step; the positions come back behind it
-                self.pos.copy_(torch.tensor([p if t is not None else -1 for p, t in zip(pos, rows)], dtype=torch.int64))
-            self._step_chunk_batch()
             if idle:
-                self.pos.copy_(torch.tensor(pos, dtype=torch.int64))
-        return self.chunk_logits.view(B, R, -1)
+                pos = self.pos.clone()
+                self.pos.masked_fill_(torch.tensor([t is None for t in rows]).to(self.dev), -1)
+            self._step_chunk()
+            if idle:
+                self.pos.copy_(pos)
 
-    def accept_batch(self, ns):
-        """pos[b] += ns[b]: the first ns[b] (1 .. R) tokens of sequence b's last verify stay in its cache, the rest is stale; 0 for a sequence
-        that idled"""
-        self._need_batch_chunk('accept_batch')
+    def _accept_rows(self, what, ns, least):
+        """accept and accept_batch: pos[b] += ns[b] for B counts in least .. R, checked (ValueError) before anything changes"""
         ns = [int(n) for n in ns] if isinstance(ns, (list, tuple)) else None
-        if ns is None or len(ns) != self.batch or any(not 0 <= n <= self.batch_chunk for n in ns):
-            raise ValueError('DecodeEngine.accept_batch: needs %d counts in 0 .. %d' % (self.batch, self.batch_chunk))
-        pos = self.pos.tolist()
-        for b, n in enumerate(ns):
-            if n and pos[b] + n > self.t_max:
-                raise ValueError('DecodeEngine.accept_batch: position %d of sequence %d beyond the engine cache (%d)' % (pos[b] + n, b, self.t_max))
+        if ns is None or len(ns) != self.batch or any(not least <= n <= self.chunk_rows for n in ns):
+            raise ValueError('DecodeEngine.%s: needs %d counts in %d .. %d' % (what, self.batch, least, self.chunk_rows))
+        for b, (p, n) in enumerate(zip(self.pos.tolist(), ns)):
+            if n and p + n > self.t_max:
+                raise ValueError('DecodeEngine.%s: position %d of sequence %d beyond the engine cache (%d)' % (what, p + n, b, self.t_max))
         self.pos.add_(torch.tensor(ns, dtype=torch.int64).to(self.dev))
         return self
 
-    def _verify_greedy_batch_step(self):
-        """_step_chunk_batch and the greedy accept rule per sequence, entirely on the device: am = argmax of every row, a_b = the length of the
-        longest prefix of sequence b's drafts with am[b, i] == chunk_ids[b, i + 1]; verify_out[b] = [a_b, am[b, 0 .. R - 1]]; pos[b] += a_b + 1
-        for the active sequences (0 <= pos[b] < t_max) only: an idle position stays as it is"""
-        B, R = self.batch, self.batch_chunk
-        self._step_chunk_batch()
+    def verify(self, tokens):
+        """chunk = R.  tokens: 1-D, 1 .. R ids -- the last accepted token followed by the drafts -- fed at positions pos .. pos + n - 1.  Returns
+        chunk_logits[:n] (the static buffer: clone it to keep it): row i is the distribution after tokens[:i + 1].  Fewer than R tokens are padded
+        with copies of the last one (their rows are computed and dropped).  pos is unchanged: accept(n) advances it.  Cache rows pos .. pos + R - 1
+        are written; what lies beyond the accepted ones is stale by contract and overwritten by the next step.  ValueError, with nothing
+        launched, when the chunk does not fit the cache."""
+        self._need_chunk('verify')
+        t = torch.as_tensor(tokens).reshape(-1)
+        self._verify_rows('verify', [t])
+        return self.chunk_logits[:int(t.numel())]
+
+    def verify_batch(self, tokens):
+        """batch_chunk = R.  tokens: a list of B entries, entry b what verify takes for sequence b, or None for a sequence that idles (nothing of
+        its cache slot is read or written).  Returns chunk_logits viewed [B, R, vocab] (the static buffer: clone it to keep it): row [b, i] is the
+        distribution after entry b's first i + 1 tokens; rows behind a short entry and the rows of an idle sequence mean nothing.  pos is
+        unchanged: accept_batch advances it.  ValueError, with nothing launched, when an active sequence's chunk does not fit the cache."""
+        self._need_chunk('verify_batch', batched=True)
+        self._verify_rows('verify_batch', tokens)
+        return self.chunk_logits.view(self.batch, self.batch_chunk, -1)
+
+    def accept(self, n):
+        """pos += n (1 .. R): the first n tokens of the last verify stay in the cache, the rest is stale"""
+        self._need_chunk('accept')
+        return self._accept_rows('accept', [n], 1)
+
+    def accept_batch(self, ns):
+        """pos[b] += ns[b]: accept per sequence; 0 for a sequence that idled"""
+        self._need_chunk('accept_batch', batched=True)
+        return self._accept_rows('accept_batch', ns, 0)
+
+    def _verify_greedy_step(self):
+        """_step_chunk and the greedy accept rule per sequence, entirely on the device: am = argmax of every row, a_b = the length of the longest
+        prefix of sequence b's drafts with am[b, i] == chunk_ids[b, i + 1]; verify_out[b] = [a_b, am[b, 0 .. R - 1]] (the tokens a step emits are
+        am[b, 0 .. a_b]); pos[b] += a_b + 1 -- with B >= 2 for the active sequences (0 <= pos[b] < t_max) only: an idle position stays as it is"""
+        B, R = self.batch, self.chunk_rows
+        self._step_chunk()
         am = torch.argmax(self.chunk_logits, dim=-1).view(B, R)
-        ok = (am[:, :-1] == self.chunk_ids[:, 1:]).to(torch.int64)
+        ok = (am[:, :-1] == self.chunk_ids.view(B, R)[:, 1:]).to(torch.int64)
         a = torch.cumprod(ok, dim=1).sum(dim=1)
-        self.verify_out[:, 0].copy_(a)
-        self.verify_out[:, 1:].copy_(am)
-        active = ((self.pos >= 0) & (self.pos < self.t_max)).to(torch.int64)
-        self.pos.add_((a + 1) * active)
+        out = self.verify_out.view(B, R + 1)
+        out[:, 0].copy_(a)
+        out[:, 1:].copy_(am)
+        if B == 1:
+            # nothing ever idles the one sequence of a chunk engine, and the mask's five element-wise nodes were measured: 9 us per replay of
+            # the 7B-shaped verify graph on average, outside the spread of its repeats at 10 of 16 points (profiles/speculate/README.md)
+            self.pos.add_(a + 1)
+        else:
+            active = ((self.pos >= 0) & (self.pos < self.t_max)).to(torch.int64)
+            self.pos.add_((a + 1) * active)
+
+    def _capture_verify(self, what, step, batched=False, keep_rng=False):
+        """the ONE capture of the verify steps, which advance pos and are fed new chunk_ids behind the warm-up run.  ValueError for an engine of
+        the other kind, or when the warm-up chunk does not fit the cache -- batched: an ACTIVE sequence's (0 <= pos[b] < t_max) only"""
+        self._need_chunk(what, batched)
+        self._chunks_fit(what, [0 <= p < self.t_max for p in self.pos.tolist()] if batched else None)
+        return self._capture(step, (self.pos, self.chunk_ids), keep_rng)
+
+    def capture_verify_greedy(self):
+        """chunk = R.  Capture _verify_greedy_step into ONE hipGraph (verify_graph): a replay verifies chunk_ids at the device position and
+        advances it by what was accepted; the host uploads chunk_ids and downloads verify_out once per step.  The capture runs the step once for
+        real at the current position: cache rows pos .. pos + R - 1 of every layer are overwritten (rows at and beyond pos are stale by contract,
+        so the history below pos is intact) and pos, chunk_ids are put back.  ValueError when the warm-up chunk does not fit the cache: capture
+        earlier in the sequence, or before the prompt (engine_generate captures at pos = 0, in front of the prefill)."""
+        self.verify_graph = self._capture_verify('capture_verify_greedy', self._verify_greedy_step)
+        return self
 
     def capture_verify_greedy_batch(self):
-        """capture _verify_greedy_batch_step into ONE hipGraph: a replay verifies chunk_ids [B, R] at the device positions and advances every
-        active sequence by what it accepted; the host uploads chunk_ids and downloads verify_out once per step.  The capture runs the step once
-        for real at the current positions (cache rows pos[b] .. pos[b] + R - 1 of every active slot are overwritten -- stale by contract) and
-        puts pos, chunk_ids back.  ValueError when an active sequence's warm-up chunk does not fit the cache: capture earlier, or before the
-        prompts (engine_generate_batch captures at pos = 0, in front of the prefill)."""
-        self._need_batch_chunk('capture_verify_greedy_batch')
-        for b, p in enumerate(self.pos.tolist()):
-            if 0 <= p < self.t_max and p + self.batch_chunk > self.t_max:
-                raise ValueError('DecodeEngine.capture_verify_greedy_batch: the warm-up step of sequence %d at positions %d .. %d does not fit the '
-                                 'engine cache (%d)' % (b, p, p + self.batch_chunk - 1, self.t_max))
-        self.verify_batch_graph = self._capture(self._verify_greedy_batch_step, (self.pos, self.chunk_ids))
+        """batch_chunk = R.  capture_verify_greedy for the B sequences -- the same step, the same stored graph (verify_batch_graph reads it) --
+        where only an active sequence's warm-up chunk has to fit; engine_generate_batch captures at pos = 0, in front of the prefill."""
+        self.verify_graph = self._capture_verify('capture_verify_greedy_batch', self._verify_greedy_step, batched=True)
         return self
 
     # -- speculative SAMPLING: the verify step followed by the accept / resample rule of gptq_spec_sample_rows_f16 (csrc/spec_sample.hip) -------
@@ -1275,12 +1230,7 @@ class DecodeEngine:
         at the device position, draws fresh uniforms, and leaves [a, tokens] in verify_out with pos advanced.  One capture serves every setting
         (set_sampling).  The generator's state is put back behind the warm-up run, as capture_sample_native does; the cache contract and the
         ValueError are capture_verify_greedy's."""
-        self._need_chunk('capture_verify_sample')
-        pos = int(self.pos[0])
-        if pos + self.chunk > self.t_max:
-            raise ValueError('DecodeEngine.capture_verify_sample: the warm-up step at positions %d .. %d does not fit the engine cache (%d)' % (
-                pos, pos + self.chunk - 1, self.t_max))
-        g = self._capture(lambda: self._verify_sample_step(bool(draft_logits)), (self.pos, self.chunk_ids), keep_rng=True)
+        g = self._capture_verify('capture_verify_sample', lambda: self._verify_sample_step(bool(draft_logits)), keep_rng=True)
         self.verify_sample_graphs[bool(draft_logits)] = g
         return g
 
@@ -1544,17 +1494,102 @@ def _draft_model_engine(eng, draft_model, settings):
     return deng
 
 
-def _engine_generate_speculative(model, input_ids, max_new_tokens, eos_token_id, eng, prefill, k, max_ngram, draft, settings=None, draft_model=None):
-    """engine_generate with speculation: prefill as the greedy path -> first token -> (draft; upload chunk_ids; replay the verify graph; read
-    (a, tokens); append the a + 1 tokens; eos / length cut) until done; the single-step graph where the chunk no longer fits or one token remains.
-    settings None: the verify-greedy graph and the greedy tail.  settings: the verify-sample graph -- with the draft model's logits rows when a draft
-    model is given, point-mass drafts otherwise --, the first token by sample_logits, the tail by the capture_sample_native graph.
-    draft_model: a batch-1 DecodeEngine of its own drafts k tokens per step under the same setting (greedily without one): it first consumes the
-    tokens it has not seen (one after a rejection, two after a full accept), its captured step leaves every step's logits row in
-    eng.chunk_draft_logits, and its position is set back behind a rejection."""
-    T, R = input_ids.shape[1], k + 1
+def _cut(tokens, left, eos_token_id):
+    """the first `left` ids of the list `tokens`, up to and including the first eos_token_id: (those ids, whether the eos is among them)"""
+    tokens = tokens[:left]
+    if eos_token_id is not None and eos_token_id in tokens:
+        return tokens[:tokens.index(eos_token_id) + 1], True
+    return tokens, False
+
+
+def _host_drafts(what, eng, k, max_ngram, draft):
+    """the HOST draft source of _generate_speculative: draft(tokens_so_far: list[int], k) -> k ids for every active sequence (default:
+    prompt_lookup_draft), behind the sequence's last token; ONE upload of chunk_ids for all sequences"""
     if draft is None:
-        draft = lambda toks, n: prompt_lookup_draft(toks, n, max_ngram)
+        draft = lambda toks, m: prompt_lookup_draft(toks, m, max_ngram)
+
+    def fill(seqs, done):
+        ids = []
+        for seq, idle in zip(seqs, done):
+            d = [0] * k if idle else [int(t) for t in draft(seq, k)]     # (the draft reads the list, it must not change it)
+            if len(d) != k:
+                raise ValueError('%s: the draft returned %d ids for k = %d' % (what, len(d), k))
+            ids.append([0 if idle else seq[-1]] + d)
+        eng.chunk_ids.view(len(seqs), k + 1).copy_(torch.tensor(ids, dtype=torch.int64))
+    return fill
+
+
+def _model_drafts(eng, deng, k, T):
+    """the draft-MODEL source of _generate_speculative, one sequence: the batch-1 engine `deng` (prompt of T tokens in its cache) first consumes the
+    tokens it has not seen (one after a rejection, two after a full accept: plain steps), then k replays of its captured draft step consume the
+    last token and d_1 .. d_{k-1} and draw d_1 .. d_k -- chunk_ids[1:] and the rows of chunk_draft_logits are written on the device"""
+    valid = [T]                                                  # deng's position behind its last drafts: its cache is seq's up to there at most
+
+    def fill(seqs, done):
+        seq = seqs[0]
+        L = len(seq)
+        seen = min(L - 1, valid[0])                              # tokens of seq it has consumed; behind a rejection its later rows are stale
+        deng.pos.fill_(seen)
+        for t in seq[seen:L - 1]:
+            deng.decode(t)
+        deng.ids.fill_(seq[-1])
+        deng.stepc.zero_()
+        for _ in range(k):
+            deng.draft_graph.replay()
+        eng.chunk_ids[0:1].fill_(seq[-1])
+        eng.chunk_ids[1:].copy_(deng.stream_rows[:k, 0])
+        valid[0] = L + k - 1
+    return fill
+
+
+def _generate_speculative(eng, prompts, first, max_new_tokens, eos_token_id, k, graph, drafts, finish):
+    """The ONE speculative loop, for n >= 1 sequences: engine_generate(speculate=...) is n = 1 on a chunk engine, engine_generate_batch(speculate=...)
+    n >= 2 on a batch_chunk engine.  prompts: n id lists already in the engine's cache; first: the token chosen behind each.  Per step: who is
+    active -- a sequence that hit its eos or its length idles (position -1) --; drafts(seqs, done) puts chunk_ids on the device (_host_drafts /
+    _model_drafts); ONE replay of `graph` (verify-greedy or verify-sample); ONE download of verify_out; every active sequence appends its
+    a_b + 1 tokens, cut at its length and its eos.  It ends when no active sequence has two tokens left or an active chunk no longer fits the
+    cache; finish(seqs, left) -> one id list per sequence then runs the caller's single-step graph for what remains and leaves the positions.
+    Returns (generated ids per sequence, dict(steps, emitted=[per sequence], accepted=[per sequence: per step]))."""
+    n, R = len(prompts), k + 1
+    seqs = [p + [f] for p, f in zip(prompts, first)]             # every token so far; the last one is not in the cache yet: pos = len - 1
+    gens = [[f] for f in first]
+    done = [(eos_token_id is not None and f == eos_token_id) or max_new_tokens <= 1 for f in first]
+    accepted, steps = [[] for _ in range(n)], 0
+    marked = [False] * n                                         # sequences whose device position holds the idle mark
+    while True:
+        active = [b for b in range(n) if not done[b]]
+        if not active or all(max_new_tokens - len(gens[b]) < 2 for b in active) or any(len(seqs[b]) - 1 + R > eng.t_max for b in active):
+            break
+        for b in range(n):
+            if done[b] and not marked[b]:
+                eng.pos[b:b + 1].fill_(-1)
+                marked[b] = True
+        drafts(seqs, done)
+        graph.replay()
+        res = eng.verify_out.view(n, R + 1).tolist()             # one copy per step: row b = [a_b, the a_b + 1 tokens of its step, ...]
+        steps += 1
+        for b in active:
+            a = res[b][0]
+            new, hit = _cut(res[b][1:a + 2], max_new_tokens - len(gens[b]), eos_token_id)
+            accepted[b].append(a)
+            gens[b].extend(new)
+            seqs[b].extend(new)
+            done[b] = hit or len(gens[b]) >= max_new_tokens
+    stats = dict(steps=steps, emitted=[len(g) - 1 for g in gens], accepted=accepted)
+    left = [0 if done[b] else max_new_tokens - len(gens[b]) for b in range(n)]
+    for b, tail in enumerate(finish(seqs, left)):
+        gens[b].extend(_cut(tail, left[b], eos_token_id)[0])
+    return gens, stats
+
+
+def _engine_generate_speculative(model, input_ids, max_new_tokens, eos_token_id, eng, prefill, k, max_ngram, draft, settings=None, draft_model=None):
+    """engine_generate with speculation: what _generate_speculative needs for the ONE sequence of a chunk engine.
+    settings None: the verify-greedy graph, the first token by argmax, the capture_greedy graph (stream_out) for the tail.  settings: the
+    verify-sample graph -- with the draft model's logits rows when a draft model is given, point-mass drafts otherwise --, the first token by
+    sample_logits, the tail by the capture_sample_native graph.
+    draft_model: _model_drafts on a batch-1 DecodeEngine of its own, under the same setting (greedily without one); else _host_drafts.
+    spec_stats: emitted as an int, accepted as the flat per-step list."""
+    T = input_ids.shape[1]
     with torch.no_grad():
         if settings is None:
             if eng.verify_graph is None:
@@ -1571,70 +1606,33 @@ def _engine_generate_speculative(model, input_ids, max_new_tokens, eos_token_id,
         deng = None if draft_model is None else _draft_model_engine(eng, draft_model, settings)
         logits = _prompt_into_engine(model, input_ids, eng, prefill)
         first = int(logits.argmax()) if settings is None else int(eng.sample_logits(logits.to(torch.float16).contiguous())[0])
-        seq = [int(t) for t in input_ids[0].tolist()] + [first]  # every token so far; the last one is not in the cache yet: pos = len(seq) - 1
         if deng is not None:
             deng.prefill(input_ids[0], start=0)
-            seen = T                                             # tokens of seq the draft engine has consumed (its position)
-        gen = [first]
-        accepted = []
-        emitted_total = 0
-        hit = eos_token_id is not None and first == eos_token_id
-        while len(gen) < max_new_tokens and not hit:
-            left = max_new_tokens - len(gen)
-            if len(seq) - 1 + R > eng.t_max or left < 2:
-                break
-            if deng is None:
-                d = [int(t) for t in draft(seq, k)]              # (the draft reads the list, it must not change it)
-                if len(d) != k:
-                    raise ValueError('engine_generate: the draft returned %d ids for k = %d' % (len(d), k))
-                eng.chunk_ids.copy_(torch.tensor([seq[-1]] + d, dtype=torch.int64))
-            else:
-                L = len(seq)
-                deng.pos.fill_(seen)
-                for t in seq[seen:L - 1]:                        # what it has not seen yet, but for the last token: plain steps
-                    deng.decode(t)
-                deng.ids.fill_(seq[-1])
-                deng.stepc.zero_()
-                for _ in range(k):                               # consumes seq[-1], d_1 .. d_{k-1}; draws d_1 .. d_k
-                    deng.draft_graph.replay()
-                eng.chunk_ids[0:1].fill_(seq[-1])
-                eng.chunk_ids[1:].copy_(deng.stream_rows[:k, 0])
-            graph.replay()
-            res = eng.verify_out.tolist()                        # one copy per step: [a, the a + 1 tokens of the step, ...]
-            a = res[0]
-            if deng is not None:
-                seen = len(seq) - 1 + min(a + 1, k)              # behind a rejection its later rows are stale
-            new = res[1:a + 2][:left]                            # the accepted drafts and the token after them
-            if eos_token_id is not None and eos_token_id in new:
-                new = new[:new.index(eos_token_id) + 1]
-                hit = True
-            accepted.append(a)
-            emitted_total += len(new)
-            gen.extend(new)
-            seq.extend(new)
-        eng.spec_stats = dict(steps=len(accepted), emitted=emitted_total, accepted=accepted)
-        eng.pos.fill_(len(seq) - 1)                              # (a step cut by the length or an eos advanced the device position further)
-        if not hit and len(gen) < max_new_tokens:                # the tail: single-step replays
-            p0, n = len(seq) - 1, max_new_tokens - len(gen)
+        drafts = _host_drafts('engine_generate', eng, k, max_ngram, draft) if deng is None else _model_drafts(eng, deng, k, T)
+
+        def finish(seqs, left):
+            seq, n = seqs[0], left[0]
+            p0 = len(seq) - 1
+            eng.pos.fill_(p0)                                    # (a step cut by the length or an eos advanced the device position further)
+            if n <= 0:
+                return [[]]
             if settings is None:
                 if eng.greedy_graph is None:
                     eng.capture_greedy()
-                eng.ids.fill_(seq[-1])
-                for _ in range(n):
-                    eng.greedy_graph.replay()
-                tail = eng.stream_out[p0 + 1:p0 + 1 + n].tolist()    # stream_out[p] = token generated after p consumed tokens
+                tail = eng.greedy_graph
             else:
                 if eng.sample_native_graph is None:
                     eng.capture_sample_native()                  # (its warm-up step writes cache row pos, which the tail overwrites first)
-                eng.ids.fill_(seq[-1])
+                tail = eng.sample_native_graph
                 eng.stepc.zero_()
-                for _ in range(n):
-                    eng.sample_native_graph.replay()
-                tail = eng.stream_rows[:n, 0].tolist()
-            if eos_token_id is not None and eos_token_id in tail:
-                tail = tail[:tail.index(eos_token_id) + 1]
-            gen.extend(tail)
-    return torch.cat([input_ids[0], torch.tensor(gen, dtype=input_ids.dtype, device=input_ids.device)]).unsqueeze(0)
+            eng.ids.fill_(seq[-1])
+            for _ in range(n):
+                tail.replay()
+            # stream_out[p] = token generated after p consumed tokens; stream_rows[i] = the token chosen by replay i
+            return [(eng.stream_out[p0 + 1:p0 + 1 + n] if settings is None else eng.stream_rows[:n, 0]).tolist()]
+        gens, st = _generate_speculative(eng, [[int(t) for t in input_ids[0].tolist()]], [first], max_new_tokens, eos_token_id, k, graph, drafts, finish)
+        eng.spec_stats = dict(steps=st['steps'], emitted=st['emitted'][0], accepted=st['accepted'][0])
+    return torch.cat([input_ids[0], torch.tensor(gens[0], dtype=input_ids.dtype, device=input_ids.device)]).unsqueeze(0)
 
 
 def _engine_generate_sampled(model, input_ids, max_new_tokens, eos_token_id, eng, prefill):
@@ -1663,75 +1661,32 @@ def _engine_generate_sampled(model, input_ids, max_new_tokens, eos_token_id, eng
 
 
 def _engine_generate_batch_speculative(prompts, max_new_tokens, eos_token_id, eng, k, max_ngram, draft):
-    """engine_generate_batch with speculation: prefill_batch -> first tokens by argmax -> (a draft per active sequence; ONE upload of chunk_ids;
-    replay the verify-greedy-batch graph; ONE download of verify_out; append every active sequence's a_b + 1 tokens; eos / length cut, after which
-    the sequence idles: position -1) until no active sequence has two tokens left or an active chunk no longer fits the cache; then the
-    capture_greedy_rows graph for what remains, the finished rows idling far below position 0."""
-    n, R = len(prompts), k + 1
-    if draft is None:
-        draft = lambda toks, m: prompt_lookup_draft(toks, m, max_ngram)
+    """engine_generate_batch with speculation: what _generate_speculative needs for the n sequences of a batch_chunk engine -- prefill_batch, the
+    first tokens by argmax, the verify-greedy graph, _host_drafts, and the capture_greedy_rows graph for the tail, the finished rows idling
+    far below position 0.  Afterwards every position is that of the sequence's last token, the one not consumed yet."""
+    n = len(prompts)
     with torch.no_grad():
-        if eng.verify_batch_graph is None:
+        if eng.verify_graph is None:
             eng.pos.zero_()                                      # (the capture's warm-up step writes cache rows pos .. pos + R - 1 of every slot)
             eng.capture_verify_greedy_batch()
         if eng.greedy_rows_graph is None:
             eng.pos.zero_()
             eng.capture_greedy_rows()
         first = eng.prefill_batch(prompts, starts=[0] * n).argmax(dim=-1).tolist()
-        seqs = [[int(t) for t in p.tolist()] + [f] for p, f in zip(prompts, first)]     # every token so far; the last one is not in the cache yet
-        gens = [[f] for f in first]
-        done = [(eos_token_id is not None and f == eos_token_id) or max_new_tokens == 1 for f in first]
-        accepted = [[] for _ in range(n)]
-        steps = 0
-        marked = [False] * n                                     # sequences whose device position holds the idle mark
-        while True:
-            active = [b for b in range(n) if not done[b]]
-            if not active or all(max_new_tokens - len(gens[b]) < 2 for b in active) or any(len(seqs[b]) - 1 + R > eng.t_max for b in active):
-                break
-            for b in range(n):
-                if done[b] and not marked[b]:
-                    eng.pos[b:b + 1].fill_(-1)
-                    marked[b] = True
-            ids = []
-            for b in range(n):
-                if done[b]:
-                    ids.append([0] * R)
-                    continue
-                d = [int(t) for t in draft(seqs[b], k)]          # (the draft reads the list, it must not change it)
-                if len(d) != k:
-                    raise ValueError('engine_generate_batch: the draft returned %d ids for k = %d' % (len(d), k))
-                ids.append([seqs[b][-1]] + d)
-            eng.chunk_ids.copy_(torch.tensor(ids, dtype=torch.int64))
-            eng.verify_batch_graph.replay()
-            res = eng.verify_out.tolist()                        # one copy per step: row b = [a_b, the a_b + 1 tokens of its step, ...]
-            steps += 1
-            for b in active:
-                a = res[b][0]
-                new = res[b][1:a + 2][:max_new_tokens - len(gens[b])]
-                if eos_token_id is not None and eos_token_id in new:
-                    new = new[:new.index(eos_token_id) + 1]
-                    done[b] = True
-                accepted[b].append(a)
-                gens[b].extend(new)
-                seqs[b].extend(new)
-                done[b] = done[b] or len(gens[b]) >= max_new_tokens
-        eng.spec_stats = dict(steps=steps, emitted=[len(g) - 1 for g in gens], accepted=accepted)
-        left = [0 if done[b] else max_new_tokens - len(gens[b]) for b in range(n)]
-        if max(left) > 0:                                        # the tail: single-step replays for all rows, the finished ones idle
+
+        def finish(seqs, left):
+            if max(left) <= 0:
+                return [[]] * n
             far = -(eng.t_max + 1)                               # (a step adds 1 to every position: still negative after the tail)
-            eng.pos.copy_(torch.tensor([far if done[b] else len(seqs[b]) - 1 for b in range(n)], dtype=torch.int64))
-            eng.ids.copy_(torch.tensor([0 if done[b] else seqs[b][-1] for b in range(n)], dtype=torch.int64))
+            eng.pos.copy_(torch.tensor([len(s) - 1 if m else far for s, m in zip(seqs, left)], dtype=torch.int64))
+            eng.ids.copy_(torch.tensor([s[-1] if m else 0 for s, m in zip(seqs, left)], dtype=torch.int64))
             eng.stepc.zero_()
             for _ in range(max(left)):
                 eng.greedy_rows_graph.replay()
-            tail = eng.stream_rows[:max(left)].t().tolist()      # [row][step]
-            for b in range(n):
-                new = tail[b][:left[b]]
-                if eos_token_id is not None and eos_token_id in new:
-                    new = new[:new.index(eos_token_id) + 1]
-                gens[b].extend(new)
-                seqs[b].extend(new)
-        eng.pos.copy_(torch.tensor([len(s) - 1 for s in seqs], dtype=torch.int64))     # every row: its last token is the one not consumed yet
+            return eng.stream_rows[:max(left)].t().tolist()      # [row][step]
+        gens, eng.spec_stats = _generate_speculative(eng, [[int(t) for t in p.tolist()] for p in prompts], first, max_new_tokens, eos_token_id, k,
+                                                     eng.verify_graph, _host_drafts('engine_generate_batch', eng, k, max_ngram, draft), finish)
+        eng.pos.copy_(torch.tensor([p.numel() + len(g) - 1 for p, g in zip(prompts, gens)], dtype=torch.int64))
         return [torch.cat([p, torch.tensor(g, dtype=p.dtype, device=p.device)]) for p, g in zip(prompts, gens)]
 
 

@@ -88,6 +88,33 @@ def test_verify_matches_the_module_chain(T):
     assert np.array_equal(short, got[:2])
 
 
+@pytest.mark.parametrize('T', [3, 64, 130])
+def test_verify_has_the_bits_of_the_single_sequence_entry(T):
+    """the engine's verify step (the batched chunk attention at one sequence) against the same step driven by hand through the single-sequence
+    entry gptq_decode_attn_chunk_f16 on kc / vc with a workspace of its own: logits and the R new cache rows agree bit for bit"""
+    eng = _engine()
+    ids = _ids(T + R, 300 + T)
+    bits = lambda t: t.clone().view(torch.int16)
+    eng.prefill(ids[0, :T], start=0)
+    eng.verify(ids[0, T:T + R])
+    got = [bits(eng.chunk_logits), bits(eng.kc[:, T:T + R]), bits(eng.vc[:, T:T + R])]
+    eng.prefill(ids[0, :T], start=0)
+    heads, hd = eng.heads, eng.head_dim
+    ws = torch.zeros(eng.lib.gptq_decode_attn_chunk_workspace_bytes(R, heads, hd, T_MAX), dtype=torch.uint8, device=DEV)
+
+    def attn(li, L, qkvb, ab, tab, s):
+        rc = eng.lib.gptq_decode_attn_chunk_f16(qkvb.data_ptr(), qkvb.stride(0), R, eng.pos.data_ptr(), eng.kc[li].data_ptr(), eng.vc[li].data_ptr(),
+                                                ab.data_ptr(), ab.stride(0), ws.data_ptr(), ws.numel(), heads, hd, T_MAX, L['theta'], eng.scale,
+                                                eng.native.ptr(tab), s)
+        eng.native.check(rc, 'gptq_decode_attn_chunk_f16')
+    with torch.no_grad(), torch.cuda.device(DEV):
+        eng._step_rows(eng.chunk_bufs, ids[0, T:T + R].contiguous(), attn, eng.chunk_logits)
+    torch.cuda.synchronize()
+    assert int(eng.pos[0]) == T
+    for new, old in zip(got, [bits(eng.chunk_logits), bits(eng.kc[:, T:T + R]), bits(eng.vc[:, T:T + R])]):
+        assert torch.equal(new, old)
+
+
 def test_accept_then_continue():
     """verify five tokens, accept two, go on: the three rejected rows leave no trace in the logits or in the cache rows below pos"""
     model, eng = _model(), _engine()
