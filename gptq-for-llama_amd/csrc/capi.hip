@@ -3,6 +3,7 @@
 // (quant/custom_autotune.py:14-127, pruner :167-193) behind the same warm-up surface.
 #include <algorithm>
 #include <atomic>
+#include <climits>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -39,10 +40,18 @@ struct Problem {
     float norm_eps;
 };
 
+static bool bits_ok(int bits) { return bits == 2 || bits == 3 || bits == 4 || bits == 8; }
+
+// the (bits, K, N, groupsize) of a quantised weight: GPTQ_E_BITS before GPTQ_E_SHAPE, as every entry reports them
+static int check_weight(int bits, int K, int N, int groupsize) {
+    if (!bits_ok(bits)) return GPTQ_E_BITS;
+    if (K <= 0 || N <= 0 || groupsize <= 0 || K % 32 != 0 || N % 32 != 0) return GPTQ_E_SHAPE;
+    return 0;
+}
+
 static int validate(const Problem &q) {
-    if (q.bits != 2 && q.bits != 3 && q.bits != 4 && q.bits != 8) return GPTQ_E_BITS;
-    if (q.M < 0 || q.K <= 0 || q.N <= 0 || q.groupsize <= 0) return GPTQ_E_SHAPE;
-    if (q.K % 32 != 0 || q.N % 32 != 0) return GPTQ_E_SHAPE;
+    if (int rc = check_weight(q.bits, q.K, q.N, q.groupsize)) return rc;
+    if (q.M < 0) return GPTQ_E_SHAPE;
     const int ns = q.fused2 ? 2 : 1;
     if (!q.x || !q.y) return GPTQ_E_NULL;
     for (int s = 0; s < ns; s++)
@@ -60,6 +69,14 @@ static bool fast_eligible(const Problem &q, int unit_k) {
     if (q.bits == 3) return false;
     if (q.gi[0] || (q.fused2 && q.gi[1])) return false;
     return q.groupsize % unit_k == 0;
+}
+// the 2/4/8-bit rowwave GEMV serves it: trivial g_idx, groups of whole packed rows (3-bit: only through run_gemv's own rule)
+static bool rowwave_eligible(const Problem &q) { return fast_eligible(q, 32 / q.bits); }
+
+// the second weight set of a gate | up pair (gi NULL: trivial g_idx)
+static void make_pair(Problem &q, const int32_t *qw, const void *sc, const int32_t *qz, const int32_t *gi) {
+    q.fused2 = true;
+    q.qw[1] = qw; q.sc[1] = sc; q.qz[1] = qz; q.gi[1] = gi;
 }
 
 static void fill_params(const Problem &q, int m0, int mcount, GemvParams &p) {
@@ -92,92 +109,61 @@ static int ilog2_exact(int v) {
     return -1;
 }
 
-// The rowwave GEMV (gemv.hip) serves M == 1 (2 <= M <= 4 at 4 bits: run_rowwave_mr, one launch); larger M here means M launches (the dispatcher
-// sends M >= 2 to the weight-streaming MFMA kernel instead).  Picks U = packed rows in flight
-// per wave and S = workgroups per 256-column tile (DESIGN.md "dispatch").
-// 3-bit rowwave: units are 32-k blocks (3 packed rows each)
-static int run_rowwave3(const Problem &q, hipStream_t s) {
-    if (q.norm_w || q.xperm) return GPTQ_E_VARIANT;
-    const int nblocks = q.K / 32;
-    const int G = n_groups(q.K, q.groupsize);
-    int gshift = -1;
-    if (G > 1) {
-        if (q.groupsize % 32 != 0) return GPTQ_E_VARIANT;
-        gshift = ilog2_exact(q.groupsize / 32);
-        if (gshift < 0) return GPTQ_E_VARIANT;
-    }
-    const int bpg = G > 1 ? q.groupsize / 32 : nblocks;
-    int u = 0;
-    const int fv = g_force_variant.load();
-    for (int c = 2; c >= 1 && !u; c >>= 1)
-        if (nblocks % c == 0 && (G == 1 || bpg % c == 0)) u = c;
-    if (fv >= 0) {
-        if (fv > 1) return GPTQ_E_VARIANT;
-        u = 2 >> fv;
-        if (!(nblocks % u == 0 && (G == 1 || bpg % u == 0))) return GPTQ_E_VARIANT;
-    }
-    const int ntile = (q.N + 255) / 256;
-    const int nchunk = (nblocks + 4 * u - 1) / (4 * u);
-    int split_k = nchunk;
-    if (ntile * split_k > 1024) split_k = 1024 / ntile;
-    if (split_k < 1) split_k = 1;
-    const int fs = g_force_split_k.load();
-    if (fs >= 1) split_k = fs;
-    if (split_k > nchunk) split_k = nchunk;
-    if (split_k > (q.fused2 ? SPLITK_MAX_PAIR : SPLITK_MAX_SINGLE)) split_k = q.fused2 ? SPLITK_MAX_PAIR : SPLITK_MAX_SINGLE;
-    // the per-column arrival counts live in the first SPLITK_TICKET_OFFSET bytes of the workspace (the rest belongs
-    // to the stream kernel's tickets and to the partials): wider layers run without a K split, and the slices are
-    // limited to the partials that fit
-    const int ns = q.fused2 ? 2 : 1;
-    const bool ws_ok = q.ws && aligned(q.ws, 8) && q.ws_bytes > SPLITK_PART_OFFSET && (size_t)q.N * 4 <= SPLITK_TICKET_OFFSET;
-    const int split_fit = ws_ok ? (int)((q.ws_bytes - SPLITK_PART_OFFSET) / splitk_part_bytes(1, q.N, ns)) : 1;
-    if (split_k > 1 && (!ws_ok || split_fit < 2)) {
-        if (fs >= 1) return GPTQ_E_WORKSPACE;
-        split_k = 1;
-    }
-    if (split_k > split_fit) {
-        if (fs >= 1) return GPTQ_E_WORKSPACE;   // as the stream kernel: a forced split the workspace cannot hold is refused
-        split_k = split_fit;
-    }
-    for (int m = 0; m < q.M; m++) {
-        GemvParams p;
-        fill_params(q, m, 1, p);
-        p.split_k = split_k;
-        p.upg_shift = gshift;
-        int rc = gemv_fast_dispatch(3, q.fused2, u, p, s);
-        if (rc) return rc;
-    }
-    return 0;
+// ---------------------------------------------------------------------------------------------- the launch planner
+// Every product on the checkpoint layout walks ONE ladder (run_auto / run_skinny / run_gemv / run_rowwave* / run_generic below) whose
+// rungs size their launch with the plan_* functions.  A Walk says where the walk ends: in launches on `s`, or -- for
+// gptq_gemv_plan_for_shape -- at the FIRST dispatch call, whose kernel family and plan are written to `plan` instead: nothing is
+// launched and no pointer of the Problem is read.  The query cannot drift from the launches: it is the same code.
+struct Walk {
+    hipStream_t s;
+    int *plan;   // NULL: launch.  Else int [1 + GPTQ_PLAN_FIELDS]: GPTQ_KERNEL_*, then the fields
+};
+constexpr int PLAN_TAKEN = INT_MIN;   // a dispatch site's answer on a query's walk: no rung mistakes it for a kernel's verdict
+
+static int take_plan(const Walk &w, int family, int rows, int unit, int split_k, int upg_shift = 0, int ntiles = 0, int chunks_per_slice = 0,
+                     int waves = 0, int xlds = 0) {
+    const int v[1 + GPTQ_PLAN_FIELDS] = {family, rows, unit, split_k, waves, xlds, upg_shift, ntiles, chunks_per_slice};   // the order of GPTQ_PLAN_*
+    std::copy(v, v + 1 + GPTQ_PLAN_FIELDS, w.plan);
+    return PLAN_TAKEN;
 }
 
-static int run_rowwave(const Problem &q, hipStream_t s) {
-    if (q.bits == 3) return run_rowwave3(q, s);
-    const int kpw = 32 / q.bits;
-    const int rows = q.K / kpw;
-    const int G = n_groups(q.K, q.groupsize);
-    const int rpg = q.groupsize / kpw;  // packed rows per group
-    int gshift = -1;
+// The rowwave GEMV (gemv.hip) in its three forms: 2/4/8-bit and 3-bit, one launch per row of x (M == 1 is the intended use; the
+// dispatcher sends M >= 2 to the weight-streaming MFMA kernel instead), and the 2..8-row _mr form, one launch for all rows.
+struct RowwaveForm {
+    int unit_k;     // k per unit: one packed row (32 / bits), 3-bit: one 32-k block (3 packed rows)
+    int uhi, ulo;   // range of U = units in flight per wave
+    int nforce;     // gptq_set_gemv_variant(v), v < nforce, forces U = uhi >> v; 0: this form has no forced U
+    bool per_row;   // one arrival count per column and a K split that shrinks to the workspace; else one count per output element
+                    // ({gate, up} pair) of all rows, and partials that do not fit are refused: the per-row / stream paths handle it
+};
+struct RowwavePlan { int u, upg_shift, split_k; };
+
+// Picks U and S = workgroups per 256-column tile (DESIGN.md "dispatch"); upg_shift = log2(units per group), -1 with one group.
+static int plan_rowwave(const Problem &q, const RowwaveForm &f, RowwavePlan &pl) {
+    const int units = q.K / f.unit_k, G = n_groups(q.K, q.groupsize), upg = q.groupsize / f.unit_k;
+    pl.upg_shift = -1;
     if (G > 1) {
-        if (q.groupsize % kpw != 0) return GPTQ_E_VARIANT;
-        gshift = ilog2_exact(rpg);
-        if (gshift < 0) return GPTQ_E_VARIANT;
+        if (q.groupsize % f.unit_k != 0) return GPTQ_E_VARIANT;
+        pl.upg_shift = ilog2_exact(upg);
+        if (pl.upg_shift < 0) return GPTQ_E_VARIANT;
     }
-    auto u_ok = [&](int u) { return rows % u == 0 && (G == 1 || rpg % u == 0); };
+    auto u_ok = [&](int u) { return units % u == 0 && (G == 1 || upg % u == 0); };
     int u = 0;
-    const int fv = g_force_variant.load();
+    const int fv = f.nforce ? g_force_variant.load() : -1;
     if (fv >= 0) {
-        if (fv >= GEMV_NUM_VARIANTS) return GPTQ_E_VARIANT;
-        u = 8 >> fv;
+        if (fv >= f.nforce) return GPTQ_E_VARIANT;
+        u = f.uhi >> fv;
         if (!u_ok(u)) return GPTQ_E_VARIANT;
     } else {
-        for (int c = 8; c >= 2 && !u; c >>= 1)
+        for (int c = f.uhi; c >= f.ulo && !u; c >>= 1)
             if (u_ok(c)) u = c;
         if (!u) return GPTQ_E_VARIANT;
     }
     if (q.norm_w && (u != 8 || q.bits != 4 || q.M != 1)) return GPTQ_E_VARIANT;
     if (q.xperm && q.bits != 4) return GPTQ_E_VARIANT;
+    pl.u = u;
     const int ntile = (q.N + 255) / 256;
-    const int nchunk = (rows + 4 * u - 1) / (4 * u);
+    const int nchunk = (units + 4 * u - 1) / (4 * u);
     const int split_max = q.fused2 ? SPLITK_MAX_PAIR : SPLITK_MAX_SINGLE;
     int split_k = nchunk;                                  // one chunk per workgroup ...
     if (ntile * split_k > 1024) split_k = 1024 / ntile;    // ... unless that is > 4 workgroups per CU
@@ -186,53 +172,68 @@ static int run_rowwave(const Problem &q, hipStream_t s) {
     if (fs >= 1) split_k = fs;
     if (split_k > nchunk) split_k = nchunk;
     if (split_k > split_max) split_k = split_max;
-    // the per-column arrival counts live in the first SPLITK_TICKET_OFFSET bytes of the workspace (the rest belongs
-    // to the stream kernel's tickets and to the partials): wider layers run without a K split, and the slices are
-    // limited to the partials that fit
+    // the arrival counts live in the first SPLITK_TICKET_OFFSET bytes of the workspace (the rest belongs to the stream kernel's
+    // tickets and to the partials): wider layers run without a K split, and the slices are limited to the partials that fit
     const int ns = q.fused2 ? 2 : 1;
-    const bool ws_ok = q.ws && aligned(q.ws, 8) && q.ws_bytes > SPLITK_PART_OFFSET && (size_t)q.N * 4 <= SPLITK_TICKET_OFFSET;
-    const int split_fit = ws_ok ? (int)((q.ws_bytes - SPLITK_PART_OFFSET) / splitk_part_bytes(1, q.N, ns)) : 1;
-    if (split_k > 1 && (!ws_ok || split_fit < 2)) {
-        if (fs >= 1) return GPTQ_E_WORKSPACE;
-        split_k = 1;
+    const size_t ncomb = f.per_row ? (size_t)q.N : (size_t)q.M * q.N;
+    const bool ws_ok = q.ws && aligned(q.ws, 8) && q.ws_bytes > SPLITK_PART_OFFSET && ncomb * 4 <= SPLITK_TICKET_OFFSET;
+    if (!f.per_row) {
+        if (split_k > 1 && !(ws_ok && q.ws_bytes - SPLITK_PART_OFFSET >= splitk_part_bytes(split_k, ncomb, ns))) return GPTQ_E_VARIANT;
+    } else {
+        const int split_fit = ws_ok ? (int)((q.ws_bytes - SPLITK_PART_OFFSET) / splitk_part_bytes(1, ncomb, ns)) : 1;
+        if (split_k > 1 && (!ws_ok || split_fit < 2)) {
+            if (fs >= 1) return GPTQ_E_WORKSPACE;
+            split_k = 1;
+        }
+        if (split_k > split_fit) {
+            if (fs >= 1) return GPTQ_E_WORKSPACE;   // as the stream kernel: a forced split the workspace cannot hold is refused
+            split_k = split_fit;
+        }
     }
-    if (split_k > split_fit) {
-        if (fs >= 1) return GPTQ_E_WORKSPACE;   // as the stream kernel: a forced split the workspace cannot hold is refused
-        split_k = split_fit;
-    }
+    pl.split_k = split_k;
+    return 0;
+}
+
+static int run_rowwave(const Problem &q, const Walk &w) {
+    RowwavePlan pl;
+    if (int rc = plan_rowwave(q, q.bits == 3 ? RowwaveForm{32, 2, 1, 2, true} : RowwaveForm{32 / q.bits, 8, 2, GEMV_NUM_VARIANTS, true}, pl)) return rc;
     for (int m = 0; m < q.M; m++) {
+        if (w.plan) return take_plan(w, GPTQ_KERNEL_ROWWAVE, 1, pl.u, pl.split_k, pl.upg_shift);
         GemvParams p;
         fill_params(q, m, 1, p);
-        p.split_k = split_k;
-        p.upg_shift = gshift;
-        int rc = gemv_fast_dispatch(q.bits, q.fused2, u, p, s);
-        if (rc) return rc;
+        p.split_k = pl.split_k;
+        p.upg_shift = pl.upg_shift;
+        if (int rc = gemv_fast_dispatch(q.bits, q.fused2, pl.u, p, w.s)) return rc;
     }
     return 0;
 }
 
-static int run_generic(const Problem &q, hipStream_t s) {
-    const int ns = q.fused2 ? 2 : 1;
+// The generic kernel's tile: mr rows of x and 4 * nl columns per workgroup against 150 KB of LDS -- x [mr][K] + g_idx + the {s, z}
+// table of the tile; narrow tiles when G is large.  false: not even one row with narrow tiles fits.
+static bool plan_generic(int rows_left, int K, int N, int G, int ns, int &mr, int &nl) {
+    mr = rows_left >= 4 ? 4 : (rows_left >= 2 ? 2 : 1);
+    if (ns == 2 && mr > 2) mr = 2;
+    nl = 16;
+    auto need = [&](int mr_, int nl_) { return (size_t)mr_ * K * 2 + (size_t)ns * K * 2 + 16 + (size_t)ns * G * 4 * nl_ * 4; };
+    if (need(mr, nl) > 150 * 1024 || (N / 64) < 128) nl = 4;
+    while (mr > 1 && need(mr, nl) > 150 * 1024) mr >>= 1;
+    return need(mr, nl) <= 150 * 1024;
+}
+
+static int run_generic(const Problem &q, const Walk &w) {
     const int nchunks = q.K / 32;
     for (int m0 = 0; m0 < q.M;) {
-        int mr = q.M - m0 >= 4 ? 4 : (q.M - m0 >= 2 ? 2 : 1);
-        if (q.fused2 && mr > 2) mr = 2;
+        int mr, nl;
+        plan_generic(q.M - m0, q.K, q.N, n_groups(q.K, q.groupsize), q.fused2 ? 2 : 1, mr, nl);   // (what does not fit, the launch refuses)
+        const int ntiles = (q.N + 4 * nl - 1) / (4 * nl);
+        if (w.plan) return take_plan(w, GPTQ_KERNEL_GENERIC, mr, nl, 1, 0, ntiles, nchunks);
         GemvParams p;
-        // LDS: x [mr][K] + g_idx + {s,z} table for the tile; narrow tiles when G is large
-        const int G = n_groups(q.K, q.groupsize);
-        int nl = 16;
-        auto need = [&](int mr_, int nl_) {
-            return (size_t)mr_ * q.K * 2 + (size_t)ns * q.K * 2 + 16 + (size_t)ns * G * 4 * nl_ * 4;
-        };
-        if (need(mr, nl) > 150 * 1024 || (q.N / 64) < 128) nl = 4;
-        while (mr > 1 && need(mr, nl) > 150 * 1024) mr >>= 1;
         fill_params(q, m0, mr, p);
-        p.ntiles = (q.N + 4 * nl - 1) / (4 * nl);
+        p.ntiles = ntiles;
         p.split_k = 1;
         p.nchunks = nchunks;
         p.chunks_per_slice = nchunks;
-        int rc = gemv_generic_dispatch(q.bits, q.fused2, nl, p, s);
-        if (rc) return rc;
+        if (int rc = gemv_generic_dispatch(q.bits, q.fused2, nl, p, w.s)) return rc;
         m0 += mr;
     }
     return 0;
@@ -244,149 +245,156 @@ static int run_generic(const Problem &q, hipStream_t s) {
 // M because the combine issues M * N * S returning atomics.  The two-block MFMA variant (M <= 8) is compiled and
 // tested (gptq_set_gemv_variant(101)) but loses to the stream kernel (M = 8: 10.4 vs 8.5 us) and is not dispatched.
 // gptq_set_gemv_variant(100) forces the dot2 kernel, 101 the MFMA kernel (A/B measurements, tests).
-static int run_rowwave_mr(const Problem &q, hipStream_t s) {
+static int run_rowwave_mr(const Problem &q, const Walk &w) {
     const int fv = g_force_variant.load();
     if (fv >= 0 && fv != 100 && fv != 101) return GPTQ_E_VARIANT;
     const bool mfma = fv == 101 || (fv != 100 && q.M >= 3);
     const int mmax = fv == 101 ? (q.fused2 ? 4 : 8) : 4;
     if (q.bits != 4 || q.M < 2 || q.M > mmax || q.norm_w || q.xperm) return GPTQ_E_VARIANT;
     if (!fast_eligible(q, 8)) return GPTQ_E_VARIANT;
-    const int rows = q.K / 8;
-    const int G = n_groups(q.K, q.groupsize);
-    const int rpg = q.groupsize / 8;
-    int gshift = -1;
-    if (G > 1) {
-        if (q.groupsize % 8 != 0) return GPTQ_E_VARIANT;
-        gshift = ilog2_exact(rpg);
-        if (gshift < 0) return GPTQ_E_VARIANT;
-    }
-    auto u_ok = [&](int u) { return rows % u == 0 && (G == 1 || rpg % u == 0); };
-    int u = 0;
-    const int uhi = (mfma || q.M == 2) ? 8 : 4, ulo = (mfma || q.M == 2) ? 4 : 2;   // dot2 variant: x rows live in SGPRs (MR * u * 4 dwords)
-    for (int c = uhi; c >= ulo && !u; c >>= 1)
-        if (u_ok(c)) u = c;
-    if (!u) return GPTQ_E_VARIANT;
-    const int ntile = (q.N + 255) / 256;
-    const int nchunk = (rows + 4 * u - 1) / (4 * u);
-    int split_k = nchunk;
-    if (ntile * split_k > 1024) split_k = 1024 / ntile;
-    if (split_k < 1) split_k = 1;
-    const int fs = g_force_split_k.load();
-    if (fs >= 1) split_k = fs;
-    if (split_k > nchunk) split_k = nchunk;
-    const int split_max = q.fused2 ? SPLITK_MAX_PAIR : SPLITK_MAX_SINGLE;
-    if (split_k > split_max) split_k = split_max;
-    const size_t ncomb = (size_t)q.M * q.N;   // one arrival count per output element ({gate, up} pair)
-    const bool ws_ok = q.ws && aligned(q.ws, 8) && q.ws_bytes > SPLITK_PART_OFFSET && ncomb * 4 <= SPLITK_TICKET_OFFSET &&
-                       q.ws_bytes - SPLITK_PART_OFFSET >= splitk_part_bytes(split_k, ncomb, q.fused2 ? 2 : 1);
-    if (split_k > 1 && !ws_ok) return GPTQ_E_VARIANT;   // the per-row / stream paths handle it
+    const bool wide = mfma || q.M == 2;   // the dot2 variant at M = 3, 4 runs narrower: its x rows live in SGPRs (MR * u * 4 dwords)
+    RowwavePlan pl;
+    if (int rc = plan_rowwave(q, RowwaveForm{8, wide ? 8 : 4, wide ? 4 : 2, 0, false}, pl)) return rc;
+    if (w.plan) return take_plan(w, mfma ? GPTQ_KERNEL_ROWWAVE_MFMA : GPTQ_KERNEL_ROWWAVE_MR, q.M, pl.u, pl.split_k, pl.upg_shift);
     GemvParams p;
     fill_params(q, 0, q.M, p);
-    p.split_k = split_k;
-    p.upg_shift = gshift;
-    return mfma ? gemv_rowwave_mfma_dispatch(q.fused2, u, p, s) : gemv_rowwave_mr_dispatch(q.fused2, u, p, s);
+    p.split_k = pl.split_k;
+    p.upg_shift = pl.upg_shift;
+    return mfma ? gemv_rowwave_mfma_dispatch(q.fused2, pl.u, p, w.s) : gemv_rowwave_mr_dispatch(q.fused2, pl.u, p, w.s);
 }
 
-static int run_gemv(const Problem &q, hipStream_t s) {
+static int run_gemv(const Problem &q, const Walk &w) {
     if (q.M >= 2 && q.M <= 8) {   // (M > 4 only when the MFMA variant is forced)
-        const int rc = run_rowwave_mr(q, s);
+        const int rc = run_rowwave_mr(q, w);
         if (rc != GPTQ_E_VARIANT) return rc;
     }
     const bool eligible3 = q.bits == 3 && !q.gi[0] && !(q.fused2 && q.gi[1]) && q.M <= GEMV_MAX_M;   // one launch per row
-    if (eligible3 || fast_eligible(q, 32 / (q.bits == 3 ? 4 : q.bits))) {
-        int rc = run_rowwave(q, s);
+    if (eligible3 || rowwave_eligible(q)) {
+        int rc = run_rowwave(q, w);
         if (rc != GPTQ_E_VARIANT || g_force_variant.load() >= 0) return rc;
     }
-    return run_generic(q, s);
+    return run_generic(q, w);
 }
 
 // The weight-streaming MFMA kernel (skinny_mfma.hip): M <= 64, trivial g_idx, whole groups.
-static int run_skinny(const Problem &q, hipStream_t s) {
+struct SkinnyPlan {
+    int stg, waves, split_k, chunks_per_slice, ntiles, upg, nunits;
+    bool xlds;
+};
+
+// the plan of one pass of mc rows; GPTQ_E_VARIANT: not this kernel's (x does not fit LDS with two-unit stages), the GEMV's
+static int plan_skinny(const Problem &q, int mc, SkinnyPlan &pl) {
     const int unit_k = (q.bits == 2) ? 64 : 32;
-    if (!fast_eligible(q, unit_k) || q.K % q.groupsize != 0) return run_gemv(q, s);
     const int upg = q.groupsize / unit_k;
     const int nunits = q.K / unit_k;
-    const int mmax = q.fused2 ? 32 : SKINNY_MAX_M;
     const int split_max = 32;
     int waves = 4;
     const int fv = g_force_variant.load();
     if (fv == 2 || fv == 4 || fv == 8) waves = fv;
+    const int ntiles = (q.N + 63) / 64;
+    // x rows staged in LDS: M <= 16 always, M <= 32 with the 4-unit-stage kernel (M = 64 measured slower than
+    // re-reading x from L2: four A fragments per unit make the wave LDS-bound)
+    bool xlds = mc <= 16 || (mc <= 32 && upg % 4 == 0);
+    const int stg = (upg % 4 == 0) ? 4 : ((upg % 2 == 0 && xlds) ? 2 : 1);
+    const int nstages = nunits / stg;
+    const int w = (xlds && stg == 4) ? waves : 4;
+    // K slices publish partial tiles [tile][slice][sets][rows][64] fp32 behind the ticket words
+    const size_t part_per_slice = (size_t)ntiles * (q.fused2 ? 2 : 1) * (mc < 64 ? mc : 64) * 64 * 4;
+    const bool ws_ok = q.ws && aligned(q.ws, 8) && q.ws_bytes > SPLITK_PART_OFFSET + 2 * part_per_slice && ntiles <= 1024;
+    const int split_fit = ws_ok ? (int)((q.ws_bytes - SPLITK_PART_OFFSET) / part_per_slice) : 1;
+    // K split: ~2 workgroups per CU, every wave of a workgroup gets at least one stage
+    int split_k = 1;
+    const int fs = g_force_split_k.load();
+    if (fs >= 1) {
+        split_k = fs;
+        if (split_k > 1 && (!ws_ok || split_k > split_fit)) return GPTQ_E_WORKSPACE;
+    } else if (ws_ok) {
+        split_k = (512 + ntiles - 1) / ntiles;
+        if (split_k > split_fit) split_k = split_fit;
+    }
+    if (split_k > split_max) split_k = split_max;
+    if (split_k * w > nstages) split_k = nstages / w;
+    if (split_k < 1) split_k = 1;
+    int sps = (nstages + split_k - 1) / split_k;  // stages per slice
+    // staged x must fit: rows * (units * unit_k + 8) halves
+    auto x_bytes = [&](int sps_) { return (size_t)mc * ((size_t)sps_ * stg * unit_k + 8) * 2 + 16; };
+    if (xlds && x_bytes(sps) > 64 * 1024) {
+        if (ws_ok && fs < 1) {
+            while (x_bytes(sps) > 64 * 1024 && split_k < split_max && (split_k + 1) * w <= nstages) {
+                split_k++;
+                sps = (nstages + split_k - 1) / split_k;
+            }
+        }
+        if (x_bytes(sps) > 64 * 1024) xlds = false;
+    }
+    if (!xlds && stg == 2) return GPTQ_E_VARIANT;
+    split_k = (nstages + sps - 1) / sps;
+    if (split_k > 1 && split_k > split_fit) return GPTQ_E_WORKSPACE;
+    pl = SkinnyPlan{stg, (xlds && stg == 4) ? waves : 4, split_k, sps * stg, ntiles, upg, nunits, xlds};
+    return 0;
+}
+
+static int run_skinny(const Problem &q, const Walk &w) {
+    if (!fast_eligible(q, (q.bits == 2) ? 64 : 32) || q.K % q.groupsize != 0) return run_gemv(q, w);
+    const int mmax = q.fused2 ? 32 : SKINNY_MAX_M;
     for (int m0 = 0; m0 < q.M; m0 += mmax) {
         const int mc = (q.M - m0 < mmax) ? (q.M - m0) : mmax;
+        SkinnyPlan pl;
+        const int rc = plan_skinny(q, mc, pl);
+        if (rc == GPTQ_E_VARIANT) return run_gemv(q, w);
+        if (rc) return rc;
+        const int upg_shift = ilog2_exact(pl.upg);
+        if (w.plan) return take_plan(w, GPTQ_KERNEL_STREAM, mc, pl.stg, pl.split_k, upg_shift, pl.ntiles, pl.chunks_per_slice, pl.waves, pl.xlds);
         GemvParams p;
         fill_params(q, m0, mc, p);
-        p.ntiles = (q.N + 63) / 64;
-        p.units_per_group = upg;
-        p.upg_shift = ilog2_exact(upg);
-        // x rows staged in LDS: M <= 16 always, M <= 32 with the 4-unit-stage kernel (M = 64 measured slower than
-        // re-reading x from L2: four A fragments per unit make the wave LDS-bound)
-        bool xlds = mc <= 16 || (mc <= 32 && upg % 4 == 0);
-        int stg = (upg % 4 == 0) ? 4 : ((upg % 2 == 0 && xlds) ? 2 : 1);
-        const int nstages = nunits / stg;
-        const int w = (xlds && stg == 4) ? waves : 4;
-        // K slices publish partial tiles [tile][slice][sets][rows][64] fp32 behind the ticket words
-        const size_t part_per_slice = (size_t)p.ntiles * (q.fused2 ? 2 : 1) * (mc < 64 ? mc : 64) * 64 * 4;
-        const bool ws_ok = q.ws && aligned(q.ws, 8) && q.ws_bytes > SPLITK_PART_OFFSET + 2 * part_per_slice && p.ntiles <= 1024;
-        const int split_fit = ws_ok ? (int)((q.ws_bytes - SPLITK_PART_OFFSET) / part_per_slice) : 1;
-        // K split: ~2 workgroups per CU, every wave of a workgroup gets at least one stage
-        int split_k = 1;
-        const int fs = g_force_split_k.load();
-        if (fs >= 1) {
-            split_k = fs;
-            if (split_k > 1 && (!ws_ok || split_k > split_fit)) return GPTQ_E_WORKSPACE;
-        } else if (ws_ok) {
-            split_k = (512 + p.ntiles - 1) / p.ntiles;
-            if (split_k > split_fit) split_k = split_fit;
-        }
-        if (split_k > split_max) split_k = split_max;
-        if (split_k * w > nstages) split_k = nstages / w;
-        if (split_k < 1) split_k = 1;
-        int sps = (nstages + split_k - 1) / split_k;  // stages per slice
-        // staged x must fit: rows * (units * unit_k + 8) halves
-        const int xrows = mc;
-        auto x_bytes = [&](int sps_) { return (size_t)xrows * ((size_t)sps_ * stg * unit_k + 8) * 2 + 16; };
-        if (xlds && x_bytes(sps) > 64 * 1024) {
-            if (ws_ok && fs < 1) {
-                while (x_bytes(sps) > 64 * 1024 && split_k < split_max && (split_k + 1) * w <= nstages) {
-                    split_k++;
-                    sps = (nstages + split_k - 1) / split_k;
-                }
-            }
-            if (x_bytes(sps) > 64 * 1024) xlds = false;
-        }
-        if (!xlds && stg == 2) return run_gemv(q, s);
-        split_k = (nstages + sps - 1) / sps;
-        if (split_k > 1 && split_k > split_fit) return GPTQ_E_WORKSPACE;
-        p.split_k = split_k;
-        p.nchunks = nunits;
-        p.chunks_per_slice = sps * stg;
-        int rc = skinny_dispatch(q.bits, q.fused2, stg, (xlds && stg == 4) ? waves : 4, xlds, p, s);
-        if (rc) return rc;
+        p.ntiles = pl.ntiles;
+        p.units_per_group = pl.upg;
+        p.upg_shift = upg_shift;
+        p.split_k = pl.split_k;
+        p.nchunks = pl.nunits;
+        p.chunks_per_slice = pl.chunks_per_slice;
+        if (int rc2 = skinny_dispatch(q.bits, q.fused2, pl.stg, pl.waves, pl.xlds, p, w.s)) return rc2;
     }
     return 0;
 }
 
-static int run_auto(const Problem &q, hipStream_t s) {
+static int run_auto(const Problem &q, const Walk &w) {
     if (q.M == 0) return 0;
-    if (q.M <= 2) return run_gemv(q, s);               // rowwave GEMV (M = 2: both rows in one launch; generic kernel for act-order)
+    if (q.M <= 2) return run_gemv(q, w);               // rowwave GEMV (M = 2: both rows in one launch; generic kernel for act-order)
     if (q.M <= 8) {                                    // small decode batch (M <= 4; M <= 8 only when the MFMA variant is forced)
-        const int rc = run_rowwave_mr(q, s);
+        const int rc = run_rowwave_mr(q, w);
         if (rc != GPTQ_E_VARIANT) return rc;
     }
-    if (q.M <= SKINNY_MAX_M) return run_skinny(q, s);  // falls back to the GEMV for act-order / 3-bit
+    if (q.M <= SKINNY_MAX_M) return run_skinny(q, w);  // falls back to the GEMV for act-order / 3-bit
     // 65 <= M <= 256: a single 256-row tile per column block cannot fill 256 CUs (4096^2: 111-113 us at M = 128 / 256); 64-row
     // passes of the weight-streaming kernel are faster there (44 / 88 us; from M = 257 the tile GEMM has two tile rows and wins).  (The Python layer prefers dequantise-once +
     // dense GEMM for this regime; this is for callers of the C ABI.)
-    if (!q.fused2 && q.M <= 4 * SKINNY_MAX_M) return run_skinny(q, s);
-    const int unit_k = (q.bits == 2) ? 64 : 32;
-    if (fast_eligible(q, unit_k)) {
+    if (!q.fused2 && q.M <= 4 * SKINNY_MAX_M) return run_skinny(q, w);
+    if (fast_eligible(q, (q.bits == 2) ? 64 : 32)) {
+        if (w.plan) return take_plan(w, GPTQ_KERNEL_TILE_GEMM, q.M, 0, 0);
         GemvParams p;
         fill_params(q, 0, q.M, p);
         // fused gate/up at prefill sizes: ONE tile GEMM whose workgroups hold gate and up of the same columns; SiLU on the fp32 sums
-        const int rc = gemm_dispatch(q.bits, q.fused2, p, s);
+        const int rc = gemm_dispatch(q.bits, q.fused2, p, w.s);
         if (rc != GPTQ_E_VARIANT) return rc;
     }
-    return run_skinny(q, s);
+    return run_skinny(q, w);
+}
+
+// The entries: validation, then the ladder each starts on.  GPTQ_PLAN_ENTRY_ROWWAVE stands for the direct rowwave entries (fused
+// norm, x permutation): no generic fall-back.  norm_align = false: gptq_rmsnorm_fused_mlp_f16 has never checked its norm weight's
+// alignment, the other norm entries answer GPTQ_E_VARIANT for an odd address.
+static int run_entry(int entry, const Problem &q, const Walk &w, bool norm_align = true) {
+    if (int rc = validate(q)) return rc;
+    switch (entry) {
+        case GPTQ_PLAN_ENTRY_AUTO: return run_auto(q, w);
+        case GPTQ_PLAN_ENTRY_GEMV: return run_gemv(q, w);
+        case GPTQ_PLAN_ENTRY_SKINNY: return run_skinny(q, w);
+        case GPTQ_PLAN_ENTRY_ROWWAVE:
+            if ((norm_align && !aligned(q.norm_w, 2)) || !rowwave_eligible(q)) return GPTQ_E_VARIANT;
+            return run_rowwave(q, w);   // one launch per row of x
+    }
+    return GPTQ_E_VARIANT;
 }
 
 // debug hook: a device uint32 every stripe decode launch (M = 1) increments when it starts (tools/warmlab.hip B paces its run-ahead
@@ -445,34 +453,19 @@ int gptq_set_gemm_kernel(int version) {
 static Problem make_problem(const void *x, int64_t ldx, const int32_t *qweight, const void *scales, const int32_t *qzeros,
                             const int32_t *g_idx, const void *bias, void *y, int64_t ldy, int M, int K, int N, int bits,
                             int groupsize, void *ws, size_t ws_bytes) {
-    Problem q{};
-    q.x = x;
-    q.ldx = ldx;
-    q.qw[0] = qweight;
-    q.sc[0] = scales;
-    q.qz[0] = qzeros;
-    q.gi[0] = g_idx;
-    q.bias = bias;
-    q.y = y;
-    q.ldy = ldy;
-    q.M = M;
-    q.K = K;
-    q.N = N;
-    q.bits = bits;
-    q.groupsize = groupsize;
-    q.fused2 = false;
-    q.ws = ws;
-    q.ws_bytes = ws_bytes;
+    Problem q{};   // (a single set; make_pair adds the second)
+    q.x = x; q.ldx = ldx; q.y = y; q.ldy = ldy; q.bias = bias;
+    q.qw[0] = qweight; q.sc[0] = scales; q.qz[0] = qzeros; q.gi[0] = g_idx;
+    q.M = M; q.K = K; q.N = N; q.bits = bits; q.groupsize = groupsize;
+    q.ws = ws; q.ws_bytes = ws_bytes;
     return q;
 }
 
 int gptq_matmul248_f16(const void *x, int64_t ldx, const int32_t *qweight, const void *scales, const int32_t *qzeros,
                        const int32_t *g_idx, const void *bias, void *y, int64_t ldy, int M, int K, int N, int bits,
                        int groupsize, void *workspace, size_t workspace_bytes, gptq_stream_t stream) {
-    Problem q = make_problem(x, ldx, qweight, scales, qzeros, g_idx, bias, y, ldy, M, K, N, bits, groupsize, workspace,
-                             workspace_bytes);
-    if (int rc = validate(q)) return rc;
-    return run_auto(q, (hipStream_t)stream);
+    Problem q = make_problem(x, ldx, qweight, scales, qzeros, g_idx, bias, y, ldy, M, K, N, bits, groupsize, workspace, workspace_bytes);
+    return run_entry(GPTQ_PLAN_ENTRY_AUTO, q, Walk{(hipStream_t)stream, nullptr});
 }
 
 /* round 6: the fp32 partial product of a ROW SHARD of a layer with any g_idx (an act-order layer cut for tensor parallelism: the shard's k range
@@ -482,17 +475,13 @@ int gptq_matmul248_f16(const void *x, int64_t ldx, const int32_t *qweight, const
  * g_idx [K]: the group of each of the shard's rows (required).  The weight is dequantised as the reference does (quant_linear.py:128). */
 int gptq_matmul248_partial_f32(const void *x, int64_t ldx, const int32_t *qweight, const void *scales, const int32_t *qzeros, const int32_t *g_idx, float *y32,
                                int64_t ldy, int M, int K, int N, int bits, int n_groups, gptq_stream_t stream) {
-    if (bits != 2 && bits != 3 && bits != 4 && bits != 8) return GPTQ_E_BITS;
-    if (M < 0 || K <= 0 || N <= 0 || n_groups <= 0 || n_groups > 65535 || K % 32 != 0 || N % 32 != 0 || ldx < K || ldy < N) return GPTQ_E_SHAPE;
+    if (int rc = check_weight(bits, K, N, 1)) return rc;
+    if (M < 0 || n_groups <= 0 || n_groups > 65535 || ldx < K || ldy < N) return GPTQ_E_SHAPE;
     if (!x || !qweight || !scales || !qzeros || !g_idx || !y32) return GPTQ_E_NULL;
     if (!aligned(x, 2) || !aligned(qweight, 16) || !aligned(scales, 2) || !aligned(qzeros, 4) || !aligned(g_idx, 4) || !aligned(y32, 4)) return GPTQ_E_ALIGN;
     for (int m0 = 0; m0 < M;) {
-        int mr = M - m0 >= 4 ? 4 : (M - m0 >= 2 ? 2 : 1);
-        int nl = 16;
-        auto need = [&](int mr_, int nl_) { return (size_t)mr_ * K * 2 + (size_t)K * 2 + 16 + (size_t)n_groups * 4 * nl_ * 4; };
-        if (need(mr, nl) > 150 * 1024 || (N / 64) < 128) nl = 4;
-        while (mr > 1 && need(mr, nl) > 150 * 1024) mr >>= 1;
-        if (need(mr, nl) > 150 * 1024) return GPTQ_E_SHAPE;
+        int mr, nl;
+        if (!plan_generic(M - m0, K, N, n_groups, 1, mr, nl)) return GPTQ_E_SHAPE;
         GemvParams p{};
         p.x = (const half_t *)x + (size_t)m0 * ldx;
         p.ldx = ldx;
@@ -513,19 +502,15 @@ int gptq_matmul248_partial_f32(const void *x, int64_t ldx, const int32_t *qweigh
 int gptq_gemv_f16(const void *x, int64_t ldx, const int32_t *qweight, const void *scales, const int32_t *qzeros,
                   const int32_t *g_idx, const void *bias, void *y, int64_t ldy, int M, int K, int N, int bits,
                   int groupsize, void *workspace, size_t workspace_bytes, gptq_stream_t stream) {
-    Problem q = make_problem(x, ldx, qweight, scales, qzeros, g_idx, bias, y, ldy, M, K, N, bits, groupsize, workspace,
-                             workspace_bytes);
-    if (int rc = validate(q)) return rc;
-    return run_gemv(q, (hipStream_t)stream);
+    Problem q = make_problem(x, ldx, qweight, scales, qzeros, g_idx, bias, y, ldy, M, K, N, bits, groupsize, workspace, workspace_bytes);
+    return run_entry(GPTQ_PLAN_ENTRY_GEMV, q, Walk{(hipStream_t)stream, nullptr});
 }
 
 int gptq_skinny_f16(const void *x, int64_t ldx, const int32_t *qweight, const void *scales, const int32_t *qzeros,
                     const int32_t *g_idx, const void *bias, void *y, int64_t ldy, int M, int K, int N, int bits,
                     int groupsize, void *workspace, size_t workspace_bytes, gptq_stream_t stream) {
-    Problem q = make_problem(x, ldx, qweight, scales, qzeros, g_idx, bias, y, ldy, M, K, N, bits, groupsize, workspace,
-                             workspace_bytes);
-    if (int rc = validate(q)) return rc;
-    return run_skinny(q, (hipStream_t)stream);
+    Problem q = make_problem(x, ldx, qweight, scales, qzeros, g_idx, bias, y, ldy, M, K, N, bits, groupsize, workspace, workspace_bytes);
+    return run_entry(GPTQ_PLAN_ENTRY_SKINNY, q, Walk{(hipStream_t)stream, nullptr});
 }
 
 int gptq_gemm_f16(const void *x, int64_t ldx, const int32_t *qweight, const void *scales, const int32_t *qzeros,
@@ -543,28 +528,46 @@ int gptq_fused_mlp_f16(const void *x, int64_t ldx, const int32_t *qweight_gate, 
                        const void *scales_up, const int32_t *qzeros_up, const int32_t *g_idx_up, void *c, int64_t ldc,
                        int M, int K, int N, int bits, int groupsize, void *workspace, size_t workspace_bytes,
                        gptq_stream_t stream) {
-    Problem q = make_problem(x, ldx, qweight_gate, scales_gate, qzeros_gate, g_idx_gate, nullptr, c, ldc, M, K, N, bits,
-                             groupsize, workspace, workspace_bytes);
-    q.fused2 = true;
-    q.qw[1] = qweight_up;
-    q.sc[1] = scales_up;
-    q.qz[1] = qzeros_up;
-    q.gi[1] = g_idx_up;
-    if (int rc = validate(q)) return rc;
-    return run_auto(q, (hipStream_t)stream);
+    Problem q = make_problem(x, ldx, qweight_gate, scales_gate, qzeros_gate, g_idx_gate, nullptr, c, ldc, M, K, N, bits, groupsize, workspace, workspace_bytes);
+    make_pair(q, qweight_up, scales_up, qzeros_up, g_idx_up);
+    return run_entry(GPTQ_PLAN_ENTRY_AUTO, q, Walk{(hipStream_t)stream, nullptr});
+}
+
+/* The plan of the checkpoint-layout kernels as a host-only query (include/gptq_mi355x.h): the walk of the entry's own ladder, ended at
+ * its first dispatch call.  The pointers of the Problem are stand-ins that pass validation (a workspace exists iff workspace_bytes > 0);
+ * none is read. */
+int gptq_gemv_plan_for_shape(int entry, int M, int K, int N, int bits, int groupsize, int nsets, int flags, size_t workspace_bytes, int *plan) {
+    if (!plan) return GPTQ_E_NULL;
+    std::fill(plan, plan + GPTQ_PLAN_FIELDS, 0);
+    const bool direct = entry == GPTQ_PLAN_ENTRY_ROWWAVE;
+    if (entry < GPTQ_PLAN_ENTRY_AUTO || entry > GPTQ_PLAN_ENTRY_ROWWAVE || (flags & ~7) || (!direct && (flags & (GPTQ_PLAN_F_NORM | GPTQ_PLAN_F_X_PERM))))
+        return GPTQ_E_VARIANT;
+    if (nsets < 1 || nsets > 2 || ((flags & GPTQ_PLAN_F_NORM) && M != 1)) return GPTQ_E_SHAPE;   // (the norm entries have no M: one row)
+    void *const some = (void *)(uintptr_t)4096;
+    const int32_t *const gi = (flags & GPTQ_PLAN_F_G_IDX) ? (const int32_t *)some : nullptr;
+    Problem q = make_problem(some, K, (const int32_t *)some, some, (const int32_t *)some, gi, nullptr, some, N, M, K, N, bits, groupsize, workspace_bytes ? some : nullptr, workspace_bytes);
+    if (nsets == 2) make_pair(q, (const int32_t *)some, some, (const int32_t *)some, gi);
+    if (flags & GPTQ_PLAN_F_NORM) q.norm_w = some;
+    if (flags & GPTQ_PLAN_F_X_PERM) q.xperm = (const int32_t *)some;
+    int taken[1 + GPTQ_PLAN_FIELDS] = {};
+    const int rc = run_entry(entry, q, Walk{nullptr, taken});
+    if (rc != PLAN_TAKEN) return rc;   // GPTQ_E_* before any launch, or 0 = GPTQ_KERNEL_NONE: no rows, nothing to launch
+    std::copy(taken + 1, taken + 1 + GPTQ_PLAN_FIELDS, plan);
+    return taken[0];
 }
 
 int gptq_transpose_matmul248_f16(const void *dy, int64_t lddy, const int32_t *qweight, const void *scales,
                                  const int32_t *qzeros, const int32_t *g_idx, void *dx, int64_t lddx, int M, int K,
                                  int N, int bits, int groupsize, gptq_stream_t stream) {
-    if (bits != 2 && bits != 3 && bits != 4 && bits != 8) return GPTQ_E_BITS;
-    if (M < 0 || K <= 0 || N <= 0 || groupsize <= 0 || K % 32 != 0 || N % 32 != 0) return GPTQ_E_SHAPE;
+    if (int rc = check_weight(bits, K, N, groupsize)) return rc;
+    if (M < 0) return GPTQ_E_SHAPE;
     if (!dy || !dx || !qweight || !scales || !qzeros) return GPTQ_E_NULL;
     if (!aligned(dy, 16) || lddy % 8 != 0 || !aligned(dx, 16) || lddx % 8 != 0 || !aligned(qweight, 16)) return GPTQ_E_ALIGN;
     if (M == 0) return 0;
     return transpose_dispatch(bits, (const half_t *)dy, lddy, (const uint32_t *)qweight, (const half_t *)scales, qzeros,
                               g_idx, (half_t *)dx, lddx, M, K, N, n_groups(K, groupsize), groupsize, (hipStream_t)stream);
 }
+
 
 int gptq_rmsnorm_f16(const void *x, int64_t ldx, const void *weight, void *y, int64_t ldy, int M, int N, float eps,
                      gptq_stream_t stream) {
@@ -616,8 +619,7 @@ int gptq_rope_f16(void *qk, int64_t row_stride, const int64_t *position_ids, int
 
 int gptq_pack_f32(const float *weight, const float *scales, const float *zeros, const int32_t *g_idx, int K, int N,
                   int bits, int groupsize, int32_t *qweight, int32_t *qzeros, void *scales_f16, gptq_stream_t stream) {
-    if (bits != 2 && bits != 3 && bits != 4 && bits != 8) return GPTQ_E_BITS;
-    if (K <= 0 || N <= 0 || groupsize <= 0 || K % 32 != 0 || N % 32 != 0) return GPTQ_E_SHAPE;
+    if (int rc = check_weight(bits, K, N, groupsize)) return rc;
     if (!weight || !scales || !zeros || !qweight || !qzeros || !scales_f16) return GPTQ_E_NULL;
     return pack_launch(weight, scales, zeros, g_idx, K, N, n_groups(K, groupsize), bits, groupsize, qweight, qzeros,
                        (half_t *)scales_f16, (hipStream_t)stream);
@@ -636,9 +638,7 @@ int gptq_rmsnorm_matmul248_f16(const void *x, const void *norm_weight, float eps
     Problem q = make_problem(x, K, qweight, scales, qzeros, g_idx, bias, y, N, 1, K, N, bits, groupsize, workspace, workspace_bytes);
     q.norm_w = norm_weight;
     q.norm_eps = eps;
-    if (int rc = validate(q)) return rc;
-    if (!aligned(norm_weight, 2) || !fast_eligible(q, 32 / (bits == 3 ? 4 : bits))) return GPTQ_E_VARIANT;
-    return run_rowwave(q, (hipStream_t)stream);
+    return run_entry(GPTQ_PLAN_ENTRY_ROWWAVE, q, Walk{(hipStream_t)stream, nullptr});
 }
 
 int gptq_rmsnorm_fused_mlp_f16(const void *x, const void *norm_weight, float eps, const int32_t *qweight_gate, const void *scales_gate,
@@ -646,37 +646,27 @@ int gptq_rmsnorm_fused_mlp_f16(const void *x, const void *norm_weight, float eps
                                const void *scales_up, const int32_t *qzeros_up, const int32_t *g_idx_up, void *c, int K, int N,
                                int bits, int groupsize, void *workspace, size_t workspace_bytes, gptq_stream_t stream) {
     if (!norm_weight) return GPTQ_E_NULL;
-    Problem q = make_problem(x, K, qweight_gate, scales_gate, qzeros_gate, g_idx_gate, nullptr, c, N, 1, K, N, bits, groupsize, workspace,
-                             workspace_bytes);
-    q.fused2 = true;
-    q.qw[1] = qweight_up;
-    q.sc[1] = scales_up;
-    q.qz[1] = qzeros_up;
-    q.gi[1] = g_idx_up;
+    Problem q = make_problem(x, K, qweight_gate, scales_gate, qzeros_gate, g_idx_gate, nullptr, c, N, 1, K, N, bits, groupsize, workspace, workspace_bytes);
+    make_pair(q, qweight_up, scales_up, qzeros_up, g_idx_up);
     q.norm_w = norm_weight;
     q.norm_eps = eps;
-    if (int rc = validate(q)) return rc;
-    if (!fast_eligible(q, 32 / (bits == 3 ? 4 : bits))) return GPTQ_E_VARIANT;
-    return run_rowwave(q, (hipStream_t)stream);
+    return run_entry(GPTQ_PLAN_ENTRY_ROWWAVE, q, Walk{(hipStream_t)stream, nullptr}, /*norm_align=*/false);
 }
 
 int gptq_dequant_f16(const int32_t *qweight, const void *scales, const int32_t *qzeros, const int32_t *g_idx, void *w, int K, int N,
                      int bits, int groupsize, gptq_stream_t stream) {
-    if (bits != 2 && bits != 3 && bits != 4 && bits != 8) return GPTQ_E_BITS;
-    if (K <= 0 || N <= 0 || groupsize <= 0 || K % 32 != 0 || N % 32 != 0) return GPTQ_E_SHAPE;
-    if (!qweight || !scales || !qzeros || !w) return GPTQ_E_NULL;
-    return dequant_launch((const uint32_t *)qweight, (const half_t *)scales, qzeros, g_idx, K, N, n_groups(K, groupsize), groupsize, bits,
-                          (half_t *)w, N, (hipStream_t)stream);
+    return gptq_dequant_ld_f16(qweight, scales, qzeros, g_idx, w, N, K, N, bits, groupsize, stream);
 }
 
 int gptq_dequant_ld_f16(const int32_t *qweight, const void *scales, const int32_t *qzeros, const int32_t *g_idx, void *w, int64_t ldw, int K,
                         int N, int bits, int groupsize, gptq_stream_t stream) {
-    if (bits != 2 && bits != 3 && bits != 4 && bits != 8) return GPTQ_E_BITS;
-    if (K <= 0 || N <= 0 || groupsize <= 0 || K % 32 != 0 || N % 32 != 0 || ldw < N) return GPTQ_E_SHAPE;
+    if (int rc = check_weight(bits, K, N, groupsize)) return rc;
+    if (ldw < N) return GPTQ_E_SHAPE;
     if (!qweight || !scales || !qzeros || !w) return GPTQ_E_NULL;
     return dequant_launch((const uint32_t *)qweight, (const half_t *)scales, qzeros, g_idx, K, N, n_groups(K, groupsize), groupsize, bits,
                           (half_t *)w, ldw, (hipStream_t)stream);
 }
+
 
 // ---------------------------------------------------------------------------------------------- prefill route
 // route 1 (default) = own kernels only: the hand-written GEMM of gemm8.hip on the transposed dequantised weight for every dense
@@ -703,8 +693,8 @@ constexpr size_t PREFILL_LIB_WS = (size_t)76 << 20;      // what the library may
 constexpr int PREFILL_CHUNK_M = 8192;                    // rows of the transient FP32 [rows, 2N] gate | up product
 inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 inline int prefill_validate(const void *x, int64_t ldx, const void *y, int64_t ldy, int M, int K, int N, int bits, int groupsize) {
-    if (bits != 2 && bits != 3 && bits != 4 && bits != 8) return GPTQ_E_BITS;
-    if (M < 0 || K <= 0 || N <= 0 || groupsize <= 0 || K % 32 != 0 || N % 32 != 0 || ldx < K || ldy < N) return GPTQ_E_SHAPE;
+    if (int rc = check_weight(bits, K, N, groupsize)) return rc;
+    if (M < 0 || ldx < K || ldy < N) return GPTQ_E_SHAPE;
     if (M > 0 && (!x || !y)) return GPTQ_E_NULL;
     if (((uintptr_t)x | (uintptr_t)y) % 16 != 0 || ldx % 8 != 0 || ldy % 8 != 0) return GPTQ_E_ALIGN;
     return GPTQ_OK;
@@ -744,8 +734,8 @@ int gptq_prefill_matmul_f16(const void *x, int64_t ldx, const int32_t *qweight, 
 int gptq_prefill_transpose_matmul248_f16(const void *dy, int64_t lddy, const int32_t *qweight, const void *scales, const int32_t *qzeros,
                                          const int32_t *g_idx, void *dx, int64_t lddx, int M, int K, int N, int bits, int groupsize, void *workspace,
                                          size_t workspace_bytes, gptq_stream_t stream) {
-    if (bits != 2 && bits != 3 && bits != 4 && bits != 8) return GPTQ_E_BITS;
-    if (M < 0 || K <= 0 || N <= 0 || groupsize <= 0 || K % 32 != 0 || N % 32 != 0 || lddy < N || lddx < K) return GPTQ_E_SHAPE;
+    if (int rc = check_weight(bits, K, N, groupsize)) return rc;
+    if (M < 0 || lddy < N || lddx < K) return GPTQ_E_SHAPE;
     if (!qweight || !scales || !qzeros || (M > 0 && (!dy || !dx))) return GPTQ_E_NULL;
     if (((uintptr_t)dy | (uintptr_t)dx) % 16 != 0 || lddy % 8 != 0 || lddx % 8 != 0) return GPTQ_E_ALIGN;
     if (M == 0) return GPTQ_OK;
@@ -852,12 +842,9 @@ int gptq_matmul248_sorted_f16(const void *x, int64_t ldx, const int32_t *perm, c
                               const int32_t *qzeros, const void *bias, void *y, int64_t ldy, int M, int K, int N, int bits,
                               int groupsize, void *workspace, size_t workspace_bytes, gptq_stream_t stream) {
     if (!perm) return GPTQ_E_NULL;
-    Problem q = make_problem(x, ldx, qweight_sorted, scales, qzeros, nullptr, bias, y, ldy, M, K, N, bits, groupsize, workspace,
-                             workspace_bytes);
+    Problem q = make_problem(x, ldx, qweight_sorted, scales, qzeros, nullptr, bias, y, ldy, M, K, N, bits, groupsize, workspace, workspace_bytes);
     q.xperm = perm;
-    if (int rc = validate(q)) return rc;
-    if (!fast_eligible(q, 32 / (bits == 3 ? 4 : bits))) return GPTQ_E_VARIANT;
-    return run_rowwave(q, (hipStream_t)stream);   // one launch per row of x
+    return run_entry(GPTQ_PLAN_ENTRY_ROWWAVE, q, Walk{(hipStream_t)stream, nullptr});
 }
 
 int gptq_fused_mlp_sorted_f16(const void *x, int64_t ldx, const int32_t *perm, const int32_t *qweight_gate_sorted, const void *scales_gate,
@@ -865,17 +852,10 @@ int gptq_fused_mlp_sorted_f16(const void *x, int64_t ldx, const int32_t *perm, c
                               const int32_t *qzeros_up, void *c, int64_t ldc, int M, int K, int N, int bits, int groupsize,
                               void *workspace, size_t workspace_bytes, gptq_stream_t stream) {
     if (!perm) return GPTQ_E_NULL;
-    Problem q = make_problem(x, ldx, qweight_gate_sorted, scales_gate, qzeros_gate, nullptr, nullptr, c, ldc, M, K, N, bits, groupsize,
-                             workspace, workspace_bytes);
-    q.fused2 = true;
-    q.qw[1] = qweight_up_sorted;
-    q.sc[1] = scales_up;
-    q.qz[1] = qzeros_up;
-    q.gi[1] = nullptr;
+    Problem q = make_problem(x, ldx, qweight_gate_sorted, scales_gate, qzeros_gate, nullptr, nullptr, c, ldc, M, K, N, bits, groupsize, workspace, workspace_bytes);
+    make_pair(q, qweight_up_sorted, scales_up, qzeros_up, nullptr);
     q.xperm = perm;
-    if (int rc = validate(q)) return rc;
-    if (!fast_eligible(q, 32 / (bits == 3 ? 4 : bits))) return GPTQ_E_VARIANT;
-    return run_rowwave(q, (hipStream_t)stream);   // one launch per row of x
+    return run_entry(GPTQ_PLAN_ENTRY_ROWWAVE, q, Walk{(hipStream_t)stream, nullptr});
 }
 
 int gptq_rmsnorm_sorted_f16(const void *x, const void *norm_weight, float eps, const int32_t *perm, const int32_t *qweight_sorted,
@@ -886,19 +866,14 @@ int gptq_rmsnorm_sorted_f16(const void *x, const void *norm_weight, float eps, c
     Problem q = make_problem(x, K, qweight_sorted, scales, qzeros, nullptr, bias, y, N, 1, K, N, bits, groupsize, workspace, workspace_bytes);
     if (qweight_up_sorted) {
         if (bias) return GPTQ_E_VARIANT;
-        q.fused2 = true;
-        q.qw[1] = qweight_up_sorted;
-        q.sc[1] = scales_up;
-        q.qz[1] = qzeros_up;
-        q.gi[1] = nullptr;
+        make_pair(q, qweight_up_sorted, scales_up, qzeros_up, nullptr);
     }
     q.xperm = perm;
     q.norm_w = norm_weight;
     q.norm_eps = eps;
-    if (int rc = validate(q)) return rc;
-    if (!aligned(norm_weight, 2) || !fast_eligible(q, 32 / (bits == 3 ? 4 : bits))) return GPTQ_E_VARIANT;
-    return run_rowwave(q, (hipStream_t)stream);
+    return run_entry(GPTQ_PLAN_ENTRY_ROWWAVE, q, Walk{(hipStream_t)stream, nullptr});
 }
+
 
 int gptq_decode_rope_kv_f16(void *qkv, const int64_t *position, void *k_cache, void *v_cache, int heads, int head_dim, int t_max,
                             float base, gptq_stream_t stream) {
@@ -923,35 +898,11 @@ int gptq_decode_attn_f16(const void *q, const void *k_cache, const void *v_cache
                               (float *)workspace, heads, t_max, scale, (hipStream_t)stream);
 }
 
-int gptq_decode_attn_fused_f16(const void *qkv, const int64_t *position, void *k_cache, void *v_cache, void *out, void *workspace,
-                               size_t workspace_bytes, int heads, int head_dim, int t_max, float base, float scale,
-                               gptq_stream_t stream) {
-    if (!qkv || !k_cache || !v_cache || !position || !out || !workspace) return GPTQ_E_NULL;
-    if (heads <= 0 || head_dim != 128 || t_max <= 0) return GPTQ_E_SHAPE;
-    if (!aligned(qkv, 16) || !aligned(k_cache, 16) || !aligned(v_cache, 16) || !aligned(workspace, 16)) return GPTQ_E_ALIGN;
-    if (workspace_bytes < decode_attn_ws_bytes(heads, t_max)) return GPTQ_E_WORKSPACE;
-    return decode_attn_fused_launch((const half_t *)qkv, position, (half_t *)k_cache, (half_t *)v_cache, (half_t *)out,
-                                    (float *)workspace, heads, t_max, base, scale, nullptr, (hipStream_t)stream, 1, 3 * (int64_t)heads * head_dim,
-                                    (int64_t)heads * head_dim);
-}
-
 int gptq_rope_table_f32(float *table, int t_max, int head_dim, float base, gptq_stream_t stream) {
     if (!table) return GPTQ_E_NULL;
     if (t_max <= 0 || head_dim != 128) return GPTQ_E_SHAPE;
     if (!aligned(table, 8)) return GPTQ_E_ALIGN;
     return rope_table_launch(table, t_max, head_dim, base, (hipStream_t)stream);
-}
-
-int gptq_decode_attn_fused_table_f16(const void *qkv, const int64_t *position, void *k_cache, void *v_cache, void *out, void *workspace,
-                                     size_t workspace_bytes, int heads, int head_dim, int t_max, float base, float scale,
-                                     const float *rope_table, gptq_stream_t stream) {
-    if (!qkv || !k_cache || !v_cache || !position || !out || !workspace || !rope_table) return GPTQ_E_NULL;
-    if (heads <= 0 || head_dim != 128 || t_max <= 0) return GPTQ_E_SHAPE;
-    if (!aligned(qkv, 16) || !aligned(k_cache, 16) || !aligned(v_cache, 16) || !aligned(workspace, 16) || !aligned(rope_table, 8)) return GPTQ_E_ALIGN;
-    if (workspace_bytes < decode_attn_ws_bytes(heads, t_max)) return GPTQ_E_WORKSPACE;
-    return decode_attn_fused_launch((const half_t *)qkv, position, (half_t *)k_cache, (half_t *)v_cache, (half_t *)out,
-                                    (float *)workspace, heads, t_max, base, scale, rope_table, (hipStream_t)stream, 1, 3 * (int64_t)heads * head_dim,
-                                    (int64_t)heads * head_dim);
 }
 
 /* round 5: a decode BATCH -- row b has its own position (positions[b]; negative = idle row), qkv row (ldq apart), output row (ldo apart) and
@@ -961,20 +912,45 @@ size_t gptq_decode_attn_batch_workspace_bytes(int batch, int heads, int head_dim
     return decode_attn_ws_bytes(heads, t_max, batch);
 }
 
-int gptq_decode_attn_batch_f16(const void *qkv, int64_t ldq, const int64_t *positions, void *k_cache, void *v_cache, void *out, int64_t ldo,
-                               void *workspace, size_t workspace_bytes, int batch, int heads, int head_dim, int t_max, float base, float scale,
-                               const float *rope_table, const int32_t *out_perm, gptq_stream_t stream) {
+// checks and launch of the three fused decode-attention entries.  single: the batch = 1 entries, which have no out_perm / ldq / ldo (packed
+// rows) and have never checked the alignment of out
+static int decode_attn_fused(const void *qkv, int64_t ldq, const int64_t *positions, void *k_cache, void *v_cache, void *out, int64_t ldo, void *workspace,
+                             size_t workspace_bytes, int batch, int heads, int head_dim, int t_max, float base, float scale, const float *rope_table,
+                             const int32_t *out_perm, bool single, gptq_stream_t stream) {
     if (!qkv || !k_cache || !v_cache || !positions || !out || !workspace) return GPTQ_E_NULL;
     if (out_perm && !aligned(out_perm, 4)) return GPTQ_E_ALIGN;
     if (batch <= 0 || batch > 65535 || heads <= 0 || head_dim != 128 || t_max <= 0 || ldq < 3 * (int64_t)heads * head_dim || ldo < (int64_t)heads * head_dim)
         return GPTQ_E_SHAPE;
     if (!aligned(qkv, 16) || !aligned(k_cache, 16) || !aligned(v_cache, 16) || !aligned(workspace, 16) || (rope_table && !aligned(rope_table, 8)) ||
-        ldq % 8 != 0 || ldo % 8 != 0 || !aligned(out, 2))
+        ldq % 8 != 0 || ldo % 8 != 0 || (!single && !aligned(out, 2)))
         return GPTQ_E_ALIGN;
     if (workspace_bytes < decode_attn_ws_bytes(heads, t_max, batch)) return GPTQ_E_WORKSPACE;
     return decode_attn_fused_launch((const half_t *)qkv, positions, (half_t *)k_cache, (half_t *)v_cache, (half_t *)out, (float *)workspace, heads, t_max,
                                     base, scale, rope_table, (hipStream_t)stream, batch, ldq, ldo, out_perm);
 }
+
+int gptq_decode_attn_batch_f16(const void *qkv, int64_t ldq, const int64_t *positions, void *k_cache, void *v_cache, void *out, int64_t ldo,
+                               void *workspace, size_t workspace_bytes, int batch, int heads, int head_dim, int t_max, float base, float scale,
+                               const float *rope_table, const int32_t *out_perm, gptq_stream_t stream) {
+    return decode_attn_fused(qkv, ldq, positions, k_cache, v_cache, out, ldo, workspace, workspace_bytes, batch, heads, head_dim, t_max, base, scale,
+                             rope_table, out_perm, false, stream);
+}
+
+int gptq_decode_attn_fused_f16(const void *qkv, const int64_t *position, void *k_cache, void *v_cache, void *out, void *workspace,
+                               size_t workspace_bytes, int heads, int head_dim, int t_max, float base, float scale,
+                               gptq_stream_t stream) {
+    return decode_attn_fused(qkv, 3 * (int64_t)heads * head_dim, position, k_cache, v_cache, out, (int64_t)heads * head_dim, workspace, workspace_bytes, 1,
+                             heads, head_dim, t_max, base, scale, nullptr, nullptr, true, stream);
+}
+
+int gptq_decode_attn_fused_table_f16(const void *qkv, const int64_t *position, void *k_cache, void *v_cache, void *out, void *workspace,
+                                     size_t workspace_bytes, int heads, int head_dim, int t_max, float base, float scale,
+                                     const float *rope_table, gptq_stream_t stream) {
+    if (!rope_table) return GPTQ_E_NULL;   // (this entry's table is required)
+    return decode_attn_fused(qkv, 3 * (int64_t)heads * head_dim, position, k_cache, v_cache, out, (int64_t)heads * head_dim, workspace, workspace_bytes, 1,
+                             heads, head_dim, t_max, base, scale, rope_table, nullptr, true, stream);
+}
+
 
 /* round 6: the same launch, but every active split of a row leaves its record {M, den, num[128]} (fp32) in the workspace and NOTHING merges them here:
  * the consumer is gptq_layer_decode_attn_f16 (o_proj's decode kernel stages x from the records).  tokens_per_split <= 0: the default. */
@@ -1121,8 +1097,7 @@ size_t gptq_stripe_bytes(int K, int N, int bits, int groupsize, int nsets) { ret
 int gptq_stripe_repack(const int32_t *qweight, const void *scales, const int32_t *qzeros, const int32_t *qweight_up, const void *scales_up,
                        const int32_t *qzeros_up, void *stripes, size_t stripes_bytes, int K, int N, int bits, int groupsize,
                        gptq_stream_t stream) {
-    if (bits != 2 && bits != 3 && bits != 4 && bits != 8) return GPTQ_E_BITS;
-    if (K <= 0 || N <= 0 || groupsize <= 0 || K % 32 != 0 || N % 32 != 0) return GPTQ_E_SHAPE;
+    if (int rc = check_weight(bits, K, N, groupsize)) return rc;
     if (!qweight || !scales || !qzeros || !stripes) return GPTQ_E_NULL;
     const bool fused = qweight_up != nullptr;
     if (fused && (!scales_up || !qzeros_up)) return GPTQ_E_NULL;
@@ -1143,80 +1118,94 @@ struct NextNorm {
     int *done;
 };
 
-static int stripe_matvec(const void *x, int64_t ldx, const void *stripes, size_t stripes_bytes, const void *bias, void *y, int64_t ldy, float *y32,
-                         int M, int K, int N, int bits, int groupsize, int nsets, const void *norm_weight, float norm_eps, const uint16_t *perm,
-                         gptq_stream_t stream, void *mm_ws = nullptr, size_t mm_ws_bytes = 0, bool gemm_only_above_128 = false, int64_t ldb = 0,
-                         const int32_t *yperm = nullptr, const AttnMerge *att = nullptr, const NextNorm *nn = nullptr) {
-    if (bits != 2 && bits != 3 && bits != 4 && bits != 8) return GPTQ_E_BITS;
-    if (M < 0 || K <= 0 || N <= 0 || groupsize <= 0 || K % 32 != 0 || N % 32 != 0 || nsets < 1 || nsets > 2) return GPTQ_E_SHAPE;
-    if (!x || !stripes || (!y && !y32)) return GPTQ_E_NULL;
-    const int gq = stripe_gq_shift(K, N, bits, groupsize);
+// the stripe16 image a product runs on: a prepared layer's (layer_image) or the caller's own
+struct StripeImage {
+    const void *stripes;
+    size_t bytes;
+    int K, N, bits, groupsize, nsets;
+};
+
+// one call of stripe_matvec.  A call site names what it sets (in this order); everything else is absent: NULL / 0 / false
+struct StripeCall {
+    const void *x;
+    int64_t ldx;
+    void *y;                    // fp16 [M][ldy] ...
+    float *y32;                 // ... or the unrounded fp32 sums
+    int64_t ldy;
+    int M;
+    const void *add;            // bias [N]; with ldb != 0 a residual [M][ldb]
+    int64_t ldb;
+    const void *norm_w;         // RMSNorm of x fused into the decode kernel
+    float norm_eps;
+    const uint16_t *xperm;      // x gathered through this permutation (M == 1)
+    const int32_t *yperm;       // the columns of y stored through this permutation (decode kernel)
+    void *mm_ws;                // scratch of the tile kernels; NULL: the decode kernel
+    size_t mm_ws_bytes;
+    bool gemm_only_above_128;   // above 128 rows the tile GEMM or nothing: no 16-row tiles there
+    const AttnMerge *att;
+    const NextNorm *nn;
+};
+
+// the tile kernels of the image are compiled per bit width.  gemm: the 2-D tile GEMM (no forced slices), else one pass of the 16-row tiles
+static int stripe_tile_dispatch(bool gemm, const StripeParams &p, void *ws, size_t ws_bytes, int forced, hipStream_t s) {
+    switch (p.bits) {
+        case 2: return gemm ? stripe_gemm_dispatch_b2(p, ws, ws_bytes, s) : stripe_mm_dispatch_b2(p, ws, ws_bytes, forced, s);
+        case 3: return gemm ? stripe_gemm_dispatch_b3(p, ws, ws_bytes, s) : stripe_mm_dispatch_b3(p, ws, ws_bytes, forced, s);
+        case 4: return gemm ? stripe_gemm_dispatch_b4(p, ws, ws_bytes, s) : stripe_mm_dispatch_b4(p, ws, ws_bytes, forced, s);
+        default: return gemm ? stripe_gemm_dispatch_b8(p, ws, ws_bytes, s) : stripe_mm_dispatch_b8(p, ws, ws_bytes, forced, s);
+    }
+}
+
+static int stripe_matvec(const StripeImage &im, const StripeCall &c, gptq_stream_t stream) {
+    const int M = c.M, K = im.K, N = im.N, bits = im.bits, nsets = im.nsets;
+    if (int rc = check_weight(bits, K, N, im.groupsize)) return rc;
+    if (M < 0 || nsets < 1 || nsets > 2) return GPTQ_E_SHAPE;
+    if (!c.x || !im.stripes || (!c.y && !c.y32)) return GPTQ_E_NULL;
+    const int gq = stripe_gq_shift(K, N, bits, im.groupsize);
     const int gemm_max = g_stripe_gemm_max_rows.load();
-    const bool gemm_rows = mm_ws && M > 128 && M <= gemm_max;
-    if (gq == -2 || (M > (mm_ws ? 256 : 16) && !gemm_rows) || (nsets == 2 && bias) || (y32 && bias)) return GPTQ_E_VARIANT;
-    if (M > 1 && (perm || (y32 && (M > 4 || norm_weight)))) return GPTQ_E_VARIANT;
-    if (norm_weight && mm_ws) return GPTQ_E_VARIANT;        // the fused norm lives in the decode kernel only (every row its own rstd)
-    if (ldb != 0 && (!bias || ldb < N || y32)) return GPTQ_E_SHAPE;
-    if (yperm && (mm_ws || y32 || !aligned(yperm, 4))) return GPTQ_E_VARIANT;          // the scattered store lives in the decode kernel only
-    if (stripes_bytes < stripe_total_bytes(K, N, bits, groupsize, nsets)) return GPTQ_E_WORKSPACE;
-    if (!aligned(x, 16) || !aligned(stripes, 16) || !aligned(y, 2) || !aligned(y32, 4) || (norm_weight && !aligned(norm_weight, 16)) ||
-        (perm && !aligned(perm, 16)) || (M > 1 && (ldx % 8 != 0 || ldy < N)))
+    const bool gemm_rows = c.mm_ws && M > 128 && M <= gemm_max;
+    if (gq == -2 || (M > (c.mm_ws ? 256 : 16) && !gemm_rows) || (nsets == 2 && c.add) || (c.y32 && c.add)) return GPTQ_E_VARIANT;
+    if (M > 1 && (c.xperm || (c.y32 && (M > 4 || c.norm_w)))) return GPTQ_E_VARIANT;
+    if (c.norm_w && c.mm_ws) return GPTQ_E_VARIANT;        // the fused norm lives in the decode kernel only (every row its own rstd)
+    if (c.ldb != 0 && (!c.add || c.ldb < N || c.y32)) return GPTQ_E_SHAPE;
+    if (c.yperm && (c.mm_ws || c.y32 || !aligned(c.yperm, 4))) return GPTQ_E_VARIANT;          // the scattered store lives in the decode kernel only
+    if (im.bytes < stripe_total_bytes(K, N, bits, im.groupsize, nsets)) return GPTQ_E_WORKSPACE;
+    if (!aligned(c.x, 16) || !aligned(im.stripes, 16) || !aligned(c.y, 2) || !aligned(c.y32, 4) || (c.norm_w && !aligned(c.norm_w, 16)) ||
+        (c.xperm && !aligned(c.xperm, 16)) || (M > 1 && (c.ldx % 8 != 0 || c.ldy < N)))
         return GPTQ_E_ALIGN;
     if (M == 0) return 0;
     StripeParams p{};
-    p.x = (const half_t *)x;
-    p.ldx = ldx;
-    p.ldy = ldy;
-    p.R = (const uint32_t *)stripes;
-    p.tab = (const uint32_t *)((const char *)stripes + stripe_tab_offset(K, N, bits, nsets));
-    p.y = (half_t *)y;
-    p.y32 = y32;
-    p.bias = (const half_t *)bias;
-    p.ldb = ldb;
-    p.yperm = yperm;
-    p.norm_w = (const half_t *)norm_weight;
-    p.norm_eps = norm_eps;
-    p.xperm = perm;
-    p.M = M;
-    p.K = K;
-    p.N = N;
-    p.G = groupsize >= K ? 1 : K / groupsize;
-    p.NS = nsets;
+    p.x = (const half_t *)c.x; p.ldx = c.ldx; p.xperm = c.xperm;
+    p.y = (half_t *)c.y; p.y32 = c.y32; p.ldy = c.ldy; p.yperm = c.yperm;
+    p.R = (const uint32_t *)im.stripes;
+    p.tab = (const uint32_t *)((const char *)im.stripes + stripe_tab_offset(K, N, bits, nsets));
+    p.bias = (const half_t *)c.add; p.ldb = c.ldb;
+    p.norm_w = (const half_t *)c.norm_w; p.norm_eps = c.norm_eps;
+    p.M = M; p.K = K; p.N = N; p.NS = nsets; p.bits = bits;
+    p.G = im.groupsize >= K ? 1 : K / im.groupsize;
     p.gq_shift = gq;
-    p.bits = bits;
     p.progress = M == 1 ? stripe_progress_counter() : nullptr;
-    if (nn && nn->w && mm_ws && M <= 16) {   // (16-row tiles: the slices' combine launch may write the next norm's rows too)
-        p.next_norm_w = (const half_t *)nn->w; p.next_norm_eps = nn->eps; p.h = (half_t *)nn->h; p.ldh = nn->ldh; p.next_norm_done = nn->done;
+    if (c.nn && c.nn->w && c.mm_ws && M <= 16) {   // (16-row tiles: the slices' combine launch may write the next norm's rows too)
+        p.next_norm_w = (const half_t *)c.nn->w; p.next_norm_eps = c.nn->eps; p.h = (half_t *)c.nn->h; p.ldh = c.nn->ldh; p.next_norm_done = c.nn->done;
     }
-    if (att && att->o16) {
-        if (M != 1 || mm_ws || y32 || yperm || perm || norm_weight || nsets != 1) return GPTQ_E_VARIANT;
-        p.att = *att;
+    if (c.att && c.att->o16) {
+        if (M != 1 || c.mm_ws || c.y32 || c.yperm || c.xperm || c.norm_w || nsets != 1) return GPTQ_E_VARIANT;
+        p.att = *c.att;
     }
     if (gemm_rows) {   // 2-D tiles, weights kept packed (stripe_gemm_kernel)
-        int rc;
-        switch (bits) {
-            case 2: rc = stripe_gemm_dispatch_b2(p, mm_ws, mm_ws_bytes, (hipStream_t)stream); break;
-            case 3: rc = stripe_gemm_dispatch_b3(p, mm_ws, mm_ws_bytes, (hipStream_t)stream); break;
-            case 4: rc = stripe_gemm_dispatch_b4(p, mm_ws, mm_ws_bytes, (hipStream_t)stream); break;
-            default: rc = stripe_gemm_dispatch_b8(p, mm_ws, mm_ws_bytes, (hipStream_t)stream); break;
-        }
+        const int rc = stripe_tile_dispatch(true, p, c.mm_ws, c.mm_ws_bytes, 0, (hipStream_t)stream);
         if (rc != GPTQ_E_VARIANT) return rc;
     }
-    if (mm_ws && M > 128 && (gemm_only_above_128 || M > 256)) return GPTQ_E_VARIANT;
-    if (mm_ws) {   // row tiles on the matrix core (stripe_mm.inc): passes of up to 128 rows (64 when the partial tiles of a 128-row pass
-                   // do not fit the scratch, or with gptq_set_stripe_mm_pass_rows(64)), each streams the weights once
+    if (c.mm_ws && M > 128 && (c.gemm_only_above_128 || M > 256)) return GPTQ_E_VARIANT;
+    if (c.mm_ws) {   // row tiles on the matrix core (stripe_mm.inc): passes of up to 128 rows (64 when the partial tiles of a 128-row pass
+                     // do not fit the scratch, or with gptq_set_stripe_mm_pass_rows(64)), each streams the weights once
         const int forced = g_force_split_k.load();
         auto pass = [&](int m0, int rows) {
-            p.x = (const half_t *)x + (size_t)m0 * ldx;
-            p.y = (half_t *)y + (size_t)m0 * ldy;
-            p.bias = (const half_t *)bias + (size_t)m0 * ldb;
+            p.x = (const half_t *)c.x + (size_t)m0 * c.ldx;
+            p.y = (half_t *)c.y + (size_t)m0 * c.ldy;
+            p.bias = (const half_t *)c.add + (size_t)m0 * c.ldb;
             p.M = rows;
-            switch (bits) {
-                case 2: return stripe_mm_dispatch_b2(p, mm_ws, mm_ws_bytes, forced, (hipStream_t)stream);
-                case 3: return stripe_mm_dispatch_b3(p, mm_ws, mm_ws_bytes, forced, (hipStream_t)stream);
-                case 4: return stripe_mm_dispatch_b4(p, mm_ws, mm_ws_bytes, forced, (hipStream_t)stream);
-                default: return stripe_mm_dispatch_b8(p, mm_ws, mm_ws_bytes, forced, (hipStream_t)stream);
-            }
+            return stripe_tile_dispatch(false, p, c.mm_ws, c.mm_ws_bytes, forced, (hipStream_t)stream);
         };
         const int pass_rows = g_stripe_mm_pass_rows.load();
         for (int m0 = 0; m0 < M;) {
@@ -1238,15 +1227,14 @@ int gptq_stripe_matmul_partial_f32(const void *x, int64_t ldx, const void *strip
                                    int bits, int groupsize, int nsets, gptq_stream_t stream) {
     if (!y_partial) return GPTQ_E_NULL;
     if (M < 1 || M > 4) return GPTQ_E_VARIANT;
-    return stripe_matvec(x, ldx, stripes, stripes_bytes, nullptr, nullptr, (int64_t)nsets * N, y_partial, M, K, N, bits, groupsize, nsets, nullptr, 0.f, nullptr,
-                         stream);
+    return stripe_matvec({stripes, stripes_bytes, K, N, bits, groupsize, nsets}, {.x = x, .ldx = ldx, .y32 = y_partial, .ldy = (int64_t)nsets * N, .M = M}, stream);
 }
 
 int gptq_stripe_matvec_f16(const void *x, int64_t ldx, const void *stripes, size_t stripes_bytes, const void *bias, void *y, int64_t ldy, int M,
                            int K, int N, int bits, int groupsize, int nsets, const void *norm_weight, float norm_eps, const uint16_t *perm,
                            gptq_stream_t stream) {
-    if (!y) return GPTQ_E_NULL;
-    return stripe_matvec(x, ldx, stripes, stripes_bytes, bias, y, ldy, nullptr, M, K, N, bits, groupsize, nsets, norm_weight, norm_eps, perm, stream);
+    return gptq_stripe_matvec_perm_out_f16(x, ldx, stripes, stripes_bytes, bias, y, ldy, M, K, N, bits, groupsize, nsets, norm_weight, norm_eps, perm, nullptr,
+                                           stream);
 }
 
 /* the same launch with the columns of y stored through a permutation: y[m][y_perm[n]] = result column n (round 5: the consumer of y is an act-order
@@ -1256,23 +1244,24 @@ int gptq_stripe_matvec_perm_out_f16(const void *x, int64_t ldx, const void *stri
                                     int K, int N, int bits, int groupsize, int nsets, const void *norm_weight, float norm_eps, const uint16_t *perm,
                                     const int32_t *y_perm, gptq_stream_t stream) {
     if (!y) return GPTQ_E_NULL;
-    return stripe_matvec(x, ldx, stripes, stripes_bytes, bias, y, ldy, nullptr, M, K, N, bits, groupsize, nsets, norm_weight, norm_eps, perm, stream, nullptr, 0,
-                         false, 0, y_perm);
+    return stripe_matvec({stripes, stripes_bytes, K, N, bits, groupsize, nsets},
+                         {.x = x, .ldx = ldx, .y = y, .ldy = ldy, .M = M, .add = bias, .norm_w = norm_weight, .norm_eps = norm_eps, .xperm = perm, .yperm = y_perm}, stream);
 }
 
 int gptq_stripe_matmul_f16(const void *x, int64_t ldx, const void *stripes, size_t stripes_bytes, const void *bias, void *y, int64_t ldy, int M,
                            int K, int N, int bits, int groupsize, int nsets, void *workspace, size_t workspace_bytes, gptq_stream_t stream) {
     if (!y || !workspace) return GPTQ_E_NULL;
     if (!aligned(workspace, 256)) return GPTQ_E_ALIGN;
-    return stripe_matvec(x, ldx, stripes, stripes_bytes, bias, y, ldy, nullptr, M, K, N, bits, groupsize, nsets, nullptr, 0.f, nullptr, stream, workspace,
-                         workspace_bytes);
+    return stripe_matvec({stripes, stripes_bytes, K, N, bits, groupsize, nsets},
+                         {.x = x, .ldx = ldx, .y = y, .ldy = ldy, .M = M, .add = bias, .mm_ws = workspace, .mm_ws_bytes = workspace_bytes}, stream);
 }
 
 int gptq_stripe_matvec_partial_f32(const void *x, const void *stripes, size_t stripes_bytes, float *y_partial, int K, int N, int bits,
                                    int groupsize, int nsets, const uint16_t *perm, gptq_stream_t stream) {
     if (!y_partial) return GPTQ_E_NULL;
-    return stripe_matvec(x, K, stripes, stripes_bytes, nullptr, nullptr, N, y_partial, 1, K, N, bits, groupsize, nsets, nullptr, 0.f, perm, stream);
+    return stripe_matvec({stripes, stripes_bytes, K, N, bits, groupsize, nsets}, {.x = x, .ldx = K, .y32 = y_partial, .ldy = N, .M = 1, .xperm = perm}, stream);
 }
+
 
 // =================================================================================================================================
 // Prepared layers: ONE handle per QuantLinear (or gate/up pair) that owns every derived copy and contains the WHOLE M dispatch.
@@ -1303,7 +1292,6 @@ struct gptq_layer {
 
 namespace {
 
-inline size_t a256(size_t v) { return (v + 255) & ~(size_t)255; }
 constexpr int LAYER_STRIPE_MM_MAX_M = 128;   // rows the 16-row MFMA tiles serve before the prefill route wins (profiles/r2c_mm/mid_m.txt)
 constexpr int LAYER_PREFILL_MIN_M = 65;      // the dense route starts above the weight-streaming kernels
 
@@ -1361,8 +1349,8 @@ size_t gptq_layer_image_bytes(int K, int N, int bits, int groupsize, int nsets, 
     if (K <= 0 || N <= 0 || groupsize <= 0 || nsets < 1 || nsets > 2 || kind < 0 || kind > 2) return 0;
     if (kind == 2 || (kind == 1 && !sorted_supported(K, bits, groupsize))) return 0;
     const size_t st = stripe_total_bytes(K, N, bits, groupsize, nsets);
-    size_t b = a256(st);
-    if (kind == 1) b += 2 * a256((size_t)K * 4) + a256((size_t)K * 2);   // perm32, invperm32, perm16 (round 4: no group-sorted qweight copy any more)
+    size_t b = align256(st);
+    if (kind == 1) b += 2 * align256((size_t)K * 4) + align256((size_t)K * 2);   // perm32, invperm32, perm16 (round 4: no group-sorted qweight copy any more)
     return b;
 }
 
@@ -1371,8 +1359,7 @@ int gptq_layer_prepare(gptq_layer_t **out, const int32_t *qweight, const void *s
                        int groupsize, void *image, size_t image_bytes, gptq_stream_t stream) {
     if (!out) return GPTQ_E_NULL;
     *out = nullptr;
-    if (bits != 2 && bits != 3 && bits != 4 && bits != 8) return GPTQ_E_BITS;
-    if (K <= 0 || N <= 0 || groupsize <= 0 || K % 32 != 0 || N % 32 != 0) return GPTQ_E_SHAPE;
+    if (int rc = check_weight(bits, K, N, groupsize)) return rc;
     if (!qweight || !scales || !qzeros) return GPTQ_E_NULL;
     const int nsets = qweight_up ? 2 : 1;
     if (nsets == 2 && (!scales_up || !qzeros_up || bias)) return GPTQ_E_NULL;
@@ -1413,11 +1400,11 @@ int gptq_layer_prepare(gptq_layer_t **out, const int32_t *qweight, const void *s
     if (need && image && image_bytes >= need) {
         char *p = (char *)image;
         void *stripe = st_bytes ? p : nullptr;
-        p += a256(st_bytes);
+        p += align256(st_bytes);
         if (kind == 1) {
-            L->perm32 = (int32_t *)p; p += a256((size_t)K * 4);
-            L->invperm32 = (int32_t *)p; p += a256((size_t)K * 4);
-            L->perm16 = (uint16_t *)p; p += a256((size_t)K * 2);
+            L->perm32 = (int32_t *)p; p += align256((size_t)K * 4);
+            L->invperm32 = (int32_t *)p; p += align256((size_t)K * 4);
+            L->perm16 = (uint16_t *)p; p += align256((size_t)K * 2);
             std::vector<uint16_t> p16(K);
             std::vector<int32_t> inv(K);
             for (int k = 0; k < K; k++) { p16[k] = (uint16_t)perm[k]; inv[perm[k]] = k; }
@@ -1468,7 +1455,7 @@ int gptq_layer_inverse_perm(const gptq_layer_t *layer, const int32_t **invperm32
  * (prefill, fall-backs) first unpack it from the image into `scratch` -- gptq_layer_scratch_bytes() accounts for that. */
 static size_t layer_unpacked_bytes(const gptq_layer &L) {
     const size_t G = L.groupsize >= L.K ? 1 : (size_t)L.K / L.groupsize;
-    return (size_t)L.nsets * (a256((size_t)(L.K / 32 * L.bits) * L.N * 4) + a256(G * L.N * 2) + a256(G * (size_t)(L.N / 32 * L.bits) * 4));
+    return (size_t)L.nsets * (align256((size_t)(L.K / 32 * L.bits) * L.N * 4) + align256(G * L.N * 2) + align256(G * (size_t)(L.N / 32 * L.bits) * 4));
 }
 int gptq_layer_release_checkpoint(gptq_layer_t *layer) {
     if (!layer) return GPTQ_E_NULL;
@@ -1520,6 +1507,13 @@ static int decode_rows_mf16(int K, int N, int nsets, int bits, int groupsize) {
     return nsets == 2 ? 2 : 0;
 }
 
+// rows the decode launch takes at this M: decode_rows_max, or sixteen where M is 9 .. 16 and decode_rows_mf16 has the bit `mf16` (2: plain
+// launches, what the forward ladder and its query ask; 1: launches with the fused norm)
+static int decode_rows(int M, int K, int N, int nsets, int bits, int groupsize, int mf16 = 2) {
+    const int rows_max = decode_rows_max(K, N, nsets, bits, groupsize);   // row groups only while ONE round of workgroups covers N
+    return (M > 8 && M <= 16 && (decode_rows_mf16(K, N, nsets, bits, groupsize) & mf16)) ? std::max(rows_max, 16) : rows_max;   // round 6: sixteen A rows (the pair)
+}
+
 // Round 5: 129 .. gptq_set_stripe_gemm_max_rows() rows -- the fused tile GEMM on the image, or dequantise + the tile GEMM of gemm8.hip?  Once gemm8 gave
 // every XCD the same number of tiles (gemm8.hip, round 5) the dense route became the faster OWN kernel where the image route's 128 x 128 tiles no
 // longer fit the chip at once (two workgroups per CU = 512 tiles; beyond that its time steps up: 4096 x 12288 at 640 / 768 rows 84.6 / 118.9 us
@@ -1538,9 +1532,22 @@ static bool image_gemm_wanted(int M, int K, int N, int nsets, int kind) {
 /* persistent workspace every forward takes: [split-K words, zero on first use and left zero][scratch of the 16-row MFMA tiles] */
 size_t gptq_layer_workspace_bytes(void) { return WS_BYTES + STRIPE_MM_WS_BYTES; }
 
+static StripeImage layer_image(const gptq_layer &L) { return {L.stripe, L.stripe_bytes, L.K, L.N, L.bits, L.groupsize, L.nsets}; }
+
 // a released layer whose dense route needs no checkpoint layout: trivial g_idx, an image, a product the tile GEMM of gemm8.hip takes
 static bool layer_dense_from_image(const gptq_layer &L, int M) {
     return L.released && L.kind == 0 && L.stripe && L.K % 128 == 0 && own_dense_route() && (L.nsets == 2 || !L.bias || aligned(L.bias, 8));
+}
+
+// Scratch of the dense route (dequantise per call + GEMM) for M rows of this layer, released or not: the dense workspace, behind the checkpoint
+// layout a released layer rebuilds first.  Round 5: a released layer that layer_dense_from_image() feeds from its image rebuilds nothing --
+// DENSE_REPORTED (what gptq_layer_scratch_bytes answers) still counts the whole dense workspace for it, DENSE_LEAST is W^T alone: what that
+// rung of gptq_layer_forward runs in.  DENSE_FALLBACK: no rung counted on, the two-pass route's full need.
+enum DenseScratch { DENSE_REPORTED, DENSE_LEAST, DENSE_FALLBACK };
+static size_t layer_dense_scratch(const gptq_layer &L, int M, DenseScratch what) {
+    const size_t dense = gptq_prefill_workspace_bytes(M, L.K, L.N, L.nsets);
+    if (what != DENSE_FALLBACK && layer_dense_from_image(L, M)) return what == DENSE_LEAST ? align256((size_t)L.K * L.N * L.nsets * 2) : dense;
+    return (L.released ? layer_unpacked_bytes(L) : 0) + dense;
 }
 
 /* transient scratch that gives forward(M) its fast route: the gathered x of an act-order batch, the per-call dequantised weight */
@@ -1549,23 +1556,19 @@ size_t gptq_layer_scratch_bytes(const gptq_layer_t *layer, int M) {
     // the fused tile GEMM on the image (129 .. gptq_set_stripe_gemm_max_rows() rows) needs no scratch beyond the gather of x for an
     // act-order layer: no K * N dequantised copy per call on the prompt path.  Should that kernel decline at launch, the ladder goes on
     // with what it was given (library-free kernels, or GPTQ_E_WORKSPACE for a released layer).
-    if (gptq_layer_route_for(layer, M) == GPTQ_ROUTE_STRIPE_GEMM) return layer->kind == 1 ? a256((size_t)M * layer->K * 2) : 0;
-    size_t unpack = (layer->released && M > 1) ? layer_unpacked_bytes(*layer) : 0;   // (M == 1 always runs on the image)
-    if (M >= LAYER_PREFILL_MIN_M && (M > LAYER_STRIPE_MM_MAX_M || !layer->stripe)) {
-        // round 5: a released layer with a trivial g_idx feeds the tile GEMM straight from its image (stripe_dequant_t_kernel): no checkpoint
-        // layout is rebuilt.  Should that GEMM decline at launch the call returns GPTQ_E_WORKSPACE: gptq_layer_fallback_scratch_bytes() is the retry.
-        if (layer_dense_from_image(*layer, M)) unpack = 0;
-        return unpack + gptq_prefill_workspace_bytes(M, layer->K, layer->N, layer->nsets);
-    }
-    return unpack + (layer->kind == 1 && M > 1 ? a256((size_t)M * layer->K * 2) : 0);
+    if (gptq_layer_route_for(layer, M) == GPTQ_ROUTE_STRIPE_GEMM) return layer->kind == 1 ? align256((size_t)M * layer->K * 2) : 0;
+    // round 5: a released layer with a trivial g_idx feeds the tile GEMM straight from its image (stripe_dequant_t_kernel): no checkpoint
+    // layout is rebuilt.  Should that GEMM decline at launch the call returns GPTQ_E_WORKSPACE: gptq_layer_fallback_scratch_bytes() is the retry.
+    if (M >= LAYER_PREFILL_MIN_M && (M > LAYER_STRIPE_MM_MAX_M || !layer->stripe)) return layer_dense_scratch(*layer, M, DENSE_REPORTED);
+    const size_t unpack = (layer->released && M > 1) ? layer_unpacked_bytes(*layer) : 0;   // (M == 1 always runs on the image)
+    return unpack + (layer->kind == 1 && M > 1 ? align256((size_t)M * layer->K * 2) : 0);
 }
 
 /* the scratch with which forward(M) cannot fail for lack of memory: every fall-back's needs (the rebuilt checkpoint layout of a released layer,
  * the dense route's workspace, the gathered x of an act-order batch).  What a caller retries with after GPTQ_E_WORKSPACE. */
 size_t gptq_layer_fallback_scratch_bytes(const gptq_layer_t *layer, int M) {
     if (!layer || M <= 0) return 0;
-    return (layer->released ? layer_unpacked_bytes(*layer) : 0) + gptq_prefill_workspace_bytes(M, layer->K, layer->N, layer->nsets) +
-           a256((size_t)M * layer->K * 2);
+    return layer_dense_scratch(*layer, M, DENSE_FALLBACK) + align256((size_t)M * layer->K * 2);
 }
 
 static int layer_forward_checkpoint(const gptq_layer &L, const void *x, int64_t ldx, void *y, int64_t ldy, int M, void *workspace, void *scratch,
@@ -1576,14 +1579,11 @@ static int layer_forward_checkpoint(const gptq_layer &L, const void *x, int64_t 
 // launch (LDS limits of the row groups ...) and hand the batch to the next rung.
 int gptq_layer_route_for_shape(int M, int K, int N, int bits, int groupsize, int nsets, int kind, int has_image) {
     if (M <= 0 || K <= 0 || N <= 0 || nsets < 1 || nsets > 2 || kind < 0 || kind > 2) return GPTQ_E_SHAPE;
-    if (bits != 2 && bits != 3 && bits != 4 && bits != 8) return GPTQ_E_BITS;
+    if (!bits_ok(bits)) return GPTQ_E_BITS;
     const int gq = stripe_gq_shift(K, N, bits, groupsize);
-    const bool image = has_image && gq != -2 && kind != 2;
-    int rows_max = decode_rows_max(K, N, nsets, bits, groupsize);
-    if (M > 8 && M <= 16 && (decode_rows_mf16(K, N, nsets, bits, groupsize) & 2)) rows_max = std::max(rows_max, 16);   // round 6: sixteen A rows (the pair)
-    if (image && (kind == 0 || M == 1) && M <= rows_max && (M <= 4 || K <= 9216 || (K <= 12288 && nsets == 1))) return GPTQ_ROUTE_STRIPE_DECODE;
+    const bool image = has_image && gq != -2 && kind != 2;   // (so kind is 0 or 1: a regular act-order batch gets there after one gather of x)
+    if (image && M <= decode_rows(M, K, N, nsets, bits, groupsize) && (M <= 4 || K <= 9216 || (K <= 12288 && nsets == 1))) return GPTQ_ROUTE_STRIPE_DECODE;
     if (image && M > 1) {
-        if (M <= rows_max && kind == 1 && (M <= 4 || K <= 9216 || (K <= 12288 && nsets == 1))) return GPTQ_ROUTE_STRIPE_DECODE;       // after one gather of x
         if (M <= LAYER_STRIPE_MM_MAX_M) return GPTQ_ROUTE_STRIPE_TILES;
         if (image_gemm_wanted(M, K, N, nsets, kind) && bits != 2 && (gq == -1 || gq >= 2)) return GPTQ_ROUTE_STRIPE_GEMM;       // groups of at least a row block
     }
@@ -1608,45 +1608,42 @@ int gptq_layer_forward(const gptq_layer_t *layer, const void *x, int64_t ldx, vo
     if (!workspace || !aligned(workspace, 256) || workspace_bytes < gptq_layer_workspace_bytes()) return GPTQ_E_WORKSPACE;
     void *mm_ws = (char *)workspace + WS_BYTES;
     const int K = L.K, N = L.N, bits = L.bits, gs = L.groupsize, ns = L.nsets;
-    int rows_max = decode_rows_max(K, N, ns, bits, gs);    // row groups only while ONE round of workgroups covers N
-    if (M > 8 && M <= 16 && (decode_rows_mf16(K, N, ns, bits, gs) & 2)) rows_max = std::max(rows_max, 16);   // round 6: sixteen A rows (the pair)
+    const int rows_max = decode_rows(M, K, N, ns, bits, gs);
+    const StripeImage im = layer_image(L);
     // ---- 1. decode and small batches on the stripe16 image ----
     if (L.stripe && L.kind == 0) {
         if (M <= rows_max) {
-            const int rc = stripe_matvec(x, ldx, L.stripe, L.stripe_bytes, L.bias, y, ldy, nullptr, M, K, N, bits, gs, ns, nullptr, 0.f, nullptr, stream);
+            const int rc = stripe_matvec(im, {.x = x, .ldx = ldx, .y = y, .ldy = ldy, .M = M, .add = L.bias}, stream);
             if (rc != GPTQ_E_VARIANT) return rc;
         }
         // ... 128 rows: 16-row tiles; above: the fused tile GEMM, unless the dense route is the faster own kernel for this batch (image_gemm_wanted)
         // AND the caller brought the scratch it needs (gptq_layer_scratch_bytes says so; without it the batch stays on the image)
         bool on_image = M <= LAYER_STRIPE_MM_MAX_M || M <= g_stripe_gemm_max_rows.load();
-        if (on_image && M > LAYER_STRIPE_MM_MAX_M && !image_gemm_wanted(M, K, N, ns, 0)) {
-            const size_t need = !L.released ? gptq_prefill_workspace_bytes(M, K, N, ns)
-                                            : layer_dense_from_image(L, M) ? a256((size_t)K * N * ns * 2) : layer_unpacked_bytes(L) + gptq_prefill_workspace_bytes(M, K, N, ns);
-            on_image = !(scratch && aligned(scratch, 256) && scratch_bytes >= need);
-        }
+        if (on_image && M > LAYER_STRIPE_MM_MAX_M && !image_gemm_wanted(M, K, N, ns, 0))
+            on_image = !(scratch && aligned(scratch, 256) && scratch_bytes >= layer_dense_scratch(L, M, DENSE_LEAST));
         if (M > 4 && on_image) {
-            const int rc = stripe_matvec(x, ldx, L.stripe, L.stripe_bytes, L.bias, y, ldy, nullptr, M, K, N, bits, gs, ns, nullptr, 0.f, nullptr, stream, mm_ws,
-                                         STRIPE_MM_WS_BYTES, true);
+            const int rc = stripe_matvec(im, {.x = x, .ldx = ldx, .y = y, .ldy = ldy, .M = M, .add = L.bias, .mm_ws = mm_ws, .mm_ws_bytes = STRIPE_MM_WS_BYTES,
+                                              .gemm_only_above_128 = true}, stream);
             if (rc != GPTQ_E_VARIANT) return rc;
         }
     }
     if (L.stripe && L.kind == 1) {
         if (M == 1) {   // the decode kernel gathers x through the permutation itself
-            const int rc = stripe_matvec(x, ldx, L.stripe, L.stripe_bytes, L.bias, y, ldy, nullptr, 1, K, N, bits, gs, ns, nullptr, 0.f, L.perm16, stream);
+            const int rc = stripe_matvec(im, {.x = x, .ldx = ldx, .y = y, .ldy = ldy, .M = 1, .add = L.bias, .xperm = L.perm16}, stream);
             if (rc != GPTQ_E_VARIANT) return rc;
         } else if (M <= std::max(LAYER_STRIPE_MM_MAX_M, g_stripe_gemm_max_rows.load()) && scratch && aligned(scratch, 16) && scratch_bytes >= (size_t)M * K * 2) {
             // batches: ONE gather of x, then the trivial-g_idx kernels on the image of the group-sorted rows
             if (int rc = gather_cols_launch((const half_t *)x, ldx, L.perm32, (half_t *)scratch, K, M, K, (hipStream_t)stream)) return rc;
             if (M <= rows_max) {
-                const int rc = stripe_matvec(scratch, K, L.stripe, L.stripe_bytes, L.bias, y, ldy, nullptr, M, K, N, bits, gs, ns, nullptr, 0.f, nullptr, stream);
+                const int rc = stripe_matvec(im, {.x = scratch, .ldx = K, .y = y, .ldy = ldy, .M = M, .add = L.bias}, stream);
                 if (rc != GPTQ_E_VARIANT) return rc;
             }
-            const int rc = stripe_matvec(scratch, K, L.stripe, L.stripe_bytes, L.bias, y, ldy, nullptr, M, K, N, bits, gs, ns, nullptr, 0.f, nullptr, stream, mm_ws,
-                                         STRIPE_MM_WS_BYTES, true);
+            const int rc = stripe_matvec(im, {.x = scratch, .ldx = K, .y = y, .ldy = ldy, .M = M, .add = L.bias, .mm_ws = mm_ws, .mm_ws_bytes = STRIPE_MM_WS_BYTES,
+                                              .gemm_only_above_128 = true}, stream);
             if (rc != GPTQ_E_VARIANT) return rc;
         }
     }
-    if (M >= LAYER_PREFILL_MIN_M && layer_dense_from_image(L, M) && scratch && aligned(scratch, 256) && scratch_bytes >= a256((size_t)K * N * ns * 2)) {
+    if (M >= LAYER_PREFILL_MIN_M && layer_dense_from_image(L, M) && scratch && aligned(scratch, 256) && scratch_bytes >= layer_dense_scratch(L, M, DENSE_LEAST)) {
         // memory mode, prompt sizes: image -> W^T in ONE pass (bit-identical to the weight the two-pass route dequantises), then the tile GEMM
         half_t *Wt = (half_t *)scratch;
         int rc = stripe_dequant_t_launch(L.stripe, K, N, bits, gs, ns, Wt, K, (hipStream_t)stream);
@@ -1663,9 +1660,9 @@ int gptq_layer_forward(const gptq_layer_t *layer, const void *x, int64_t ldx, vo
         char *p = (char *)scratch;
         const size_t G = gs >= K ? 1 : (size_t)K / gs;
         for (int i = 0; i < ns; i++) {
-            int32_t *qw_i = (int32_t *)p; p += a256((size_t)(K / 32 * bits) * N * 4);
-            void *sc_i = p; p += a256(G * N * 2);
-            int32_t *qz_i = (int32_t *)p; p += a256(G * (size_t)(N / 32 * bits) * 4);
+            int32_t *qw_i = (int32_t *)p; p += align256((size_t)(K / 32 * bits) * N * 4);
+            void *sc_i = p; p += align256(G * N * 2);
+            int32_t *qz_i = (int32_t *)p; p += align256(G * (size_t)(N / 32 * bits) * 4);
             if (int rc = stripe_unpack_launch(L.stripe, K, N, bits, gs, ns, i, (uint32_t *)qw_i, (half_t *)sc_i, qz_i, (hipStream_t)stream,
                                               L.kind == 1 ? L.invperm32 : nullptr))
                 return rc;
@@ -1695,14 +1692,10 @@ static int layer_forward_checkpoint(const gptq_layer &L, const void *x, int64_t 
     }
     // ---- 3. kernels on the checkpoint layout (split-K rowwave / stream / tile GEMM; generic kernels for an irregular g_idx) ----
     Problem q = make_problem(x, ldx, L.qw[0], L.sc[0], L.qz[0], L.gi[0], L.bias, y, ldy, M, K, N, bits, gs, workspace, WS_BYTES);
-    if (ns == 2) {
-        q.fused2 = true;
-        q.qw[1] = L.qw[1]; q.sc[1] = L.sc[1]; q.qz[1] = L.qz[1]; q.gi[1] = L.gi[1];
-    }
+    if (ns == 2) make_pair(q, L.qw[1], L.sc[1], L.qz[1], L.gi[1]);
     // (a regular act-order layer that gets here -- no scratch for the gather, a kernel declined -- runs the generic g_idx kernels on the
     // checkpoint rows: round 3's group-sorted qweight copy, one more qweight per layer kept for this corner, is gone)
-    if (int rc = validate(q)) return rc;
-    return run_auto(q, (hipStream_t)stream);
+    return run_entry(GPTQ_PLAN_ENTRY_AUTO, q, Walk{(hipStream_t)stream, nullptr});
 }
 
 // ---- round 5: the operator of the batched decode engine -- y = residual + layer(rmsnorm(x)) for 1 .. 128 rows ----
@@ -1712,7 +1705,7 @@ static int layer_forward_checkpoint(const gptq_layer &L, const void *x, int64_t 
 // stand-alone launch into `scratch`; everything else is gptq_layer_forward + an add.
 size_t gptq_layer_decode_scratch_bytes(const gptq_layer_t *layer, int M) {
     if (!layer || M <= 0) return 0;
-    return a256((size_t)M * layer->K * 2) + gptq_layer_scratch_bytes(layer, M);
+    return align256((size_t)M * layer->K * 2) + gptq_layer_scratch_bytes(layer, M);
 }
 
 static int layer_decode(const gptq_layer_t *layer, const void *x, int64_t ldx, void *y, int64_t ldy, int M, const void *norm_weight, float norm_eps,
@@ -1732,7 +1725,6 @@ static int layer_decode(const gptq_layer_t *layer, const void *x, int64_t ldx, v
     if (scratch && !aligned(scratch, 256)) return GPTQ_E_ALIGN;
     void *mm_ws = (char *)workspace + WS_BYTES;
     const int K = L.K, N = L.N, bits = L.bits, gs = L.groupsize, ns = L.nsets;
-    const int rows_max = decode_rows_max(K, N, ns, bits, gs);
     const bool add_fused = !(L.bias && residual);                   // one add slot per launch: bias OR residual
     const void *add = residual && add_fused ? residual : L.bias;
     const int64_t ldb = residual && add_fused ? ldr : 0;
@@ -1741,11 +1733,11 @@ static int layer_decode(const gptq_layer_t *layer, const void *x, int64_t ldx, v
         return rc;
     };
     const bool image = L.stripe != nullptr && L.kind != 2;
-    const int mf16 = M > 8 && M <= 16 ? decode_rows_mf16(K, N, ns, bits, gs) : 0;
-    // 1. everything in the decode kernel's launch
-    if (image && (M <= rows_max || (norm_weight ? (mf16 & 1) : (mf16 & 2))) && (L.kind == 0 || M == 1)) {
-        const int rc = stripe_matvec(x, ldx, L.stripe, L.stripe_bytes, add, y, ldy, nullptr, M, K, N, bits, gs, ns, norm_weight, norm_eps,
-                                     L.kind == 1 ? L.perm16 : nullptr, stream, nullptr, 0, false, ldb);
+    const StripeImage im = layer_image(L);
+    // 1. everything in the decode kernel's launch (its own rule for sixteen rows: bit 1 of decode_rows_mf16 with the norm fused, bit 2 without)
+    if (image && M <= decode_rows(M, K, N, ns, bits, gs, norm_weight ? 1 : 2) && (L.kind == 0 || M == 1)) {
+        const int rc = stripe_matvec(im, {.x = x, .ldx = ldx, .y = y, .ldy = ldy, .M = M, .add = add, .ldb = ldb, .norm_w = norm_weight, .norm_eps = norm_eps,
+                                          .xperm = L.kind == 1 ? L.perm16 : nullptr}, stream);
         if (rc != GPTQ_E_VARIANT) return finish(rc);
     }
     // 2. the norm on its own, into scratch
@@ -1754,7 +1746,7 @@ static int layer_decode(const gptq_layer_t *layer, const void *x, int64_t ldx, v
     char *sp = (char *)scratch;
     size_t left = scratch_bytes;
     if (norm_weight) {
-        const size_t nb = a256((size_t)M * K * 2);
+        const size_t nb = align256((size_t)M * K * 2);
         if (!scratch || left < nb) return GPTQ_E_WORKSPACE;
         if ((size_t)K * 2 > 65536) return GPTQ_E_NORM_WIDTH;
         if (int rc = rmsnorm_launch((const half_t *)x, ldx, (const half_t *)norm_weight, (half_t *)sp, K, M, K, norm_eps, (hipStream_t)stream)) return rc;
@@ -1762,14 +1754,13 @@ static int layer_decode(const gptq_layer_t *layer, const void *x, int64_t ldx, v
         sp += nb; left -= nb;
     }
     if (image && L.kind == 0) {
-        if ((M <= rows_max || (mf16 & 2)) && norm_weight) {   // (the decode kernel declined WITH the norm -- LDS -- but may take the rows without it)
-            const int rc = stripe_matvec(xin, ldin, L.stripe, L.stripe_bytes, add, y, ldy, nullptr, M, K, N, bits, gs, ns, nullptr, 0.f, nullptr, stream, nullptr, 0,
-                                         false, ldb);
+        if (M <= decode_rows(M, K, N, ns, bits, gs) && norm_weight) {   // (the decode kernel declined WITH the norm -- LDS -- but may take the rows without it)
+            const int rc = stripe_matvec(im, {.x = xin, .ldx = ldin, .y = y, .ldy = ldy, .M = M, .add = add, .ldb = ldb}, stream);
             if (rc != GPTQ_E_VARIANT) return finish(rc);
         }
         if (M > 4) {                           // 16-row MFMA tiles, the residual in their epilogue (and, with K slices, the next norm: nn)
-            const int rc = stripe_matvec(xin, ldin, L.stripe, L.stripe_bytes, add, y, ldy, nullptr, M, K, N, bits, gs, ns, nullptr, 0.f, nullptr, stream, mm_ws,
-                                         STRIPE_MM_WS_BYTES, true, ldb, nullptr, nullptr, add_fused ? nn : nullptr);
+            const int rc = stripe_matvec(im, {.x = xin, .ldx = ldin, .y = y, .ldy = ldy, .M = M, .add = add, .ldb = ldb, .mm_ws = mm_ws,
+                                              .mm_ws_bytes = STRIPE_MM_WS_BYTES, .gemm_only_above_128 = true, .nn = add_fused ? nn : nullptr}, stream);
             if (rc != GPTQ_E_VARIANT) return finish(rc);
         }
     }
@@ -1835,9 +1826,8 @@ int gptq_layer_decode_attn_f16(const gptq_layer_t *layer, const void *attn_works
     am.tps = tokens_per_split > 0 ? tokens_per_split : decode_attn_tps(true);
     am.heads = heads;
     am.t_max = t_max;
-    const void *add = residual ? residual : L.bias;
-    return stripe_matvec(attn_workspace, L.K, L.stripe, L.stripe_bytes, add, y, ldy, nullptr, 1, L.K, L.N, L.bits, L.groupsize, 1, nullptr, 0.f, nullptr, stream,
-                         nullptr, 0, false, residual ? ldr : 0, nullptr, &am);
+    return stripe_matvec(layer_image(L), {.x = attn_workspace, .ldx = L.K, .y = y, .ldy = ldy, .M = 1, .add = residual ? residual : L.bias,
+                                          .ldb = residual ? ldr : 0, .att = &am}, stream);
 }
 
 // ---- GPTQ solver: the sequential loop of one column block (gptq_solver.hip) ----

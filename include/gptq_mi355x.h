@@ -160,6 +160,52 @@ int gptq_fused_mlp_f16(const void *x, int64_t ldx, const int32_t *qweight_gate,
                        size_t workspace_bytes, gptq_stream_t stream);
 
 /*
+ * The launch plan of the entries above as a host-only query: what the reference's autotuner would have chosen per shape
+ * (quant/custom_autotune.py:76-102), here a static function of the arguments that a caller -- and a CPU test -- can read.  It
+ * walks the entry's own dispatch code up to its FIRST dispatch call, launches nothing and touches no pointer; it honours the
+ * current gptq_set_gemv_variant / gptq_set_split_k.
+ *   entry      GPTQ_PLAN_ENTRY_AUTO: gptq_matmul248_f16 (nsets = 1) / gptq_fused_mlp_f16 (nsets = 2); _GEMV: gptq_gemv_f16;
+ *              _SKINNY: gptq_skinny_f16; _ROWWAVE: the direct rowwave entries gptq_rmsnorm_matmul248_f16 / gptq_rmsnorm_fused_mlp_f16
+ *              (GPTQ_PLAN_F_NORM; they have no M: M must be 1), gptq_matmul248_sorted_f16 / gptq_fused_mlp_sorted_f16
+ *              (GPTQ_PLAN_F_X_PERM), gptq_rmsnorm_sorted_f16 (both flags).  Those two flags belong to this entry alone.
+ *   flags      GPTQ_PLAN_F_G_IDX: a g_idx is passed (for every set); GPTQ_PLAN_F_NORM: a norm weight; GPTQ_PLAN_F_X_PERM: an x permutation
+ *   workspace_bytes   what the call would bring (0: no workspace; the pointer counts as aligned)
+ * Returns the kernel family of that first call (GPTQ_KERNEL_*; GPTQ_KERNEL_NONE: M = 0, nothing to launch) and fills
+ * plan[GPTQ_PLAN_FIELDS] -- or the GPTQ_E_* the entry returns before any launch for such arguments (plan is zeroed; GPTQ_E_VARIANT
+ * also for an unknown entry / flag, GPTQ_E_SHAPE for nsets outside 1 .. 2).  Fields a family does not have are 0:
+ *   ROWWAVE (one launch per row) / ROWWAVE_MR / ROWWAVE_MFMA (all rows):  ROWS, UNIT = U packed rows (3-bit: 32-k blocks) in flight per
+ *              wave, SPLIT_K, UPG_SHIFT = log2(units per group), -1 with one group
+ *   GENERIC    ROWS, UNIT = nl (4 nl columns per workgroup), SPLIT_K = 1, NTILES, CHUNKS_PER_SLICE
+ *   STREAM     ROWS of the pass, UNIT = units per stage, SPLIT_K, WAVES, XLDS (x staged in LDS), UPG_SHIFT, NTILES, CHUNKS_PER_SLICE
+ *   TILE_GEMM  ROWS
+ * The kernel may still decline at launch and hand the product to the next rung; the plan is that of the first call all the same.
+ * Pinned over a grid of shapes, recorded from the dispatch calls themselves, by tests/test_host_gemv_plan.py.
+ */
+enum { GPTQ_PLAN_ENTRY_AUTO = 0, GPTQ_PLAN_ENTRY_GEMV = 1, GPTQ_PLAN_ENTRY_SKINNY = 2, GPTQ_PLAN_ENTRY_ROWWAVE = 3 };
+enum { GPTQ_PLAN_F_G_IDX = 1, GPTQ_PLAN_F_NORM = 2, GPTQ_PLAN_F_X_PERM = 4 };
+enum {
+    GPTQ_KERNEL_NONE = 0,
+    GPTQ_KERNEL_ROWWAVE = 1,       /* gemv_fast_dispatch (csrc/gemv.hip) */
+    GPTQ_KERNEL_ROWWAVE_MR = 2,    /* gemv_rowwave_mr_dispatch */
+    GPTQ_KERNEL_ROWWAVE_MFMA = 3,  /* gemv_rowwave_mfma_dispatch */
+    GPTQ_KERNEL_GENERIC = 4,       /* gemv_generic_dispatch */
+    GPTQ_KERNEL_STREAM = 5,        /* skinny_dispatch (csrc/skinny_mfma.hip) */
+    GPTQ_KERNEL_TILE_GEMM = 6      /* gemm_dispatch (csrc/gemm_mfma.hip) */
+};
+enum {
+    GPTQ_PLAN_ROWS = 0,
+    GPTQ_PLAN_UNIT = 1,
+    GPTQ_PLAN_SPLIT_K = 2,
+    GPTQ_PLAN_WAVES = 3,
+    GPTQ_PLAN_XLDS = 4,
+    GPTQ_PLAN_UPG_SHIFT = 5,
+    GPTQ_PLAN_NTILES = 6,
+    GPTQ_PLAN_CHUNKS_PER_SLICE = 7,
+    GPTQ_PLAN_FIELDS = 8
+};
+int gptq_gemv_plan_for_shape(int entry, int M, int K, int N, int bits, int groupsize, int nsets, int flags, size_t workspace_bytes, int *plan);
+
+/*
  * dx[M,K] = dy[M,N] . deq(B)^T -- reference transpose_matmul248() +
  * transpose_matmul_248_kernel (quant/quant_linear.py:272-279, :191-258); the backward of
  * QuantLinearFunction (:294-301).
