@@ -1,5 +1,8 @@
-// spec_sample.hip -- gptq_spec_sample_rows_f16: the accept / resample rule of speculative sampling for one verify step of R rows, ONE launch, one
-// workgroup per row (include/gptq_mi355x.h "speculative sampling" states the semantics; tests/spec_sample_ref.py restates them in float64).
+// spec_sample.hip -- gptq_spec_sample_rows_f16 / gptq_spec_sample_batch_f16: the accept / resample rule of speculative sampling for one verify step
+// of R rows of each of B sequences, ONE launch, grid (R, B), one workgroup per row (include/gptq_mi355x.h "speculative sampling" states the
+// semantics; tests/spec_sample_ref.py restates them in float64).  ONE kernel, two entries: the rows entry is the B = 1 launch without the idle rule.
+// What follows describes one sequence; sequence b reads rows b R .. b R + R - 1 of the packed per-row arrays, rows b (R - 1) .. of the draft
+// logits, ids + b R, pos[b], and owns out + b (R + 1) and workspace words b (R + 1) .. : its own ticket and records.
 //
 // Row i of the target logits is the distribution p after ids[0 .. i]; ids[i + 1] = d is the token drafted for that place, from q: row i of the draft
 // logits under the row's own setting, or a point mass at d without draft logits.  p and q are the kept sets and integer masses of sample.hip
@@ -13,6 +16,9 @@
 // The rows meet through the workspace: a workgroup stores its record {accepted, token} with a system-scope store, drains it and takes a ticket;
 // the last to arrive reads all records with system-scope loads, finds the first rejecting row a, writes out = [a, d_0 .. d_{a-1}, t_a, t_a ..] and
 // pos += a + 1, and puts the ticket word back to 0 for the next launch or replay.  Who arrives last decides nothing but who writes.
+//
+// Idle sequences (t_max > 0, the batch entry): sequence b is active iff 0 <= pos[b] < t_max, the rule of chunk_attn.hip.  The workgroups of an idle
+// sequence return at once: no logits read, no ticket, nothing written.
 #include "../../include/gptq_mi355x.h"
 #include "sample_common.h"
 
@@ -27,22 +33,34 @@ GPTQ_DEV float clamp_u(float u) { return isnan(u) || u < 0.f ? 0.f : (u >= 1.f ?
 __global__ __launch_bounds__(SM_NT) void spec_sample_rows_kernel(const uint16_t *logits, int64_t ld, const uint16_t *qlogits, int64_t ldq, int rows,
                                                                  int vocab, const int64_t *ids, const float *temperature, const int32_t *top_k,
                                                                  const float *top_p, const float *u_accept, const float *u_draw, int64_t *pos,
-                                                                 int64_t *out, u64 *ws) {
+                                                                 int64_t t_max, int64_t *out, u64 *ws) {
     __shared__ SelectLds L;
     __shared__ u64 wsum[2][SM_NW];
     __shared__ int s_tok, s_last, s_first;
     __shared__ uint32_t s_dbits[2];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int r = blockIdx.x;
-    const bool bonus = r == rows - 1;
+    const int ri = blockIdx.x, sq = blockIdx.y;                     // row ri of sequence sq
+    const bool bonus = ri == rows - 1;
+    pos += sq;
+    if (t_max > 0) {
+        // The sequence's verdict, read ONCE, before this workgroup's ticket.  The only writer of pos[sq] in this launch is the sequence's last
+        // arriver, and it writes behind the last ticket -- which every workgroup of an active sequence takes after this read -- so all R
+        // workgroups see the launch's initial value and reach the same verdict.  A second read further down could see the advanced position.
+        const int64_t p0 = __hip_atomic_load(pos, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (p0 < 0 || p0 >= t_max) return;                          // (uniform over the workgroup: nobody waits at a barrier below)
+    }
+    const int r = sq * rows + ri;                                     // the row of the packed [B, R] arrays
+    ids += (int64_t)sq * rows;
+    out += (int64_t)sq * (rows + 1);
+    ws += (int64_t)sq * (rows + 1);
     const uint16_t *row = logits + (int64_t)r * ld;
-    const uint16_t *qrow = (qlogits && !bonus) ? qlogits + (int64_t)r * ldq : nullptr;
+    const uint16_t *qrow = (qlogits && !bonus) ? qlogits + ((int64_t)sq * (rows - 1) + ri) * ldq : nullptr;
     const float T = temperature[r];
     const int kraw = top_k[r];
     const float praw = top_p[r];
     const float ud = clamp_u(u_draw[r]);
-    const int64_t d64 = bonus ? -1 : ids[r + 1];
+    const int64_t d64 = bonus ? -1 : ids[ri + 1];
     const int d = (d64 >= 0 && d64 < vocab) ? (int)d64 : -1;        // a draft outside the vocabulary is a draft nobody keeps
     const int sh = mass_exponent(vocab);
 
@@ -96,7 +114,7 @@ __global__ __launch_bounds__(SM_NT) void spec_sample_rows_kernel(const uint16_t 
 
     // ---- the record, the ticket, and the last arriver's prefix ----
     if (tid == 0) {
-        __hip_atomic_store(ws + 1 + r, ((u64)acc << 32) | (uint32_t)s_tok, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store(ws + 1 + ri, ((u64)acc << 32) | (uint32_t)s_tok, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         unsigned *ticket = (unsigned *)ws;
         const unsigned t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -117,27 +135,49 @@ __global__ __launch_bounds__(SM_NT) void spec_sample_rows_kernel(const uint16_t 
     const int a = s_first;
     const int64_t ta = (int64_t)(uint32_t)__hip_atomic_load(ws + 1 + a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     for (int j = tid; j <= rows; j += SM_NT) out[j] = j == 0 ? (int64_t)a : (j <= a ? ids[j] : ta);
-    if (tid == 0) pos[0] += a + 1;
+    if (tid == 0) *pos += a + 1;
 }
 
 inline bool aligned(const void *p, size_t a) { return ((uintptr_t)p % a) == 0; }
 
 }  // namespace
 
+// the ONE validation and launch behind both entries; idle_rule false (the rows entry): t_max is not looked at and the kernel gets 0, any pos runs
+static int launch(const void *logits, int64_t ld, const void *draft_logits, int64_t ld_draft, int seqs, int rows, int vocab, const int64_t *ids,
+                  const float *temperature, const int32_t *top_k, const float *top_p, const float *u_accept, const float *u_draw, int64_t *pos,
+                  bool idle_rule, int64_t t_max, int64_t *out, void *workspace, size_t workspace_bytes, gptq_stream_t stream) {
+    if (!logits || !ids || !temperature || !top_k || !top_p || !u_accept || !u_draw || !pos || !out || !workspace) return GPTQ_E_NULL;
+    if (seqs < 1 || seqs > 65535 || rows < 2 || vocab < 1 || ld < vocab || (draft_logits && ld_draft < vocab) ||
+        (idle_rule && t_max < 1))
+        return GPTQ_E_SHAPE;
+    if (workspace_bytes < gptq_spec_sample_batch_workspace_bytes(seqs, rows)) return GPTQ_E_WORKSPACE;
+    if (!aligned(logits, 2) || !aligned(draft_logits, 2) || !aligned(ids, 8) || !aligned(temperature, 4) || !aligned(top_k, 4) ||
+        !aligned(top_p, 4) || !aligned(u_accept, 4) || !aligned(u_draw, 4) || !aligned(pos, 8) || !aligned(out, 8) || !aligned(workspace, 8))
+        return GPTQ_E_ALIGN;
+    hipLaunchKernelGGL(spec_sample_rows_kernel, dim3(rows, seqs), dim3(SM_NT), 0, (hipStream_t)stream, (const uint16_t *)logits, ld,
+                       (const uint16_t *)draft_logits, ld_draft, rows, vocab, ids, temperature, top_k, top_p, u_accept, u_draw, pos,
+                       idle_rule ? t_max : (int64_t)0, out, (u64 *)workspace);
+    return (int)hipGetLastError();
+}
+
 extern "C" size_t gptq_spec_sample_workspace_bytes(int rows) { return rows < 2 ? 0 : ((size_t)rows + 1) * sizeof(u64); }
+
+extern "C" size_t gptq_spec_sample_batch_workspace_bytes(int seqs, int rows) {
+    return seqs < 1 ? 0 : (size_t)seqs * gptq_spec_sample_workspace_bytes(rows);
+}
 
 extern "C" int gptq_spec_sample_rows_f16(const void *logits, int64_t ld, const void *draft_logits, int64_t ld_draft, int rows, int vocab,
                                          const int64_t *ids, const float *temperature, const int32_t *top_k, const float *top_p,
                                          const float *u_accept, const float *u_draw, int64_t *pos, int64_t *out, void *workspace,
                                          size_t workspace_bytes, gptq_stream_t stream) {
-    if (!logits || !ids || !temperature || !top_k || !top_p || !u_accept || !u_draw || !pos || !out || !workspace) return GPTQ_E_NULL;
-    if (rows < 2 || vocab < 1 || ld < vocab || (draft_logits && ld_draft < vocab)) return GPTQ_E_SHAPE;
-    if (workspace_bytes < gptq_spec_sample_workspace_bytes(rows)) return GPTQ_E_WORKSPACE;
-    if (!aligned(logits, 2) || !aligned(draft_logits, 2) || !aligned(ids, 8) || !aligned(temperature, 4) || !aligned(top_k, 4) ||
-        !aligned(top_p, 4) || !aligned(u_accept, 4) || !aligned(u_draw, 4) || !aligned(pos, 8) || !aligned(out, 8) || !aligned(workspace, 8))
-        return GPTQ_E_ALIGN;
-    hipLaunchKernelGGL(spec_sample_rows_kernel, dim3(rows), dim3(SM_NT), 0, (hipStream_t)stream, (const uint16_t *)logits, ld,
-                       (const uint16_t *)draft_logits, ld_draft, rows, vocab, ids, temperature, top_k, top_p, u_accept, u_draw, pos, out,
-                       (u64 *)workspace);
-    return (int)hipGetLastError();
+    return launch(logits, ld, draft_logits, ld_draft, 1, rows, vocab, ids, temperature, top_k, top_p, u_accept, u_draw, pos, false, 0, out,
+                  workspace, workspace_bytes, stream);
+}
+
+extern "C" int gptq_spec_sample_batch_f16(const void *logits, int64_t ld, const void *draft_logits, int64_t ld_draft, int seqs, int rows, int vocab,
+                                          const int64_t *ids, const float *temperature, const int32_t *top_k, const float *top_p,
+                                          const float *u_accept, const float *u_draw, int64_t *pos, int64_t t_max, int64_t *out, void *workspace,
+                                          size_t workspace_bytes, gptq_stream_t stream) {
+    return launch(logits, ld, draft_logits, ld_draft, seqs, rows, vocab, ids, temperature, top_k, top_p, u_accept, u_draw, pos, true, t_max, out,
+                  workspace, workspace_bytes, stream);
 }

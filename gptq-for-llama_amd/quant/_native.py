@@ -178,6 +178,10 @@ _SIGNATURES = {
     'gptq_spec_sample_workspace_bytes': [c_int],
     'gptq_spec_sample_rows_f16': [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                   c_void_p, c_void_p, c_void_p, c_size_t, c_void_p],
+    # ... for B sequences in one launch, grid (R, B), an idle rule on pos[b] (the same kernel; the rows entry is its B = 1 launch)
+    'gptq_spec_sample_batch_workspace_bytes': [c_int, c_int],
+    'gptq_spec_sample_batch_f16': [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_size_t, c_void_p],
 }
 
 
@@ -220,6 +224,7 @@ def lib():
             L.gptq_decode_attn_chunk_workspace_bytes.restype = c_size_t
             L.gptq_decode_attn_chunk_batch_workspace_bytes.restype = c_size_t
             L.gptq_spec_sample_workspace_bytes.restype = c_size_t
+            L.gptq_spec_sample_batch_workspace_bytes.restype = c_size_t
             L.gptq_layer_destroy.restype = None
             L.gptq_strerror.argtypes = [c_int]
             L.gptq_strerror.restype = ctypes.c_char_p

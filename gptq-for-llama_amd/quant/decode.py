@@ -210,7 +210,7 @@ def lm_head_logits(eng, x, logits, s, h=None):
 
 class DecodeEngine:
 
-    def __init__(self, model, t_max=2048, fuse_norm=True, fuse_attn=True, batch=1, chunk=0, batch_chunk=0):
+    def __init__(self, model, t_max=2048, fuse_norm=True, fuse_attn=True, batch=1, chunk=0, batch_chunk=0, spec_sample=False):
         """chunk = R or batch_chunk = R (2 .. 16) adds the VERIFY step of speculative decoding: R consecutive tokens of each of the B = batch
         sequences -- the last accepted token and R - 1 drafts -- go through every layer at M = B R in one pass over the weights; attention by
         gptq_decode_attn_chunk_batch_f16 -- two launches for all sequences -- on every sequence's own cache slice and position.  It is ONE
@@ -220,6 +220,10 @@ class DecodeEngine:
         batch_chunk = R needs batch B >= 2 with B R <= 128: verify_batch / accept_batch / capture_verify_greedy_batch,
         engine_generate_batch(speculate=...); chunk_ids [B, R], verify_out [B, R + 1].
         0 for both (the default) allocates nothing and changes nothing; NotImplementedError when a layer has no decode route for B R rows.
+        spec_sample = True (with batch_chunk = R) adds speculative SAMPLING for the B sequences: the [B R] settings and uniforms, the draft
+        logits rows and the workspace of gptq_spec_sample_batch_f16 -- verify_sample_batch / capture_verify_sample_batch,
+        engine_generate_batch(speculate=dict(sample=..., draft_model=...)).  A chunk engine always has them (its B = 1 case); a batch_chunk
+        engine without the flag allocates nothing of it and refuses those calls.  ValueError without chunk rows.
         batch (round 5): rows of a decode BATCH -- B sequences advance by one token per step, every row with its own position and its
         own slice of the K/V cache (the reference's one kernel serves any batch, quant_linear.py:263-269; HF generate drives it with
         [B, 1] steps).  The linears run at M = B through gptq_layer_decode_f16 (norm and residual inside the decode kernel's launch up to
@@ -239,6 +243,9 @@ class DecodeEngine:
         if self.batch_chunk != 0 and (self.batch < 2 or not 2 <= self.batch_chunk <= MAX_BATCH or self.batch * self.batch_chunk > MAX_CHUNK_ROWS):
             raise ValueError('DecodeEngine: batch_chunk must be 0 or 2 .. %d, and needs batch >= 2 with batch x batch_chunk <= %d' % (
                 MAX_BATCH, MAX_CHUNK_ROWS))
+        if spec_sample and not (self.chunk or self.batch_chunk):
+            raise ValueError('DecodeEngine: spec_sample needs batch_chunk = R (a chunk engine always samples speculatively)')
+        self.spec_sample = bool(spec_sample or self.chunk)
         self.fuse_norm, self.fuse_attn = bool(fuse_norm), bool(fuse_attn)
         self.native = _native
         self.lib = _native.lib()
@@ -702,9 +709,9 @@ class DecodeEngine:
     def set_sampling(self, temperature=1.0, top_k=0, top_p=1.0):
         """the rows' sampling settings: a scalar for all rows or one value per row.  temperature 0 makes a row greedy, top_k 0 and top_p 1 switch
         the filter off.  Only the static device buffers change: a captured graph (capture_sample_native) serves the new setting at its next
-        replay.  An engine with chunk=R also gets row 0's setting in all R rows of its verify step (capture_verify_sample: the rows are
-        consecutive tokens of the one sequence).  ValueError for a temperature that is negative or not finite, a negative top_k, a top_p outside
-        (0, 1]."""
+        replay.  An engine that samples speculatively (chunk=R, or batch_chunk=R with spec_sample) also gets sequence b's setting in rows
+        b R .. b R + R - 1 of its verify step (capture_verify_sample / _batch: those rows are consecutive tokens of sequence b).  ValueError
+        for a temperature that is negative or not finite, a negative top_k, a top_p outside (0, 1]."""
         B = self.batch
 
         def per_row(name, v, ok):
@@ -722,10 +729,11 @@ class DecodeEngine:
             self.temperature.copy_(torch.tensor(t, dtype=torch.float32))
             self.top_k.copy_(torch.tensor([int(x) for x in k], dtype=torch.int32))
             self.top_p.copy_(torch.tensor(p, dtype=torch.float32))
-            if self.chunk:                           # every row of a verify step decodes the one sequence: row 0's setting
-                self.chunk_temperature.fill_(t[0])
-                self.chunk_top_k.fill_(int(k[0]))
-                self.chunk_top_p.fill_(p[0])
+            if self.spec_sample:                     # the R rows of sequence b in a verify step decode that sequence: row b's setting
+                R = self.chunk_rows
+                self.chunk_temperature.view(B, R).copy_(self.temperature.unsqueeze(1).expand(B, R))
+                self.chunk_top_k.view(B, R).copy_(self.top_k.unsqueeze(1).expand(B, R))
+                self.chunk_top_p.view(B, R).copy_(self.top_p.unsqueeze(1).expand(B, R))
         return self
 
     def sample_logits(self, logits, out=None, u=None):
@@ -1014,16 +1022,17 @@ class DecodeEngine:
         # the verify-greedy graph's result, read by the host in ONE copy per step: row b = [a_b, am_b[0 .. R - 1]]
         ids, out = torch.zeros((B, R), dtype=torch.int64, device=dev), torch.zeros((B, R + 1), dtype=torch.int64, device=dev)
         self.chunk_ids, self.verify_out = (ids[0], out[0]) if self.chunk else (ids, out)
-        if not self.chunk:
+        if not self.spec_sample:
             return
-        # speculative sampling (gptq_spec_sample_rows_f16; B = 1 only): the R rows' setting (set_sampling fills them from row 0), their uniforms,
-        # the draft model's logits rows, and the kernel's workspace [ticket, R records] -- zero once, the ticket puts itself back
+        # speculative sampling (gptq_spec_sample_batch_f16): the B R rows' setting (set_sampling: sequence b's in its R rows), their uniforms, the
+        # draft model's logits rows [B (R - 1), vocab], and the kernel's workspace, per sequence [ticket, R records] -- zero once, a ticket
+        # puts itself back
         f32 = dict(dtype=torch.float32, device=dev)
-        self.chunk_temperature, self.chunk_top_p = torch.ones(R, **f32), torch.ones(R, **f32)
-        self.chunk_top_k = torch.zeros(R, dtype=torch.int32, device=dev)
-        self.chunk_u_accept, self.chunk_u_draw = torch.zeros(R, **f32), torch.zeros(R, **f32)
-        self.chunk_draft_logits = torch.zeros((R - 1, self.lm_head.shape[0]), **f16)
-        self.spec_ws = torch.zeros(self.lib.gptq_spec_sample_workspace_bytes(R) // 8, dtype=torch.int64, device=dev)
+        self.chunk_temperature, self.chunk_top_p = torch.ones(M, **f32), torch.ones(M, **f32)
+        self.chunk_top_k = torch.zeros(M, dtype=torch.int32, device=dev)
+        self.chunk_u_accept, self.chunk_u_draw = torch.zeros(M, **f32), torch.zeros(M, **f32)
+        self.chunk_draft_logits = torch.zeros((B * (R - 1), self.lm_head.shape[0]), **f16)
+        self.spec_ws = torch.zeros(self.lib.gptq_spec_sample_batch_workspace_bytes(B, R) // 8, dtype=torch.int64, device=dev)
 
     def _step_chunk(self):
         """_step_rows at M = B R: row b R + r is token r of sequence b (chunk_ids[b, r] at position pos[b] + r); gptq_decode_attn_chunk_batch_f16 on
@@ -1160,19 +1169,25 @@ class DecodeEngine:
         self.verify_graph = self._capture_verify('capture_verify_greedy_batch', self._verify_greedy_step, batched=True)
         return self
 
-    # -- speculative SAMPLING: the verify step followed by the accept / resample rule of gptq_spec_sample_rows_f16 (csrc/spec_sample.hip) -------
+    # -- speculative SAMPLING: the verify step followed by the accept / resample rule of gptq_spec_sample_batch_f16 (csrc/spec_sample.hip), for the
+    # -- B sequences in one launch; the chunk engine is its B = 1 case -----------------------------------------------------------------------
+    def _need_spec_sample(self, what, batched):
+        self._need_chunk(what, batched)
+        if not self.spec_sample:
+            raise ValueError('DecodeEngine.%s: the engine was built without spec_sample=True' % what)
+
     def _spec_sample_rows(self, draft_logits):
-        """the kernel on chunk_logits / chunk_ids under the chunk rows' setting and the uniforms in chunk_u_accept / chunk_u_draw: verify_out =
-        [a, d_0 .. d_{a-1}, t_a, ..] and pos += a + 1, in one launch"""
+        """the kernel on chunk_logits / chunk_ids under the chunk rows' setting and the uniforms in chunk_u_accept / chunk_u_draw, for every active
+        sequence b (0 <= pos[b] < t_max): verify_out[b] = [a_b, d_0 .. d_{a_b - 1}, t_a, ..] and pos[b] += a_b + 1, in one launch"""
         dl = self.chunk_draft_logits if draft_logits else None
         with self.native.on_device(self.dev):
-            rc = self.lib.gptq_spec_sample_rows_f16(self.chunk_logits.data_ptr(), self.chunk_logits.stride(0), dl.data_ptr() if draft_logits else None,
-                                                    dl.stride(0) if draft_logits else 0, self.chunk, self.chunk_logits.shape[1],
-                                                    self.chunk_ids.data_ptr(), self.chunk_temperature.data_ptr(), self.chunk_top_k.data_ptr(),
-                                                    self.chunk_top_p.data_ptr(), self.chunk_u_accept.data_ptr(), self.chunk_u_draw.data_ptr(),
-                                                    self.pos.data_ptr(), self.verify_out.data_ptr(), self.spec_ws.data_ptr(),
-                                                    self.spec_ws.numel() * 8, self.native.stream_ptr(self.dev))
-        self.native.check(rc, 'gptq_spec_sample_rows_f16')
+            rc = self.lib.gptq_spec_sample_batch_f16(self.chunk_logits.data_ptr(), self.chunk_logits.stride(0), dl.data_ptr() if draft_logits else None,
+                                                     dl.stride(0) if draft_logits else 0, self.batch, self.chunk_rows, self.chunk_logits.shape[1],
+                                                     self.chunk_ids.data_ptr(), self.chunk_temperature.data_ptr(), self.chunk_top_k.data_ptr(),
+                                                     self.chunk_top_p.data_ptr(), self.chunk_u_accept.data_ptr(), self.chunk_u_draw.data_ptr(),
+                                                     self.pos.data_ptr(), self.t_max, self.verify_out.data_ptr(), self.spec_ws.data_ptr(),
+                                                     self.spec_ws.numel() * 8, self.native.stream_ptr(self.dev))
+        self.native.check(rc, 'gptq_spec_sample_batch_f16')
 
     def _verify_sample_step(self, draft_logits=False):
         """_step_chunk, fresh uniforms from torch's CUDA generator (inside a graph its Philox offset advances per replay as per eager call), the
@@ -1182,48 +1197,85 @@ class DecodeEngine:
         self.chunk_u_draw.uniform_()
         self._spec_sample_rows(draft_logits)
 
+    def _verify_sample_rows(self, what, tokens, draft_logits, u_accept, u_draw):
+        """verify_sample and verify_sample_batch: tokens a list of B entries (2 .. R ids, or None: the sequence idles under the mark -1 and gets its
+        position back), draft_logits None or a list of B fp16 [n_b - 1, vocab] tensors, the uniforms None or float32 [B, R].  Everything is checked
+        (ValueError) before anything is uploaded or launched.  Returns one (a_b, tokens_b) per sequence, None for an idle one."""
+        B, R, V = self.batch, self.chunk_rows, self.chunk_logits.shape[1]
+        if not isinstance(tokens, (list, tuple)) or len(tokens) != B:
+            raise ValueError('DecodeEngine.%s: tokens must be a list of %d entries (ids or None)' % (what, B))
+        rows = []
+        for t in tokens:
+            if t is not None:
+                t = [int(x) for x in (t.reshape(-1).tolist() if torch.is_tensor(t) else list(t))]
+                if not 2 <= len(t) <= R:
+                    raise ValueError('DecodeEngine.%s: 2 .. %d tokens per sequence, not %d' % (what, R, len(t)))
+            rows.append(t)
+        if draft_logits is not None:
+            if not isinstance(draft_logits, (list, tuple)) or len(draft_logits) != B:
+                raise ValueError('DecodeEngine.%s: draft_logits must be None or a list of %d tensors' % (what, B))
+            for t, dl in zip(rows, draft_logits):
+                if t is not None and (not torch.is_tensor(dl) or dl.shape != (len(t) - 1, V) or dl.dtype != torch.float16):
+                    raise ValueError('DecodeEngine.%s: draft_logits must be fp16 [%d, %d]' % (what, len(t) - 1, V))
+        for name, u in (('u_accept', u_accept), ('u_draw', u_draw)):
+            if u is not None and (not torch.is_tensor(u) or u.dtype != torch.float32 or u.shape != (B, R)):
+                raise ValueError('DecodeEngine.%s: %s must be float32 %s' % (what, name, [B, R] if self.batch_chunk else [R]))
+        active = [t is not None for t in rows]
+        self._chunks_fit(what, active)
+        pos = self.pos.tolist()
+        with torch.no_grad(), torch.cuda.device(self.dev):
+            self.chunk_ids.view(B, R).copy_(torch.tensor([t + [t[-1]] * (R - len(t)) if t is not None else [0] * R for t in rows], dtype=torch.int64))
+            if draft_logits is not None:
+                rows_q = self.chunk_draft_logits.view(B, R - 1, V)
+                for b, t in enumerate(rows):
+                    if t is not None:
+                        n = len(t)
+                        rows_q[b, :n - 1].copy_(draft_logits[b])
+                        if n < R:                                # a padding row's draft is a point mass: -inf everywhere but at the token
+                            rows_q[b, n - 1:].fill_(float('-inf'))
+                            rows_q[b, n - 1:, t[-1]] = 0.0
+            if not all(active):
+                self.pos.masked_fill_(torch.tensor([not x for x in active]).to(self.dev), -1)
+            self._step_chunk()
+            for buf, u in ((self.chunk_u_accept, u_accept), (self.chunk_u_draw, u_draw)):
+                if u is None:
+                    buf.uniform_()
+                else:
+                    buf.copy_(u.reshape(-1))
+            self._spec_sample_rows(draft_logits is not None)
+            res = self.verify_out.view(B, R + 1).tolist()
+            out = []
+            for b, t in enumerate(rows):
+                if t is not None:
+                    a = min(res[b][0], len(t) - 1)               # (padding rows do not count; their tokens are dropped)
+                    out.append((a, res[b][1:a + 2]))
+                    pos[b] += a + 1
+                else:
+                    out.append(None)
+            if not all(active) or any(t is not None and o[0] < r[0] for t, o, r in zip(rows, out, res)):
+                self.pos.copy_(torch.tensor(pos, dtype=torch.int64))
+        return out
+
     def verify_sample(self, tokens, draft_logits=None, u_accept=None, u_draw=None):
         """Speculative sampling of one step, eagerly.  tokens: 1-D, 2 .. R ids -- the last accepted token followed by the drafts, fed at positions
         pos .. pos + n - 1 and padded as verify pads (a step of fewer than R tokens runs as R rows; the copies of the last draft behind it can only
         be accepted after it, and what they emit is dropped).  draft_logits: [n - 1, vocab] fp16 rows the drafts were drawn from under the engine's
         setting (set_sampling), None: every draft is a point mass.  u_accept / u_draw: float32 [R] on the device; None draws them from torch's CUDA
         generator.  Returns (a, tokens): a accepted drafts and the a + 1 ids the step emits (a list of ints); pos has advanced by a + 1."""
-        self._need_chunk('verify_sample')
-        R = self.chunk
-        t = torch.as_tensor(tokens).reshape(-1)
-        n = int(t.numel())
-        if not 2 <= n <= R:
-            raise ValueError('DecodeEngine.verify_sample: 2 .. %d tokens, not %d' % (R, n))
-        if draft_logits is not None and (draft_logits.shape != (n - 1, self.chunk_logits.shape[1]) or draft_logits.dtype != torch.float16):
-            raise ValueError('DecodeEngine.verify_sample: draft_logits must be fp16 [%d, %d]' % (n - 1, self.chunk_logits.shape[1]))
-        for name, u in (('u_accept', u_accept), ('u_draw', u_draw)):
-            if u is not None and (u.dtype != torch.float32 or u.shape != (R,)):
-                raise ValueError('DecodeEngine.verify_sample: %s must be float32 [%d]' % (name, R))
-        pos = int(self.pos[0])
-        if pos + R > self.t_max:
-            raise ValueError('DecodeEngine.verify_sample: positions %d .. %d do not fit the engine cache (%d)' % (pos, pos + R - 1, self.t_max))
-        with torch.no_grad(), torch.cuda.device(self.dev):
-            t = t.to(device=self.dev, dtype=torch.int64)
-            self.chunk_ids[:n].copy_(t)
-            if n < R:
-                self.chunk_ids[n:].copy_(t[n - 1:n].expand(R - n))
-            if draft_logits is not None:
-                self.chunk_draft_logits[:n - 1].copy_(draft_logits)
-                if n < R:                                        # a padding row's draft is a point mass: -inf everywhere but at the token
-                    self.chunk_draft_logits[n - 1:].fill_(float('-inf'))
-                    self.chunk_draft_logits[n - 1:].index_fill_(1, t[n - 1:n], 0.0)
-            self._step_chunk()
-            for buf, u in ((self.chunk_u_accept, u_accept), (self.chunk_u_draw, u_draw)):
-                if u is None:
-                    buf.uniform_()
-                else:
-                    buf.copy_(u)
-            self._spec_sample_rows(draft_logits is not None)
-            res = self.verify_out.tolist()
-        a = min(res[0], n - 1)                                   # (padding rows do not count; their tokens are dropped)
-        if a < res[0]:
-            self.pos.fill_(pos + a + 1)
-        return a, res[1:a + 2]
+        self._need_spec_sample('verify_sample', False)
+        row = lambda u: u.unsqueeze(0) if torch.is_tensor(u) and u.dim() == 1 else u
+        return self._verify_sample_rows('verify_sample', [torch.as_tensor(tokens)], None if draft_logits is None else [draft_logits], row(u_accept),
+                                        row(u_draw))[0]
+
+    def verify_sample_batch(self, tokens, draft_logits=None, u_accept=None, u_draw=None):
+        """batch_chunk = R with spec_sample.  verify_sample for the B sequences in ONE step: tokens a list of B entries, entry b what verify_sample
+        takes for sequence b (2 .. R ids, padded alike) or None for a sequence that idles (nothing of its cache slot, its position or its row of
+        verify_out changes).  draft_logits: None, or a list of B fp16 tensors [n_b - 1, vocab] (an idle sequence's entry is ignored) under the
+        sequences' own settings.  u_accept / u_draw: float32 [B, R] on the device; None draws them from torch's CUDA generator.  Returns a list of
+        B entries (a_b, tokens_b), None for an idle sequence; pos[b] has advanced by a_b + 1.  ValueError, with nothing uploaded or launched: an
+        engine without spec_sample, a wrong count or shape, an active chunk that does not fit the cache."""
+        self._need_spec_sample('verify_sample_batch', True)
+        return self._verify_sample_rows('verify_sample_batch', tokens, draft_logits, u_accept, u_draw)
 
     def capture_verify_sample(self, draft_logits=False):
         """capture _verify_sample_step into ONE hipGraph: a replay verifies chunk_ids (and, draft_logits=True, reads the static chunk_draft_logits)
@@ -1234,21 +1286,33 @@ class DecodeEngine:
         self.verify_sample_graphs[bool(draft_logits)] = g
         return g
 
+    def capture_verify_sample_batch(self, draft_logits=False):
+        """batch_chunk = R with spec_sample.  capture_verify_sample for the B sequences -- the same step, the same verify_sample_graphs -- under
+        the cache contract of capture_verify_greedy_batch: only an active sequence's warm-up chunk has to fit, an idle position stays."""
+        self._need_spec_sample('capture_verify_sample_batch', True)
+        g = self._capture_verify('capture_verify_sample_batch', lambda: self._verify_sample_step(bool(draft_logits)), batched=True, keep_rng=True)
+        self.verify_sample_graphs[bool(draft_logits)] = g
+        return g
+
     def _draft_step(self, target):
-        """the self-feeding sampling step of a DRAFT engine (batch 1) in front of `target` (a chunk engine of the same vocabulary): as
-        _sample_native_step, and the step's logits row -- what the token was drawn from -- goes into row stepc of target.chunk_draft_logits"""
+        """the self-feeding sampling step of a DRAFT engine in front of `target` (a speculative-sampling engine of the same batch B and
+        vocabulary): as _sample_native_step, and the step's [B, vocab] logits -- what the tokens were drawn from -- go into draft row stepc of
+        every sequence of target.chunk_draft_logits"""
         self._step()
-        target.chunk_draft_logits.index_copy_(0, self.stepc, self.logits)
+        B, V = self.logits.shape
+        target.chunk_draft_logits.view(B, -1, V).index_copy_(1, self.stepc, self.logits.unsqueeze(1))
         self.u.uniform_()
         self.sample_logits(self.logits, out=self.ids, u=self.u)
         self.stream_rows.index_copy_(0, self.stepc, self.ids.unsqueeze(0))
         self.stepc.add_(1)
 
     def capture_draft_step(self, target):
-        """capture _draft_step once for `target`: at most target.chunk - 1 replays between two resets of stepc.  ValueError for a batch other than
-        1, a target without chunk rows, or another vocabulary."""
-        if self.batch != 1 or not target.chunk or target.chunk_draft_logits.shape[1] != self.logits.shape[1] or target.dev != self.dev:
-            raise ValueError('DecodeEngine.capture_draft_step: needs a batch-1 engine and a chunk engine of the same vocabulary on one device')
+        """capture _draft_step once for `target`: at most R - 1 replays (R the target's chunk rows) between two resets of stepc.  ValueError for
+        a target that does not sample speculatively, or of another batch, vocabulary or device."""
+        if (not getattr(target, 'spec_sample', False) or self.batch != target.batch or target.chunk_draft_logits.shape[1] != self.logits.shape[1] or
+                target.dev != self.dev):
+            raise ValueError('DecodeEngine.capture_draft_step: needs a target engine with speculative sampling, of the same batch and vocabulary, '
+                             'on one device')
         self.draft_graph = self._capture_rows(lambda: self._draft_step(target), keep_rng=True)
         return self.draft_graph
 
@@ -1393,16 +1457,16 @@ def _speculate_settings(speculate):
     return k, max_ngram, draft
 
 
-def _speculate_sampling(speculate, model):
+def _speculate_sampling(speculate, model, what='engine_generate'):
     """the keys of `speculate` that ask for speculative SAMPLING and for a draft MODEL: (sampling settings or None, draft model or None)"""
     sample, draft_model = speculate.get('sample'), speculate.get('draft_model')
-    settings = None if sample is None else _sampling_settings('engine_generate', sample)
+    settings = None if sample is None else _sampling_settings(what, sample)
     if draft_model is not None:
         if speculate.get('draft') is not None:
-            raise ValueError('engine_generate: speculate takes draft or draft_model, not both')
+            raise ValueError('%s: speculate takes draft or draft_model, not both' % what)
         dv, tv = getattr(getattr(draft_model, 'config', None), 'vocab_size', None), model.config.vocab_size
         if dv != tv:
-            raise ValueError('engine_generate: the draft model has a vocabulary of %r tokens, the model one of %d' % (dv, tv))
+            raise ValueError('%s: the draft model has a vocabulary of %r tokens, the model one of %d' % (what, dv, tv))
     return settings, draft_model
 
 
@@ -1483,10 +1547,11 @@ def engine_generate(model, input_ids, max_new_tokens, eos_token_id=None, engine=
 
 
 def _draft_model_engine(eng, draft_model, settings):
-    """the batch-1 engine of the draft model that belongs to the target engine `eng`: built and captured once (plain step, draft step), kept on eng"""
+    """the engine of the draft model that belongs to the target engine `eng`, of its batch: built and captured once (plain step, draft step), kept
+    on eng"""
     kept = eng._draft_engine
     if kept is None or kept[0] is not draft_model:
-        deng = DecodeEngine(draft_model, t_max=eng.t_max).capture()
+        deng = DecodeEngine(draft_model, t_max=eng.t_max, batch=eng.batch).capture()
         deng.capture_draft_step(eng)
         kept = eng._draft_engine = (draft_model, deng)
     deng = kept[1]
@@ -1519,26 +1584,35 @@ def _host_drafts(what, eng, k, max_ngram, draft):
     return fill
 
 
-def _model_drafts(eng, deng, k, T):
-    """the draft-MODEL source of _generate_speculative, one sequence: the batch-1 engine `deng` (prompt of T tokens in its cache) first consumes the
-    tokens it has not seen (one after a rejection, two after a full accept: plain steps), then k replays of its captured draft step consume the
-    last token and d_1 .. d_{k-1} and draw d_1 .. d_k -- chunk_ids[1:] and the rows of chunk_draft_logits are written on the device"""
-    valid = [T]                                                  # deng's position behind its last drafts: its cache is seq's up to there at most
+def _model_drafts(eng, deng, k, lens):
+    """the draft-MODEL source of _generate_speculative: the draft engine `deng` of the target's batch holds prompt b (lens[b] tokens) in cache row b.
+    Per step, the sequences whose last step accepted all k drafts first consume the one token they have not seen (d_k) in a plain step, the
+    others idling far below position 0; then every active sequence is put at its last token, and k replays of the captured draft step consume it
+    and d_1 .. d_{k-1} and draw d_1 .. d_k -- chunk_ids[:, 1:] and the rows of chunk_draft_logits are written on the device.  Finished
+    sequences idle throughout."""
+    n = len(lens)
+    valid = list(lens)                                           # deng's position behind its last drafts: row b's cache is seq b's up to there at most
+    far = -(eng.t_max + 1)                                       # (a step adds 1 to every position: still negative after the k draft steps)
 
     def fill(seqs, done):
-        seq = seqs[0]
-        L = len(seq)
-        seen = min(L - 1, valid[0])                              # tokens of seq it has consumed; behind a rejection its later rows are stale
-        deng.pos.fill_(seen)
-        for t in seq[seen:L - 1]:
-            deng.decode(t)
-        deng.ids.fill_(seq[-1])
+        L = [len(seq) for seq in seqs]
+        seen = [min(l - 1, v) for l, v in zip(L, valid)]         # tokens of seq b it has consumed; behind a rejection its later rows are stale
+        unseen = [not d and sn < l - 1 for d, sn, l in zip(done, seen, L)]
+        if any(unseen):
+            deng.pos.copy_(torch.tensor([sn if u else far for sn, u in zip(seen, unseen)], dtype=torch.int64))
+            deng.decode(torch.tensor([seq[sn] if u else 0 for seq, sn, u in zip(seqs, seen, unseen)], dtype=torch.int64))
+        last = torch.tensor([0 if d else seq[-1] for seq, d in zip(seqs, done)], dtype=torch.int64)
+        deng.pos.copy_(torch.tensor([far if d else l - 1 for l, d in zip(L, done)], dtype=torch.int64))
+        deng.ids.copy_(last)
         deng.stepc.zero_()
         for _ in range(k):
             deng.draft_graph.replay()
-        eng.chunk_ids[0:1].fill_(seq[-1])
-        eng.chunk_ids[1:].copy_(deng.stream_rows[:k, 0])
-        valid[0] = L + k - 1
+        ids = eng.chunk_ids.view(n, k + 1)
+        ids[:, 0].copy_(last)
+        ids[:, 1:].copy_(deng.stream_rows[:k].t())
+        for b in range(n):
+            if not done[b]:
+                valid[b] = L[b] + k - 1
     return fill
 
 
@@ -1587,7 +1661,7 @@ def _engine_generate_speculative(model, input_ids, max_new_tokens, eos_token_id,
     settings None: the verify-greedy graph, the first token by argmax, the capture_greedy graph (stream_out) for the tail.  settings: the
     verify-sample graph -- with the draft model's logits rows when a draft model is given, point-mass drafts otherwise --, the first token by
     sample_logits, the tail by the capture_sample_native graph.
-    draft_model: _model_drafts on a batch-1 DecodeEngine of its own, under the same setting (greedily without one); else _host_drafts.
+    draft_model: _model_drafts on a DecodeEngine of its own, under the same setting (greedily without one); else _host_drafts.
     spec_stats: emitted as an int, accepted as the flat per-step list."""
     T = input_ids.shape[1]
     with torch.no_grad():
@@ -1608,7 +1682,7 @@ def _engine_generate_speculative(model, input_ids, max_new_tokens, eos_token_id,
         first = int(logits.argmax()) if settings is None else int(eng.sample_logits(logits.to(torch.float16).contiguous())[0])
         if deng is not None:
             deng.prefill(input_ids[0], start=0)
-        drafts = _host_drafts('engine_generate', eng, k, max_ngram, draft) if deng is None else _model_drafts(eng, deng, k, T)
+        drafts = _host_drafts('engine_generate', eng, k, max_ngram, draft) if deng is None else _model_drafts(eng, deng, k, [T])
 
         def finish(seqs, left):
             seq, n = seqs[0], left[0]
@@ -1660,19 +1734,42 @@ def _engine_generate_sampled(model, input_ids, max_new_tokens, eos_token_id, eng
     return torch.cat([input_ids[0], gen.to(input_ids.dtype)]).unsqueeze(0)
 
 
-def _engine_generate_batch_speculative(prompts, max_new_tokens, eos_token_id, eng, k, max_ngram, draft):
-    """engine_generate_batch with speculation: what _generate_speculative needs for the n sequences of a batch_chunk engine -- prefill_batch, the
-    first tokens by argmax, the verify-greedy graph, _host_drafts, and the capture_greedy_rows graph for the tail, the finished rows idling
-    far below position 0.  Afterwards every position is that of the sequence's last token, the one not consumed yet."""
+def _engine_generate_batch_speculative(prompts, max_new_tokens, eos_token_id, eng, k, max_ngram, draft, settings=None, draft_model=None):
+    """engine_generate_batch with speculation: what _generate_speculative needs for the n sequences of a batch_chunk engine -- prefill_batch and
+    the tail with the finished rows idling far below position 0.
+    settings None: the first tokens by argmax, the verify-greedy graph, the capture_greedy_rows graph for the tail.  settings (one value for all
+    or one per prompt): the verify-sample graph -- with the draft model's logits rows when a draft model is given, point-mass drafts otherwise
+    --, the first tokens by sample_logits, the tail by the capture_sample_native graph.
+    draft_model: _model_drafts on a DecodeEngine of this batch, under the same settings (greedily without them); else _host_drafts.
+    Afterwards every position is that of the sequence's last token, the one not consumed yet."""
     n = len(prompts)
     with torch.no_grad():
-        if eng.verify_graph is None:
-            eng.pos.zero_()                                      # (the capture's warm-up step writes cache rows pos .. pos + R - 1 of every slot)
-            eng.capture_verify_greedy_batch()
-        if eng.greedy_rows_graph is None:
-            eng.pos.zero_()
-            eng.capture_greedy_rows()
-        first = eng.prefill_batch(prompts, starts=[0] * n).argmax(dim=-1).tolist()
+        if settings is None:
+            if eng.verify_graph is None:
+                eng.pos.zero_()                                  # (the capture's warm-up step writes cache rows pos .. pos + R - 1 of every slot)
+                eng.capture_verify_greedy_batch()
+            if eng.greedy_rows_graph is None:
+                eng.pos.zero_()
+                eng.capture_greedy_rows()
+            graph, tail = eng.verify_graph, eng.greedy_rows_graph
+        else:
+            eng.set_sampling(**settings)                         # (validates before anything changes)
+            with_q = draft_model is not None
+            if eng.verify_sample_graphs.get(with_q) is None:
+                eng.pos.zero_()
+                eng.capture_verify_sample_batch(draft_logits=with_q)
+            if eng.sample_native_graph is None:
+                eng.pos.zero_()
+                eng.capture_sample_native()
+            graph, tail = eng.verify_sample_graphs[with_q], eng.sample_native_graph
+        deng = None if draft_model is None else _draft_model_engine(eng, draft_model, settings)
+        logits = eng.prefill_batch(prompts, starts=[0] * n)
+        first = (logits.argmax(dim=-1) if settings is None else eng.sample_logits(logits.to(torch.float16).contiguous())).tolist()
+        if deng is not None:
+            deng.prefill_batch(prompts, starts=[0] * n)
+            drafts = _model_drafts(eng, deng, k, [int(p.numel()) for p in prompts])
+        else:
+            drafts = _host_drafts('engine_generate_batch', eng, k, max_ngram, draft)
 
         def finish(seqs, left):
             if max(left) <= 0:
@@ -1682,10 +1779,10 @@ def _engine_generate_batch_speculative(prompts, max_new_tokens, eos_token_id, en
             eng.ids.copy_(torch.tensor([s[-1] if m else 0 for s, m in zip(seqs, left)], dtype=torch.int64))
             eng.stepc.zero_()
             for _ in range(max(left)):
-                eng.greedy_rows_graph.replay()
+                tail.replay()
             return eng.stream_rows[:max(left)].t().tolist()      # [row][step]
         gens, eng.spec_stats = _generate_speculative(eng, [[int(t) for t in p.tolist()] for p in prompts], first, max_new_tokens, eos_token_id, k,
-                                                     eng.verify_graph, _host_drafts('engine_generate_batch', eng, k, max_ngram, draft), finish)
+                                                     graph, drafts, finish)
         eng.pos.copy_(torch.tensor([p.numel() + len(g) - 1 for p, g in zip(prompts, gens)], dtype=torch.int64))
         return [torch.cat([p, torch.tensor(g, dtype=p.dtype, device=p.device)]) for p, g in zip(prompts, gens)]
 
@@ -1700,7 +1797,7 @@ def engine_generate_batch(model, prompts, max_new_tokens, eos_token_id=None, eng
     (DecodeEngine.set_sampling; a row with temperature 0 stays greedy).  The first tokens are drawn from the prompts' logits by
     DecodeEngine.sample_logits, every further step is a replay of the capture_sample_native graph; the draws follow torch.manual_seed.  The
     settings STAY in the engine's buffers afterwards, until set_sampling is called again.
-    speculate=dict(k=4, max_ngram=3, draft=None) (every key optional, validated as engine_generate's) decodes SPECULATIVELY, greedy, at least two
+    speculate=dict(k=4, max_ngram=3, draft=None) (every key optional, validated as engine_generate's) decodes SPECULATIVELY, at least two
     prompts: per step every active sequence gets a draft of k tokens -- draft(tokens_so_far: list[int], k) -> k ids, by default
     prompt_lookup_draft -- and all sequences' chunks go through the model as ONE replay of the capture_verify_greedy_batch graph (a DecodeEngine
     with batch = len(prompts), batch_chunk = k + 1: one pass over the weights at M = batch x (k + 1)), which accepts per sequence the longest
@@ -1708,16 +1805,25 @@ def engine_generate_batch(model, prompts, max_new_tokens, eos_token_id=None, eng
     copy each per step.  A sequence that has hit its eos or its length idles; where no active sequence has two tokens left, or an active chunk no
     longer fits the cache, the capture_greedy_rows graph finishes.  Same return value and eos semantics as the greedy path;
     eng.spec_stats = dict(steps, emitted=[per sequence], accepted=[per sequence: per step]) describes the last run.
-    ValueError: speculate together with sample, or with the keys sample / draft_model (sampled batched verification is not built); k outside
-    1 .. 15; an engine passed in whose batch is not len(prompts) or whose batch_chunk is not k + 1; fewer than two prompts; unknown keys."""
+    speculate=dict(..., sample=dict(temperature, top_k, top_p)) SAMPLES speculatively, every value a scalar or one per prompt: the
+    capture_verify_sample_batch graph (an engine built with spec_sample=True) applies the accept / resample rule of gptq_spec_sample_batch_f16
+    to all sequences in one launch, so every sequence's tokens are distributed exactly as engine_generate_batch(sample=...) draws them, whatever
+    the draft; host drafts count as point masses; first tokens by sample_logits, tail by the capture_sample_native graph.
+    speculate=dict(..., draft_model=<fused model of the same vocabulary>) drafts with a MODEL: a DecodeEngine of the same batch (kept on the
+    engine) draws the k tokens of every sequence under the same settings and hands its logits rows to the verify step; without `sample` it
+    drafts greedily and the verify-greedy graph checks it.
+    ValueError: speculate together with the sample ARGUMENT; the keys sample / draft_model with an engine passed in that was built without
+    spec_sample=True; draft together with draft_model; a draft model of another vocabulary size; k outside 1 .. 15; an engine passed in whose
+    batch is not len(prompts) or whose batch_chunk is not k + 1; fewer than two prompts; unknown keys."""
     settings = None if sample is None else _sampling_settings('engine_generate_batch', sample)
     spec = None
     if speculate is not None:
         if sample is not None:
-            raise ValueError('engine_generate_batch: speculate and sample exclude each other (greedy speculation only)')
-        spec = _speculate_settings(speculate)
-        if speculate.get('sample') is not None or speculate.get('draft_model') is not None:
-            raise ValueError('engine_generate_batch: speculate takes k, max_ngram and draft only (greedy, host drafts)')
+            raise ValueError('engine_generate_batch: speculate and the sample argument exclude each other (speculative sampling: the key '
+                             'sample inside speculate)')
+        spec = _speculate_settings(speculate) + _speculate_sampling(speculate, model, 'engine_generate_batch')
+        if (spec[3] is not None or spec[4] is not None) and engine is not None and not engine.spec_sample:
+            raise ValueError('engine_generate_batch: speculate with sample or draft_model needs an engine built with spec_sample=True')
     n = len(prompts)
     if n < 1 or any((not torch.is_tensor(p)) or p.dim() != 1 or p.numel() == 0 for p in prompts):
         raise ValueError('engine_generate_batch: prompts must be a non-empty list of non-empty 1-D id tensors')
@@ -1730,7 +1836,7 @@ def engine_generate_batch(model, prompts, max_new_tokens, eos_token_id=None, eng
     if engine is not None:
         eng = engine
     elif spec is not None:
-        eng = DecodeEngine(model, t_max=t_max, batch=n, batch_chunk=spec[0] + 1)
+        eng = DecodeEngine(model, t_max=t_max, batch=n, batch_chunk=spec[0] + 1, spec_sample=spec[3] is not None or spec[4] is not None)
     else:
         eng = DecodeEngine(model, t_max=t_max, batch=n)
     if eng.batch != n:

@@ -753,6 +753,29 @@ int gptq_spec_sample_rows_f16(const void *logits, int64_t ld, const void *draft_
                               const float *temperature, const int32_t *top_k, const float *top_p, const float *u_accept, const float *u_draw,
                               int64_t *pos, int64_t *out, void *workspace, size_t workspace_bytes, gptq_stream_t stream);
 
+/* ---- batched speculative sampling: gptq_spec_sample_rows_f16 for `seqs` = B sequences of `rows` = R rows each in ONE launch, grid (R, B): workgroup
+ * (i, b) is row i of sequence b.  The same kernel -- gptq_spec_sample_rows_f16 is its B = 1 launch without the idle rule -- so per sequence the
+ * records, out and pos are bit-identical to that entry on the sequence's rows, whatever the neighbours hold and whether they idle.
+ *   logits [B R, vocab] (ld)         packed [B, R]: row b R + i is row i of sequence b.  So are ids, temperature, top_k, top_p, u_accept, u_draw
+ *   draft_logits [B (R - 1), vocab]  row b (R - 1) + i is draft row i of sequence b (ld_draft).  NULL: every draft is a point mass
+ *   pos                              device int64 [B]; pos[b] += a_b + 1 for an active sequence
+ *   t_max                            sequence b is ACTIVE iff 0 <= pos[b] < t_max (the rule of gptq_decode_attn_chunk_batch_f16).  The workgroups
+ *                                    of an idle sequence read no logits and take no ticket: out[b], pos[b] and the sequence's workspace words stay
+ *                                    as they are.  Every workgroup reads pos[b] once, before its ticket; the last arriver writes it behind the last
+ *                                    ticket, so all R workgroups of a sequence reach the same verdict
+ *   out                              device int64 [B, R + 1]: row b = [a_b, d_0 .. d_{a_b - 1}, t_a, copies of t_a]
+ *   workspace                        gptq_spec_sample_batch_workspace_bytes(B, R) = B gptq_spec_sample_workspace_bytes(R) bytes, 8-byte aligned:
+ *                                    int64 [B, R + 1], sequence b's words = [its ticket, its R records] (B = 1: the layout above).  Every ticket
+ *                                    ZERO before the first launch; each puts itself back
+ * No atomics beyond the one ticket per sequence (and the LDS atomics of the select); all sums are integer sums.
+ * Validated before the launch: GPTQ_E_NULL (any pointer but draft_logits, reported first), GPTQ_E_SHAPE (seqs < 1, seqs > 65535, rows < 2,
+ * vocab < 1, ld < vocab, ld_draft < vocab with draft logits, t_max < 1), GPTQ_E_WORKSPACE, GPTQ_E_ALIGN (as gptq_spec_sample_rows_f16). */
+size_t gptq_spec_sample_batch_workspace_bytes(int seqs, int rows);
+int gptq_spec_sample_batch_f16(const void *logits, int64_t ld, const void *draft_logits, int64_t ld_draft, int seqs, int rows, int vocab,
+                               const int64_t *ids, const float *temperature, const int32_t *top_k, const float *top_p, const float *u_accept,
+                               const float *u_draw, int64_t *pos, int64_t t_max, int64_t *out, void *workspace, size_t workspace_bytes,
+                               gptq_stream_t stream);
+
 /* ---- GPTQ solver (the caller that PRODUCES the weights; reference gptq.py:128-228) -------------------------------
  * One column block [i1, i1 + count), count <= 128, of the sequential quantise / error-feedback loop (gptq.py:177-199)
  * for all rows at once, in the reference's own fp32 arithmetic (IEEE division, round-half-even, no contraction).
