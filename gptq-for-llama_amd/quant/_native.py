@@ -182,6 +182,10 @@ _SIGNATURES = {
     'gptq_spec_sample_batch_workspace_bytes': [c_int, c_int],
     'gptq_spec_sample_batch_f16': [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                    c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_size_t, c_void_p],
+    # logit processors: penalties, bias and the min-new-tokens EOS mask in place on B R rows, grid (R, B), history append included
+    # (csrc/logits_process.hip)
+    'gptq_logits_process_f16': [c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
+                                c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p],
 }
 
 

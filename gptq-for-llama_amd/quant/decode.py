@@ -178,6 +178,7 @@ LM_HEAD_KERNEL = os.environ.get('GPTQ_LM_HEAD_KERNEL', '1') != '0'   # 0: final 
 
 MAX_BATCH = 16         # rows of a decode batch one engine serves (the LM head kernel and the decode kernel's row groups end there)
 MAX_CHUNK_ROWS = 128   # rows of a batched verify step (batch x batch_chunk): what gptq_layer_decode_f16 and the batched chunk attention take
+MAX_PROCESS_EOS, MAX_PROCESS_BIAS, MAX_PROCESS_VOCAB = 8, 256, 131072      # GPTQ_LOGITS_PROCESS_MAX_EOS / _BIAS / _VOCAB
 
 
 def lm_head_logits(eng, x, logits, s, h=None):
@@ -210,8 +211,14 @@ def lm_head_logits(eng, x, logits, s, h=None):
 
 class DecodeEngine:
 
-    def __init__(self, model, t_max=2048, fuse_norm=True, fuse_attn=True, batch=1, chunk=0, batch_chunk=0, spec_sample=False):
-        """chunk = R or batch_chunk = R (2 .. 16) adds the VERIFY step of speculative decoding: R consecutive tokens of each of the B = batch
+    def __init__(self, model, t_max=2048, fuse_norm=True, fuse_attn=True, batch=1, chunk=0, batch_chunk=0, spec_sample=False, logits_process=False):
+        """logits_process = True adds the LOGIT PROCESSORS (gptq_logits_process_f16: repetition / presence penalty, logit bias, the
+        min-new-tokens EOS mask) to every step: hist int32 [B, t_max] -- hist[b, p] = the token row b consumed at position p, kept by the prompt
+        calls and by the process launch itself --, gen_start int64 [B], rep_penalty / presence_penalty float [B], min_new int32 [B], eos_ids
+        int32 [8], bias_ids / bias_vals [256] with their counts on the host (set_logits_process, set_history, process_logits).  decode(token)
+        and every self-feeding step then return / draw from PROCESSED logits.  False (the default) allocates nothing and changes no step.
+        ValueError together with chunk / batch_chunk: processors under speculation are not built yet (the kernel takes R > 1 rows already).
+        chunk = R or batch_chunk = R (2 .. 16) adds the VERIFY step of speculative decoding: R consecutive tokens of each of the B = batch
         sequences -- the last accepted token and R - 1 drafts -- go through every layer at M = B R in one pass over the weights; attention by
         gptq_decode_attn_chunk_batch_f16 -- two launches for all sequences -- on every sequence's own cache slice and position.  It is ONE
         mechanism (_chunk_buffers, _step_chunk, _verify_greedy_step, one graph) with two entry points that differ in the shapes they show:
@@ -246,6 +253,9 @@ class DecodeEngine:
         if spec_sample and not (self.chunk or self.batch_chunk):
             raise ValueError('DecodeEngine: spec_sample needs batch_chunk = R (a chunk engine always samples speculatively)')
         self.spec_sample = bool(spec_sample or self.chunk)
+        self.logits_process = bool(logits_process)
+        if self.logits_process and (self.chunk or self.batch_chunk):
+            raise ValueError('DecodeEngine: logits_process together with chunk / batch_chunk is not built yet (processors under speculation)')
         self.fuse_norm, self.fuse_attn = bool(fuse_norm), bool(fuse_attn)
         self.native = _native
         self.lib = _native.lib()
@@ -296,6 +306,19 @@ class DecodeEngine:
         self.top_k = torch.zeros(B, dtype=torch.int32, device=dev)
         self.top_p = torch.ones(B, dtype=torch.float32, device=dev)
         self.sample_native_graph = None
+        if self.logits_process:
+            # gptq_logits_process_f16: the rows' token history and settings, read by the kernel at every replay (set_logits_process)
+            if self.logits.shape[1] > MAX_PROCESS_VOCAB:
+                raise NotImplementedError('DecodeEngine: logits_process takes vocabularies up to %d' % MAX_PROCESS_VOCAB)
+            self.hist = torch.zeros((B, self.t_max), dtype=torch.int32, device=dev)
+            self.gen_start = torch.zeros(B, dtype=torch.int64, device=dev)
+            self.rep_penalty = torch.ones(B, dtype=torch.float32, device=dev)
+            self.presence_penalty = torch.zeros(B, dtype=torch.float32, device=dev)
+            self.min_new = torch.zeros(B, dtype=torch.int32, device=dev)
+            self.eos_ids = torch.zeros(MAX_PROCESS_EOS, dtype=torch.int32, device=dev)
+            self.bias_ids = torch.zeros(MAX_PROCESS_BIAS, dtype=torch.int32, device=dev)
+            self.bias_vals = torch.zeros(MAX_PROCESS_BIAS, dtype=torch.float32, device=dev)
+            self.n_eos, self.n_bias = 0, 0                  # launch arguments: a captured step holds the counts it was captured with
         nl = len(self.layers)
         self.kcb = torch.zeros((nl, B, self.t_max, H), **f16)          # [layer][row][t][heads * head_dim]
         self.vcb = torch.zeros((nl, B, self.t_max, H), **f16)
@@ -631,6 +654,7 @@ class DecodeEngine:
         """one decode step whose argmax becomes the next input token, entirely on the device: ids <- argmax(logits),
         and the choice is appended to stream_out[pos] (pos = number of tokens consumed so far)."""
         self._step()                                   # consumes self.ids, advances pos
+        self._process_step()
         torch.argmax(self.logits, dim=-1, out=self.ids)
         self.stream_out.index_copy_(0, self.pos, self.ids)
 
@@ -678,6 +702,7 @@ class DecodeEngine:
         """the self-feeding greedy step for ANY batch: every row's argmax becomes its next input token, and the choices of step n are row n of
         stream_rows (n = stepc, a device counter the step advances itself)"""
         self._step()
+        self._process_step()
         torch.argmax(self.logits, dim=-1, out=self.ids)
         self.stream_rows.index_copy_(0, self.stepc, self.ids.unsqueeze(0))
         self.stepc.add_(1)
@@ -691,6 +716,7 @@ class DecodeEngine:
         """the self-feeding SAMPLING step: HF's own arithmetic on the step's logits (generation/utils.py `_sample`: fp32 copy, the warpers in HF's order,
         softmax, torch.multinomial) -- inside the graph, where the default generator's Philox offset advances per replay exactly as per eager call"""
         self._step()
+        self._process_step()
         scores = self.logits.to(copy=True, dtype=torch.float32)
         for w in warpers:
             scores = w(None, scores)
@@ -762,9 +788,12 @@ class DecodeEngine:
     def _sample_native_step(self):
         """the self-feeding sampling step of the engine's own, for ANY batch: one decode step, fresh uniforms from torch's CUDA generator (inside a
         graph its Philox offset advances per replay exactly as per eager call), ONE launch that draws every row's next token under that row's
-        setting, and the bookkeeping of _greedy_rows_step."""
+        setting, and the bookkeeping of _greedy_rows_step.  With logits_process the ONE process launch sits between the step and the uniforms:
+        the row's token history -- the token just consumed included, appended by that launch -- edits self.logits in place before the draw;
+        temperature 0 (set_sampling) makes this graph the greedy step under the processors."""
         self._stream_buffers()
         self._step()
+        self._process_step()
         self.u.uniform_()
         self.sample_logits(self.logits, out=self.ids, u=self.u)
         self.stream_rows.index_copy_(0, self.stepc, self.ids.unsqueeze(0))
@@ -775,6 +804,117 @@ class DecodeEngine:
         The generator's state is put back behind the warm-up run, as capture_sample_rows does."""
         self.sample_native_graph = self._capture_rows(self._sample_native_step, keep_rng=True)
         return self.sample_native_graph
+
+    # -- logit processors: gptq_logits_process_f16 (csrc/logits_process.hip) on the rows' token history, every setting in device memory ---------
+    def _need_logits_process(self, what):
+        if not self.logits_process:
+            raise ValueError('DecodeEngine.%s: the engine was built without logits_process=True' % what)
+
+    def set_logits_process(self, repetition_penalty=1.0, presence_penalty=0.0, min_new_tokens=0, eos_token_id=None, logit_bias=None):
+        """the rows' processor settings.  repetition_penalty (finite, > 0; 1 is off: HF's rule, the prompt counts), presence_penalty (finite;
+        subtracted once from every token GENERATED so far) and min_new_tokens (an int >= 0: no eos token before that many generated ones) are
+        a scalar for all rows or one value per row.  eos_token_id: None, an int or up to 8 ints -- what min_new_tokens masks.  logit_bias:
+        None or {id: value} of at most 256 distinct ids in [0, vocab), values finite or -inf (-inf bans the token); added AFTER the
+        penalties, shared by all rows.  Every call sets all five.  Only the static device buffers change -- a captured step serves the new
+        values at its next replay -- EXCEPT the two list lengths, which are launch arguments: a call that changes the number of eos ids or of
+        bias entries drops the captured self-feeding graphs (capture_sample_native, capture_greedy, capture_greedy_rows,
+        capture_sample_rows), which are captured again at their next use.  ValueError before anything changes."""
+        self._need_logits_process('set_logits_process')
+        B, V = self.batch, self.logits.shape[1]
+
+        def per_row(name, v, ok):
+            vals = [v] * B if not isinstance(v, (list, tuple)) and not torch.is_tensor(v) else [x for x in (v.tolist() if torch.is_tensor(v) else v)]
+            if len(vals) != B:
+                raise ValueError('DecodeEngine.set_logits_process: %s has %d values for a batch of %d' % (name, len(vals), B))
+            for x in vals:
+                if isinstance(x, bool) or not isinstance(x, (int, float)) or not ok(x):
+                    raise ValueError('DecodeEngine.set_logits_process: %s = %r' % (name, x))
+            return vals
+        rp = per_row('repetition_penalty', repetition_penalty, lambda x: math.isfinite(x) and x > 0)
+        pp = per_row('presence_penalty', presence_penalty, math.isfinite)
+        mn = per_row('min_new_tokens', min_new_tokens, lambda x: float(x).is_integer() and 0 <= x < 2 ** 31)
+        eos = [] if eos_token_id is None else (eos_token_id.tolist() if torch.is_tensor(eos_token_id) else eos_token_id)
+        eos = list(eos) if isinstance(eos, (list, tuple)) else [eos]
+        if len(eos) > MAX_PROCESS_EOS or any(isinstance(e, bool) or not isinstance(e, int) or not -2 ** 31 <= e < 2 ** 31 for e in eos):
+            raise ValueError('DecodeEngine.set_logits_process: eos_token_id must be an int or up to %d ints, not %r' % (MAX_PROCESS_EOS, eos_token_id))
+        pairs = [] if logit_bias is None else (list(logit_bias.items()) if isinstance(logit_bias, dict) else logit_bias)
+        if not isinstance(pairs, (list, tuple)) or len(pairs) > MAX_PROCESS_BIAS or any(not isinstance(e, (list, tuple)) or len(e) != 2 for e in pairs):
+            raise ValueError('DecodeEngine.set_logits_process: logit_bias must be a dict {id: value} (or a list of (id, value) pairs) of at most '
+                             '%d entries' % MAX_PROCESS_BIAS)
+        ids, bias = [], {}
+        for k, x in pairs:
+            if isinstance(k, bool) or not isinstance(k, int) or not 0 <= k < V:
+                raise ValueError('DecodeEngine.set_logits_process: logit_bias id %r outside [0, %d)' % (k, V))
+            if isinstance(x, bool) or not isinstance(x, (int, float)) or not (math.isfinite(x) or x == -math.inf):
+                raise ValueError('DecodeEngine.set_logits_process: logit_bias[%d] = %r must be finite or -inf' % (k, x))
+            if k in bias:                                    # (the kernel gives every entry its own thread: one entry per token)
+                raise ValueError('DecodeEngine.set_logits_process: logit_bias id %d is listed twice' % k)
+            ids.append(k)
+            bias[k] = x
+        with torch.no_grad():
+            self.rep_penalty.copy_(torch.tensor(rp, dtype=torch.float32))
+            self.presence_penalty.copy_(torch.tensor(pp, dtype=torch.float32))
+            self.min_new.copy_(torch.tensor([int(x) for x in mn], dtype=torch.int32))
+            if eos:
+                self.eos_ids[:len(eos)].copy_(torch.tensor(eos, dtype=torch.int32))
+            if ids:
+                self.bias_ids[:len(ids)].copy_(torch.tensor(ids, dtype=torch.int32))
+                self.bias_vals[:len(ids)].copy_(torch.tensor([float(bias[k]) for k in ids], dtype=torch.float32))
+        if (len(eos), len(ids)) != (self.n_eos, self.n_bias):
+            self.n_eos, self.n_bias = len(eos), len(ids)
+            self.sample_native_graph, self.greedy_graph, self.greedy_rows_graph, self.sample_graphs = None, None, None, {}
+        return self
+
+    def _write_history(self, row, start, ids):
+        """hist[row, start : start + T] = ids and gen_start[row] = start + T: what every prompt path does behind its layers"""
+        T = int(ids.numel())
+        self.hist[row, start:start + T].copy_(ids.reshape(-1))
+        self.gen_start[row:row + 1].fill_(start + T)
+
+    def set_history(self, row, ids, gen_start=None):
+        """for callers that fill cache row `row` by other means than prefill / prefill_batch / decode: ids (1-D, T <= t_max) are the tokens at
+        positions 0 .. T - 1 of that row, gen_start (default T) the first position that counts as generated.  pos is not touched."""
+        self._need_logits_process('set_history')
+        row, T = int(row), int(ids.numel())
+        if not 0 <= row < self.batch or ids.dim() != 1 or not 1 <= T <= self.t_max:
+            raise ValueError('DecodeEngine.set_history: needs a row of the batch of %d and 1 .. %d ids' % (self.batch, self.t_max))
+        with torch.no_grad():
+            self._write_history(row, 0, ids)
+            if gen_start is not None:
+                self.gen_start[row:row + 1].fill_(int(gen_start))
+        return self
+
+    def _process_launch(self, logits, n, last, len_add):
+        with self.native.on_device(self.dev):
+            rc = self.lib.gptq_logits_process_f16(
+                logits.data_ptr(), logits.stride(0) if n > 1 else logits.shape[1], n, 1, logits.shape[1], self.hist.data_ptr(), self.hist.stride(0),
+                self.t_max, self.native.ptr(last), self.pos.data_ptr(), len_add, self.gen_start.data_ptr(), self.rep_penalty.data_ptr(),
+                self.presence_penalty.data_ptr(), self.min_new.data_ptr(), self.eos_ids.data_ptr(), self.n_eos, self.bias_ids.data_ptr(),
+                self.bias_vals.data_ptr(), self.n_bias, self.native.stream_ptr(self.dev))
+        self.native.check(rc, 'gptq_logits_process_f16')
+
+    def _process_step(self):
+        """behind _step() (pos is advanced already: len_add = -1): the processors on self.logits under every row's history INCLUDING the token
+        this step consumed (self.ids), which the same launch appends to hist.  A row idling at a negative position, or past the cache, is
+        left alone.  Nothing without the flag."""
+        if self.logits_process:
+            self._process_launch(self.logits, self.batch, self.ids, -1)
+
+    def process_logits(self, logits, last=None):
+        """the eager counterpart of sample_logits: rows 0 .. n - 1 of `logits` ([n, vocab] or [vocab] fp16 on the engine's device, unit column
+        stride, n <= batch) IN PLACE under those rows' settings (set_logits_process) and their history hist[b, 0 : pos[b]] -- what the first
+        token after a prompt needs.  last: int64 [n] on the device, tokens consumed at positions pos[b] that hist does not hold yet: they
+        count, and are appended at hist[b, pos[b]].  Returns logits."""
+        self._need_logits_process('process_logits')
+        rows = logits.unsqueeze(0) if logits.dim() == 1 else logits
+        n = rows.shape[0] if rows.dim() == 2 else 0
+        if not 1 <= n <= self.batch or rows.dtype != torch.float16 or rows.device != self.ids.device or rows.stride(1) != 1 or \
+                not 1 <= rows.shape[1] <= MAX_PROCESS_VOCAB:
+            raise ValueError('DecodeEngine.process_logits: logits must be fp16 [n <= %d, vocab] with unit column stride on %s' % (self.batch, self.dev))
+        if last is not None and (last.dtype != torch.int64 or last.device != self.ids.device or last.shape != (n,) or not last.is_contiguous()):
+            raise ValueError('DecodeEngine.process_logits: last must be a contiguous int64 [%d] on %s' % (n, self.dev))
+        self._process_launch(rows, n, last, 0)
+        return logits
 
     def capture(self):
         """warm up once (module loads, workspace), then capture one decode step into a hipGraph."""
@@ -858,7 +998,10 @@ class DecodeEngine:
                                                    ab.data_ptr(), ab.stride(0), ws.data_ptr(), ws.numel(), self.heads, self.head_dim, self.t_max,
                                                    L['theta'], self.scale, self.native.ptr(tab), s)
                 self.native.check(rc, 'gptq_prompt_attn_f16')
-            x, _ = self._prompt_layers(ids.to(device=self.dev, dtype=torch.int64), attn, s)
+            ids = ids.to(device=self.dev, dtype=torch.int64)
+            x, _ = self._prompt_layers(ids, attn, s)
+            if self.logits_process:
+                self._write_history(row, start, ids)
             return self._head_rows(x[T - 1:T], row, start + T, s)
 
     def _packed(self, what, prompts, rows, starts, max_rows, score=False, one_row=False):
@@ -938,6 +1081,9 @@ class DecodeEngine:
                     self._norm_rows(x, self.final_norm, h, s)                       # all rows: the model's final norm in front of the head
                     self._nll_rows(h, targets[p0:p0 + M], nll[p0:p0 + M], s)
             new_pos = [st + T for st, T in zip(starts, lens)]
+            if self.logits_process:
+                for i in range(n):
+                    self._write_history(rows[i], starts[i], ids[offs[i]:offs[i] + lens[i]])
             logits = self._head_rows(last, rows[0], new_pos[0], s) if one_row else self._head_rows(last, rows, new_pos, s)
         return logits, nll, offs, lens
 
@@ -1317,7 +1463,8 @@ class DecodeEngine:
         return self.draft_graph
 
     def decode(self, token):
-        """one token per row in ([batch] ids), logits [batch, vocab] out (the static buffer: clone it to keep it)."""
+        """one token per row in ([batch] ids), logits [batch, vocab] out (the static buffer: clone it to keep it).  An engine built with
+        logits_process=True returns the PROCESSED logits (set_logits_process) and appends the tokens to its history."""
         if torch.is_tensor(token):
             self.ids.copy_(token.reshape(self.batch))
         else:
@@ -1327,6 +1474,7 @@ class DecodeEngine:
                 self.graph.replay()
             else:
                 self._step()
+            self._process_step()
         return self.logits
 
 
@@ -1385,6 +1533,8 @@ def _prompt_into_engine(model, input_ids, eng, prefill):
         eng.kc[li, :T].copy_(k[0].transpose(0, 1).reshape(T, -1))
         eng.vc[li, :T].copy_(v[0].transpose(0, 1).reshape(T, -1))
     eng.pos.fill_(T)
+    if eng.logits_process:
+        eng.set_history(0, input_ids[0])
     return out.logits[0, -1]
 
 
@@ -1401,10 +1551,26 @@ def _sampling_settings(what, sample):
     """the `sample` argument of engine_generate / engine_generate_batch as keywords of DecodeEngine.set_sampling (which validates the values)"""
     if not isinstance(sample, dict):
         raise ValueError('%s: sample must be None or a dict with the keys temperature, top_k, top_p' % what)
-    unknown = sorted(set(sample) - {'temperature', 'top_k', 'top_p'})
+    unknown = sorted(set(sample) - {'temperature', 'top_k', 'top_p'} - set(_PROCESS_NEUTRAL))
     if unknown:
         raise ValueError('%s: unknown sampling keys %r' % (what, unknown))
-    return dict(sample)
+    return {k: v for k, v in sample.items() if k not in _PROCESS_NEUTRAL}
+
+
+_PROCESS_NEUTRAL = dict(repetition_penalty=1.0, presence_penalty=0.0, min_new_tokens=0, logit_bias=None)
+
+
+def _process_settings(sample):
+    """the logit-processor keys of the `sample` argument as keywords of DecodeEngine.set_logits_process (which validates the values), or None
+    when every one of them is absent or neutral (1.0, 0.0, 0, None / empty -- also as one neutral value per prompt): then nothing is processed"""
+    def neutral(k, v):
+        if k == 'logit_bias':
+            return v is None or (isinstance(v, (dict, list, tuple)) and len(v) == 0)
+        vals = v.tolist() if torch.is_tensor(v) else v
+        vals = list(vals) if isinstance(vals, (list, tuple)) else [vals]
+        return all(isinstance(x, (int, float)) and not isinstance(x, bool) and x == _PROCESS_NEUTRAL[k] for x in vals)
+    keys = {k: sample[k] for k in _PROCESS_NEUTRAL if k in sample}
+    return None if all(neutral(k, v) for k, v in keys.items()) else keys
 
 
 def prompt_lookup_draft(tokens, k, max_ngram=3):
@@ -1461,6 +1627,9 @@ def _speculate_sampling(speculate, model, what='engine_generate'):
     """the keys of `speculate` that ask for speculative SAMPLING and for a draft MODEL: (sampling settings or None, draft model or None)"""
     sample, draft_model = speculate.get('sample'), speculate.get('draft_model')
     settings = None if sample is None else _sampling_settings(what, sample)
+    if sample is not None and _process_settings(sample) is not None:
+        raise ValueError('%s: logit processors (%s) under speculate= are not built yet: the verify step does not apply them' % (
+            what, ', '.join(sorted(_PROCESS_NEUTRAL))))
     if draft_model is not None:
         if speculate.get('draft') is not None:
             raise ValueError('%s: speculate takes draft or draft_model, not both' % what)
@@ -1483,6 +1652,13 @@ def engine_generate(model, input_ids, max_new_tokens, eos_token_id=None, engine=
     (llama_inference.py:119-127): the first token is drawn from the prompt's logits by DecodeEngine.sample_logits, every further one by a replay of
     the capture_sample_native graph; the draws follow torch.manual_seed.  temperature 0 gives the greedy tokens.  The settings STAY in the engine's
     buffers afterwards: a later eng.sample_logits(...) or a replay of the native graph uses them until set_sampling is called again.
+    The same dict takes the LOGIT PROCESSORS repetition_penalty, presence_penalty, min_new_tokens and logit_bias
+    (DecodeEngine.set_logits_process; eos_token_id of this call is what min_new_tokens masks).  The prompt counts for repetition_penalty (HF's
+    rule), only generated tokens for presence_penalty; they act before temperature, top-k and top-p.  With any of them non-neutral the engine is
+    built with logits_process=True (one passed in without the flag: ValueError), the first token is process_logits then sample_logits, and
+    the tail is the same native graph with one more launch per step; temperature 0 gives the greedy tokens under the processors.  All
+    neutral (1.0, 0.0, 0, None) is exactly the call without the keys: the same tokens for a seed and no process launch.  Inside
+    speculate=dict(sample=...) a non-neutral processor key is a ValueError: processors under speculation are not built yet.
     speculate=dict(k=4, max_ngram=3, draft=None) (every key optional) decodes SPECULATIVELY, greedy: per step a draft of k tokens -- from
     draft(tokens_so_far: list[int], k) -> k ids, by default prompt_lookup_draft -- goes through the model together with the last token as ONE
     replay of the capture_verify_greedy graph (a DecodeEngine with chunk = k + 1: one pass over the weights), which accepts the longest prefix the
@@ -1501,6 +1677,7 @@ def engine_generate(model, input_ids, max_new_tokens, eos_token_id=None, engine=
     if prefill not in ('hf', 'engine'):
         raise ValueError("engine_generate: prefill must be 'hf' or 'engine', not %r" % (prefill,))
     settings = None if sample is None else _sampling_settings('engine_generate', sample)
+    proc = None if sample is None else _process_settings(sample)
     spec = None
     if speculate is not None:
         if sample is not None:
@@ -1515,10 +1692,12 @@ def engine_generate(model, input_ids, max_new_tokens, eos_token_id=None, engine=
     T = input_ids.shape[1]
     if engine is not None:
         eng = engine
+        if proc is not None and not eng.logits_process:
+            raise ValueError('engine_generate: %s need an engine built with logits_process=True' % ', '.join(sorted(proc)))
     elif spec is not None:
         eng = DecodeEngine(model, t_max=t_max, chunk=spec[0] + 1)
     else:
-        eng = DecodeEngine(model, t_max=t_max).capture()
+        eng = DecodeEngine(model, t_max=t_max, logits_process=proc is not None).capture()
     if T + max_new_tokens > eng.t_max:
         raise ValueError('engine_generate: prompt + max_new_tokens exceeds the engine cache (%d)' % eng.t_max)
     if spec is not None:
@@ -1527,6 +1706,8 @@ def engine_generate(model, input_ids, max_new_tokens, eos_token_id=None, engine=
         if eng.batch != 1:
             raise ValueError('engine_generate: sampling needs an engine of batch 1')
         eng.set_sampling(**settings)
+        if eng.logits_process:                               # (an engine passed in with the flag, neutral keys: its processors are switched off)
+            eng.set_logits_process(eos_token_id=eos_token_id, **(proc or {}))
         return _engine_generate_sampled(model, input_ids, max_new_tokens, eos_token_id, eng, prefill)
     with torch.no_grad():
         first = _prompt_into_engine(model, input_ids, eng, prefill).argmax().reshape(1)
@@ -1718,6 +1899,8 @@ def _engine_generate_sampled(model, input_ids, max_new_tokens, eos_token_id, eng
             eng.pos.zero_()                                      # (the capture's warm-up step writes cache row pos -- and the logits buffer)
             eng.capture_sample_native()
         logits = _prompt_into_engine(model, input_ids, eng, prefill).to(torch.float16).contiguous()
+        if eng.logits_process:
+            eng.process_logits(logits)
         first = eng.sample_logits(logits)
         eng.ids.copy_(first)
         eng.stepc.zero_()                                        # stream_rows[k] = the token chosen by replay k
@@ -1797,6 +1980,10 @@ def engine_generate_batch(model, prompts, max_new_tokens, eos_token_id=None, eng
     (DecodeEngine.set_sampling; a row with temperature 0 stays greedy).  The first tokens are drawn from the prompts' logits by
     DecodeEngine.sample_logits, every further step is a replay of the capture_sample_native graph; the draws follow torch.manual_seed.  The
     settings STAY in the engine's buffers afterwards, until set_sampling is called again.
+    The same dict takes the logit processors repetition_penalty, presence_penalty, min_new_tokens (each a scalar or one value per prompt) and
+    logit_bias (one dict for all), as engine_generate's: an engine with logits_process=True, process_logits ahead of the first draw, one more
+    launch per step of the native graph; the prompts are pad-free here, so every row's history is its own prompt and tokens.  A row that has
+    emitted its eos keeps stepping, as without processors, and disturbs no other row.
     speculate=dict(k=4, max_ngram=3, draft=None) (every key optional, validated as engine_generate's) decodes SPECULATIVELY, at least two
     prompts: per step every active sequence gets a draft of k tokens -- draft(tokens_so_far: list[int], k) -> k ids, by default
     prompt_lookup_draft -- and all sequences' chunks go through the model as ONE replay of the capture_verify_greedy_batch graph (a DecodeEngine
@@ -1816,6 +2003,7 @@ def engine_generate_batch(model, prompts, max_new_tokens, eos_token_id=None, eng
     spec_sample=True; draft together with draft_model; a draft model of another vocabulary size; k outside 1 .. 15; an engine passed in whose
     batch is not len(prompts) or whose batch_chunk is not k + 1; fewer than two prompts; unknown keys."""
     settings = None if sample is None else _sampling_settings('engine_generate_batch', sample)
+    proc = None if sample is None else _process_settings(sample)
     spec = None
     if speculate is not None:
         if sample is not None:
@@ -1835,10 +2023,12 @@ def engine_generate_batch(model, prompts, max_new_tokens, eos_token_id=None, eng
                          '%d, batch_chunk %d)' % (spec[0], n, n, spec[0] + 1, engine.batch, engine.batch_chunk))
     if engine is not None:
         eng = engine
+        if proc is not None and not eng.logits_process:
+            raise ValueError('engine_generate_batch: %s need an engine built with logits_process=True' % ', '.join(sorted(proc)))
     elif spec is not None:
         eng = DecodeEngine(model, t_max=t_max, batch=n, batch_chunk=spec[0] + 1, spec_sample=spec[3] is not None or spec[4] is not None)
     else:
-        eng = DecodeEngine(model, t_max=t_max, batch=n)
+        eng = DecodeEngine(model, t_max=t_max, batch=n, logits_process=proc is not None)
     if eng.batch != n:
         raise ValueError('engine_generate_batch: %d prompts for an engine of batch %d' % (n, eng.batch))
     if max(int(p.numel()) for p in prompts) + max_new_tokens > eng.t_max:
@@ -1847,13 +2037,18 @@ def engine_generate_batch(model, prompts, max_new_tokens, eos_token_id=None, eng
         return _engine_generate_batch_speculative(prompts, max_new_tokens, eos_token_id, eng, *spec)
     if settings is not None:
         eng.set_sampling(**settings)
+        if eng.logits_process:                               # (an engine passed in with the flag, neutral keys: its processors are switched off)
+            eng.set_logits_process(eos_token_id=eos_token_id, **(proc or {}))
     with torch.no_grad():
         if settings is not None:
             if eng.sample_native_graph is None:
                 eng.pos.zero_()
                 eng.capture_sample_native()
             graph = eng.sample_native_graph
-            first = eng.sample_logits(eng.prefill_batch(prompts, starts=[0] * n))
+            logits = eng.prefill_batch(prompts, starts=[0] * n)
+            if eng.logits_process:
+                eng.process_logits(logits)
+            first = eng.sample_logits(logits)
         else:
             if eng.greedy_rows_graph is None:
                 eng.pos.zero_()                                  # (the capture's warm-up step writes cache row pos of every row)

@@ -776,6 +776,43 @@ int gptq_spec_sample_batch_f16(const void *logits, int64_t ld, const void *draft
                                const float *u_draw, int64_t *pos, int64_t t_max, int64_t *out, void *workspace, size_t workspace_bytes,
                                gptq_stream_t stream);
 
+/* ---- logit processors: repetition / presence penalty, logit bias and the min-new-tokens EOS mask, applied IN PLACE to rows of fp16 logits ahead
+ * of the sampler, in ONE launch (csrc/logits_process.hip), grid (R, B): workgroup (i, b) edits row b R + i under sequence b's settings and token
+ * history.  Every per-sequence setting is in device memory: a captured graph serves any setting.  No workspace, no global atomics: the same inputs
+ * give the same bits on every call.
+ *   logits [B R, vocab] (ld)     fp16, in place; 2-byte alignment only (ld = 32001 is fine), ld >= vocab
+ *   hist [B, ld_hist]            device int32: hist[b, p] = the token sequence b consumed at position p; t_hist <= ld_hist positions can be held
+ *   last                         device int64 [B R] or NULL: the tokens consumed by THIS step
+ *   len, len_add                 device int64 [B] and a scalar: n_b = len[b] + len_add.  The history of row (i, b) is hist[b, 0 : n_b] followed by
+ *                                last[b R + 0 .. i]; without `last` it is hist[b, 0 : n_b + i].  n = its length
+ *   gen_start                    device int64 [B]: positions below it are the prompt
+ *   repetition_penalty, presence_penalty   device float [B];  min_new_tokens device int32 [B]
+ *   eos_ids, n_eos               device int32 [n_eos], 0 <= n_eos <= GPTQ_LOGITS_PROCESS_MAX_EOS, shared by all sequences
+ *   bias_ids, bias_vals, n_bias  device int32 / float [n_bias], 0 <= n_bias <= GPTQ_LOGITS_PROCESS_MAX_BIAS, shared by all sequences; the ids
+ *                                must be DISTINCT (the caller's duty)
+ * Append: with `last`, workgroup (i, b) also writes hist[b, n_b + i] = (int32) last[b R + i]; its siblings read those tokens from `last`, never from
+ * hist, so no workgroup reads a hist word another one writes in the same launch.
+ * Idle: a row with n_b < 0 or n > t_hist is left untouched and writes nothing (finished rows of a batch, an exhausted cache).
+ * One row: S = the ids of its history that lie in [0, vocab) (others are ignored), G = those of S found at a position >= gen_start[b].
+ *   sanitising   repetition_penalty not finite or <= 0: 1 (off).  presence_penalty NaN: 0.  min_new_tokens <= 0: off.
+ *   1 penalties  every v in S, in fp32 from the fp16 logit l, rounded to fp16 ONCE (nearest even): x = l < 0 ? l rp : l / rp (an IEEE division; -0 is
+ *                not < 0 -- the arithmetic of HF's RepetitionPenaltyLogitsProcessor), and for v in G: x -= presence_penalty
+ *   2 bias       every listed id in [0, vocab): l = fp16(float(l) + bias), on what step 1 stored (a second rounding).  -inf bans the token
+ *   3 EOS mask   if n - gen_start[b] < min_new_tokens[b]: every eos_ids[j] in [0, vocab) becomes fp16 -inf (HF's MinNewTokensLengthLogitsProcessor)
+ * NaN and +-inf follow IEEE through these operations.  Nothing else of the row is written.
+ * Validated before the launch: GPTQ_E_NULL first (any pointer but `last`, and but eos_ids / bias_ids / bias_vals when their count is not
+ * positive), GPTQ_E_SHAPE (B < 1, B > 65535, R < 1, R > GPTQ_LOGITS_PROCESS_MAX_ROWS, vocab < 1, vocab > GPTQ_LOGITS_PROCESS_MAX_VOCAB -- the two
+ * bitmaps are 32 KiB of LDS there --, ld < vocab, t_hist < 1, ld_hist < t_hist, n_eos or n_bias outside their range), GPTQ_E_ALIGN (logits 2 bytes,
+ * int32 / float arrays 4, int64 arrays 8). */
+#define GPTQ_LOGITS_PROCESS_MAX_ROWS 16
+#define GPTQ_LOGITS_PROCESS_MAX_EOS 8
+#define GPTQ_LOGITS_PROCESS_MAX_BIAS 256
+#define GPTQ_LOGITS_PROCESS_MAX_VOCAB 131072
+int gptq_logits_process_f16(void *logits, int64_t ld, int seqs, int rows, int vocab, int32_t *hist, int64_t ld_hist, int64_t t_hist,
+                            const int64_t *last, const int64_t *len, int64_t len_add, const int64_t *gen_start, const float *repetition_penalty,
+                            const float *presence_penalty, const int32_t *min_new_tokens, const int32_t *eos_ids, int n_eos,
+                            const int32_t *bias_ids, const float *bias_vals, int n_bias, gptq_stream_t stream);
+
 /* ---- GPTQ solver (the caller that PRODUCES the weights; reference gptq.py:128-228) -------------------------------
  * One column block [i1, i1 + count), count <= 128, of the sequential quantise / error-feedback loop (gptq.py:177-199)
  * for all rows at once, in the reference's own fp32 arithmetic (IEEE division, round-half-even, no contraction).
