@@ -7,6 +7,7 @@ performs (llama_inference.py:27-72): ``make_quant_linear`` on every decoder line
 fp16, :46-48), then ``make_quant_attn``, ``make_quant_norm``, ``make_fused_mlp``.  The packed
 buffers are filled with the synthetic distribution of SURVEY 8(d) directly on the GPU.
 """
+import functools
 import math
 import time
 
@@ -698,14 +699,19 @@ class DecodeEngine:
         self.stepc.zero_()
         return self._capture(step, (self.pos, self.ids, self.stepc), keep_rng)
 
-    def _greedy_rows_step(self):
-        """the self-feeding greedy step for ANY batch: every row's argmax becomes its next input token, and the choices of step n are row n of
-        stream_rows (n = stepc, a device counter the step advances itself)"""
+    def _self_feeding_step(self, choose):
+        """THE self-feeding step, for any batch: one decode step, the processors (nothing without the flag), choose() puts every row's next input
+        token into self.ids, and the choices of step n become row n of stream_rows (n = stepc, a device counter the step advances itself)"""
+        self._stream_buffers()
         self._step()
         self._process_step()
-        torch.argmax(self.logits, dim=-1, out=self.ids)
+        choose()
         self.stream_rows.index_copy_(0, self.stepc, self.ids.unsqueeze(0))
         self.stepc.add_(1)
+
+    def _greedy_rows_step(self):
+        """the self-feeding greedy step: every row's argmax becomes its next input token"""
+        self._self_feeding_step(lambda: torch.argmax(self.logits, dim=-1, out=self.ids))
 
     def capture_greedy_rows(self):
         """capture _greedy_rows_step (quant/engine_hook.py _greedy_fast: greedy model.generate without a host round trip per token)"""
@@ -715,21 +721,31 @@ class DecodeEngine:
     def _sample_rows_step(self, warpers):
         """the self-feeding SAMPLING step: HF's own arithmetic on the step's logits (generation/utils.py `_sample`: fp32 copy, the warpers in HF's order,
         softmax, torch.multinomial) -- inside the graph, where the default generator's Philox offset advances per replay exactly as per eager call"""
-        self._step()
-        self._process_step()
-        scores = self.logits.to(copy=True, dtype=torch.float32)
-        for w in warpers:
-            scores = w(None, scores)
-        probs = torch.nn.functional.softmax(scores, dim=-1)
-        self.ids.copy_(torch.multinomial(probs, num_samples=1).squeeze(1))
-        self.stream_rows.index_copy_(0, self.stepc, self.ids.unsqueeze(0))
-        self.stepc.add_(1)
+        def choose():
+            scores = self.logits.to(copy=True, dtype=torch.float32)
+            for w in warpers:
+                scores = w(None, scores)
+            probs = torch.nn.functional.softmax(scores, dim=-1)
+            self.ids.copy_(torch.multinomial(probs, num_samples=1).squeeze(1))
+        self._self_feeding_step(choose)
 
     def capture_sample_rows(self, key, warpers):
         """capture _sample_rows_step for one (temperature, top_k, top_p) setting; the generator's state is put back behind the warm-up run"""
         g = self._capture_rows(lambda: self._sample_rows_step(warpers), keep_rng=True)
         self.sample_graphs = {key: g}              # (one setting at a time: a graph holds the temporaries of a vocabulary-sized sort per row)
         return g
+
+    def _per_row(self, what, name, v, ok):
+        """a setting of the rows -- a scalar for all or one value per row -- as a list of `batch` numbers that ok() accepts; `what` opens the
+        ValueError's message"""
+        B = self.batch
+        vals = [v] * B if not isinstance(v, (list, tuple)) and not torch.is_tensor(v) else [x for x in (v.tolist() if torch.is_tensor(v) else v)]
+        if len(vals) != B:
+            raise ValueError('%s: %s has %d values for a batch of %d' % (what, name, len(vals), B))
+        for x in vals:
+            if isinstance(x, bool) or not isinstance(x, (int, float)) or not ok(x):
+                raise ValueError('%s: %s = %r' % (what, name, x))
+        return vals
 
     # -- sampling of the engine's own: gptq_sample_rows_f16 (csrc/sample.hip) with every row's setting in device memory --------------------
     def set_sampling(self, temperature=1.0, top_k=0, top_p=1.0):
@@ -739,15 +755,7 @@ class DecodeEngine:
         b R .. b R + R - 1 of its verify step (capture_verify_sample / _batch: those rows are consecutive tokens of sequence b).  ValueError
         for a temperature that is negative or not finite, a negative top_k, a top_p outside (0, 1]."""
         B = self.batch
-
-        def per_row(name, v, ok):
-            vals = [v] * B if not isinstance(v, (list, tuple)) and not torch.is_tensor(v) else [x for x in (v.tolist() if torch.is_tensor(v) else v)]
-            if len(vals) != B:
-                raise ValueError('DecodeEngine.set_sampling: %s has %d values for a batch of %d' % (name, len(vals), B))
-            for x in vals:
-                if isinstance(x, bool) or not isinstance(x, (int, float)) or not ok(x):
-                    raise ValueError('DecodeEngine.set_sampling: %s = %r' % (name, x))
-            return vals
+        per_row = functools.partial(self._per_row, 'DecodeEngine.set_sampling')
         t = per_row('temperature', temperature, lambda x: math.isfinite(x) and x >= 0)
         k = per_row('top_k', top_k, lambda x: float(x).is_integer() and 0 <= x < 2 ** 31)
         p = per_row('top_p', top_p, lambda x: 0 < x <= 1)
@@ -788,16 +796,13 @@ class DecodeEngine:
     def _sample_native_step(self):
         """the self-feeding sampling step of the engine's own, for ANY batch: one decode step, fresh uniforms from torch's CUDA generator (inside a
         graph its Philox offset advances per replay exactly as per eager call), ONE launch that draws every row's next token under that row's
-        setting, and the bookkeeping of _greedy_rows_step.  With logits_process the ONE process launch sits between the step and the uniforms:
+        setting, and the bookkeeping of _self_feeding_step.  With logits_process the ONE process launch sits between the step and the uniforms:
         the row's token history -- the token just consumed included, appended by that launch -- edits self.logits in place before the draw;
         temperature 0 (set_sampling) makes this graph the greedy step under the processors."""
-        self._stream_buffers()
-        self._step()
-        self._process_step()
-        self.u.uniform_()
-        self.sample_logits(self.logits, out=self.ids, u=self.u)
-        self.stream_rows.index_copy_(0, self.stepc, self.ids.unsqueeze(0))
-        self.stepc.add_(1)
+        def choose():
+            self.u.uniform_()
+            self.sample_logits(self.logits, out=self.ids, u=self.u)
+        self._self_feeding_step(choose)
 
     def capture_sample_native(self):
         """capture _sample_native_step ONCE: the settings are device buffers the kernel reads at every replay, so set_sampling never re-captures.
@@ -820,16 +825,8 @@ class DecodeEngine:
         bias entries drops the captured self-feeding graphs (capture_sample_native, capture_greedy, capture_greedy_rows,
         capture_sample_rows), which are captured again at their next use.  ValueError before anything changes."""
         self._need_logits_process('set_logits_process')
-        B, V = self.batch, self.logits.shape[1]
-
-        def per_row(name, v, ok):
-            vals = [v] * B if not isinstance(v, (list, tuple)) and not torch.is_tensor(v) else [x for x in (v.tolist() if torch.is_tensor(v) else v)]
-            if len(vals) != B:
-                raise ValueError('DecodeEngine.set_logits_process: %s has %d values for a batch of %d' % (name, len(vals), B))
-            for x in vals:
-                if isinstance(x, bool) or not isinstance(x, (int, float)) or not ok(x):
-                    raise ValueError('DecodeEngine.set_logits_process: %s = %r' % (name, x))
-            return vals
+        V = self.logits.shape[1]
+        per_row = functools.partial(self._per_row, 'DecodeEngine.set_logits_process')
         rp = per_row('repetition_penalty', repetition_penalty, lambda x: math.isfinite(x) and x > 0)
         pp = per_row('presence_penalty', presence_penalty, math.isfinite)
         mn = per_row('min_new_tokens', min_new_tokens, lambda x: float(x).is_integer() and 0 <= x < 2 ** 31)
@@ -1443,14 +1440,13 @@ class DecodeEngine:
     def _draft_step(self, target):
         """the self-feeding sampling step of a DRAFT engine in front of `target` (a speculative-sampling engine of the same batch B and
         vocabulary): as _sample_native_step, and the step's [B, vocab] logits -- what the tokens were drawn from -- go into draft row stepc of
-        every sequence of target.chunk_draft_logits"""
-        self._step()
-        B, V = self.logits.shape
-        target.chunk_draft_logits.view(B, -1, V).index_copy_(1, self.stepc, self.logits.unsqueeze(1))
-        self.u.uniform_()
-        self.sample_logits(self.logits, out=self.ids, u=self.u)
-        self.stream_rows.index_copy_(0, self.stepc, self.ids.unsqueeze(0))
-        self.stepc.add_(1)
+        every sequence of target.chunk_draft_logits.  (A draft engine has no processors: _self_feeding_step's process call does nothing here.)"""
+        def choose():
+            B, V = self.logits.shape
+            target.chunk_draft_logits.view(B, -1, V).index_copy_(1, self.stepc, self.logits.unsqueeze(1))
+            self.u.uniform_()
+            self.sample_logits(self.logits, out=self.ids, u=self.u)
+        self._self_feeding_step(choose)
 
     def capture_draft_step(self, target):
         """capture _draft_step once for `target`: at most R - 1 replays (R the target's chunk rows) between two resets of stepc.  ValueError for
@@ -1461,6 +1457,27 @@ class DecodeEngine:
                              'on one device')
         self.draft_graph = self._capture_rows(lambda: self._draft_step(target), keep_rng=True)
         return self.draft_graph
+
+    def graph_for(self, kind, draft_logits=False):
+        """THE place that hands out the graphs of the generation drivers: the captured graph of `kind` -- 'greedy' (batch 1: capture_greedy),
+        'greedy_rows', 'sample_native', 'verify_greedy', 'verify_sample' (draft_logits: the one that reads the draft model's logits rows) --,
+        captured by the public capture_* method on first use.  A capture warms up with a real step, which writes the cache rows at pos: pos is
+        put to 0 first, so that the step fits whatever an earlier sequence left there.  A driver therefore asks for EVERY graph it will need
+        BEFORE its prompt enters the cache: behind a prompt, the warm-up step at position 0 would overwrite the prompt's first cache row, and
+        this method must not be called there."""
+        with_q = bool(draft_logits)
+        held, capture = {
+            'greedy': (lambda: self.greedy_graph, self.capture_greedy),
+            'greedy_rows': (lambda: self.greedy_rows_graph, self.capture_greedy_rows),
+            'sample_native': (lambda: self.sample_native_graph, self.capture_sample_native),
+            'verify_greedy': (lambda: self.verify_graph, self.capture_verify_greedy_batch if self.batch_chunk else self.capture_verify_greedy),
+            'verify_sample': (lambda: self.verify_sample_graphs.get(with_q), lambda: (
+                self.capture_verify_sample_batch if self.batch_chunk else self.capture_verify_sample)(draft_logits=with_q)),
+        }[kind]
+        if held() is None:
+            self.pos.zero_()
+            capture()
+        return held()
 
     def decode(self, token):
         """one token per row in ([batch] ids), logits [batch, vocab] out (the static buffer: clone it to keep it).  An engine built with
@@ -1606,24 +1623,24 @@ def prompt_lookup_draft(tokens, k, max_ngram=3):
     return out
 
 
-def _speculate_settings(speculate):
-    """the `speculate` argument of engine_generate: (k, max_ngram, draft) -- every key optional"""
+def _speculate_settings(speculate, what='engine_generate'):
+    """the `speculate` argument of `what` (engine_generate / engine_generate_batch): (k, max_ngram, draft) -- every key optional"""
     if not isinstance(speculate, dict):
-        raise ValueError('engine_generate: speculate must be None or a dict with the keys k, max_ngram, draft')
+        raise ValueError('%s: speculate must be None or a dict with the keys k, max_ngram, draft' % what)
     unknown = sorted(set(speculate) - {'k', 'max_ngram', 'draft', 'sample', 'draft_model'})
     if unknown:
-        raise ValueError('engine_generate: unknown speculation keys %r' % (unknown,))
+        raise ValueError('%s: unknown speculation keys %r' % (what, unknown))
     k, max_ngram, draft = speculate.get('k', 4), speculate.get('max_ngram', 3), speculate.get('draft')
     if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= MAX_BATCH - 1:
-        raise ValueError('engine_generate: speculate k must be 1 .. %d, not %r' % (MAX_BATCH - 1, k))
+        raise ValueError('%s: speculate k must be 1 .. %d, not %r' % (what, MAX_BATCH - 1, k))
     if isinstance(max_ngram, bool) or not isinstance(max_ngram, int) or max_ngram < 1:
-        raise ValueError('engine_generate: speculate max_ngram must be a positive int, not %r' % (max_ngram,))
+        raise ValueError('%s: speculate max_ngram must be a positive int, not %r' % (what, max_ngram))
     if draft is not None and not callable(draft):
-        raise ValueError('engine_generate: speculate draft must be a callable (tokens_so_far, k) -> k ids')
+        raise ValueError('%s: speculate draft must be a callable (tokens_so_far, k) -> k ids' % what)
     return k, max_ngram, draft
 
 
-def _speculate_sampling(speculate, model, what='engine_generate'):
+def _speculate_sampling(speculate, model, what):
     """the keys of `speculate` that ask for speculative SAMPLING and for a draft MODEL: (sampling settings or None, draft model or None)"""
     sample, draft_model = speculate.get('sample'), speculate.get('draft_model')
     settings = None if sample is None else _sampling_settings(what, sample)
@@ -1639,92 +1656,20 @@ def _speculate_sampling(speculate, model, what='engine_generate'):
     return settings, draft_model
 
 
-def engine_generate(model, input_ids, max_new_tokens, eos_token_id=None, engine=None, t_max=2048, prefill='hf', sample=None, speculate=None):
-    """Greedy generation: the prompt goes through the HF model once (the drop-in modules' prefill path: MFMA GEMMs,
-    fused MLP epilogue), its KV cache is copied into the engine's static cache, and every further token is ONE hipGraph
-    replay (DecodeEngine).  Returns the full sequence [1, prompt + generated].  Batch 1; the reference equivalent is
-    ``model.generate(input_ids, do_sample=False, max_new_tokens=...)`` through llama_inference.py:109-115.
-    prefill='engine': the prompt goes through DecodeEngine.prefill instead (the engine's own launches with the hand-written causal
-    attention kernel straight into its cache: no HF module chain, no DynamicCache, no copy); 'hf' (the default) is the route above.
-    Measured on the 7B shape (profiles/prompt_attn/README.md): 'engine' reaches the first token sooner at 16, 128, 512 and 2047 tokens
-    (2.1 / 4.2 / 9.5 / 29.0 ms against 7.9 / 8.3 / 12.2 / 38.1) -- at no measured length is it slower than 'hf'.
-    sample=dict(temperature=..., top_k=..., top_p=...) (every key optional: DecodeEngine.set_sampling) SAMPLES instead, as the reference's script does
-    (llama_inference.py:119-127): the first token is drawn from the prompt's logits by DecodeEngine.sample_logits, every further one by a replay of
-    the capture_sample_native graph; the draws follow torch.manual_seed.  temperature 0 gives the greedy tokens.  The settings STAY in the engine's
-    buffers afterwards: a later eng.sample_logits(...) or a replay of the native graph uses them until set_sampling is called again.
-    The same dict takes the LOGIT PROCESSORS repetition_penalty, presence_penalty, min_new_tokens and logit_bias
-    (DecodeEngine.set_logits_process; eos_token_id of this call is what min_new_tokens masks).  The prompt counts for repetition_penalty (HF's
-    rule), only generated tokens for presence_penalty; they act before temperature, top-k and top-p.  With any of them non-neutral the engine is
-    built with logits_process=True (one passed in without the flag: ValueError), the first token is process_logits then sample_logits, and
-    the tail is the same native graph with one more launch per step; temperature 0 gives the greedy tokens under the processors.  All
-    neutral (1.0, 0.0, 0, None) is exactly the call without the keys: the same tokens for a seed and no process launch.  Inside
-    speculate=dict(sample=...) a non-neutral processor key is a ValueError: processors under speculation are not built yet.
-    speculate=dict(k=4, max_ngram=3, draft=None) (every key optional) decodes SPECULATIVELY, greedy: per step a draft of k tokens -- from
-    draft(tokens_so_far: list[int], k) -> k ids, by default prompt_lookup_draft -- goes through the model together with the last token as ONE
-    replay of the capture_verify_greedy graph (a DecodeEngine with chunk = k + 1: one pass over the weights), which accepts the longest prefix the
-    greedy rule agrees with and emits one token more; the host reads (accepted, tokens) in one copy per step.  Where fewer than 2 tokens remain or
-    the chunk no longer fits the cache, the single-step greedy graph finishes.  Same return value and eos semantics as the greedy path (the tokens
-    are the greedy ones up to the near ties that any change of the arithmetic's row count moves); eng.spec_stats = dict(steps, emitted,
-    accepted=[per step]) describes the last run.
-    speculate=dict(..., sample=dict(temperature, top_k, top_p)) SAMPLES speculatively: the capture_verify_sample graph applies the accept /
-    resample rule of gptq_spec_sample_rows_f16 on the device, so the emitted tokens are distributed exactly as engine_generate(sample=...) draws
-    them, whatever the draft; drafts from prompt lookup or `draft` count as point masses; first token by sample_logits, tail by the
-    capture_sample_native graph.  speculate=dict(..., draft_model=<fused model of the same vocabulary>) drafts with a MODEL instead: a batch-1
-    DecodeEngine of its own (kept on the engine) draws the k tokens under the same setting and hands its logits rows to the verify step; without
-    `sample` it drafts greedily and the verify-greedy graph checks it.
-    ValueError: speculate together with the sample ARGUMENT; k outside 1 .. 15; an engine passed in whose chunk is not k + 1 or whose batch is
-    not 1; unknown keys; draft together with draft_model; a draft model of another vocabulary size."""
-    if prefill not in ('hf', 'engine'):
-        raise ValueError("engine_generate: prefill must be 'hf' or 'engine', not %r" % (prefill,))
-    settings = None if sample is None else _sampling_settings('engine_generate', sample)
+def _generation_settings(what, model, sample, speculate, engine):
+    """what the arguments sample= / speculate= / engine= of `what` (engine_generate / engine_generate_batch) ask for, validated ONCE for both:
+    (sampling settings or None, processor settings or None, (k, max_ngram, draft, sampling settings or None, draft model or None) or None)"""
+    settings = None if sample is None else _sampling_settings(what, sample)
     proc = None if sample is None else _process_settings(sample)
     spec = None
     if speculate is not None:
         if sample is not None:
-            raise ValueError('engine_generate: speculate and sample exclude each other (greedy speculation only)')
-        spec = _speculate_settings(speculate) + _speculate_sampling(speculate, model)
-        if engine is not None and (engine.batch != 1 or engine.chunk != spec[0] + 1):
-            raise ValueError('engine_generate: speculate k = %d needs an engine of batch 1 with chunk = %d (this one: batch %d, chunk %d)' % (
-                spec[0], spec[0] + 1, engine.batch, engine.chunk))
-    if input_ids.dim() != 2 or input_ids.shape[0] != 1:
-        raise ValueError('engine_generate: batch 1 only')
-    dev = input_ids.device
-    T = input_ids.shape[1]
-    if engine is not None:
-        eng = engine
-        if proc is not None and not eng.logits_process:
-            raise ValueError('engine_generate: %s need an engine built with logits_process=True' % ', '.join(sorted(proc)))
-    elif spec is not None:
-        eng = DecodeEngine(model, t_max=t_max, chunk=spec[0] + 1)
-    else:
-        eng = DecodeEngine(model, t_max=t_max, logits_process=proc is not None).capture()
-    if T + max_new_tokens > eng.t_max:
-        raise ValueError('engine_generate: prompt + max_new_tokens exceeds the engine cache (%d)' % eng.t_max)
-    if spec is not None:
-        return _engine_generate_speculative(model, input_ids, max_new_tokens, eos_token_id, eng, prefill, *spec)
-    if settings is not None:
-        if eng.batch != 1:
-            raise ValueError('engine_generate: sampling needs an engine of batch 1')
-        eng.set_sampling(**settings)
-        if eng.logits_process:                               # (an engine passed in with the flag, neutral keys: its processors are switched off)
-            eng.set_logits_process(eos_token_id=eos_token_id, **(proc or {}))
-        return _engine_generate_sampled(model, input_ids, max_new_tokens, eos_token_id, eng, prefill)
-    with torch.no_grad():
-        first = _prompt_into_engine(model, input_ids, eng, prefill).argmax().reshape(1)
-        if eng.greedy_graph is None:
-            eng.capture_greedy()
-        eng.ids.copy_(first)
-        eng.stream_out[T] = first[0]                         # stream_out[p] = token generated after p consumed tokens
-        done = 1
-        while done < max_new_tokens:
-            burst = min(16, max_new_tokens - done)           # the host looks at the stream every 16 tokens only
-            for _ in range(burst):
-                eng.greedy_graph.replay()
-            done += burst
-            if eos_token_id is not None and bool((eng.stream_out[T:T + done] == eos_token_id).any()):
-                break
-        gen = _cut_after_eos(eng.stream_out[T:T + done].clone(), eos_token_id)
-    return torch.cat([input_ids[0], gen.to(input_ids.dtype)]).unsqueeze(0)
+            raise ValueError('%s: speculate and the sample argument exclude each other (speculative sampling: the key sample inside '
+                             'speculate)' % what)
+        spec = _speculate_settings(speculate, what) + _speculate_sampling(speculate, model, what)
+    if engine is not None and proc is not None and not engine.logits_process:
+        raise ValueError('%s: %s need an engine built with logits_process=True' % (what, ', '.join(sorted(proc))))
+    return settings, proc, spec
 
 
 def _draft_model_engine(eng, draft_model, settings):
@@ -1797,6 +1742,30 @@ def _model_drafts(eng, deng, k, lens):
     return fill
 
 
+def _self_feeding_tail(eng, graph, first, n, eos=None, record=None):
+    """THE tail loop of every generation driver.  graph: a captured self-feeding step of `eng`; first: the B tokens chosen behind the prompts
+    (int64 on the device), which the first replay consumes; n >= 1: tokens wanted per row, `first` included; eos: None, an id or a list of
+    ids.  Replays in bursts of min(16, what remains) -- the host looks at the stream between bursts only -- until n tokens per row exist or
+    every row has shown an eos.  record = (buffer [., B], the row the first replay writes): where the step keeps its choices; None: stream_rows
+    from row 0, with stepc put to 0.  Returns the stream [done, B] with `first` in front: done - 1 replays have run."""
+    if record is None:
+        eng.stepc.zero_()
+        record = (eng.stream_rows, 0)
+    rows, r0 = record
+    eng.ids.copy_(first)
+    eos_t = None if eos is None else torch.tensor(eos, dtype=torch.int64, device=first.device).reshape(-1)
+    hit = None if eos_t is None else torch.isin(first, eos_t)
+    done = 1
+    while done < n and not (hit is not None and bool(hit.all())):
+        burst = min(16, n - done)
+        for _ in range(burst):
+            graph.replay()
+        if hit is not None:
+            hit = hit | torch.isin(rows[r0 + done - 1:r0 + done - 1 + burst], eos_t).any(dim=0)
+        done += burst
+    return torch.cat([first.unsqueeze(0), rows[r0:r0 + done - 1]])
+
+
 def _generate_speculative(eng, prompts, first, max_new_tokens, eos_token_id, k, graph, drafts, finish):
     """The ONE speculative loop, for n >= 1 sequences: engine_generate(speculate=...) is n = 1 on a chunk engine, engine_generate_batch(speculate=...)
     n >= 2 on a batch_chunk engine.  prompts: n id lists already in the engine's cache; first: the token chosen behind each.  Per step: who is
@@ -1837,181 +1806,157 @@ def _generate_speculative(eng, prompts, first, max_new_tokens, eos_token_id, k, 
     return gens, stats
 
 
-def _engine_generate_speculative(model, input_ids, max_new_tokens, eos_token_id, eng, prefill, k, max_ngram, draft, settings=None, draft_model=None):
-    """engine_generate with speculation: what _generate_speculative needs for the ONE sequence of a chunk engine.
-    settings None: the verify-greedy graph, the first token by argmax, the capture_greedy graph (stream_out) for the tail.  settings: the
-    verify-sample graph -- with the draft model's logits rows when a draft model is given, point-mass drafts otherwise --, the first token by
-    sample_logits, the tail by the capture_sample_native graph.
-    draft_model: _model_drafts on a DecodeEngine of its own, under the same setting (greedily without one); else _host_drafts.
-    spec_stats: emitted as an int, accepted as the flat per-step list."""
-    T = input_ids.shape[1]
-    with torch.no_grad():
-        if settings is None:
-            if eng.verify_graph is None:
-                eng.pos.zero_()                                  # (the capture's warm-up step writes cache rows pos .. pos + R - 1)
-                eng.capture_verify_greedy()
-            graph = eng.verify_graph
-        else:
-            eng.set_sampling(**settings)
-            with_q = draft_model is not None
-            if eng.verify_sample_graphs.get(with_q) is None:
-                eng.pos.zero_()
-                eng.capture_verify_sample(draft_logits=with_q)
-            graph = eng.verify_sample_graphs[with_q]
-        deng = None if draft_model is None else _draft_model_engine(eng, draft_model, settings)
-        logits = _prompt_into_engine(model, input_ids, eng, prefill)
-        first = int(logits.argmax()) if settings is None else int(eng.sample_logits(logits.to(torch.float16).contiguous())[0])
-        if deng is not None:
-            deng.prefill(input_ids[0], start=0)
-        drafts = _host_drafts('engine_generate', eng, k, max_ngram, draft) if deng is None else _model_drafts(eng, deng, k, [T])
-
-        def finish(seqs, left):
-            seq, n = seqs[0], left[0]
-            p0 = len(seq) - 1
-            eng.pos.fill_(p0)                                    # (a step cut by the length or an eos advanced the device position further)
-            if n <= 0:
-                return [[]]
-            if settings is None:
-                if eng.greedy_graph is None:
-                    eng.capture_greedy()
-                tail = eng.greedy_graph
-            else:
-                if eng.sample_native_graph is None:
-                    eng.capture_sample_native()                  # (its warm-up step writes cache row pos, which the tail overwrites first)
-                tail = eng.sample_native_graph
-                eng.stepc.zero_()
-            eng.ids.fill_(seq[-1])
-            for _ in range(n):
-                tail.replay()
-            # stream_out[p] = token generated after p consumed tokens; stream_rows[i] = the token chosen by replay i
-            return [(eng.stream_out[p0 + 1:p0 + 1 + n] if settings is None else eng.stream_rows[:n, 0]).tolist()]
-        gens, st = _generate_speculative(eng, [[int(t) for t in input_ids[0].tolist()]], [first], max_new_tokens, eos_token_id, k, graph, drafts, finish)
-        eng.spec_stats = dict(steps=st['steps'], emitted=st['emitted'][0], accepted=st['accepted'][0])
-    return torch.cat([input_ids[0], torch.tensor(gens[0], dtype=input_ids.dtype, device=input_ids.device)]).unsqueeze(0)
-
-
-def _engine_generate_sampled(model, input_ids, max_new_tokens, eos_token_id, eng, prefill):
-    """engine_generate with sampling (the settings are already in the engine): the greedy loop with sample_logits for the first token and the
-    capture_sample_native graph -- whose choices land in stream_rows -- for the others"""
-    T = input_ids.shape[1]
-    with torch.no_grad():
-        if eng.sample_native_graph is None:
-            eng.pos.zero_()                                      # (the capture's warm-up step writes cache row pos -- and the logits buffer)
-            eng.capture_sample_native()
-        logits = _prompt_into_engine(model, input_ids, eng, prefill).to(torch.float16).contiguous()
-        if eng.logits_process:
-            eng.process_logits(logits)
-        first = eng.sample_logits(logits)
-        eng.ids.copy_(first)
-        eng.stepc.zero_()                                        # stream_rows[k] = the token chosen by replay k
-        done = 1
-        hit = eos_token_id is not None and int(first[0]) == eos_token_id
-        while done < max_new_tokens and not hit:
-            burst = min(16, max_new_tokens - done)               # the host looks at the stream every 16 tokens only
-            for _ in range(burst):
-                eng.sample_native_graph.replay()
-            if eos_token_id is not None:
-                hit = bool((eng.stream_rows[done - 1:done - 1 + burst, 0] == eos_token_id).any())
-            done += burst
-        gen = _cut_after_eos(torch.cat([first, eng.stream_rows[:done - 1, 0]]), eos_token_id)
-    return torch.cat([input_ids[0], gen.to(input_ids.dtype)]).unsqueeze(0)
-
-
-def _engine_generate_batch_speculative(prompts, max_new_tokens, eos_token_id, eng, k, max_ngram, draft, settings=None, draft_model=None):
-    """engine_generate_batch with speculation: what _generate_speculative needs for the n sequences of a batch_chunk engine -- prefill_batch and
-    the tail with the finished rows idling far below position 0.
-    settings None: the first tokens by argmax, the verify-greedy graph, the capture_greedy_rows graph for the tail.  settings (one value for all
+def _speculate_rows(what, eng, prompts, into, max_new_tokens, eos_token_id, k, max_ngram, draft, settings, draft_model):
+    """_generate_rows with speculation: what _generate_speculative needs for the n sequences of a chunk (n = 1) or batch_chunk engine.
+    settings None: the verify-greedy graph, the first tokens by argmax, the capture_greedy_rows graph for the tail.  settings (one value for all
     or one per prompt): the verify-sample graph -- with the draft model's logits rows when a draft model is given, point-mass drafts otherwise
     --, the first tokens by sample_logits, the tail by the capture_sample_native graph.
     draft_model: _model_drafts on a DecodeEngine of this batch, under the same settings (greedily without them); else _host_drafts.
-    Afterwards every position is that of the sequence's last token, the one not consumed yet."""
+    Afterwards every position is that of the sequence's last token, the one not consumed yet, and eng.spec_stats describes the run."""
     n = len(prompts)
-    with torch.no_grad():
-        if settings is None:
-            if eng.verify_graph is None:
-                eng.pos.zero_()                                  # (the capture's warm-up step writes cache rows pos .. pos + R - 1 of every slot)
-                eng.capture_verify_greedy_batch()
-            if eng.greedy_rows_graph is None:
-                eng.pos.zero_()
-                eng.capture_greedy_rows()
-            graph, tail = eng.verify_graph, eng.greedy_rows_graph
-        else:
-            eng.set_sampling(**settings)                         # (validates before anything changes)
-            with_q = draft_model is not None
-            if eng.verify_sample_graphs.get(with_q) is None:
-                eng.pos.zero_()
-                eng.capture_verify_sample_batch(draft_logits=with_q)
-            if eng.sample_native_graph is None:
-                eng.pos.zero_()
-                eng.capture_sample_native()
-            graph, tail = eng.verify_sample_graphs[with_q], eng.sample_native_graph
-        deng = None if draft_model is None else _draft_model_engine(eng, draft_model, settings)
-        logits = eng.prefill_batch(prompts, starts=[0] * n)
-        first = (logits.argmax(dim=-1) if settings is None else eng.sample_logits(logits.to(torch.float16).contiguous())).tolist()
-        if deng is not None:
-            deng.prefill_batch(prompts, starts=[0] * n)
-            drafts = _model_drafts(eng, deng, k, [int(p.numel()) for p in prompts])
-        else:
-            drafts = _host_drafts('engine_generate_batch', eng, k, max_ngram, draft)
+    if settings is None:
+        graph, tail = eng.graph_for('verify_greedy'), eng.graph_for('greedy_rows')
+    else:
+        eng.set_sampling(**settings)                             # (validates before anything changes)
+        graph, tail = eng.graph_for('verify_sample', draft_logits=draft_model is not None), eng.graph_for('sample_native')
+    deng = None if draft_model is None else _draft_model_engine(eng, draft_model, settings)
+    logits = into(eng)
+    first = (logits.argmax(dim=-1) if settings is None else eng.sample_logits(logits.to(torch.float16).contiguous())).tolist()
+    if deng is not None:
+        into(deng)
+        drafts = _model_drafts(eng, deng, k, [int(p.numel()) for p in prompts])
+    else:
+        drafts = _host_drafts(what, eng, k, max_ngram, draft)
 
-        def finish(seqs, left):
-            if max(left) <= 0:
-                return [[]] * n
-            far = -(eng.t_max + 1)                               # (a step adds 1 to every position: still negative after the tail)
-            eng.pos.copy_(torch.tensor([len(s) - 1 if m else far for s, m in zip(seqs, left)], dtype=torch.int64))
-            eng.ids.copy_(torch.tensor([s[-1] if m else 0 for s, m in zip(seqs, left)], dtype=torch.int64))
-            eng.stepc.zero_()
-            for _ in range(max(left)):
-                tail.replay()
-            return eng.stream_rows[:max(left)].t().tolist()      # [row][step]
-        gens, eng.spec_stats = _generate_speculative(eng, [[int(t) for t in p.tolist()] for p in prompts], first, max_new_tokens, eos_token_id, k,
-                                                     graph, drafts, finish)
-        eng.pos.copy_(torch.tensor([p.numel() + len(g) - 1 for p, g in zip(prompts, gens)], dtype=torch.int64))
-        return [torch.cat([p, torch.tensor(g, dtype=p.dtype, device=p.device)]) for p, g in zip(prompts, gens)]
+    def finish(seqs, left):
+        if max(left) <= 0:
+            return [[]] * n
+        far = -(eng.t_max + 1)                                   # (a step adds 1 to every position: still negative after the tail)
+        eng.pos.copy_(torch.tensor([len(s) - 1 if m else far for s, m in zip(seqs, left)], dtype=torch.int64))
+        last = torch.tensor([s[-1] if m else 0 for s, m in zip(seqs, left)], dtype=torch.int64, device=eng.dev)
+        return _self_feeding_tail(eng, tail, last, max(left) + 1)[1:].t().tolist()      # [row][step]: no eos, the exact count
+    gens, eng.spec_stats = _generate_speculative(eng, [[int(t) for t in p.tolist()] for p in prompts], first, max_new_tokens, eos_token_id, k,
+                                                 graph, drafts, finish)
+    eng.pos.copy_(torch.tensor([p.numel() + len(g) - 1 for p, g in zip(prompts, gens)], dtype=torch.int64))
+    return [torch.tensor(g, dtype=torch.int64) for g in gens]
+
+
+def _generate_rows(what, eng, prompts, into, max_new_tokens, eos_token_id, settings, proc, spec, one_prompt=False):
+    """THE generation driver behind engine_generate (one prompt) and engine_generate_batch: prompts are n = eng.batch 1-D id tensors,
+    into(engine) puts them into that engine's cache from position 0 and returns the [n, vocab] logits behind their last tokens.  In this order:
+    the settings go into the engine; every graph the run will need is taken from graph_for, while no prompt is in the cache yet; the prompts
+    enter; the processors act on the first logits; the first tokens come from argmax or sample_logits; _self_feeding_tail makes the others.
+    Returns the generated ids of every row, cut after its first eos.
+    one_prompt: the greedy tail of ONE prompt replays the capture_greedy graph, which records into stream_out[pos]: one element-wise node less
+    per step than the rows graph, a difference that was measured (profiles/generate_drivers/README.md)."""
+    with torch.no_grad():
+        if spec is not None:
+            return _speculate_rows(what, eng, prompts, into, max_new_tokens, eos_token_id, *spec)
+        record = None
+        if settings is not None:
+            eng.set_sampling(**settings)
+            if eng.logits_process:                               # (an engine passed in with the flag, neutral keys: its processors are switched off)
+                eng.set_logits_process(eos_token_id=eos_token_id, **(proc or {}))
+            graph = eng.graph_for('sample_native')
+        elif one_prompt:
+            graph = eng.graph_for('greedy')
+            record = (eng.stream_out.unsqueeze(1), int(prompts[0].numel()) + 1)      # stream_out[p] = the token chosen after p consumed ones
+        else:
+            graph = eng.graph_for('greedy_rows')
+        logits = into(eng)
+        if settings is None:
+            first = logits.argmax(dim=-1)
+        else:
+            logits = logits.to(torch.float16).contiguous()
+            if eng.logits_process:
+                eng.process_logits(logits)
+            first = eng.sample_logits(logits)
+        gen = _self_feeding_tail(eng, graph, first, max_new_tokens, eos_token_id, record).t()      # [row][step]
+        return [_cut_after_eos(g, eos_token_id) for g in gen]
+
+
+def engine_generate(model, input_ids, max_new_tokens, eos_token_id=None, engine=None, t_max=2048, prefill='hf', sample=None, speculate=None):
+    """Generation for ONE prompt ([1, T] ids) on the DecodeEngine: the prompt enters the engine's static cache, the first token is chosen from
+    its logits, and every further token is ONE hipGraph replay of a self-feeding step; the host looks at the stream every 16 tokens only.
+    Returns the full sequence [1, prompt + generated], cut after the first eos_token_id.  The reference equivalent is
+    ``model.generate(input_ids, do_sample=False, max_new_tokens=...)`` through llama_inference.py:109-115.
+    prefill='hf' (the default): the prompt goes through the HF model once (the drop-in modules' prefill path: MFMA GEMMs, fused MLP
+    epilogue) and its KV cache is copied into the engine's.  'engine': DecodeEngine.prefill instead (the engine's own launches with the
+    hand-written causal attention kernel straight into its cache: no HF module chain, no DynamicCache, no copy) -- it reaches the first token
+    sooner at every measured length (profiles/prompt_attn/README.md: 2.1 / 4.2 / 9.5 / 29.0 ms against 7.9 / 8.3 / 12.2 / 38.1 at 16, 128,
+    512 and 2047 tokens of the 7B shape).
+    engine=None builds a DecodeEngine for the call (t_max; chunk = k + 1 under speculate; logits_process when a processor is asked for).
+    sample=dict(temperature=..., top_k=..., top_p=...) (every key optional: DecodeEngine.set_sampling) SAMPLES, as the reference's script does
+    (llama_inference.py:119-127): the first token by DecodeEngine.sample_logits, the others by the capture_sample_native graph; the draws
+    follow torch.manual_seed, temperature 0 gives the greedy tokens.  The settings STAY in the engine's buffers afterwards.
+    The same dict takes the LOGIT PROCESSORS repetition_penalty, presence_penalty, min_new_tokens and logit_bias
+    (DecodeEngine.set_logits_process; eos_token_id of this call is what min_new_tokens masks).  The prompt counts for repetition_penalty (HF's
+    rule), only generated tokens for presence_penalty; they act before temperature, top-k and top-p: process_logits ahead of the first draw,
+    one more launch per step of the native graph.  They need an engine with logits_process=True.  All neutral (1.0, 0.0, 0, None) is exactly
+    the call without the keys: the same tokens for a seed and no process launch.
+    speculate=dict(k=4, max_ngram=3, draft=None) (every key optional) decodes SPECULATIVELY, greedy: per step a draft of k tokens -- from
+    draft(tokens_so_far: list[int], k) -> k ids, by default prompt_lookup_draft -- goes through the model together with the last token as ONE
+    replay of the capture_verify_greedy graph (an engine with chunk = k + 1: one pass over the weights), which accepts the longest prefix the
+    greedy rule agrees with and emits one token more; the host reads (accepted, tokens) in one copy per step.  Where fewer than 2 tokens remain
+    or the chunk no longer fits the cache, the single-step graph finishes.  Same return value and eos semantics (the tokens are the greedy
+    ones up to the near ties that any change of the arithmetic's row count moves); eng.spec_stats = dict(steps, emitted, accepted=[per step])
+    describes the last run, and eng.pos is the position of the last token.
+    speculate=dict(..., sample=dict(temperature, top_k, top_p)) SAMPLES speculatively: the capture_verify_sample graph applies the accept /
+    resample rule of gptq_spec_sample_rows_f16 on the device, so the emitted tokens are distributed exactly as engine_generate(sample=...) draws
+    them, whatever the draft; drafts from prompt lookup or `draft` count as point masses.  A processor key in there is a ValueError:
+    processors under speculation are not built yet.  speculate=dict(..., draft_model=<fused model of the same vocabulary>) drafts with a MODEL:
+    a DecodeEngine of its own (kept on the engine) draws the k tokens under the same setting and hands its logits rows to the verify step;
+    without `sample` it drafts greedily and the verify-greedy graph checks it.
+    ValueError: speculate together with the sample ARGUMENT; k outside 1 .. 15; an engine passed in whose chunk is not k + 1 or whose batch is
+    not 1; unknown keys; draft together with draft_model; a draft model of another vocabulary size; a prompt that is not [1, T]; prompt +
+    max_new_tokens beyond the cache."""
+    what = 'engine_generate'
+    if prefill not in ('hf', 'engine'):
+        raise ValueError("engine_generate: prefill must be 'hf' or 'engine', not %r" % (prefill,))
+    settings, proc, spec = _generation_settings(what, model, sample, speculate, engine)
+    if spec is not None and engine is not None and (engine.batch != 1 or engine.chunk != spec[0] + 1):
+        raise ValueError('engine_generate: speculate k = %d needs an engine of batch 1 with chunk = %d (this one: batch %d, chunk %d)' % (
+            spec[0], spec[0] + 1, engine.batch, engine.chunk))
+    if input_ids.dim() != 2 or input_ids.shape[0] != 1:
+        raise ValueError('engine_generate: batch 1 only')
+    if engine is not None:
+        eng = engine
+    elif spec is not None:
+        eng = DecodeEngine(model, t_max=t_max, chunk=spec[0] + 1)
+    else:
+        eng = DecodeEngine(model, t_max=t_max, logits_process=proc is not None)
+    if input_ids.shape[1] + max_new_tokens > eng.t_max:
+        raise ValueError('engine_generate: prompt + max_new_tokens exceeds the engine cache (%d)' % eng.t_max)
+    if settings is not None and eng.batch != 1:
+        raise ValueError('engine_generate: sampling needs an engine of batch 1')
+
+    def into(e):                                                 # (a draft model's engine takes the prompt by its own prefill)
+        return _prompt_into_engine(model, input_ids, e, prefill if e is eng else 'engine').reshape(1, -1)
+    gen = _generate_rows(what, eng, [input_ids[0]], into, max_new_tokens, eos_token_id, settings, proc, spec, one_prompt=True)[0]
+    if spec is not None:                                         # one sequence: emitted as an int, accepted as the flat per-step list
+        eng.spec_stats = dict(eng.spec_stats, emitted=eng.spec_stats['emitted'][0], accepted=eng.spec_stats['accepted'][0])
+    return torch.cat([input_ids[0], gen.to(device=input_ids.device, dtype=input_ids.dtype)]).unsqueeze(0)
 
 
 def engine_generate_batch(model, prompts, max_new_tokens, eos_token_id=None, engine=None, t_max=2048, sample=None, speculate=None):
-    """Greedy generation for a LIST of prompts of different lengths (1-D id tensors): all prompts enter the engine through ONE
-    DecodeEngine.prefill_batch, and every further step is one replay of the capture_greedy_rows graph for all rows; the host looks at the
-    stream every 16 steps.  Returns a list of 1-D tensors, prompt + generated, each cut after its first eos_token_id.  engine.batch must
-    equal len(prompts) (without an engine, one of that batch is built); max(T) + max_new_tokens <= t_max.  Nothing of `transformers` is
-    involved.
-    sample=dict(temperature=..., top_k=..., top_p=...) SAMPLES instead: every key optional, a scalar for all rows or one value per prompt
-    (DecodeEngine.set_sampling; a row with temperature 0 stays greedy).  The first tokens are drawn from the prompts' logits by
-    DecodeEngine.sample_logits, every further step is a replay of the capture_sample_native graph; the draws follow torch.manual_seed.  The
-    settings STAY in the engine's buffers afterwards, until set_sampling is called again.
-    The same dict takes the logit processors repetition_penalty, presence_penalty, min_new_tokens (each a scalar or one value per prompt) and
-    logit_bias (one dict for all), as engine_generate's: an engine with logits_process=True, process_logits ahead of the first draw, one more
-    launch per step of the native graph; the prompts are pad-free here, so every row's history is its own prompt and tokens.  A row that has
-    emitted its eos keeps stepping, as without processors, and disturbs no other row.
-    speculate=dict(k=4, max_ngram=3, draft=None) (every key optional, validated as engine_generate's) decodes SPECULATIVELY, at least two
-    prompts: per step every active sequence gets a draft of k tokens -- draft(tokens_so_far: list[int], k) -> k ids, by default
-    prompt_lookup_draft -- and all sequences' chunks go through the model as ONE replay of the capture_verify_greedy_batch graph (a DecodeEngine
-    with batch = len(prompts), batch_chunk = k + 1: one pass over the weights at M = batch x (k + 1)), which accepts per sequence the longest
-    prefix the greedy rule agrees with and emits one token more; the host uploads the chunks and reads (accepted, tokens) of all sequences in one
-    copy each per step.  A sequence that has hit its eos or its length idles; where no active sequence has two tokens left, or an active chunk no
-    longer fits the cache, the capture_greedy_rows graph finishes.  Same return value and eos semantics as the greedy path;
-    eng.spec_stats = dict(steps, emitted=[per sequence], accepted=[per sequence: per step]) describes the last run.
-    speculate=dict(..., sample=dict(temperature, top_k, top_p)) SAMPLES speculatively, every value a scalar or one per prompt: the
-    capture_verify_sample_batch graph (an engine built with spec_sample=True) applies the accept / resample rule of gptq_spec_sample_batch_f16
-    to all sequences in one launch, so every sequence's tokens are distributed exactly as engine_generate_batch(sample=...) draws them, whatever
-    the draft; host drafts count as point masses; first tokens by sample_logits, tail by the capture_sample_native graph.
-    speculate=dict(..., draft_model=<fused model of the same vocabulary>) drafts with a MODEL: a DecodeEngine of the same batch (kept on the
-    engine) draws the k tokens of every sequence under the same settings and hands its logits rows to the verify step; without `sample` it
-    drafts greedily and the verify-greedy graph checks it.
-    ValueError: speculate together with the sample ARGUMENT; the keys sample / draft_model with an engine passed in that was built without
-    spec_sample=True; draft together with draft_model; a draft model of another vocabulary size; k outside 1 .. 15; an engine passed in whose
-    batch is not len(prompts) or whose batch_chunk is not k + 1; fewer than two prompts; unknown keys."""
-    settings = None if sample is None else _sampling_settings('engine_generate_batch', sample)
-    proc = None if sample is None else _process_settings(sample)
-    spec = None
-    if speculate is not None:
-        if sample is not None:
-            raise ValueError('engine_generate_batch: speculate and the sample argument exclude each other (speculative sampling: the key '
-                             'sample inside speculate)')
-        spec = _speculate_settings(speculate) + _speculate_sampling(speculate, model, 'engine_generate_batch')
-        if (spec[3] is not None or spec[4] is not None) and engine is not None and not engine.spec_sample:
-            raise ValueError('engine_generate_batch: speculate with sample or draft_model needs an engine built with spec_sample=True')
+    """engine_generate for a LIST of prompts of different lengths (1-D id tensors): the same driver, arguments and ValueErrors, and what differs:
+    all prompts enter through ONE DecodeEngine.prefill_batch (there is no prefill= route: nothing of `transformers` is involved, and the
+    prompts are pad-free, so every row's history is its own prompt and tokens); a step is one replay for all rows, and a row that has emitted
+    its eos keeps stepping and disturbs no other row.  Returns a list of 1-D tensors, prompt + generated, each cut after its first
+    eos_token_id.  engine.batch must equal len(prompts) (engine=None builds one of that batch); max(T) + max_new_tokens <= t_max.
+    sample=: every value a scalar for all rows or one value per prompt (logit_bias: one dict for all); a row with temperature 0 stays greedy.
+    speculate=: at least two prompts, on an engine with batch = len(prompts) and batch_chunk = k + 1 (one pass over the weights at M = batch
+    x (k + 1) per step: capture_verify_greedy_batch); a sequence that has hit its eos or its length idles; where no active sequence has two
+    tokens left, or an active chunk no longer fits the cache, the single-step graph finishes all rows.  eng.spec_stats = dict(steps,
+    emitted=[per sequence], accepted=[per sequence: per step]).  The keys sample / draft_model in there need an engine built with
+    spec_sample=True (capture_verify_sample_batch: gptq_spec_sample_batch_f16 on all sequences in one launch).
+    ValueError also: an engine passed in whose batch is not len(prompts) or whose batch_chunk is not k + 1, or that lacks spec_sample where it
+    is needed; an empty list or prompt; max_new_tokens below 1."""
+    what = 'engine_generate_batch'
+    settings, proc, spec = _generation_settings(what, model, sample, speculate, engine)
+    sampled = spec is not None and (spec[3] is not None or spec[4] is not None)
+    if sampled and engine is not None and not engine.spec_sample:
+        raise ValueError('engine_generate_batch: speculate with sample or draft_model needs an engine built with spec_sample=True')
     n = len(prompts)
     if n < 1 or any((not torch.is_tensor(p)) or p.dim() != 1 or p.numel() == 0 for p in prompts):
         raise ValueError('engine_generate_batch: prompts must be a non-empty list of non-empty 1-D id tensors')
@@ -2023,55 +1968,16 @@ def engine_generate_batch(model, prompts, max_new_tokens, eos_token_id=None, eng
                          '%d, batch_chunk %d)' % (spec[0], n, n, spec[0] + 1, engine.batch, engine.batch_chunk))
     if engine is not None:
         eng = engine
-        if proc is not None and not eng.logits_process:
-            raise ValueError('engine_generate_batch: %s need an engine built with logits_process=True' % ', '.join(sorted(proc)))
     elif spec is not None:
-        eng = DecodeEngine(model, t_max=t_max, batch=n, batch_chunk=spec[0] + 1, spec_sample=spec[3] is not None or spec[4] is not None)
+        eng = DecodeEngine(model, t_max=t_max, batch=n, batch_chunk=spec[0] + 1, spec_sample=sampled)
     else:
         eng = DecodeEngine(model, t_max=t_max, batch=n, logits_process=proc is not None)
     if eng.batch != n:
         raise ValueError('engine_generate_batch: %d prompts for an engine of batch %d' % (n, eng.batch))
     if max(int(p.numel()) for p in prompts) + max_new_tokens > eng.t_max:
         raise ValueError('engine_generate_batch: prompt + max_new_tokens exceeds the engine cache (%d)' % eng.t_max)
-    if spec is not None:
-        return _engine_generate_batch_speculative(prompts, max_new_tokens, eos_token_id, eng, *spec)
-    if settings is not None:
-        eng.set_sampling(**settings)
-        if eng.logits_process:                               # (an engine passed in with the flag, neutral keys: its processors are switched off)
-            eng.set_logits_process(eos_token_id=eos_token_id, **(proc or {}))
-    with torch.no_grad():
-        if settings is not None:
-            if eng.sample_native_graph is None:
-                eng.pos.zero_()
-                eng.capture_sample_native()
-            graph = eng.sample_native_graph
-            logits = eng.prefill_batch(prompts, starts=[0] * n)
-            if eng.logits_process:
-                eng.process_logits(logits)
-            first = eng.sample_logits(logits)
-        else:
-            if eng.greedy_rows_graph is None:
-                eng.pos.zero_()                                  # (the capture's warm-up step writes cache row pos of every row)
-                eng.capture_greedy_rows()
-            graph = eng.greedy_rows_graph
-            first = eng.prefill_batch(prompts, starts=[0] * n).argmax(dim=-1)
-        eng.ids.copy_(first)
-        eng.stepc.zero_()                                        # stream_rows[k] = the tokens chosen by replay k
-        done = 1
-        hit = (first == eos_token_id) if eos_token_id is not None else None
-        while done < max_new_tokens and not (hit is not None and bool(hit.all())):
-            burst = min(16, max_new_tokens - done)               # the host looks at the stream every 16 steps only
-            for _ in range(burst):
-                graph.replay()
-            if hit is not None:
-                hit = hit | (eng.stream_rows[done - 1:done - 1 + burst] == eos_token_id).any(dim=0)
-            done += burst
-        gen = torch.cat([first.unsqueeze(0), eng.stream_rows[:done - 1]]).t()      # [row][step]
-        out = []
-        for i, p in enumerate(prompts):
-            g = _cut_after_eos(gen[i], eos_token_id)
-            out.append(torch.cat([p, g.to(device=p.device, dtype=p.dtype)]))
-    return out
+    gens = _generate_rows(what, eng, prompts, lambda e: e.prefill_batch(prompts, starts=[0] * n), max_new_tokens, eos_token_id, settings, proc, spec)
+    return [torch.cat([p, g.to(device=p.device, dtype=p.dtype)]) for p, g in zip(prompts, gens)]
 
 
 def benchmark_decode_engine(model, tokens=64, t_max=2048, seed=0, graph=True, fuse_norm=True, fuse_attn=True, start_pos=0, batch=1):

@@ -42,7 +42,7 @@ import weakref
 
 import torch
 
-from .decode import MAX_BATCH
+from .decode import MAX_BATCH, _self_feeding_tail
 
 ENABLED = os.environ.get('GPTQ_DECODE_ENGINE', '1') != '0'
 # Memory mode is the DEFAULT since round 4: when the engine is first built every eligible module (trivial g_idx, 2 / 4 / 8 bits, an image)
@@ -414,6 +414,7 @@ def _greedy_fast(model, st, orig_generate, args, kwargs):
     st.engine, st.cache_ref = None, None
     rng0 = torch.cuda.get_rng_state(dev) if sample else None          # (a call handed back to HF's loop must draw what it would have drawn)
     with torch.no_grad():
+        graph = None if sample else eng.graph_for('greedy_rows')          # (before the prompt is in the engine's cache: DecodeEngine.graph_for)
         # the prompt and the FIRST token are HF's own: its generate for one new token (its prefill inputs, its processors on that step)
         kw1 = {k: v for k, v in kwargs.items() if k not in ('input_ids', 'inputs', 'max_new_tokens', 'max_length', 'min_length', 'min_new_tokens')}
         if min_new >= 1:
@@ -433,24 +434,10 @@ def _greedy_fast(model, st, orig_generate, args, kwargs):
             graph = eng.sample_graphs.get(wkey) or eng.capture_sample_rows(wkey, warpers)
             gen_state = torch.cuda.default_generators[dev.index if dev.index is not None else torch.cuda.current_device()]
             off0 = gen_state.get_offset()
-        else:
-            if eng.greedy_rows_graph is None:
-                eng.capture_greedy_rows()
-            graph = eng.greedy_rows_graph
-        eng.stepc.zero_()
-        eng.ids.copy_(first)
         eos_t = torch.tensor(eos, device=dev, dtype=torch.int64) if eos else None
-        done = 1                              # tokens per row so far: `first`, then rows 0 .. done - 2 of stream_rows
-        stream = lambda: torch.cat([first[None, :], eng.stream_rows[:done - 1]], 0)           # [done, B]
-        all_hit = lambda: eos_t is not None and bool(torch.isin(stream(), eos_t).any(0).all())
-        while done < new and not all_hit():
-            burst = min(16, new - done)                       # the host looks at the stream every 16 tokens only
-            for _ in range(burst):
-                graph.replay()
-            done += burst
-            st.steps += burst
-        gen = stream().t().contiguous()                       # [B, done]
-        length = done
+        gen = _self_feeding_tail(eng, graph, first, new, eos or None).t().contiguous()          # [B, done]: `first` and done - 1 replays
+        done = length = gen.shape[1]
+        st.steps += done - 1
         if eos_t is not None:
             hit = torch.isin(gen, eos_t)
             anyhit = hit.any(1)
