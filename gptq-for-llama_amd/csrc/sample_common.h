@@ -1,7 +1,8 @@
 // sample_common.h -- the device code gptq_sample_rows_f16 (sample.hip) and gptq_spec_sample_rows_f16 (spec_sample.hip) share: the order-preserving
 // 16-bit key of an fp16 logit, the row scan that needs 2-byte alignment only, a token's integer mass, the 256-bin radix select of one wave, and --
 // for kernels that look at more than one row per workgroup -- the passes A .. D of sample.hip as a function (select_row) and its pass E as a
-// function of any mass (draw_row).  sample.hip states the method; its kernel keeps its own straight-line copy of the passes.
+// function of any mass (draw_row).  sample.hip states the method; its kernel keeps its own straight-line copy of the passes.  beam.hip takes the
+// key, the row scan and the count-only select from here.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -112,6 +113,28 @@ GPTQ_DEV void wave_select(const uint32_t *hc, const u64 *hm, uint32_t baseC, u64
             out->pabove = ma[j];
             out->pge = ma[j] + m[j];
         }
+    }
+}
+
+// the same for counts alone (beam.hip: no masses): sets out->kbin and out->kcnt for k > 0
+GPTQ_DEV void wave_select(const uint32_t *hc, uint32_t baseC, uint32_t k, Select *out, int lane) {
+    uint32_t c[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) c[j] = hc[4 * lane + j];
+    const uint32_t cs = c[0] + c[1] + c[2] + c[3];
+    uint32_t ci = cs;
+    for (int d = 1; d < 64; d <<= 1) {           // inclusive suffix sums over the lanes
+        const uint32_t cn = __shfl_down(ci, d, 64);
+        if (lane + d < 64) ci += cn;
+    }
+    uint32_t cr = baseC + ci - cs;               // elements above this lane's bins
+#pragma unroll
+    for (int j = 3; j >= 0; j--) {
+        if (cr < k && cr + c[j] >= k) {
+            out->kbin = 4 * lane + j;
+            out->kcnt = cr;
+        }
+        cr += c[j];
     }
 }
 

@@ -186,6 +186,11 @@ _SIGNATURES = {
     # (csrc/logits_process.hip)
     'gptq_logits_process_f16': [c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
                                 c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p],
+    # beam search: one step on N rows of logits with all bookkeeping in one device block, and the in-place move of K/V histories between cache
+    # rows (csrc/beam.hip)
+    'gptq_beam_state_bytes': [c_int, c_int],
+    'gptq_beam_select_f16': [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p],
+    'gptq_kv_reorder_f16': [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p],
 }
 
 
@@ -229,6 +234,7 @@ def lib():
             L.gptq_decode_attn_chunk_batch_workspace_bytes.restype = c_size_t
             L.gptq_spec_sample_workspace_bytes.restype = c_size_t
             L.gptq_spec_sample_batch_workspace_bytes.restype = c_size_t
+            L.gptq_beam_state_bytes.restype = c_size_t
             L.gptq_layer_destroy.restype = None
             L.gptq_strerror.argtypes = [c_int]
             L.gptq_strerror.restype = ctypes.c_char_p

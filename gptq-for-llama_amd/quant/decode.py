@@ -180,6 +180,11 @@ LM_HEAD_KERNEL = os.environ.get('GPTQ_LM_HEAD_KERNEL', '1') != '0'   # 0: final 
 MAX_BATCH = 16         # rows of a decode batch one engine serves (the LM head kernel and the decode kernel's row groups end there)
 MAX_CHUNK_ROWS = 128   # rows of a batched verify step (batch x batch_chunk): what gptq_layer_decode_f16 and the batched chunk attention take
 MAX_PROCESS_EOS, MAX_PROCESS_BIAS, MAX_PROCESS_VOCAB = 8, 256, 131072      # GPTQ_LOGITS_PROCESS_MAX_EOS / _BIAS / _VOCAB
+MAX_BEAMS = 16         # GPTQ_BEAM_MAX_BEAMS
+BEAM_DEAD = -1e9
+# gptq_beam_select_f16's state block in 4-byte words (gptq_mi355x.h "beam search")
+(BEAM_W_EOS, BEAM_W_MAX_NEW, BEAM_W_LP, BEAM_W_ES, BEAM_W_T_CAP, BEAM_W_BEAMS, BEAM_W_T, BEAM_W_OPEN, BEAM_W_DONE, BEAM_W_STATUS) = range(10)
+BEAM_W_SCORE, BEAM_W_PARENT, BEAM_W_TOKEN, BEAM_W_POOL, BEAM_W_CAND, BEAM_W_REC, BEAM_W_TABLES = 16, 32, 48, 80, 160, 288, 1376
 
 
 def lm_head_logits(eng, x, logits, s, h=None):
@@ -212,8 +217,12 @@ def lm_head_logits(eng, x, logits, s, h=None):
 
 class DecodeEngine:
 
-    def __init__(self, model, t_max=2048, fuse_norm=True, fuse_attn=True, batch=1, chunk=0, batch_chunk=0, spec_sample=False, logits_process=False):
-        """logits_process = True adds the LOGIT PROCESSORS (gptq_logits_process_f16: repetition / presence penalty, logit bias, the
+    def __init__(self, model, t_max=2048, fuse_norm=True, fuse_attn=True, batch=1, chunk=0, batch_chunk=0, spec_sample=False, logits_process=False, beam_search=False):
+        """beam_search = True (with batch = N, 2 .. 16) makes the N rows the running beams of ONE beam search (HF's rule: gptq_mi355x.h "beam
+        search"): the state block of gptq_beam_select_f16 -- set_beam_search, beam_select, beam_begin, capture_beam_step, beam_result,
+        engine_generate_beam.  False (the default) allocates nothing and those calls raise.  ValueError together with logits_process, chunk or
+        batch_chunk.
+        logits_process = True adds the LOGIT PROCESSORS (gptq_logits_process_f16: repetition / presence penalty, logit bias, the
         min-new-tokens EOS mask) to every step: hist int32 [B, t_max] -- hist[b, p] = the token row b consumed at position p, kept by the prompt
         calls and by the process launch itself --, gen_start int64 [B], rep_penalty / presence_penalty float [B], min_new int32 [B], eos_ids
         int32 [8], bias_ids / bias_vals [256] with their counts on the host (set_logits_process, set_history, process_logits).  decode(token)
@@ -257,6 +266,10 @@ class DecodeEngine:
         self.logits_process = bool(logits_process)
         if self.logits_process and (self.chunk or self.batch_chunk):
             raise ValueError('DecodeEngine: logits_process together with chunk / batch_chunk is not built yet (processors under speculation)')
+        self.beam_search = bool(beam_search)
+        if self.beam_search and (self.logits_process or self.chunk or self.batch_chunk or not 2 <= self.batch <= MAX_BEAMS):
+            raise ValueError('DecodeEngine: beam_search needs batch = 2 .. %d beams and combines with neither logits_process, chunk nor batch_chunk'
+                             % MAX_BEAMS)
         self.fuse_norm, self.fuse_attn = bool(fuse_norm), bool(fuse_attn)
         self.native = _native
         self.lib = _native.lib()
@@ -328,6 +341,19 @@ class DecodeEngine:
                                    dtype=torch.uint8, device=dev)
         self.ws = _native.workspace(dev)
         self.graph = None
+        self.beam_graph = None
+        if self.beam_search:
+            # gptq_beam_select_f16's ONE state block (int32 words, gptq_mi355x.h): settings, scores, the step's parents and tokens, the pool, the
+            # back-pointer tables of t_max steps
+            if self.logits.shape[1] < 2 * B:
+                raise ValueError('DecodeEngine: beam_search with %d beams needs a vocabulary of at least %d' % (B, 2 * B))
+            nbytes = self.lib.gptq_beam_state_bytes(B, self.t_max)
+            if nbytes != 4 * (BEAM_W_TABLES + 2 * self.t_max * B):
+                raise RuntimeError('DecodeEngine: the library lays the beam state block out differently from BEAM_W_* (%d bytes)' % nbytes)
+            self.beam_state = torch.zeros(nbytes // 4, dtype=torch.int32, device=dev)
+            self.beam_parent = self.beam_state[BEAM_W_PARENT:BEAM_W_PARENT + B]
+            self.beam_token = self.beam_state[BEAM_W_TOKEN:BEAM_W_TOKEN + 2 * B].view(torch.int64)
+            self.set_beam_search(self.t_max)
         self.scratch = None
         self._rope_tabs, self._prefill_bufs, self._nll_ws = {}, None, None      # filled on first use: _rope_table, _prefill_buffers, _nll_rows
         # batch 1: the attention's splits are merged by o_proj's decode kernel when every o_proj can (trivial g_idx, an image, no bias next to the residual)
@@ -913,6 +939,115 @@ class DecodeEngine:
         self._process_launch(rows, n, last, 0)
         return logits
 
+    # -- beam search: the N rows are the running beams; gptq_beam_select_f16 + gptq_kv_reorder_f16 (csrc/beam.hip) behind the batch step ---------
+    def _need_beam_search(self, what):
+        if not self.beam_search:
+            raise ValueError('DecodeEngine.%s: the engine was built without beam_search=True' % what)
+
+    def set_beam_search(self, max_new_tokens, eos_token_id=None, length_penalty=1.0, early_stopping=False):
+        """the settings of the next search, and its state put back to the start: scores [0, DEAD ..], an empty pool, t = 0, open, not done.
+        Only the device block changes: a captured beam step serves the new search at its next replay.  ValueError: max_new_tokens outside
+        1 .. t_max; more than one EOS id, or one outside the vocabulary; a length_penalty that is not finite; early_stopping other than
+        False, True or 'never'."""
+        self._need_beam_search('set_beam_search')
+        what = 'DecodeEngine.set_beam_search'
+        if isinstance(max_new_tokens, bool) or not isinstance(max_new_tokens, int) or not 1 <= max_new_tokens <= self.t_max:
+            raise ValueError('%s: max_new_tokens = %r must be 1 .. %d' % (what, max_new_tokens, self.t_max))
+        if isinstance(eos_token_id, (list, tuple)):
+            if len(eos_token_id) > 1:
+                raise ValueError('%s: beam search takes one EOS id, not %r' % (what, eos_token_id))
+            eos_token_id = eos_token_id[0] if eos_token_id else None
+        if eos_token_id is not None and (isinstance(eos_token_id, bool) or not isinstance(eos_token_id, int) or
+                                         not 0 <= eos_token_id < self.logits.shape[1]):
+            raise ValueError('%s: eos_token_id = %r outside [0, %d)' % (what, eos_token_id, self.logits.shape[1]))
+        if isinstance(length_penalty, bool) or not isinstance(length_penalty, (int, float)) or not math.isfinite(length_penalty):
+            raise ValueError('%s: length_penalty = %r' % (what, length_penalty))
+        modes = [m for m, v in ((0, False), (1, True), (2, 'never')) if early_stopping is v or (isinstance(v, str) and early_stopping == v)]
+        if not modes:
+            raise ValueError("%s: early_stopping = %r must be False, True or 'never'" % (what, early_stopping))
+        B = self.batch
+        w = np.zeros(BEAM_W_TABLES, dtype=np.int32)
+        f = w.view(np.float32)
+        w[BEAM_W_EOS], w[BEAM_W_MAX_NEW], w[BEAM_W_ES] = -1 if eos_token_id is None else eos_token_id, max_new_tokens, modes[0]
+        f[BEAM_W_LP] = length_penalty
+        w[BEAM_W_T_CAP], w[BEAM_W_BEAMS], w[BEAM_W_OPEN] = self.t_max, B, 1
+        f[BEAM_W_SCORE:BEAM_W_SCORE + MAX_BEAMS] = BEAM_DEAD
+        f[BEAM_W_SCORE] = 0.0
+        f[BEAM_W_POOL:BEAM_W_CAND:5] = BEAM_DEAD
+        with torch.no_grad():
+            self.beam_state.zero_()
+            self.beam_state[:BEAM_W_TABLES].copy_(torch.from_numpy(w))
+        return self
+
+    def beam_select(self, logits):
+        """one beam step (gptq_beam_select_f16) on `logits`, any fp16 [N, vocab] tensor with unit column stride on the engine's device: the
+        state block advances -- scores, beam_parent (int32 [N]), beam_token (int64 [N]), pool, tables, flags"""
+        self._need_beam_search('beam_select')
+        B = self.batch
+        if logits.dim() != 2 or logits.shape[0] != B or logits.dtype != torch.float16 or logits.device != self.ids.device or \
+                logits.stride(1) != 1 or logits.shape[1] < 2 * B or logits.stride(0) < logits.shape[1]:
+            raise ValueError('DecodeEngine.beam_select: logits must be fp16 [%d, vocab >= %d] with unit column stride on %s' % (B, 2 * B, self.dev))
+        with self.native.on_device(self.dev):
+            rc = self.lib.gptq_beam_select_f16(logits.data_ptr(), logits.stride(0), B, logits.shape[1], self.beam_state.data_ptr(),
+                                               self.native.stream_ptr(self.dev))
+        self.native.check(rc, 'gptq_beam_select_f16')
+
+    def _beam_reorder(self):
+        """cache row b continues row beam_parent[b] at positions [0, pos[0]) (gptq_kv_reorder_f16: in place, every layer, both caches)"""
+        with self.native.on_device(self.dev):
+            rc = self.lib.gptq_kv_reorder_f16(self.kcb.data_ptr(), self.vcb.data_ptr(), self.kcb.shape[0], self.batch, self.t_max, self.hidden,
+                                              self.kcb.stride(0), self.beam_parent.data_ptr(), self.pos.data_ptr(),
+                                              self.native.stream_ptr(self.dev))
+        self.native.check(rc, 'gptq_kv_reorder_f16')
+
+    def _beam_advance(self, logits):
+        self.beam_select(logits)
+        self._beam_reorder()
+        self.ids.copy_(self.beam_token)
+
+    def beam_begin(self, first_logits):
+        """the first step of a search whose prompt sits in cache row 0 (prefill; pos[0] = its length): the one row of prompt logits stands for all
+        N beams -- only beam 0 is alive --, select, the reorder replicates row 0's prompt into every row, ids <- the N first tokens"""
+        self._need_beam_search('beam_begin')
+        with torch.no_grad():
+            rows = first_logits.reshape(1, -1).to(device=self.dev, dtype=torch.float16).expand(self.batch, -1).contiguous()
+            self.pos.copy_(self.pos[:1].clone().expand(self.batch))
+            self._beam_advance(rows)
+
+    def _beam_step(self):
+        """one step of the search: the batch step on the beams' tokens, select on its logits, the reorder, ids <- the step's tokens"""
+        self._step()
+        self._beam_advance(self.logits)
+
+    def capture_beam_step(self):
+        """capture _beam_step ONCE: settings and state are device memory, so set_beam_search never re-captures"""
+        self._need_beam_search('capture_beam_step')
+        self.beam_graph = self._capture(self._beam_step, (self.pos, self.ids, self.beam_state))
+        return self.beam_graph
+
+    def beam_result(self, num_return_sequences=1):
+        """the best finished hypotheses of the pool, best first: (list of 1-D int64 tensors -- the tokens, a closing EOS included --, float32
+        scores: HF's sequences_scores).  One download of the state block; the tokens come from the back-pointer tables."""
+        self._need_beam_search('beam_result')
+        B, T = self.batch, self.t_max
+        if not 1 <= num_return_sequences <= B:
+            raise ValueError('DecodeEngine.beam_result: num_return_sequences = %r for %d beams' % (num_return_sequences, B))
+        w = self.beam_state.cpu().numpy()
+        parent_at = w[BEAM_W_TABLES:BEAM_W_TABLES + T * B].reshape(T, B)
+        token_at = w[BEAM_W_TABLES + T * B:BEAM_W_TABLES + 2 * T * B].reshape(T, B)
+        seqs, scores = [], []
+        for i in range(num_return_sequences):
+            e = w[BEAM_W_POOL + 5 * i:BEAM_W_POOL + 5 * i + 5]
+            if not e[1]:
+                raise RuntimeError('DecodeEngine.beam_result: the pool holds %d finished hypotheses, %d were asked for' % (i, num_return_sequences))
+            step, beam = int(e[2]), int(e[3])
+            toks = [0] * step + [int(e[4])]
+            for u in range(step - 1, -1, -1):
+                toks[u], beam = int(token_at[u, beam]), int(parent_at[u, beam])
+            seqs.append(torch.tensor(toks, dtype=torch.int64))
+            scores.append(e[:1].view(np.float32)[0])
+        return seqs, torch.tensor(np.array(scores, dtype=np.float32))
+
     def capture(self):
         """warm up once (module loads, workspace), then capture one decode step into a hipGraph."""
         self.reset()
@@ -1460,7 +1595,7 @@ class DecodeEngine:
 
     def graph_for(self, kind, draft_logits=False):
         """THE place that hands out the graphs of the generation drivers: the captured graph of `kind` -- 'greedy' (batch 1: capture_greedy),
-        'greedy_rows', 'sample_native', 'verify_greedy', 'verify_sample' (draft_logits: the one that reads the draft model's logits rows) --,
+        'greedy_rows', 'sample_native', 'verify_greedy', 'verify_sample' (draft_logits: the one that reads the draft model's logits rows), 'beam' --,
         captured by the public capture_* method on first use.  A capture warms up with a real step, which writes the cache rows at pos: pos is
         put to 0 first, so that the step fits whatever an earlier sequence left there.  A driver therefore asks for EVERY graph it will need
         BEFORE its prompt enters the cache: behind a prompt, the warm-up step at position 0 would overwrite the prompt's first cache row, and
@@ -1473,6 +1608,7 @@ class DecodeEngine:
             'verify_greedy': (lambda: self.verify_graph, self.capture_verify_greedy_batch if self.batch_chunk else self.capture_verify_greedy),
             'verify_sample': (lambda: self.verify_sample_graphs.get(with_q), lambda: (
                 self.capture_verify_sample_batch if self.batch_chunk else self.capture_verify_sample)(draft_logits=with_q)),
+            'beam': (lambda: self.beam_graph, self.capture_beam_step),
         }[kind]
         if held() is None:
             self.pos.zero_()
@@ -1978,6 +2114,50 @@ def engine_generate_batch(model, prompts, max_new_tokens, eos_token_id=None, eng
         raise ValueError('engine_generate_batch: prompt + max_new_tokens exceeds the engine cache (%d)' % eng.t_max)
     gens = _generate_rows(what, eng, prompts, lambda e: e.prefill_batch(prompts, starts=[0] * n), max_new_tokens, eos_token_id, settings, proc, spec)
     return [torch.cat([p, g.to(device=p.device, dtype=p.dtype)]) for p, g in zip(prompts, gens)]
+
+
+def engine_generate_beam(model, input_ids, max_new_tokens, num_beams=4, eos_token_id=None, length_penalty=1.0, early_stopping=False,
+                         num_return_sequences=1, engine=None, t_max=2048, prefill='engine'):
+    """Beam search for ONE prompt ([1, T] ids) on the DecodeEngine, by HF's rule (`generate(num_beams=N, do_sample=False)` with at most one EOS id
+    and no logit processors; gptq_mi355x.h "beam search"): the prompt enters cache row 0 (prefill: 'engine' or 'hf', as engine_generate), beam_begin
+    chooses the N first tokens and replicates the prompt's cache rows, and every further step is ONE replay of the capture_beam_step graph -- the
+    batch step at M = N, the select, the in-place cache reorder -- behind which the host reads the 4-byte `done` flag.  Returns (sequences, scores):
+    the num_return_sequences best hypotheses, best first, each a 1-D tensor prompt + tokens (a closing EOS included), and their float32
+    length-penalised scores (HF's sequences_scores).  engine=None builds DecodeEngine(model, t_max, batch=num_beams, beam_search=True).
+    ValueError: a prompt that is not [1, T]; num_beams outside 2 .. 16; an engine whose batch is not num_beams or that lacks beam_search;
+    num_return_sequences outside 1 .. num_beams; more than one EOS id; prompt + max_new_tokens beyond the cache; a vocabulary below 2 num_beams;
+    a row of logits that was not finite (the state's status word) -- raised after the run."""
+    what = 'engine_generate_beam'
+    if prefill not in ('hf', 'engine'):
+        raise ValueError("%s: prefill must be 'hf' or 'engine', not %r" % (what, prefill))
+    if input_ids.dim() != 2 or input_ids.shape[0] != 1 or input_ids.shape[1] < 1:
+        raise ValueError('%s: one prompt [1, T] only' % what)
+    if isinstance(num_beams, bool) or not isinstance(num_beams, int) or not 2 <= num_beams <= MAX_BEAMS:
+        raise ValueError('%s: num_beams = %r must be 2 .. %d' % (what, num_beams, MAX_BEAMS))
+    if engine is not None and (engine.batch != num_beams or not engine.beam_search):
+        raise ValueError('%s: needs an engine of batch %d built with beam_search=True' % (what, num_beams))
+    if isinstance(num_return_sequences, bool) or not isinstance(num_return_sequences, int) or not 1 <= num_return_sequences <= num_beams:
+        raise ValueError('%s: num_return_sequences = %r for %d beams' % (what, num_return_sequences, num_beams))
+    max_new_tokens = int(max_new_tokens)
+    if max_new_tokens < 1:
+        raise ValueError('%s: max_new_tokens must be positive' % what)
+    if model.lm_head.weight.shape[0] < 2 * num_beams:
+        raise ValueError('%s: %d beams need a vocabulary of at least %d' % (what, num_beams, 2 * num_beams))
+    eng = engine if engine is not None else DecodeEngine(model, t_max=t_max, batch=num_beams, beam_search=True)
+    if input_ids.shape[1] + max_new_tokens > eng.t_max:
+        raise ValueError('%s: prompt + max_new_tokens exceeds the engine cache (%d)' % (what, eng.t_max))
+    with torch.no_grad():
+        graph = eng.graph_for('beam')                            # (before the prompt: a capture warms up with a real step)
+        eng.set_beam_search(max_new_tokens, eos_token_id, length_penalty, early_stopping)
+        eng.beam_begin(_prompt_into_engine(model, input_ids, eng, prefill))
+        done = eng.beam_state[BEAM_W_DONE:BEAM_W_DONE + 1]
+        while not int(done):
+            graph.replay()
+        if int(eng.beam_state[BEAM_W_STATUS]):
+            raise ValueError('%s: a row of logits was not finite, or the state block was not set up (status %d)' % (
+                what, int(eng.beam_state[BEAM_W_STATUS])))
+        seqs, scores = eng.beam_result(num_return_sequences)
+    return [torch.cat([input_ids[0], g.to(device=input_ids.device, dtype=input_ids.dtype)]) for g in seqs], scores
 
 
 def benchmark_decode_engine(model, tokens=64, t_max=2048, seed=0, graph=True, fuse_norm=True, fuse_attn=True, start_pos=0, batch=1):

@@ -10,8 +10,8 @@ per layer and replayed as one hipGraph -- and everything else (prefill, training
 original forward untouched.  Beam search goes the eager way too (round 6): HF permutes the rows of the cache IN PLACE after
 every step (``cache.reorder_cache(beam_idx)``), which the engine's static per-row K/V cache would not follow -- ``generate(num_beams > 1)``
 switches the hook off for the call, and a tracked cache whose ``reorder_cache`` is called by anyone is completed, released and never
-tracked again.  The caller keeps its API: HF ``generate`` with its own sampling, stopping
-criteria and cache object.  Round 6: the one call HF's loop only slows down -- plain GREEDY ``generate`` of one prompt with nothing between the steps --
+tracked again (beam search at graph speed is a call of its own, ``quant.decode.engine_generate_beam``).  The caller keeps its API:
+HF ``generate`` with its own sampling, stopping criteria and cache object.  Round 6: the one call HF's loop only slows down -- plain GREEDY ``generate`` of one prompt with nothing between the steps --
 runs the engine's self-feeding greedy graph instead (``_greedy_fast`` below: the same tokens, no host round trip per token).
 
 Cache protocol: the engine owns a static K/V cache.  The first decode step after a prefill copies the caller's cache

@@ -813,6 +813,56 @@ int gptq_logits_process_f16(void *logits, int64_t ld, int seqs, int rows, int vo
                             const float *presence_penalty, const int32_t *min_new_tokens, const int32_t *eos_ids, int n_eos,
                             const int32_t *bias_ids, const float *bias_vals, int n_bias, gptq_stream_t stream);
 
+/* ---- beam search: one step of HF's `_beam_search` (one prompt, do_sample=False, at most one EOS id, no logit processors) on N = `beams` rows
+ * of fp16 logits, every piece of bookkeeping in ONE device block, and the in-place move of K/V histories between cache rows (csrc/beam.hip;
+ * tests/beam_ref.py restates the rule in float64).
+ *
+ * The state block: gptq_beam_state_bytes(beams, t_max) bytes, 16-byte aligned, 4-byte words (0 for beams outside 2 .. 16 or t_max < 1).  The
+ * HOST writes words 0 .. 9, the scores and the pool before the first step; the select entry trusts t_cap and must be given the block it was
+ * sized for.  Per-beam arrays have 16 slots whatever N is.  DEAD = -1e9.
+ *   word 0 eos (int32, -1: none)   1 max_new   2 length_penalty (float)   3 early_stopping (0 False, 1 True, 2 "never")
+ *        4 t_cap = the t_max the block was sized with   5 beams = N   6 t = steps done   7 open   8 done   9 status   10 .. 15 reserved (0)
+ *   16   score[16]   float: the running beams; [0, DEAD, ..] before the first step
+ *   32   parent[16]  int32: the last step's parents -- what gptq_kv_reorder_f16 reads
+ *   48   token[16]   int64: the last step's tokens -- the next step's input ids
+ *   80   pool[16]    5 words each {score float, finished, step, parent, token}: the finished hypotheses in descending score order; an entry
+ *                    stands for token at step `step` behind running beam `parent` of step `step` - 1; {DEAD, 0, 0, 0, 0} before the first step
+ *   160  cand[32]    4 words each {score float, parent, token, hit}: the 2N candidates of the last step in rank order, for inspection
+ *   288  rec[16]     68 words each: launch A's record of a row {max float, log sum float, bad, 0, 2N x (id, fp16 bits)} in (logit descending,
+ *                    id ascending) order -- the hand-off between the two launches
+ *   1376 parent_at[t_cap][N] int32, then token_at[t_cap][N] int32: the back-pointers; the host rebuilds a hypothesis from them (no token history
+ *                    moves on the device): tokens[step] = token, beam = parent, then for u = step - 1 .. 0: tokens[u] = token_at[u][beam],
+ *                    beam = parent_at[u][beam]
+ * status: bit 0 a row held a NaN or +inf or -inf only (all its candidates score DEAD; parents and ids stay in range); bit 1 the block was not set
+ * up for the call (beams differs, t outside [0, t_cap)): nothing but status and done is written.  With done set the step changes nothing.
+ *
+ * gptq_beam_select_f16: one step on logits [N, vocab] (ld >= vocab, rows 2-byte aligned only; row b follows running beam b), two launches:
+ *   1  c(b, v) = fp32(score[b] + log_softmax(logits_b)(v)), log_softmax from the row's maximum and the fp32 log of a fixed-tree sum of exp(l - max):
+ *      equal logits of a row give bit-equal scores, and the same inputs the same bits on every call
+ *   2  the 2N best candidates by (score descending, b ascending, v ascending) -- vocab >= 2N, so the first step takes them all from beam 0
+ *   3  hit[r] = v_r == eos or t + 1 >= min(max_new, t_cap).  The next running beams: the candidates ordered by (score with every hit at DEAD,
+ *      descending; rank ascending), the first N of them with that score, their parent b_r and token v_r; row t of the tables
+ *   4  candidate r is offered to the pool with score c_r / (t + 1)^length_penalty iff hit[r], r < N, open, and not (pool full before this step
+ *      and early_stopping 1).  The pool keeps the best N of its entries and the offers; an entry wins a tie against an offer, offers keep rank order
+ *   5  t += 1; open &= any_i (score[0] / L^length_penalty > (pool[i] finished ? the pool's minimum score : DEAD)), L = max_new where
+ *      early_stopping is 2 and length_penalty > 0, else t
+ *   6  done = not (open and not (pool full and early_stopping 1) and not all 2N candidates hit)
+ * Validated before any launch: GPTQ_E_NULL (logits, state), GPTQ_E_SHAPE (beams outside 2 .. 16, vocab < 2 beams, ld < vocab), GPTQ_E_ALIGN
+ * (logits 2 bytes, state 16).
+ *
+ * gptq_kv_reorder_f16: caches [layers][rows][t_max][row_elems] fp16 (layer l at + l layer_stride elements, layer_stride >= rows t_max row_elems).
+ * Row b of every layer of both caches becomes a copy of row parent[b] at positions [0, len[0]) -- in place, swaps and cycles included: one
+ * thread owns a 16-byte column across all rows, loads what it needs and stores only the rows with parent[b] != b.  parent (int32 [rows]) and len
+ * (int64 [1], clamped into [0, t_max]) are DEVICE memory: a captured launch serves every step.  Nothing at or past len is read or written; an
+ * identity step writes nothing; a parent outside [0, rows) leaves its row alone.  parent = 0 for all rows replicates row 0 (a prompt).
+ * Validated before the launch: GPTQ_E_NULL (the caches, parent, len), GPTQ_E_SHAPE (layers < 1, rows outside 1 .. 16, t_max < 1, row_elems < 8 or
+ * not a multiple of 8, layer_stride too small or not a multiple of 8), GPTQ_E_ALIGN (caches 16 bytes, parent 4, len 8). */
+#define GPTQ_BEAM_MAX_BEAMS 16
+size_t gptq_beam_state_bytes(int beams, int t_max);
+int gptq_beam_select_f16(const void *logits, int64_t ld, int beams, int vocab, void *state, gptq_stream_t stream);
+int gptq_kv_reorder_f16(void *k_cache, void *v_cache, int layers, int rows, int t_max, int row_elems, int64_t layer_stride, const int32_t *parent,
+                        const int64_t *len, gptq_stream_t stream);
+
 /* ---- GPTQ solver (the caller that PRODUCES the weights; reference gptq.py:128-228) -------------------------------
  * One column block [i1, i1 + count), count <= 128, of the sequential quantise / error-feedback loop (gptq.py:177-199)
  * for all rows at once, in the reference's own fp32 arithmetic (IEEE division, round-half-even, no contraction).
