@@ -4,7 +4,8 @@
 //                          no flags, no global atomics;
 //   gptq_kv_reorder_f16    cache row b of every layer continues row parent[b], in place, ONE launch.
 //
-// Launch A, one workgroup per row: pass 1 finds the row's largest key and its first NaN / +inf; pass 2 sums exp(l - max) in fp32 -- eight
+// Launch A, one workgroup per row (passes 2 .. 4 are row_select.h's row_select, shared with logprobs.hip; what a bad row means and what is written
+// stay here): pass 1 finds the row's largest key and its first NaN / +inf; pass 2 sums exp(l - max) in fp32 -- eight
 // accumulators per thread added pairwise, a shuffle tree per wave, the 16 wave sums in a fixed tree: the same bits on every call -- and counts the
 // high byte of the 16-bit order-preserving key (sample_common.h) into 256 bins; the wave's radix select finds the bin of the 2N-th largest element,
 // pass 3 counts the low byte inside that bin, the select gives the threshold key; pass 4 collects every element above the threshold and, of the
@@ -22,7 +23,7 @@
 // writes nothing.  A fixed grid walks the columns below len[0] (read from device memory: one captured launch serves every step).
 // Built with the strict flags: accurate expf / logf / powf and IEEE division.
 #include "../../include/gptq_mi355x.h"
-#include "sample_common.h"
+#include "row_select.h"
 
 namespace {
 
@@ -35,19 +36,15 @@ constexpr int POOL_WORDS = 5, CAND_WORDS = 4, REC_WORDS = 4 + 4 * BM_MAX;
 static_assert(ST_TOKEN + 2 * BM_MAX == ST_POOL && ST_POOL + POOL_WORDS * BM_MAX == ST_CAND && ST_CAND + CAND_WORDS * 2 * BM_MAX == ST_REC &&
                   ST_REC + REC_WORDS * BM_MAX == ST_TABLES && ST_TOKEN % 2 == 0,
               "the layout of the state block");
+static_assert(2 * BM_MAX <= RS_MAX_N, "row_select's list holds a row's 2N entries");
 
 GPTQ_DEV uint32_t bits_of_key(uint32_t key) { return (key & 0x8000u) ? (key & 0x7FFFu) : (~key & 0xFFFFu); }
 
 // ---- launch A ------------------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(SM_NT) void beam_row_kernel(const uint16_t *logits, int64_t ld, int vocab, int n2, uint32_t *state) {
-    __shared__ uint32_t h1c[256], h2c[256];
+    __shared__ RowSelectLds L;
     __shared__ u64 red64[SM_NW];
     __shared__ int red32[SM_NW];
-    __shared__ float redf[SM_NW];
-    __shared__ int wcnt[2][SM_NW];
-    __shared__ Select sel;
-    __shared__ u64 list[2 * BM_MAX];
-    __shared__ uint32_t filled;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint16_t *row = logits + (int64_t)blockIdx.x * ld;
@@ -68,11 +65,7 @@ __global__ __launch_bounds__(SM_NT) void beam_row_kernel(const uint16_t *logits,
         red64[wave] = maxkey;
         red32[wave] = bad;
     }
-    if (tid < 256) {
-        h1c[tid] = 0;
-        h2c[tid] = 0;
-    }
-    if (tid == 0) filled = 0;
+    row_select_clear(L, tid);
     __syncthreads();
 #pragma unroll
     for (int w = 0; w < SM_NW; w++) {
@@ -94,101 +87,9 @@ __global__ __launch_bounds__(SM_NT) void beam_row_kernel(const uint16_t *logits,
     }
     const float lmax = logit_of_key(maxkey);
 
-    // ---- 2: sum exp(l - max) through a fixed tree, and the level-1 histogram ----
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f, a4 = 0.f, a5 = 0.f, a6 = 0.f, a7 = 0.f;
-    auto one = [&](uint32_t b) -> float {
-        const uint32_t key = key_of(b);
-        atomicAdd(&h1c[key >> 8], 1u);
-        return expf(logit_of_key(key) - lmax);                 // -inf gives 0
-    };
-    {
-        const int head = min(vocab, (int)(((16u - (uint32_t)((uintptr_t)row & 15u)) & 15u) >> 1));
-        if (tid < head) a0 += one((uint32_t)row[tid]);
-        const int nvec = (vocab - head) >> 3;
-        const u32x4 *v = (const u32x4 *)(row + head);
-        for (int i = tid; i < nvec; i += SM_NT) {
-            const u32x4 q = v[i];
-            a0 += one(q[0] & 0xFFFFu);
-            a1 += one(q[0] >> 16);
-            a2 += one(q[1] & 0xFFFFu);
-            a3 += one(q[1] >> 16);
-            a4 += one(q[2] & 0xFFFFu);
-            a5 += one(q[2] >> 16);
-            a6 += one(q[3] & 0xFFFFu);
-            a7 += one(q[3] >> 16);
-        }
-        const int t = head + nvec * 8 + tid;
-        if (t < vocab) a1 += one((uint32_t)row[t]);
-    }
-    float sum = ((a0 + a1) + (a2 + a3)) + ((a4 + a5) + (a6 + a7));
-    for (int d = 32; d > 0; d >>= 1) sum += __shfl_xor(sum, d, 64);
-    if (lane == 0) redf[wave] = sum;
-    __syncthreads();
-    static_assert(SM_NW == 16, "the tree over the wave sums");
-    const float total = (((redf[0] + redf[1]) + (redf[2] + redf[3])) + ((redf[4] + redf[5]) + (redf[6] + redf[7]))) +
-                        (((redf[8] + redf[9]) + (redf[10] + redf[11])) + ((redf[12] + redf[13]) + (redf[14] + redf[15])));
-
-    // ---- 3: the key of the 2N-th largest element (vocab >= 2N: there is one) ----
-    if (tid < 64) wave_select(h1c, 0u, (uint32_t)n2, &sel, lane);
-    __syncthreads();
-    const int kbin = sel.kbin;
-    const uint32_t kcnt = sel.kcnt;
-    scan_row(row, vocab, tid, [&](int, uint32_t b) {
-        const uint32_t key = key_of(b);
-        if ((int)(key >> 8) == kbin) atomicAdd(&h2c[key & 255u], 1u);
-    });
-    __syncthreads();
-    if (tid < 64) wave_select(h2c, kcnt, (uint32_t)n2, &sel, lane);
-    __syncthreads();
-    const uint32_t fkey = ((uint32_t)kbin << 8) | (uint32_t)sel.kbin;
-    const int above = (int)sel.kcnt;                           // elements with a key above fkey: at most 2N - 1
-    const int need = n2 - above;                               // places for the elements AT fkey: 1 .. ties
-    const int ties = (int)h2c[sel.kbin];
-
-    // ---- 4: collect ----
-    const bool all_ties = ties == need;
-    scan_row(row, vocab, tid, [&](int i, uint32_t b) {
-        const uint32_t key = key_of(b);
-        if (key > fkey || (all_ties && key == fkey)) {
-            const uint32_t slot = atomicAdd(&filled, 1u);      // exactly 2N (or `above`) elements qualify
-            if (slot < 2 * BM_MAX) list[slot] = ((u64)key << 32) | (uint32_t)~(uint32_t)i;
-        }
-    });
-    if (!all_ties) {                                           // the `need` lowest ids at fkey: a running count in ascending id
-        int running = 0, parity = 0;
-        for (int base = 0; base < vocab && running < need; base += SM_NT * 8) {
-            const int i0 = base + tid * 8;
-            uint32_t mask = 0;
-#pragma unroll
-            for (int j = 0; j < 8; j++)
-                if (i0 + j < vocab && key_of((uint32_t)row[i0 + j]) == fkey) mask |= 1u << j;
-            const int c = __builtin_popcount(mask);
-            int incl = c;
-            for (int d = 1; d < 64; d <<= 1) {
-                const int o = __shfl_up(incl, d, 64);
-                if (lane >= d) incl += o;
-            }
-            if (lane == 63) wcnt[parity][wave] = incl;
-            __syncthreads();
-            int tot = 0, below = 0;
-#pragma unroll
-            for (int w = 0; w < SM_NW; w++) {
-                const int x = wcnt[parity][w];
-                below += w < wave ? x : 0;
-                tot += x;
-            }
-            parity ^= 1;
-            int rank = running + below + incl - c;
-#pragma unroll
-            for (int j = 0; j < 8; j++)
-                if ((mask >> j) & 1u) {
-                    if (rank < need) list[above + rank] = ((u64)fkey << 32) | (uint32_t)~(uint32_t)(i0 + j);
-                    rank++;
-                }
-            running += tot;
-        }
-    }
-    __syncthreads();
+    // ---- 2 .. 4: the sum of exp(l - max) and the row's first 2N tokens (row_select.h) ----
+    const float total = row_select(row, vocab, tid, lmax, n2, L, [](int, uint32_t) {});
+    const u64 *list = L.list;
 
     // ---- 5: (logit descending, id ascending) = the composite descending; the entries are distinct ----
     if (tid == 0) {

@@ -1,8 +1,8 @@
 // sample_common.h -- the device code gptq_sample_rows_f16 (sample.hip) and gptq_spec_sample_rows_f16 (spec_sample.hip) share: the order-preserving
 // 16-bit key of an fp16 logit, the row scan that needs 2-byte alignment only, a token's integer mass, the 256-bin radix select of one wave, and --
 // for kernels that look at more than one row per workgroup -- the passes A .. D of sample.hip as a function (select_row) and its pass E as a
-// function of any mass (draw_row).  sample.hip states the method; its kernel keeps its own straight-line copy of the passes.  beam.hip takes the
-// key, the row scan and the count-only select from here.
+// function of any mass (draw_row).  sample.hip states the method; its kernel keeps its own straight-line copy of the passes.  row_select.h
+// (beam.hip, logprobs.hip) takes the key, the row scan and the count-only select from here.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>

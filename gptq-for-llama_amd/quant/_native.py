@@ -191,6 +191,8 @@ _SIGNATURES = {
     'gptq_beam_state_bytes': [c_int, c_int],
     'gptq_beam_select_f16': [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p],
     'gptq_kv_reorder_f16': [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p],
+    # token log-probabilities: the chosen token's log p and rank and the row's top K, into slot step[0] of a record ring (csrc/logprobs.hip)
+    'gptq_logprobs_rows_f16': [c_void_p, c_int64, c_int, c_int, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
 }
 
 

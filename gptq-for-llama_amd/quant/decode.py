@@ -182,6 +182,7 @@ MAX_CHUNK_ROWS = 128   # rows of a batched verify step (batch x batch_chunk): wh
 MAX_PROCESS_EOS, MAX_PROCESS_BIAS, MAX_PROCESS_VOCAB = 8, 256, 131072      # GPTQ_LOGITS_PROCESS_MAX_EOS / _BIAS / _VOCAB
 MAX_BEAMS = 16         # GPTQ_BEAM_MAX_BEAMS
 BEAM_DEAD = -1e9
+MAX_LOGPROBS, MAX_LOGPROBS_ROWS = 32, 128      # GPTQ_LOGPROBS_MAX_TOP, the rows of one gptq_logprobs_rows_f16 launch
 # gptq_beam_select_f16's state block in 4-byte words (gptq_mi355x.h "beam search")
 (BEAM_W_EOS, BEAM_W_MAX_NEW, BEAM_W_LP, BEAM_W_ES, BEAM_W_T_CAP, BEAM_W_BEAMS, BEAM_W_T, BEAM_W_OPEN, BEAM_W_DONE, BEAM_W_STATUS) = range(10)
 BEAM_W_SCORE, BEAM_W_PARENT, BEAM_W_TOKEN, BEAM_W_POOL, BEAM_W_CAND, BEAM_W_REC, BEAM_W_TABLES = 16, 32, 48, 80, 160, 288, 1376
@@ -217,8 +218,16 @@ def lm_head_logits(eng, x, logits, s, h=None):
 
 class DecodeEngine:
 
-    def __init__(self, model, t_max=2048, fuse_norm=True, fuse_attn=True, batch=1, chunk=0, batch_chunk=0, spec_sample=False, logits_process=False, beam_search=False):
-        """beam_search = True (with batch = N, 2 .. 16) makes the N rows the running beams of ONE beam search (HF's rule: gptq_mi355x.h "beam
+    def __init__(self, model, t_max=2048, fuse_norm=True, fuse_attn=True, batch=1, chunk=0, batch_chunk=0, spec_sample=False, logits_process=False, beam_search=False,
+                 logprobs=None):
+        """logprobs = K (0 .. 32) makes every self-feeding step (capture_greedy_rows, capture_sample_native, capture_sample_rows) RECORD the
+        log-probability of the token it chose, that token's rank and the row's K most probable tokens (gptq_logprobs_rows_f16, gptq_mi355x.h
+        "token log-probabilities": one more launch per step, no host round trip): lp_chosen float [t_max + 1, B], lp_rank int32 [t_max + 1, B],
+        lp_top_ids int32 / lp_top float [t_max + 1, B, K]; row n belongs to row n of stream_rows.  The logits are the ones the draw sees:
+        behind the logit processors when logits_process is on, BEFORE temperature / top-k / top-p -- the model's distribution, not the
+        warped one.  The batch-1 capture_greedy graph records nothing.  None (the default) allocates nothing and adds no launch.  ValueError
+        for K outside 0 .. 32 and together with chunk, batch_chunk or beam_search (not built yet).  token_logprobs() is the eager entry.
+        beam_search = True (with batch = N, 2 .. 16) makes the N rows the running beams of ONE beam search (HF's rule: gptq_mi355x.h "beam
         search"): the state block of gptq_beam_select_f16 -- set_beam_search, beam_select, beam_begin, capture_beam_step, beam_result,
         engine_generate_beam.  False (the default) allocates nothing and those calls raise.  ValueError together with logits_process, chunk or
         batch_chunk.
@@ -270,6 +279,13 @@ class DecodeEngine:
         if self.beam_search and (self.logits_process or self.chunk or self.batch_chunk or not 2 <= self.batch <= MAX_BEAMS):
             raise ValueError('DecodeEngine: beam_search needs batch = 2 .. %d beams and combines with neither logits_process, chunk nor batch_chunk'
                              % MAX_BEAMS)
+        if logprobs is not None:
+            if isinstance(logprobs, bool) or not isinstance(logprobs, int) or not 0 <= logprobs <= MAX_LOGPROBS:
+                raise ValueError('DecodeEngine: logprobs must be None or an int in 0 .. %d, not %r' % (MAX_LOGPROBS, logprobs))
+            if self.chunk or self.batch_chunk or self.beam_search:
+                raise ValueError('DecodeEngine: logprobs together with chunk / batch_chunk / beam_search is not built yet (records of a verify '
+                                 'step, of a beam)')
+        self.logprobs = logprobs
         self.fuse_norm, self.fuse_attn = bool(fuse_norm), bool(fuse_attn)
         self.native = _native
         self.lib = _native.lib()
@@ -314,6 +330,9 @@ class DecodeEngine:
         self.stream_out = torch.zeros(self.t_max + 1, dtype=torch.int64, device=dev)   # greedy mode (batch 1): token chosen after position p
         self.greedy_graph = None
         self.greedy_rows_graph, self.stream_rows, self.stepc, self.sample_graphs = None, None, None, {}
+        self.lp_chosen, self.lp_rank, self.lp_top_ids, self.lp_top = None, None, None, None      # with logprobs: allocated next to stream_rows
+        if self.logprobs is not None and self.logits.shape[1] < max(self.logprobs, 1):
+            raise ValueError('DecodeEngine: logprobs = %d needs a vocabulary of at least that many tokens' % self.logprobs)
         # gptq_sample_rows_f16: the uniforms and every row's (temperature, top_k, top_p), read by the kernel at every replay (set_sampling)
         self.u = torch.zeros(B, dtype=torch.float32, device=dev)
         self.temperature = torch.ones(B, dtype=torch.float32, device=dev)
@@ -718,6 +737,58 @@ class DecodeEngine:
         if self.stream_rows is None:
             self.stream_rows = torch.zeros((self.t_max + 1, self.batch), dtype=torch.int64, device=self.dev)
             self.stepc = torch.zeros(1, dtype=torch.int64, device=self.dev)
+            if self.logprobs is not None:                  # the record ring of _logprobs_step: row n belongs to row n of stream_rows
+                n, B, K = self.t_max + 1, self.batch, self.logprobs
+                self.lp_chosen = torch.zeros((n, B), dtype=torch.float32, device=self.dev)
+                self.lp_rank = torch.zeros((n, B), dtype=torch.int32, device=self.dev)
+                self.lp_top_ids = torch.zeros((n, B, K), dtype=torch.int32, device=self.dev)
+                self.lp_top = torch.zeros((n, B, K), dtype=torch.float32, device=self.dev)
+
+    def _logprobs_launch(self, logits, ids, top, step, steps, chosen, rank, top_ids, top_logprobs):
+        n = logits.shape[0]
+        with self.native.on_device(self.dev):
+            rc = self.lib.gptq_logprobs_rows_f16(logits.data_ptr(), logits.stride(0) if n > 1 else logits.shape[1], n, logits.shape[1], ids.data_ptr(),
+                                                 top, self.native.ptr(step), steps, chosen.data_ptr(), rank.data_ptr(),
+                                                 top_ids.data_ptr() if top else None, top_logprobs.data_ptr() if top else None,
+                                                 self.native.stream_ptr(self.dev))
+        self.native.check(rc, 'gptq_logprobs_rows_f16')
+
+    def _logprobs_step(self):
+        """behind choose(): the record of the tokens in self.ids under self.logits -- the logits the draw saw: behind the processors, before
+        temperature / top-k / top-p -- into row stepc of the lp_* buffers, ONE launch that reads the step counter on the device and draws no
+        random numbers.  Nothing without the flag."""
+        if self.logprobs is not None:
+            self._logprobs_launch(self.logits, self.ids, self.logprobs, self.stepc, self.t_max + 1, self.lp_chosen, self.lp_rank, self.lp_top_ids,
+                                  self.lp_top)
+
+    def token_logprobs(self, logits, ids, top=None):
+        """the eager entry of gptq_logprobs_rows_f16, on any engine: for each row of `logits` ([n, vocab] or [vocab] fp16 on the engine's device,
+        unit column stride, n <= 128) and its token ids[r] (int64 [n] on the device) -> (chosen float [n]: the token's log-probability, rank
+        int32 [n]: its 0-based place among the row's tokens by (logit descending, id ascending), top_ids int32 [n, top], top_logprobs float
+        [n, top]: the row's first `top` tokens), new tensors.  top: 0 .. 32; None: the engine's logprobs setting (0 without one).  What the
+        drivers use for the first token of a generation, from the prompt's logits; decode()'s logits are as good.  A row with a NaN or +inf
+        or of -inf only, and an id outside the vocabulary, give NaN and rank -1 (gptq_mi355x.h "token log-probabilities")."""
+        what = 'DecodeEngine.token_logprobs'
+        if top is None:
+            top = self.logprobs or 0
+        if isinstance(top, bool) or not isinstance(top, int) or not 0 <= top <= MAX_LOGPROBS:
+            raise ValueError('%s: top must be None or an int in 0 .. %d, not %r' % (what, MAX_LOGPROBS, top))
+        if logits.dim() == 1:
+            logits = logits.unsqueeze(0)
+        n = logits.shape[0] if logits.dim() == 2 else 0
+        if not 1 <= n <= MAX_LOGPROBS_ROWS or logits.dtype != torch.float16 or logits.device != self.ids.device or logits.stride(1) != 1 or \
+                logits.shape[1] < max(top, 1):
+            raise ValueError('%s: logits must be fp16 [n <= %d, vocab >= %d] with unit column stride on %s' % (
+                what, MAX_LOGPROBS_ROWS, max(top, 1), self.dev))
+        if not torch.is_tensor(ids) or ids.dtype != torch.int64 or ids.device != self.ids.device or ids.shape != (n,) or not ids.is_contiguous():
+            raise ValueError('%s: ids must be a contiguous int64 [%d] on %s' % (what, n, self.dev))
+        dev = self.ids.device
+        chosen = torch.empty(n, dtype=torch.float32, device=dev)
+        rank = torch.empty(n, dtype=torch.int32, device=dev)
+        top_ids = torch.empty((n, top), dtype=torch.int32, device=dev)
+        top_logprobs = torch.empty((n, top), dtype=torch.float32, device=dev)
+        self._logprobs_launch(logits, ids, top, None, 1, chosen, rank, top_ids, top_logprobs)
+        return chosen, rank, top_ids, top_logprobs
 
     def _capture_rows(self, step, keep_rng=False):
         """_capture for the steps that append to stream_rows: the step counter starts at 0, and is 0 again afterwards"""
@@ -727,11 +798,13 @@ class DecodeEngine:
 
     def _self_feeding_step(self, choose):
         """THE self-feeding step, for any batch: one decode step, the processors (nothing without the flag), choose() puts every row's next input
-        token into self.ids, and the choices of step n become row n of stream_rows (n = stepc, a device counter the step advances itself)"""
+        token into self.ids, the logprobs record of the choices (nothing without the flag), and the choices of step n become row n of stream_rows
+        (n = stepc, a device counter the step advances itself)"""
         self._stream_buffers()
         self._step()
         self._process_step()
         choose()
+        self._logprobs_step()
         self.stream_rows.index_copy_(0, self.stepc, self.ids.unsqueeze(0))
         self.stepc.add_(1)
 
@@ -1977,12 +2050,30 @@ def _speculate_rows(what, eng, prompts, into, max_new_tokens, eos_token_id, k, m
     return [torch.tensor(g, dtype=torch.int64) for g in gens]
 
 
-def _generate_rows(what, eng, prompts, into, max_new_tokens, eos_token_id, settings, proc, spec, one_prompt=False):
+def _logprobs_setting(what, logprobs, speculate, engine):
+    """the logprobs= argument of `what` (engine_generate / engine_generate_batch), validated: None or K in 0 .. 32; ValueError under speculate=,
+    and for an engine passed in that has beam search, no logprobs flag or a smaller one"""
+    if logprobs is None:
+        return None
+    if isinstance(logprobs, bool) or not isinstance(logprobs, int) or not 0 <= logprobs <= MAX_LOGPROBS:
+        raise ValueError('%s: logprobs must be None or an int in 0 .. %d, not %r' % (what, MAX_LOGPROBS, logprobs))
+    if speculate is not None:
+        raise ValueError('%s: logprobs together with speculate is not built yet (records of a verify step)' % what)
+    if engine is not None:
+        if engine.beam_search:
+            raise ValueError('%s: logprobs on a beam-search engine is not built yet' % what)
+        if engine.logprobs is None or engine.logprobs < logprobs:
+            raise ValueError('%s: logprobs = %d needs an engine built with logprobs >= %d (this one: %r)' % (what, logprobs, logprobs, engine.logprobs))
+    return logprobs
+
+
+def _generate_rows(what, eng, prompts, into, max_new_tokens, eos_token_id, settings, proc, spec, one_prompt=False, logprobs=None):
     """THE generation driver behind engine_generate (one prompt) and engine_generate_batch: prompts are n = eng.batch 1-D id tensors,
     into(engine) puts them into that engine's cache from position 0 and returns the [n, vocab] logits behind their last tokens.  In this order:
     the settings go into the engine; every graph the run will need is taken from graph_for, while no prompt is in the cache yet; the prompts
     enter; the processors act on the first logits; the first tokens come from argmax or sample_logits; _self_feeding_tail makes the others.
-    Returns the generated ids of every row, cut after its first eos.
+    Returns the generated ids of every row, cut after its first eos; with logprobs = K, (those, one info dict per row: the records of
+    DecodeEngine.token_logprobs for the first token and of the step's own launch for the others, cut alike).
     one_prompt: the greedy tail of ONE prompt replays the capture_greedy graph, which records into stream_out[pos]: one element-wise node less
     per step than the rows graph, a difference that was measured (profiles/generate_drivers/README.md)."""
     with torch.no_grad():
@@ -1994,7 +2085,7 @@ def _generate_rows(what, eng, prompts, into, max_new_tokens, eos_token_id, setti
             if eng.logits_process:                               # (an engine passed in with the flag, neutral keys: its processors are switched off)
                 eng.set_logits_process(eos_token_id=eos_token_id, **(proc or {}))
             graph = eng.graph_for('sample_native')
-        elif one_prompt:
+        elif one_prompt and eng.logprobs is None:                # (the capture_greedy graph records no logprobs)
             graph = eng.graph_for('greedy')
             record = (eng.stream_out.unsqueeze(1), int(prompts[0].numel()) + 1)      # stream_out[p] = the token chosen after p consumed ones
         else:
@@ -2007,11 +2098,22 @@ def _generate_rows(what, eng, prompts, into, max_new_tokens, eos_token_id, setti
             if eng.logits_process:
                 eng.process_logits(logits)
             first = eng.sample_logits(logits)
+        if logprobs is not None:                                 # the first token's record, from the logits it was drawn from
+            head = eng.token_logprobs(logits.to(torch.float16).contiguous(), first, top=logprobs)
         gen = _self_feeding_tail(eng, graph, first, max_new_tokens, eos_token_id, record).t()      # [row][step]
-        return [_cut_after_eos(g, eos_token_id) for g in gen]
+        gens = [_cut_after_eos(g, eos_token_id) for g in gen]
+        if logprobs is None:
+            return gens
+        # replay n wrote row n of the lp_* buffers, as of stream_rows: [first, rows 0 .. done - 2], cut where the tokens are cut
+        done = gen.shape[1]
+        tails = (eng.lp_chosen, eng.lp_rank, eng.lp_top_ids[:, :, :logprobs], eng.lp_top[:, :, :logprobs])
+        full = [torch.cat([h.unsqueeze(0), t[:done - 1]]) for h, t in zip(head, tails)]              # [step][row] (, K)
+        keys = ('token_logprobs', 'ranks', 'top_ids', 'top_logprobs')
+        return gens, [{k: f[:g.numel(), b].clone() for k, f in zip(keys, full)} for b, g in enumerate(gens)]
 
 
-def engine_generate(model, input_ids, max_new_tokens, eos_token_id=None, engine=None, t_max=2048, prefill='hf', sample=None, speculate=None):
+def engine_generate(model, input_ids, max_new_tokens, eos_token_id=None, engine=None, t_max=2048, prefill='hf', sample=None, speculate=None,
+                    logprobs=None):
     """Generation for ONE prompt ([1, T] ids) on the DecodeEngine: the prompt enters the engine's static cache, the first token is chosen from
     its logits, and every further token is ONE hipGraph replay of a self-feeding step; the host looks at the stream every 16 tokens only.
     Returns the full sequence [1, prompt + generated], cut after the first eos_token_id.  The reference equivalent is
@@ -2043,13 +2145,22 @@ def engine_generate(model, input_ids, max_new_tokens, eos_token_id=None, engine=
     processors under speculation are not built yet.  speculate=dict(..., draft_model=<fused model of the same vocabulary>) drafts with a MODEL:
     a DecodeEngine of its own (kept on the engine) draws the k tokens under the same setting and hands its logits rows to the verify step;
     without `sample` it drafts greedily and the verify-greedy graph checks it.
-    ValueError: speculate together with the sample ARGUMENT; k outside 1 .. 15; an engine passed in whose chunk is not k + 1 or whose batch is
+    logprobs = K (0 .. 32; None, the default: the call as it always was) returns (sequences, info): info is a dict on the device of the returned
+    ids with, for the n generated tokens -- the first one included, cut after the first eos exactly as the tokens are, the eos entry kept --,
+    token_logprobs float [n] (the log-probability of each token), ranks int32 [n] (its 0-based place among the vocabulary by (logit
+    descending, id ascending)), top_ids int32 [n, K] and top_logprobs float [n, K] (the K most probable tokens of each step):
+    gptq_logprobs_rows_f16, one more launch per step of the captured graph (DecodeEngine(logprobs=K)).  The probabilities are the MODEL's,
+    from the logits the draw sees: behind the logit processors, before temperature / top-k / top-p.  Greedy, sample= and the processor keys
+    all record; an engine passed in must have been built with logprobs >= K.
+    ValueError: logprobs together with speculate, on a beam-search engine, outside 0 .. 32, or on an engine built with a smaller K or none;
+    speculate together with the sample ARGUMENT; k outside 1 .. 15; an engine passed in whose chunk is not k + 1 or whose batch is
     not 1; unknown keys; draft together with draft_model; a draft model of another vocabulary size; a prompt that is not [1, T]; prompt +
     max_new_tokens beyond the cache."""
     what = 'engine_generate'
     if prefill not in ('hf', 'engine'):
         raise ValueError("engine_generate: prefill must be 'hf' or 'engine', not %r" % (prefill,))
     settings, proc, spec = _generation_settings(what, model, sample, speculate, engine)
+    logprobs = _logprobs_setting(what, logprobs, speculate, engine)
     if spec is not None and engine is not None and (engine.batch != 1 or engine.chunk != spec[0] + 1):
         raise ValueError('engine_generate: speculate k = %d needs an engine of batch 1 with chunk = %d (this one: batch %d, chunk %d)' % (
             spec[0], spec[0] + 1, engine.batch, engine.chunk))
@@ -2060,7 +2171,7 @@ def engine_generate(model, input_ids, max_new_tokens, eos_token_id=None, engine=
     elif spec is not None:
         eng = DecodeEngine(model, t_max=t_max, chunk=spec[0] + 1)
     else:
-        eng = DecodeEngine(model, t_max=t_max, logits_process=proc is not None)
+        eng = DecodeEngine(model, t_max=t_max, logits_process=proc is not None, logprobs=logprobs)
     if input_ids.shape[1] + max_new_tokens > eng.t_max:
         raise ValueError('engine_generate: prompt + max_new_tokens exceeds the engine cache (%d)' % eng.t_max)
     if settings is not None and eng.batch != 1:
@@ -2068,13 +2179,17 @@ def engine_generate(model, input_ids, max_new_tokens, eos_token_id=None, engine=
 
     def into(e):                                                 # (a draft model's engine takes the prompt by its own prefill)
         return _prompt_into_engine(model, input_ids, e, prefill if e is eng else 'engine').reshape(1, -1)
-    gen = _generate_rows(what, eng, [input_ids[0]], into, max_new_tokens, eos_token_id, settings, proc, spec, one_prompt=True)[0]
+    out = _generate_rows(what, eng, [input_ids[0]], into, max_new_tokens, eos_token_id, settings, proc, spec, one_prompt=True, logprobs=logprobs)
+    gen = (out if logprobs is None else out[0])[0]
     if spec is not None:                                         # one sequence: emitted as an int, accepted as the flat per-step list
         eng.spec_stats = dict(eng.spec_stats, emitted=eng.spec_stats['emitted'][0], accepted=eng.spec_stats['accepted'][0])
-    return torch.cat([input_ids[0], gen.to(device=input_ids.device, dtype=input_ids.dtype)]).unsqueeze(0)
+    seq = torch.cat([input_ids[0], gen.to(device=input_ids.device, dtype=input_ids.dtype)]).unsqueeze(0)
+    if logprobs is None:
+        return seq
+    return seq, {k: v.to(input_ids.device) for k, v in out[1][0].items()}
 
 
-def engine_generate_batch(model, prompts, max_new_tokens, eos_token_id=None, engine=None, t_max=2048, sample=None, speculate=None):
+def engine_generate_batch(model, prompts, max_new_tokens, eos_token_id=None, engine=None, t_max=2048, sample=None, speculate=None, logprobs=None):
     """engine_generate for a LIST of prompts of different lengths (1-D id tensors): the same driver, arguments and ValueErrors, and what differs:
     all prompts enter through ONE DecodeEngine.prefill_batch (there is no prefill= route: nothing of `transformers` is involved, and the
     prompts are pad-free, so every row's history is its own prompt and tokens); a step is one replay for all rows, and a row that has emitted
@@ -2086,10 +2201,13 @@ def engine_generate_batch(model, prompts, max_new_tokens, eos_token_id=None, eng
     tokens left, or an active chunk no longer fits the cache, the single-step graph finishes all rows.  eng.spec_stats = dict(steps,
     emitted=[per sequence], accepted=[per sequence: per step]).  The keys sample / draft_model in there need an engine built with
     spec_sample=True (capture_verify_sample_batch: gptq_spec_sample_batch_f16 on all sequences in one launch).
+    logprobs = K: returns (list of sequences, list of info dicts), one dict per prompt as engine_generate's, each as long as that row's generated
+    tokens.
     ValueError also: an engine passed in whose batch is not len(prompts) or whose batch_chunk is not k + 1, or that lacks spec_sample where it
     is needed; an empty list or prompt; max_new_tokens below 1."""
     what = 'engine_generate_batch'
     settings, proc, spec = _generation_settings(what, model, sample, speculate, engine)
+    logprobs = _logprobs_setting(what, logprobs, speculate, engine)
     sampled = spec is not None and (spec[3] is not None or spec[4] is not None)
     if sampled and engine is not None and not engine.spec_sample:
         raise ValueError('engine_generate_batch: speculate with sample or draft_model needs an engine built with spec_sample=True')
@@ -2107,13 +2225,18 @@ def engine_generate_batch(model, prompts, max_new_tokens, eos_token_id=None, eng
     elif spec is not None:
         eng = DecodeEngine(model, t_max=t_max, batch=n, batch_chunk=spec[0] + 1, spec_sample=sampled)
     else:
-        eng = DecodeEngine(model, t_max=t_max, batch=n, logits_process=proc is not None)
+        eng = DecodeEngine(model, t_max=t_max, batch=n, logits_process=proc is not None, logprobs=logprobs)
     if eng.batch != n:
         raise ValueError('engine_generate_batch: %d prompts for an engine of batch %d' % (n, eng.batch))
     if max(int(p.numel()) for p in prompts) + max_new_tokens > eng.t_max:
         raise ValueError('engine_generate_batch: prompt + max_new_tokens exceeds the engine cache (%d)' % eng.t_max)
-    gens = _generate_rows(what, eng, prompts, lambda e: e.prefill_batch(prompts, starts=[0] * n), max_new_tokens, eos_token_id, settings, proc, spec)
-    return [torch.cat([p, g.to(device=p.device, dtype=p.dtype)]) for p, g in zip(prompts, gens)]
+    out = _generate_rows(what, eng, prompts, lambda e: e.prefill_batch(prompts, starts=[0] * n), max_new_tokens, eos_token_id, settings, proc, spec,
+                         logprobs=logprobs)
+    gens = out if logprobs is None else out[0]
+    seqs = [torch.cat([p, g.to(device=p.device, dtype=p.dtype)]) for p, g in zip(prompts, gens)]
+    if logprobs is None:
+        return seqs
+    return seqs, [{k: v.to(p.device) for k, v in info.items()} for p, info in zip(prompts, out[1])]
 
 
 def engine_generate_beam(model, input_ids, max_new_tokens, num_beams=4, eos_token_id=None, length_penalty=1.0, early_stopping=False,

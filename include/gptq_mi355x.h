@@ -863,6 +863,29 @@ int gptq_beam_select_f16(const void *logits, int64_t ld, int beams, int vocab, v
 int gptq_kv_reorder_f16(void *k_cache, void *v_cache, int layers, int rows, int t_max, int row_elems, int64_t layer_stride, const int32_t *parent,
                         const int64_t *len, gptq_stream_t stream);
 
+/* ---- token log-probabilities: how probable the chosen token of a row of fp16 logits was, where it ranks, and the row's first `top` tokens
+ * (csrc/logprobs.hip; tests/logprobs_ref.py restates the rule in float64).  ONE launch, one workgroup per row, rows = 1 .. 128, no workspace.
+ *
+ * For row r of logits [rows, vocab] (ld >= vocab, rows 2-byte aligned only) and its token ids[r] (int64):
+ *   m      = the row's maximum;  S = sum_v expf(fp32(l_v) - m) in fp32, in a fixed order (the tree of gptq_beam_select_f16);
+ *   lp(v)  = (fp32(l_v) - m) - logf(S)
+ *   order  : tokens by the 16-bit order-preserving key of their fp16 bits, descending (-0 counts as +0), then by id ascending
+ *   top_ids / top_logprobs [0 .. top) = the first `top` tokens of that order and their lp;  rank = the 0-based place of ids[r] in that order;
+ *   chosen = lp(ids[r]).  Hence rank < top <=> top_ids[rank] == ids[r], and then top_logprobs[rank] has the bits of chosen.
+ * top = 0 .. GPTQ_LOGPROBS_MAX_TOP; 0 gives chosen and rank only (top_ids and top_logprobs may be NULL).  vocab >= max(top, 1).
+ * -inf entries are legal (a banned token): their lp is -inf and they sort last, in id order among themselves.  A row that holds a NaN or +inf,
+ * or -inf only, has no distribution: chosen = NaN, rank = -1, top_ids = 0 .. top - 1, top_logprobs = NaN; the other rows are unaffected.
+ * ids[r] outside [0, vocab) gives chosen = NaN and rank = -1; the row's top list is still written.
+ * Addressing: chosen and rank are [steps][rows], top_ids and top_logprobs [steps][rows][top].  step == NULL writes slot 0; otherwise the launch
+ * reads step[0] on the DEVICE -- a captured launch serves every step of a generation -- and a value outside [0, steps) writes nothing at all.
+ * Deterministic: no global atomics, only integer counts go through LDS atomics; the same bits on every call, and a row's record depends neither
+ * on the other rows of the launch nor on the slot it goes to.
+ * Validated before the launch: GPTQ_E_NULL (logits, ids, chosen, rank; top_ids and top_logprobs when top > 0), GPTQ_E_SHAPE (rows outside
+ * 1 .. 128, top outside 0 .. 32, vocab < max(top, 1), ld < vocab, steps < 1), GPTQ_E_ALIGN (logits 2 bytes, ids and step 8, the outputs 4). */
+#define GPTQ_LOGPROBS_MAX_TOP 32
+int gptq_logprobs_rows_f16(const void *logits, int64_t ld, int rows, int vocab, const int64_t *ids, int top, const int64_t *step, int64_t steps,
+                           float *chosen, int32_t *rank, int32_t *top_ids, float *top_logprobs, gptq_stream_t stream);
+
 /* ---- GPTQ solver (the caller that PRODUCES the weights; reference gptq.py:128-228) -------------------------------
  * One column block [i1, i1 + count), count <= 128, of the sequential quantise / error-feedback loop (gptq.py:177-199)
  * for all rows at once, in the reference's own fp32 arithmetic (IEEE division, round-half-even, no contraction).
