@@ -9,11 +9,13 @@
 //     cheapest grid-wide hand-off on this chip, DESIGN 3.6 -- the in-kernel merge below cost 5.5 us per layer from 129 tokens of context on);
 //   * the last split to arrive (system-scope records + an arrival ticket): callers without a merging consumer.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 namespace gptq {
 
-constexpr int ATT_TILE = 128;        // timesteps per tile; a split's range is a multiple of it (the last one: what is left)
+constexpr int ATT_HD = 128;          // head_dim the decode-side attention entries serve
+constexpr int ATT_TILE = 128;       // timesteps per tile; a split's range is a multiple of it (the last one: what is left)
 constexpr int ATT_MAX_SPLITS = 8;    // splits per (row, head) a launch is ever cut into
 constexpr float ATT_M_FLOOR = -1.0e30f;   // running maximum of a wave that has seen no timestep (finite: exp2(floor - M) = 0, never NaN)
 
@@ -57,6 +59,46 @@ struct AttnMerge {
     const int64_t *pos;              // per row: position of the new token (history length); < 0 = idle row
     int S, tps, heads, t_max;
 };
+
+// ---- workspace layouts (host): byte offsets into the caller's workspace, each computed in ONE place for the size query, the producer's launch and
+// the consumer that is pointed at the records ----
+int decode_attn_grid_splits(int heads, int t_max, int batch);   // S of the decode launch's grid (decode_attn.hip)
+int chunk_attn_grid_splits(int heads, int t_max);               // ... of the chunk launch's (chunk_attn.hip)
+
+// decode attention: [batch][S][heads * 128] fp16 partial outputs | [batch][S][heads] fp32 {M, den} | [batch][heads] uint32 tickets
+struct DecodeAttnWs {
+    int S;
+    size_t o16, md, tickets, bytes;
+};
+inline DecodeAttnWs decode_attn_ws(int batch, int heads, int t_max) {
+    DecodeAttnWs w{};
+    w.S = decode_attn_grid_splits(heads, t_max, batch);
+    const size_t recs = (size_t)batch * w.S * heads;
+    w.o16 = 0;
+    w.md = w.o16 + recs * ATT_HD * sizeof(_Float16);
+    w.tickets = w.md + recs * 2 * sizeof(float);
+    w.bytes = w.tickets + (size_t)batch * heads * sizeof(unsigned);
+    return w;
+}
+
+// chunk attention: rotated q [seqs][rows][hd] fp16 | records [seqs][S][rows][hd] fp16 | {M, den} [seqs][S][heads][rows] fp32 x 2 | tickets
+// [seqs][heads], each part rounded up to 256 bytes (seqs = 1: the layout and the size of the single-sequence entry)
+struct ChunkAttnWs {
+    int S;
+    size_t qrot, o16, md, tickets, bytes;
+};
+inline ChunkAttnWs chunk_attn_ws(int seqs, int rows, int heads, int t_max) {
+    const auto align = [](size_t n) { return (n + 255) & ~(size_t)255; };
+    ChunkAttnWs w{};
+    w.S = chunk_attn_grid_splits(heads, t_max);
+    const size_t n = (size_t)seqs, hd = (size_t)heads * ATT_HD;
+    w.qrot = 0;
+    w.o16 = w.qrot + align(n * rows * hd * sizeof(_Float16));
+    w.md = w.o16 + align(n * w.S * rows * hd * sizeof(_Float16));
+    w.tickets = w.md + align(n * w.S * heads * rows * 2 * sizeof(float));
+    w.bytes = w.tickets + align(n * heads * sizeof(unsigned));
+    return w;
+}
 
 #if defined(__HIPCC__)
 // The merge of a row's records, shared by the in-kernel merge (decode_attn.hip) and the consumer-side merge (stripe_kernel.inc) so that both

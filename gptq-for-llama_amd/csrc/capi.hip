@@ -1817,12 +1817,12 @@ int gptq_layer_decode_attn_f16(const gptq_layer_t *layer, const void *attn_works
     if (L.bias && residual) return GPTQ_E_VARIANT;                  // one add slot per launch
     if (!aligned(attn_workspace, 16) || !aligned(y, 16) || ldy % 8 != 0 || (residual && (!aligned(residual, 16) || ldr % 8 != 0))) return GPTQ_E_ALIGN;
     if (attn_workspace_bytes < decode_attn_ws_bytes(heads, t_max, batch)) return GPTQ_E_WORKSPACE;
-    const int S = decode_attn_grid_splits(heads, t_max, batch);
+    const DecodeAttnWs w = decode_attn_ws(batch, heads, t_max);
     AttnMerge am{};
-    am.o16 = (const half_t *)attn_workspace;
-    am.md = (const float *)(am.o16 + (size_t)batch * S * heads * 128);
+    am.o16 = (const half_t *)((const char *)attn_workspace + w.o16);
+    am.md = (const float *)((const char *)attn_workspace + w.md);
     am.pos = positions;
-    am.S = S;
+    am.S = w.S;
     am.tps = tokens_per_split > 0 ? tokens_per_split : decode_attn_tps(true);
     am.heads = heads;
     am.t_max = t_max;

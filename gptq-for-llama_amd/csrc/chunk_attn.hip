@@ -5,8 +5,8 @@
 //
 // rows (1..16, a host value: it shapes the grid) tokens sit at positions p .. p + rows - 1, p = *position read on the device, so a captured graph
 // replays the call at any position.  Two launches:
-//   1. chunk_rope_kv_kernel, grid (rows, heads): the arithmetic of rope_kv_kernel (decode_attn.hip) / prompt_rope_kv_kernel (prompt_attn.hip) per
-//      (row, head) -- same instructions, same flags (see the Makefile), so cache rows p + r get the bits a token-by-token feed writes; the rotated q
+//   1. chunk_rope_kv_kernel, grid (rows, heads): the shared RoPE + append of attn_device.h (rope_cos_sin, rope_kv_row) per (row, head) -- the
+//      instructions and flags of every other entry, so cache rows p + r get the bits a token-by-token feed writes; the rotated q
 //      goes to the workspace, qkv is never written.  It also clears the arrival tickets of launch 2 (no state is asked of the caller's workspace).
 //      The kernel boundary orders the append against every read of launch 2.
 //   2. chunk_attn_kernel, grid (heads, S): the key range [0, p + rows) is cut into splits by attn_split() from its length at run time, as the decode
@@ -16,13 +16,13 @@
 //        S^T[key][query] = K Q^T   v_mfma_f32_16x16x32_f16, K straight from global memory in the A layout (lane = key, 64 contiguous bytes per
 //                                  lane), Q^T fragments in registers for the whole walk;
 //        O^T[dim][query] += V^T P^T  the accumulator layout of the first product is the B operand of the second (P rounded to fp16 in registers);
-//                                  V^T comes through ds_read_b64_tr_b16 from the wave's own LDS image of the V tile (256-byte rows with the
-//                                  chunk swizzle of prompt_attn.hip; the key order of a 16-key block is permuted so that the two 4-row blocks a
+//                                  V^T comes through ds_read_b64_tr_b16 from the wave's own LDS image of the V tile (the swizzled
+//                                  256-byte rows of attn_device.h; the key order of a 16-key block is permuted so that the two 4-row blocks a
 //                                  32-lane half reads lie 8 rows apart: conflict-free).
 //      The next tile's K / V are requested into registers before the current one is computed.  No workgroup barrier inside the walk: the LDS image
 //      is private to the wave.  The four waves meet once (LDS), giving the split's {M, den, o = num / den in fp16} per row.  One active split: that
-//      IS the output row.  Several: records go out with system-scope stores, an arrival ticket per head elects the last split, which merges the
-//      records in split order with the shared attn_merge_* helpers -- the ticket decides who merges, never what is computed: same inputs, same bits.
+//      IS the output row.  Several: the split hand-off of attn_device.h (system-scope records, attn_ticket_last, attn_merge_records), as in the decode
+//      attention -- the ticket decides who merges, never what is computed: same inputs, same bits.
 // Bounds: keys at and beyond min(p + rows, t_max) are never loaded (their slots of a tile are zeros); for row r everything above p + r is masked by a
 // select before the maximum.  p < 0 or p >= t_max: nothing is read or written.  A row whose position is >= t_max is skipped.
 // Several sequences (batched speculative decoding): both grids get the sequence b as blockIdx.z -- its packed rows b rows .. of qkv / out, its cache
@@ -30,8 +30,7 @@
 // values as a single-sequence call (which is the seqs = 1 case), hence the same bits; still two launches for any number of sequences.
 #include <algorithm>
 
-#include "attn_split.h"
-#include "gptq_device.h"
+#include "attn_device.h"
 #include "gptq_internal.h"
 
 namespace gptq {
@@ -54,59 +53,13 @@ __global__ void __launch_bounds__(64) chunk_rope_kv_kernel(const half_t *__restr
     const int64_t pos = p + r;
     if (pos >= t_max) return;
     float cs, sn;
-    if (tab) {   // {cos, sin} of (pos, c) from the table rope_table_kernel filled with the SAME instructions
-        const float2 e = tab[(size_t)pos * half + c];
-        cs = e.x;
-        sn = e.y;
-    } else {
-        const float freq = expf((float)c * inv_base) * (float)pos;
-        cs = cosf(freq);
-        sn = sinf(freq);
-    }
+    rope_cos_sin(tab, pos, c, half, inv_base, cs, sn);
     const int hd = heads * CA_HD;
     const half_t *q = qkv + ((size_t)b * rows + r) * ldq + (size_t)h * CA_HD + c;
-    const half_t *k = q + hd;
-    const half_t *v = q + 2 * hd;
-    const float qx = (float)q[0], qy = (float)q[half];
     half_t *qd = qrot + ((size_t)b * rows + r) * hd + (size_t)h * CA_HD + c;
-    qd[0] = (half_t)(qx * cs - qy * sn);
-    qd[half] = (half_t)(qx * sn + qy * cs);
-    const float kx = (float)k[0], ky = (float)k[half];
     half_t *kd = kc + (size_t)b * slot_stride + (size_t)pos * hd + (size_t)h * CA_HD + c;
-    kd[0] = (half_t)(kx * cs - ky * sn);
-    kd[half] = (half_t)(kx * sn + ky * cs);
     half_t *vd = vc + (size_t)b * slot_stride + (size_t)pos * hd + (size_t)h * CA_HD + c;
-    vd[0] = v[0];
-    vd[half] = v[half];
-}
-
-// byte offset of 16-byte chunk ch (0..15) of row `row` in a [rows][128 fp16] LDS image (the swizzle of prompt_attn.hip)
-GPTQ_DEV int ca_off(int row, int ch) { return 256 * row + 16 * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3))); }
-
-typedef short ca_short4 __attribute__((__vector_size__(4 * sizeof(short))));
-#define CA_LDS __attribute__((address_space(3)))
-
-// ds_read_b64_tr_b16: per 16-lane group a block of 4 rows x 16 columns, lane i receives column i (row q in element q).  Every lane supplies an
-// address (EXEC must be full: only ever called under wave-uniform control flow).
-GPTQ_DEV half4_t ca_tr_read(const half_t *img, int off) {
-    return __builtin_bit_cast(half4_t, __builtin_amdgcn_ds_read_tr16_b64_v4i16((CA_LDS ca_short4 *)((CA_LDS char *)img + off)));
-}
-// over the wave's four 16-lane rows (xor 16, 32): every lane of a column ends with the column's value
-GPTQ_DEV float ca_rows_max(float v) {
-    const uint32_t u = __builtin_bit_cast(uint32_t, v);
-    auto a = __builtin_amdgcn_permlane16_swap(u, u, false, false);
-    const float m16 = fmaxf(__builtin_bit_cast(float, (uint32_t)a[0]), __builtin_bit_cast(float, (uint32_t)a[1]));
-    const uint32_t u2 = __builtin_bit_cast(uint32_t, m16);
-    auto b = __builtin_amdgcn_permlane32_swap(u2, u2, false, false);
-    return fmaxf(__builtin_bit_cast(float, (uint32_t)b[0]), __builtin_bit_cast(float, (uint32_t)b[1]));
-}
-GPTQ_DEV float ca_rows_sum(float v) {
-    const uint32_t u = __builtin_bit_cast(uint32_t, v);
-    auto a = __builtin_amdgcn_permlane16_swap(u, u, false, false);
-    const float s16 = __builtin_bit_cast(float, (uint32_t)a[0]) + __builtin_bit_cast(float, (uint32_t)a[1]);
-    const uint32_t u2 = __builtin_bit_cast(uint32_t, s16);
-    auto b = __builtin_amdgcn_permlane32_swap(u2, u2, false, false);
-    return __builtin_bit_cast(float, (uint32_t)b[0]) + __builtin_bit_cast(float, (uint32_t)b[1]);
+    rope_kv_row(q, q + hd, q + 2 * hd, qd, kd, vd, half, cs, sn);
 }
 
 struct ChunkAttnArgs {
@@ -186,7 +139,7 @@ __global__ void __launch_bounds__(CA_NW * 64) chunk_attn_kernel(const ChunkAttnA
 
     auto tile = [&](const u32x4 (&K)[2][4], const u32x4 (&V)[8], int tb) {
 #pragma unroll
-        for (int i = 0; i < 8; i++) *(CA_LDS u32x4 *)((CA_LDS char *)img + ca_off(vrow + 4 * i, vch)) = V[i];
+        for (int i = 0; i < 8; i++) *(ATTN_LDS u32x4 *)((ATTN_LDS char *)img + attn_lds_off(vrow + 4 * i, vch)) = V[i];
         float4_t sc[2];
 #pragma unroll
         for (int b = 0; b < 2; b++) {
@@ -206,7 +159,7 @@ __global__ void __launch_bounds__(CA_NW * 64) chunk_attn_kernel(const ChunkAttnA
                 sc[b][r] = v;
                 mt = fmaxf(mt, v);
             }
-        mt = ca_rows_max(mt);
+        mt = rows_max(mt);
         const float Mn = fmaxf(M, mt);                     // finite: M starts at the floor
         const float alpha = __builtin_amdgcn_exp2f(M - Mn);
         M = Mn;
@@ -228,8 +181,8 @@ __global__ void __launch_bounds__(CA_NW * 64) chunk_attn_kernel(const ChunkAttnA
 #pragma unroll
         for (int d = 0; d < 8; d++) {
             const int r0 = kreg0 + (qi >> 2), ch = 2 * d + ((qi & 3) >> 1), sub = 8 * (qi & 1);
-            const half4_t lo = ca_tr_read(img, ca_off(r0, ch) + sub);
-            const half4_t up = ca_tr_read(img, ca_off(r0 + 16, ch) + sub);
+            const half4_t lo = attn_tr_read(img, attn_lds_off(r0, ch) + sub);
+            const half4_t up = attn_tr_read(img, attn_lds_off(r0 + 16, ch) + sub);
             const half8_t vf = half8_t{lo[0], lo[1], lo[2], lo[3], up[0], up[1], up[2], up[3]};
             acc[d] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf, pf, acc[d], 0, 0, 0);
         }
@@ -250,10 +203,10 @@ __global__ void __launch_bounds__(CA_NW * 64) chunk_attn_kernel(const ChunkAttnA
     }
 
     // ---- the lane rows of a column -> one, the waves -> one (LDS): {Mx, den, num} of the split per query row ----
-    l = ca_rows_sum(l);
+    l = rows_sum(l);
     float *const ow = (float *)img;                        // [16 queries][128 dims] fp32: the wave is done with its own V image
 #pragma unroll
-    for (int d = 0; d < 8; d++) *(CA_LDS float4_t *)((CA_LDS float *)ow + qi * CA_HD + 16 * d + 4 * g) = acc[d];
+    for (int d = 0; d < 8; d++) *(ATTN_LDS float4_t *)((ATTN_LDS float *)ow + qi * CA_HD + 16 * d + 4 * g) = acc[d];
     if (g == 0) {
         mw[wave][qi] = M;
         lw[wave][qi] = l;
@@ -298,38 +251,10 @@ __global__ void __launch_bounds__(CA_NW * 64) chunk_attn_kernel(const ChunkAttnA
             __hip_atomic_store(rmd + (size_t)s * mstride + 1, den, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         }
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) {
-        unsigned *ticket = a.tickets + (size_t)b * a.heads + h;
-        const unsigned t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const int last = (t == (unsigned)(sp.nsp - 1));
-        if (last) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        last_flag = last;
-    }
-    __syncthreads();
-    if (!last_flag || qq >= nr) return;
-    float mi[ATT_MAX_SPLITS], di[ATT_MAX_SPLITS];
-    u32x4 oi[ATT_MAX_SPLITS];
-#pragma unroll
-    for (int i = 0; i < ATT_MAX_SPLITS; i++) {
-        const int ii = min(i, sp.nsp - 1);
-        mi[i] = __hip_atomic_load(rmd + (size_t)ii * mstride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        di[i] = __hip_atomic_load(rmd + (size_t)ii * mstride + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-#pragma unroll
-        for (int j = 0; j < 4; j++) oi[i][j] = __hip_atomic_load(ro + (size_t)ii * rstride + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-    float c[ATT_MAX_SPLITS];
-    attn_merge_coeffs(mi, di, sp.nsp, c);
-    half8_t res;
-#pragma unroll
-    for (int j = 0; j < 8; j++) {
-        half_t oj[ATT_MAX_SPLITS];
-#pragma unroll
-        for (int i = 0; i < ATT_MAX_SPLITS; i++) oj[i] = __builtin_bit_cast(half8_t, oi[i])[j];
-        res[j] = attn_round_f16(attn_merge_value(oj, c));
-    }
-    *(half8_t *)orow = res;
+    if (!attn_ticket_last(a.tickets + (size_t)b * a.heads + h, sp.nsp, &last_flag) || qq >= nr) return;
+    half_t res[8];
+    attn_merge_records(rmd, mstride, ro, rstride, sp.nsp, res);
+    *(half8_t *)orow = half8_t{res[0], res[1], res[2], res[3], res[4], res[5], res[6], res[7]};
 }
 
 // S of the launch's grid: as the decode attention of one row (heads x S <= 256 workgroups, at most ATT_MAX_SPLITS, one split per tile of tokens)
@@ -338,15 +263,7 @@ int chunk_attn_grid_splits(int heads, int t_max) { return decode_attn_grid_split
 // active splits of a call whose rows end at token `len` (= p + rows, capped at t_max): what attn_split() gives the kernel
 int chunk_attn_active_splits(int heads, int t_max, int len) { return attn_split(len, chunk_attn_grid_splits(heads, t_max), CA_TPS).nsp; }
 
-static size_t ca_align(size_t n) { return (n + 255) & ~(size_t)255; }
-
-// rotated q [seqs][rows][hd] fp16 | records [seqs][S][rows][hd] fp16 | {M, den} [seqs][S][heads][rows] fp32 x 2 | tickets [seqs][heads]
-// (seqs = 1: the layout and the size of the single-sequence entry)
-size_t chunk_attn_batch_ws_bytes(int seqs, int rows, int heads, int t_max) {
-    const size_t S = (size_t)chunk_attn_grid_splits(heads, t_max), hd = (size_t)heads * CA_HD, n = (size_t)seqs;
-    return ca_align(n * rows * hd * sizeof(half_t)) + ca_align(n * S * rows * hd * sizeof(half_t)) + ca_align(n * S * heads * rows * 2 * sizeof(float)) +
-           ca_align(n * heads * sizeof(unsigned));
-}
+size_t chunk_attn_batch_ws_bytes(int seqs, int rows, int heads, int t_max) { return chunk_attn_ws(seqs, rows, heads, t_max).bytes; }
 
 size_t chunk_attn_ws_bytes(int rows, int heads, int t_max) { return chunk_attn_batch_ws_bytes(1, rows, heads, t_max); }
 
@@ -356,24 +273,18 @@ size_t chunk_attn_ws_bytes(int rows, int heads, int t_max) { return chunk_attn_b
 int chunk_attn_batch_launch(const half_t *qkv, int64_t ldq, int seqs, int rows, const int64_t *pos, half_t *kc, half_t *vc, int64_t slot_stride,
                             half_t *out, int64_t ldo, void *ws, int heads, int t_max, float base, float scale, const float *rope_table,
                             hipStream_t s) {
-    const int S = chunk_attn_grid_splits(heads, t_max);
-    const size_t hd = (size_t)heads * CA_HD, n = (size_t)seqs;
-    char *w = (char *)ws;
-    half_t *qrot = (half_t *)w;
-    w += ca_align(n * rows * hd * sizeof(half_t));
+    const ChunkAttnWs w = chunk_attn_ws(seqs, rows, heads, t_max);
+    half_t *qrot = (half_t *)((char *)ws + w.qrot);
     ChunkAttnArgs a{};
-    a.o16 = (uint32_t *)w;
-    w += ca_align(n * S * rows * hd * sizeof(half_t));
-    a.md = (float *)w;
-    w += ca_align(n * S * heads * rows * 2 * sizeof(float));
-    a.tickets = (unsigned *)w;
-    const float inv_base = -2.0f * logf(base) / (float)CA_HD;   // reference fused_attn.py:91
+    a.o16 = (uint32_t *)((char *)ws + w.o16);
+    a.md = (float *)((char *)ws + w.md);
+    a.tickets = (unsigned *)((char *)ws + w.tickets);
     hipLaunchKernelGGL(chunk_rope_kv_kernel, dim3(rows, heads, seqs), dim3(CA_HD / 2), 0, s, qkv, ldq, pos, kc, vc, slot_stride, qrot, a.tickets, heads,
-                       t_max, inv_base, (const float2 *)rope_table);
+                       t_max, rope_inv_base(base, CA_HD), (const float2 *)rope_table);
     a.q = qrot; a.pos = pos; a.kc = kc; a.vc = vc; a.out = out;
     a.heads = heads; a.rows = rows; a.t_max = t_max; a.ldo = ldo; a.slot_stride = slot_stride;
     a.scale2 = scale * 1.44269504088896340736f;
-    hipLaunchKernelGGL(chunk_attn_kernel, dim3(heads, S, seqs), dim3(CA_NW * 64), 0, s, a);
+    hipLaunchKernelGGL(chunk_attn_kernel, dim3(heads, w.S, seqs), dim3(CA_NW * 64), 0, s, a);
     return (int)hipGetLastError();
 }
 

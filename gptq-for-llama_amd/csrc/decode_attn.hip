@@ -9,56 +9,13 @@
 #include <algorithm>
 #include <type_traits>
 
-#include "attn_split.h"
-#include "gptq_device.h"
+#include "attn_device.h"
 #include "gptq_internal.h"
 
 namespace gptq {
 
-
-// Cross-lane reductions on the VALU (DPP row operations + gfx950 permlane swaps) instead of __shfl_xor, which hipcc lowers to
-// ds_bpermute_b32: ~120 cycles of LDS round trip per dependent step -- the per-wave stamps (tools/timeline_attn.py) showed 3500
-// cycles in the 32 dependent shuffles of the score loop alone, 6500 of the launch's 10 000.  Same operand pairs as the xor
-// butterfly: bit-identical results.
-template <int CTRL>
-GPTQ_DEV float att_dpp(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
-GPTQ_DEV float att_sum16(float v) {   // every lane of a 16-lane row ends with the row's sum (xor 1, 2, 4, 8)
-    v += att_dpp<0xB1>(v);   // quad_perm [1,0,3,2]
-    v += att_dpp<0x4E>(v);   // quad_perm [2,3,0,1]
-    v += att_dpp<0x141>(v);  // row_half_mirror
-    v += att_dpp<0x140>(v);  // row_mirror
-    return v;
-}
-GPTQ_DEV float att_max16(float v) {
-    v = fmaxf(v, att_dpp<0xB1>(v));
-    v = fmaxf(v, att_dpp<0x4E>(v));
-    v = fmaxf(v, att_dpp<0x141>(v));
-    v = fmaxf(v, att_dpp<0x140>(v));
-    return v;
-}
-GPTQ_DEV float att_rows_sum(float v) {   // sum over the four 16-lane rows of the wave (xor 16, 32)
-    const uint32_t u = __builtin_bit_cast(uint32_t, v);
-    auto a = __builtin_amdgcn_permlane16_swap(u, u, false, false);
-    const float s16 = __builtin_bit_cast(float, (uint32_t)a[0]) + __builtin_bit_cast(float, (uint32_t)a[1]);
-    const uint32_t u2 = __builtin_bit_cast(uint32_t, s16);
-    auto b = __builtin_amdgcn_permlane32_swap(u2, u2, false, false);
-    return __builtin_bit_cast(float, (uint32_t)b[0]) + __builtin_bit_cast(float, (uint32_t)b[1]);
-}
-GPTQ_DEV float att_rows_max(float v) {
-    const uint32_t u = __builtin_bit_cast(uint32_t, v);
-    auto a = __builtin_amdgcn_permlane16_swap(u, u, false, false);
-    const float m16 = fmaxf(__builtin_bit_cast(float, (uint32_t)a[0]), __builtin_bit_cast(float, (uint32_t)a[1]));
-    const uint32_t u2 = __builtin_bit_cast(uint32_t, m16);
-    auto b = __builtin_amdgcn_permlane32_swap(u2, u2, false, false);
-    return fmaxf(__builtin_bit_cast(float, (uint32_t)b[0]), __builtin_bit_cast(float, (uint32_t)b[1]));
-}
-GPTQ_DEV float att_wave_sum(float v) { return att_rows_sum(att_sum16(v)); }
-GPTQ_DEV float att_wave_max(float v) { return att_rows_max(att_max16(v)); }
-
 // ---------------------------------------------------------------------------------------
-// RoPE (rotate-half, fp32 trig exactly like rope_kernel / reference :43-57) on q (in place) and
+// RoPE (attn_device.h: fp32 trig exactly like rope_kernel / reference :43-57) on q (in place) and
 // k, then k,v -> cache row `pos`.  grid = heads, block = head_dim/2 threads.
 // ---------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) rope_kv_kernel(half_t *__restrict__ qkv, const int64_t *__restrict__ pos_ptr,
@@ -68,22 +25,15 @@ __global__ void __launch_bounds__(256) rope_kv_kernel(half_t *__restrict__ qkv, 
     if (c >= half) return;
     const int64_t pos = pos_ptr[0];
     if (pos < 0 || pos >= t_max) return;
-    const float freq = expf((float)c * inv_base) * (float)pos;
-    const float cs = cosf(freq), sn = sinf(freq);
+    float cs, sn;
+    rope_cos_sin(nullptr, pos, c, half, inv_base, cs, sn);
     const int hd = heads * head_dim;
     half_t *q = qkv + (size_t)h * head_dim + c;
-    half_t *k = qkv + hd + (size_t)h * head_dim + c;
+    const half_t *k = qkv + hd + (size_t)h * head_dim + c;
     const half_t *v = qkv + 2 * hd + (size_t)h * head_dim + c;
-    const float qx = (float)q[0], qy = (float)q[half];
-    q[0] = (half_t)(qx * cs - qy * sn);
-    q[half] = (half_t)(qx * sn + qy * cs);
-    const float kx = (float)k[0], ky = (float)k[half];
     half_t *kd = kc + (size_t)pos * hd + (size_t)h * head_dim + c;
-    kd[0] = (half_t)(kx * cs - ky * sn);
-    kd[half] = (half_t)(kx * sn + ky * cs);
     half_t *vd = vc + (size_t)pos * hd + (size_t)h * head_dim + c;
-    vd[0] = v[0];
-    vd[half] = v[half];
+    rope_kv_row(q, k, v, q, kd, vd, half, cs, sn);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -92,7 +42,6 @@ __global__ void __launch_bounds__(256) rope_kv_kernel(half_t *__restrict__ qkv, 
 // exit at once.  Partial = {max, sum, acc[128]} in fp32; attn_combine_kernel merges the splits.
 // ---------------------------------------------------------------------------------------
 constexpr int ATT_TS = 128;   // timesteps per split
-constexpr int ATT_HD = 128;   // head_dim served
 constexpr int ATT_REC = ATT_HD + 2;
 
 __global__ void __launch_bounds__(256) attn_partial_kernel(const half_t *__restrict__ q, const half_t *__restrict__ kc,
@@ -125,7 +74,7 @@ __global__ void __launch_bounds__(256) attn_partial_kernel(const half_t *__restr
 #pragma unroll
             for (int j = 0; j < 8; j++) dot += qf[j] * (float)k8[j];
         }
-        dot = att_sum16(dot);
+        dot = row_sum16(dot);
         if (d8 == 0) sc[tl] = (tl < nact) ? dot * scale : -INFINITY;
     }
     __syncthreads();
@@ -133,13 +82,13 @@ __global__ void __launch_bounds__(256) attn_partial_kernel(const half_t *__restr
     // ---- softmax statistics of the chunk ------------------------------------------------------
     float sv = (tid < ATT_TS) ? sc[tid] : -INFINITY;
     float m = sv;
-    m = att_wave_max(m);
+    m = rows_max(row_max16(m));
     if (lane == 0) red[wave] = m;
     __syncthreads();
     m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
     const float p = (tid < nact) ? __expf(sv - m) : 0.f;
     float l = p;
-    l = att_wave_sum(l);
+    l = rows_sum(row_sum16(l));
     __syncthreads();                 // everyone has read sc[] and red[0..3]
     if (tid < ATT_TS) sc[tid] = p;
     if (lane == 0) red[4 + wave] = l;
@@ -208,7 +157,7 @@ __global__ void __launch_bounds__(ATT_HD) attn_combine_kernel(const float *__res
 //                              of up to ATT_MAX_SPLITS splits (stripe_kernel.inc, ATT instances) -- the kernel boundary is the hand-off;
 //   several splits, !REC    -> records go out with system-scope stores, an arrival ticket per (row, head) elects the last split, which merges
 //                              them (callers without a merging consumer; act-order o_proj with the producer-side permutation).
-// ws = [batch][S][heads * 128] fp16 partial outputs | [batch][S][heads] fp32 {M, den} | [batch][heads] uint32 tickets (zero between launches).
+// ws = DecodeAttnWs (attn_split.h): fp16 partial outputs | fp32 {M, den} | uint32 tickets (zero between launches).
 // A negative position marks an idle row of the batch: nothing is read or written for it.
 // ---------------------------------------------------------------------------------------
 struct AttnArgs {
@@ -300,22 +249,13 @@ __global__ void __launch_bounds__(NW * 64) attn_stream_kernel(const AttnArgs a) 
     if (tid < ATT_HD / 2) {
         const int c = tid;
         float cs, sn;
-        if (a.rope_tab) {   // {cos, sin} of (pos, c) from the table rope_table_kernel filled with the SAME instructions
-            const float2 e = a.rope_tab[(size_t)pos * (ATT_HD / 2) + c];
-            cs = e.x;
-            sn = e.y;
-        } else {
-            const float freq = expf((float)c * a.inv_base) * (float)pos;
-            cs = cosf(freq);
-            sn = sinf(freq);
-        }
-        const float qx = (float)q0, qy = (float)q1;
-        qs[c] = (float)(half_t)(qx * cs - qy * sn);       // rounded to fp16 like the in-place reference RoPE (fused_attn.py:43-57)
-        qs[c + ATT_HD / 2] = (float)(half_t)(qx * sn + qy * cs);
+        rope_cos_sin(a.rope_tab, pos, c, ATT_HD / 2, a.inv_base, cs, sn);
+        half_t rq0, rq1;
+        rope_rotate(q0, q1, cs, sn, rq0, rq1);
+        qs[c] = (float)rq0;
+        qs[c + ATT_HD / 2] = (float)rq1;
         if (owner) {
-            const float kx = (float)k0, ky = (float)k1;
-            nk0 = (half_t)(kx * cs - ky * sn);
-            nk1 = (half_t)(kx * sn + ky * cs);
+            rope_rotate(k0, k1, cs, sn, nk0, nk1);
             knew[c] = nk0;
             knew[c + ATT_HD / 2] = nk1;
             vnew[c] = nv0;
@@ -336,7 +276,7 @@ __global__ void __launch_bounds__(NW * 64) attn_stream_kernel(const AttnArgs a) 
         float dot = 0.f;
 #pragma unroll
         for (int j = 0; j < 8; j++) dot = __builtin_fmaf(qf[j], (float)k8[j], dot);
-        return att_sum16(dot) * a.scale2;
+        return row_sum16(dot) * a.scale2;
     };
     auto tile_full = [&](const u32x4 (&K)[NP], const u32x4 (&V)[NP]) {
         float sc[NP];
@@ -345,7 +285,7 @@ __global__ void __launch_bounds__(NW * 64) attn_stream_kernel(const AttnArgs a) 
         float mt = sc[0];
 #pragma unroll
         for (int it = 1; it < NP; it++) mt = fmaxf(mt, sc[it]);
-        mt = att_rows_max(mt);                                   // the wave's four rows: M stays wave-uniform
+        mt = rows_max(mt);                                   // the wave's four rows: M stays wave-uniform
         const float Mn = fmaxf(M, mt), alpha = __builtin_amdgcn_exp2f(M - Mn);
         float p[NP], ps = 0.f;
 #pragma unroll
@@ -383,7 +323,7 @@ __global__ void __launch_bounds__(NW * 64) attn_stream_kernel(const AttnArgs a) 
             sc[it] = t < t_end ? v : -INFINITY;
             mt = fmaxf(mt, sc[it]);
         }
-        mt = att_rows_max(mt);
+        mt = rows_max(mt);
         const float Mn = fmaxf(M, mt), alpha = __builtin_amdgcn_exp2f(M - Mn);
         float p[PASSES], ps = 0.f;
 #pragma unroll
@@ -434,8 +374,8 @@ __global__ void __launch_bounds__(NW * 64) attn_stream_kernel(const AttnArgs a) 
 
     // ---- the wave's four rows -> one, the NW waves -> one (LDS): {Mx, den, num[tid]} of the split ----
 #pragma unroll
-    for (int j = 0; j < 8; j++) av[j] = att_rows_sum(av[j]);
-    l = att_rows_sum(l);
+    for (int j = 0; j < 8; j++) av[j] = rows_sum(av[j]);
+    l = rows_sum(l);
     if (lane < 16) {
         *(float4_t *)(&accs[wave][lane * 8]) = float4_t{av[0], av[1], av[2], av[3]};
         *(float4_t *)(&accs[wave][lane * 8 + 4]) = float4_t{av[4], av[5], av[6], av[7]};
@@ -475,38 +415,18 @@ __global__ void __launch_bounds__(NW * 64) attn_stream_kernel(const AttnArgs a) 
         __hip_atomic_store(rmd + (size_t)s * a.heads * 2, Mx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         __hip_atomic_store(rmd + (size_t)s * a.heads * 2 + 1, den, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    unsigned *ticket = a.tickets + (size_t)b * a.heads + h;
-    if (tid == 0) {
-        const unsigned t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const int last = (t == (unsigned)(sp.nsp - 1));
-        if (last) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        last_flag = last;
-    }
-    __syncthreads();
-    if (!last_flag) return;
-    if (tid < ATT_HD) {      // the records of all splits requested together (one memory latency), merged in split order
-        float mi[ATT_MAX_SPLITS], di[ATT_MAX_SPLITS];
-        half_t oi[ATT_MAX_SPLITS];
-#pragma unroll
-        for (int i = 0; i < ATT_MAX_SPLITS; i++) {
-            const int ii = min(i, sp.nsp - 1);
-            mi[i] = __hip_atomic_load(rmd + (size_t)ii * a.heads * 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            di[i] = __hip_atomic_load(rmd + (size_t)ii * a.heads * 2 + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            const uint16_t u = __hip_atomic_load((const uint16_t *)(ro + (size_t)ii * hd + tid), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            oi[i] = __builtin_bit_cast(half_t, u);
-        }
-        float c[ATT_MAX_SPLITS];
-        attn_merge_coeffs(mi, di, sp.nsp, c);
-        a.out[(size_t)b * a.ldo + ocol] = attn_round_f16(attn_merge_value(oi, c));
+    if (!attn_ticket_last(a.tickets + (size_t)b * a.heads + h, sp.nsp, &last_flag)) return;
+    if (tid < ATT_HD) {
+        half_t res[1];
+        attn_merge_records(rmd, (size_t)a.heads * 2, (const uint16_t *)ro + tid, hd, sp.nsp, res);
+        a.out[(size_t)b * a.ldo + ocol] = res[0];
     }
 }
 
 int decode_rope_kv_launch(half_t *qkv, const int64_t *pos, half_t *kc, half_t *vc, int heads, int head_dim, int t_max, float base,
                           hipStream_t s) {
-    const float inv_base = -2.0f * logf(base) / (float)head_dim;   // reference fused_attn.py:91
-    hipLaunchKernelGGL(rope_kv_kernel, dim3(heads), dim3(head_dim / 2), 0, s, qkv, pos, kc, vc, heads, head_dim, t_max, inv_base);
+    hipLaunchKernelGGL(rope_kv_kernel, dim3(heads), dim3(head_dim / 2), 0, s, qkv, pos, kc, vc, heads, head_dim, t_max,
+                       rope_inv_base(base, head_dim));
     return (int)hipGetLastError();
 }
 
@@ -535,46 +455,44 @@ int decode_attn_tps(bool rec) { return rec ? 128 : 768; }
 int decode_attn_fused_launch(const half_t *qkv, const int64_t *pos, half_t *kc, half_t *vc, half_t *out, float *ws, int heads, int t_max,
                              float base, float scale, const float *rope_table, hipStream_t s, int batch, int64_t ldq, int64_t ldo,
                              const int32_t *out_perm, bool rec, int tps) {
-    const int S = decode_attn_grid_splits(heads, t_max, batch);
+    const DecodeAttnWs w = decode_attn_ws(batch, heads, t_max);
     AttnArgs a{};
     a.qkv = qkv; a.pos = pos; a.kc = kc; a.vc = vc; a.out = out;
-    a.o16 = (half_t *)ws;
-    a.md = (float *)((half_t *)ws + (size_t)batch * S * heads * ATT_HD);
-    a.tickets = (unsigned *)(a.md + (size_t)batch * S * heads * 2);
+    a.o16 = (half_t *)((char *)ws + w.o16);
+    a.md = (float *)((char *)ws + w.md);
+    a.tickets = (unsigned *)((char *)ws + w.tickets);
     a.rope_tab = (const float2 *)rope_table;
     a.out_perm = out_perm;
     a.heads = heads; a.t_max = t_max; a.ldq = (int)ldq; a.ldo = (int)ldo;
     a.tps = tps > 0 ? tps : decode_attn_tps(rec);
-    a.inv_base = -2.0f * logf(base) / (float)ATT_HD;   // reference fused_attn.py:91
+    a.inv_base = rope_inv_base(base, ATT_HD);
     a.scale2 = scale * 1.44269504088896340736f;
-    const dim3 grid(heads, batch, S);
+    const dim3 grid(heads, batch, w.S);
     // (four waves: eight -- two per SIMD, 256-step tiles -- measured the same within noise at every depth, gpurun_out r6a / r6b, and spill)
     if (rec) hipLaunchKernelGGL((attn_stream_kernel<4, true>), grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL((attn_stream_kernel<4, false>), grid, dim3(256), 0, s, a);
     return (int)hipGetLastError();
 }
 
-// {cos, sin}(pos * base^(-2c / head_dim)) for pos < t_max, c < head_dim / 2: the arithmetic of the in-kernel RoPE above, once
+// {cos, sin}(pos * base^(-2c / head_dim)) for pos < t_max, c < head_dim / 2: rope_cos_sin's own arithmetic, once
 __global__ void __launch_bounds__(64) rope_table_kernel(float2 *__restrict__ tab, int half, float inv_base) {
     const int pos = blockIdx.x, c = threadIdx.x;
     if (c >= half) return;
-    const float freq = expf((float)c * inv_base) * (float)pos;
-    tab[(size_t)pos * half + c] = float2{cosf(freq), sinf(freq)};
+    float cs, sn;
+    rope_cos_sin(nullptr, pos, c, half, inv_base, cs, sn);
+    tab[(size_t)pos * half + c] = float2{cs, sn};
 }
 
 int rope_table_launch(float *table, int t_max, int head_dim, float base, hipStream_t s) {
-    const float inv_base = -2.0f * logf(base) / (float)head_dim;
-    hipLaunchKernelGGL(rope_table_kernel, dim3(t_max), dim3(64), 0, s, (float2 *)table, head_dim / 2, inv_base);
+    hipLaunchKernelGGL(rope_table_kernel, dim3(t_max), dim3(64), 0, s, (float2 *)table, head_dim / 2, rope_inv_base(base, head_dim));
     return (int)hipGetLastError();
 }
 
-// records of the streaming kernel [batch][S][heads * 128] fp16 + [batch][S][heads][2] fp32 + tickets [batch][heads]; never less than the records of the two-launch
-// path above (batch 1: [heads][t_max / 128][130])
+// the records of the streaming kernel (DecodeAttnWs, attn_split.h); never less than the records of the two-launch path above (batch 1:
+// [heads][t_max / 128][130])
 size_t decode_attn_ws_bytes(int heads, int t_max, int batch) {
-    const int S = decode_attn_grid_splits(heads, t_max, batch);
-    const size_t stream = (size_t)batch * ((size_t)S * heads * (ATT_HD * sizeof(half_t) + 2 * sizeof(float)) + (size_t)heads * sizeof(unsigned));
     const size_t two = batch == 1 ? (size_t)heads * ((t_max + ATT_TS - 1) / ATT_TS) * ATT_REC * sizeof(float) : 0;
-    return std::max(stream, two);
+    return std::max(decode_attn_ws(batch, heads, t_max).bytes, two);
 }
 
 }  // namespace gptq

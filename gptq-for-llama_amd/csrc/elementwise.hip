@@ -4,7 +4,7 @@
 //   pack      reference quant/quant_linear.py:325-371 (QuantLinear.pack, CPU upstream)
 //   g_idx triviality check (load-time helper, no reference counterpart)
 // All are bandwidth/latency bound: 16-byte vector accesses, wave shuffles + one LDS hop.
-#include "gptq_device.h"
+#include "attn_device.h"
 #include "gptq_internal.h"
 
 namespace gptq {
@@ -196,8 +196,8 @@ int slices_combine_norm_launch(const float *partials, int S, int M, int N, const
 
 // --------------------------------------------------------------------------------- RoPE
 // One workgroup per (batch, position) row.  A thread owns VW adjacent rotary columns: it
-// computes their cos/sin once (fp32, accurate expf/cosf/sinf like the reference's libdevice
-// calls) and walks over the 2*heads head slots of q and k.
+// computes their cos/sin once (rope_cos_sin, attn_device.h: fp32, the accurate libm exp / cos / sin like
+// the reference's libdevice calls) and walks over the 2*heads head slots of q and k.
 template <int VW>
 __global__ void __launch_bounds__(256) rope_kernel(half_t *qk, int64_t row_stride, const int64_t *pos,
                                                    int64_t pos_batch_stride, int seq, int nheads2, int head_dim,
@@ -213,20 +213,17 @@ __global__ void __launch_bounds__(256) rope_kernel(half_t *qk, int64_t row_strid
     const float p = (float)pos[(size_t)b * pos_batch_stride + t];
     float cs[VW], sn[VW];
 #pragma unroll
-    for (int j = 0; j < VW; j++) {
-        const float freq = expf((float)(c + j) * inv_base) * p;
-        cs[j] = cosf(freq);
-        sn[j] = sinf(freq);
-    }
+    for (int j = 0; j < VW; j++) rope_cos_sin(nullptr, p, c + j, half, inv_base, cs[j], sn[j]);
     half_t *base = qk + (size_t)row * row_stride + c;
     for (int h = h0; h < nheads2; h += hstep) {
         half_t *px = base + (size_t)h * head_dim;
         vec_t xv = *(const vec_t *)px, yv = *(const vec_t *)(px + half), ox, oy;
 #pragma unroll
         for (int j = 0; j < VW; j++) {
-            const float xf = (float)xv[j], yf = (float)yv[j];
-            ox[j] = (half_t)(xf * cs[j] - yf * sn[j]);
-            oy[j] = (half_t)(xf * sn[j] + yf * cs[j]);
+            half_t rx, ry;
+            rope_rotate(xv[j], yv[j], cs[j], sn[j], rx, ry);
+            ox[j] = rx;
+            oy[j] = ry;
         }
         *(vec_t *)px = ox;
         *(vec_t *)(px + half) = oy;
@@ -238,7 +235,7 @@ int rope_launch(half_t *qk, int64_t row_stride, const int64_t *pos, int64_t pos_
     const int rows = bsz * seq;
     if (rows == 0) return 0;
     const int half = head_dim / 2;
-    const float inv_base = -2.0f * logf(base) / (float)head_dim;
+    const float inv_base = rope_inv_base(base, head_dim);
     dim3 grid(rows), block(256);
     const bool a16 = ((uintptr_t)qk % 16 == 0) && (row_stride % 8 == 0);
     if (half % 8 == 0 && a16 && half / 8 <= 256) {

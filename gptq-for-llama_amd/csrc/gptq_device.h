@@ -143,35 +143,59 @@ GPTQ_DEV int zero_of(const int32_t *zrow, int n) {
     }
 }
 
-// sum over the xor butterfly offsets from, 2 from, ... 32.  __shfl_xor lowers to ds_bpermute_b32 (an LDS round trip, ~120 cycles per
-// dependent step); the offsets inside a 16-lane row run as DPP row operations and 16 / 32 as gfx950 permlane swaps instead -- same
-// operand pairs, bit-identical sums.  (from = 2, 4, 8 keep the shuffle for the in-row steps: the mirror patterns only equal the
-// xor pairs when the finer steps ran first.)
+// Cross-lane reductions on the VALU.  __shfl_xor lowers to ds_bpermute_b32 (an LDS round trip, ~120 cycles per dependent step: the
+// per-wave stamps of tools/timeline_attn.py showed 3500 cycles in the 32 dependent shuffles of the decode attention's score loop, 6500 of
+// the launch's 10 000); the xor offsets inside a 16-lane row run as DPP row operations and 16 / 32 as gfx950 permlane swaps instead -- the
+// SAME operand pairs in the same order as the xor butterfly, so the results are bit-identical to it.  Do not reorder the steps.
 template <int CTRL>
 GPTQ_DEV float dpp_row_f32(float v) {
     return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
 }
+GPTQ_DEV float row_sum16(float v) {   // every lane of a 16-lane row ends with the row's sum (xor 1, 2, 4, 8)
+    v += dpp_row_f32<0xB1>(v);    // quad_perm [1,0,3,2]
+    v += dpp_row_f32<0x4E>(v);    // quad_perm [2,3,0,1]
+    v += dpp_row_f32<0x141>(v);   // row_half_mirror
+    v += dpp_row_f32<0x140>(v);   // row_mirror
+    return v;
+}
+GPTQ_DEV float row_max16(float v) {
+    v = fmaxf(v, dpp_row_f32<0xB1>(v));
+    v = fmaxf(v, dpp_row_f32<0x4E>(v));
+    v = fmaxf(v, dpp_row_f32<0x141>(v));
+    v = fmaxf(v, dpp_row_f32<0x140>(v));
+    return v;
+}
+GPTQ_DEV float halves_sum(float v) {   // over the wave's two 32-lane halves (xor 32)
+    const uint32_t u = __builtin_bit_cast(uint32_t, v);
+    auto a = __builtin_amdgcn_permlane32_swap(u, u, false, false);
+    return __builtin_bit_cast(float, (uint32_t)a[0]) + __builtin_bit_cast(float, (uint32_t)a[1]);
+}
+GPTQ_DEV float halves_max(float v) {
+    const uint32_t u = __builtin_bit_cast(uint32_t, v);
+    auto a = __builtin_amdgcn_permlane32_swap(u, u, false, false);
+    return fmaxf(__builtin_bit_cast(float, (uint32_t)a[0]), __builtin_bit_cast(float, (uint32_t)a[1]));
+}
+GPTQ_DEV float rows_sum(float v) {   // over the wave's four 16-lane rows (xor 16, then 32): every lane ends with the total of its lane position
+    const uint32_t u = __builtin_bit_cast(uint32_t, v);
+    auto a = __builtin_amdgcn_permlane16_swap(u, u, false, false);
+    return halves_sum(__builtin_bit_cast(float, (uint32_t)a[0]) + __builtin_bit_cast(float, (uint32_t)a[1]));
+}
+GPTQ_DEV float rows_max(float v) {
+    const uint32_t u = __builtin_bit_cast(uint32_t, v);
+    auto a = __builtin_amdgcn_permlane16_swap(u, u, false, false);
+    return halves_max(fmaxf(__builtin_bit_cast(float, (uint32_t)a[0]), __builtin_bit_cast(float, (uint32_t)a[1])));
+}
+// sum over the xor butterfly offsets from, 2 from, ... 32.  (from = 2, 4, 8 keep the shuffle for the in-row steps: the mirror patterns
+// only equal the xor pairs when the finer steps ran first.)
 GPTQ_DEV float wave_sum_xor(float v, int from) {
     if (from == 1) {
-        v += dpp_row_f32<0xB1>(v);    // quad_perm [1,0,3,2]
-        v += dpp_row_f32<0x4E>(v);    // quad_perm [2,3,0,1]
-        v += dpp_row_f32<0x141>(v);   // row_half_mirror
-        v += dpp_row_f32<0x140>(v);   // row_mirror
+        v = row_sum16(v);
     } else {
 #pragma unroll
         for (int off = from; off < 16; off <<= 1) v += __shfl_xor(v, off, 64);
     }
-    if (from <= 16) {
-        const uint32_t u = __builtin_bit_cast(uint32_t, v);
-        auto a = __builtin_amdgcn_permlane16_swap(u, u, false, false);
-        v = __builtin_bit_cast(float, (uint32_t)a[0]) + __builtin_bit_cast(float, (uint32_t)a[1]);
-    }
-    if (from <= 32) {
-        const uint32_t u = __builtin_bit_cast(uint32_t, v);
-        auto b = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-        v = __builtin_bit_cast(float, (uint32_t)b[0]) + __builtin_bit_cast(float, (uint32_t)b[1]);
-    }
-    return v;
+    if (from <= 16) return rows_sum(v);
+    return from <= 32 ? halves_sum(v) : v;
 }
 
 typedef unsigned long long u64_t;

@@ -7,15 +7,15 @@
 // however many segments there are -- the table travels BY VALUE in the launch arguments (256 bytes: nothing is allocated or copied, the
 // caller's array is free at once), and a workgroup finds its segment with a scan of scalars (blockIdx and the table: wave-uniform).
 // gptq_prompt_attn_f16 is the table of one segment: one kernel body, the same bits.
-//   1. prompt_rope_kv_kernel: the arithmetic of rope_kv_kernel (decode_attn.hip) per (row, head) -- rotated k and v go to cache rows
-//      start + r (bit-identical to a token-by-token feed: same instructions, same flags, see the Makefile), the rotated q to a
-//      workspace copy; qkv itself is never written.
+//   1. prompt_rope_kv_kernel: the shared RoPE + append of attn_device.h (rope_cos_sin, rope_kv_row) per (row, head) -- rotated k and
+//      v go to cache rows start + r (bit-identical to a token-by-token feed: the instructions and flags of every other entry), the
+//      rotated q to a workspace copy; qkv itself is never written.
 //   2. prompt_attn_kernel: flash-style attention, grid = (q tiles of all segments, head); the host sorts the table by start + rows
 //      (longest key range first), within a segment the q tiles are issued last (longest) first.  A workgroup is four
 //      waves x 32 query rows; it walks the keys [0, last position of the tile] in tiles of 64 with an online softmax (log2 domain).
 //      Q fragments live in registers; the K / V tile is requested into registers BEFORE the current tile is computed and written to
-//      LDS behind the barrier that ends it.  Both LDS images are plain 256-byte rows with the chunk swizzle
-//      ch ^ (((row & 3) << 2) | ((row >> 2) & 3)): conflict-free for the ds_read_b128 row reads of K and for the ds_read_b64_tr_b16
+//      LDS behind the barrier that ends it.  Both LDS images are the swizzled 256-byte rows of attn_device.h
+//      (attn_lds_off): conflict-free for the ds_read_b128 row reads of K and for the ds_read_b64_tr_b16
 //      transposed reads of V.  S^T = K Q^T (v_mfma_f32_32x32x16_f16, keys on the registers, the query on the lane: a lane owns half a
 //      score row, its partner lane ^ 32 the other half -> max / sum are in-lane plus one permlane32 swap), P is rounded to fp16 in
 //      registers and IS the B operand of O^T = V^T P^T (the accumulator layout of the first product is the operand layout of the
@@ -25,7 +25,7 @@
 // zeros: 0 * NaN would poison P V).
 #include <algorithm>
 
-#include "gptq_device.h"
+#include "attn_device.h"
 #include "gptq_internal.h"
 
 namespace gptq {
@@ -63,53 +63,13 @@ __global__ void __launch_bounds__(64) prompt_rope_kv_kernel(const half_t *__rest
     kc += (int64_t)sg.slot * slot_stride;
     vc += (int64_t)sg.slot * slot_stride;
     float cs, sn;
-    if (tab) {   // {cos, sin} of (pos, c) from the table rope_table_kernel filled with the SAME instructions
-        const float2 e = tab[(size_t)pos * half + c];
-        cs = e.x;
-        sn = e.y;
-    } else {
-        const float freq = expf((float)c * inv_base) * (float)pos;
-        cs = cosf(freq);
-        sn = sinf(freq);
-    }
+    rope_cos_sin(tab, pos, c, half, inv_base, cs, sn);
     const int hd = heads * PA_HD;
     const half_t *q = qkv + (size_t)row * ldq + (size_t)h * PA_HD + c;
-    const half_t *k = q + hd;
-    const half_t *v = q + 2 * hd;
-    const float qx = (float)q[0], qy = (float)q[half];
     half_t *qd = qrot + (size_t)row * hd + (size_t)h * PA_HD + c;
-    qd[0] = (half_t)(qx * cs - qy * sn);
-    qd[half] = (half_t)(qx * sn + qy * cs);
-    const float kx = (float)k[0], ky = (float)k[half];
     half_t *kd = kc + (size_t)pos * hd + (size_t)h * PA_HD + c;
-    kd[0] = (half_t)(kx * cs - ky * sn);
-    kd[half] = (half_t)(kx * sn + ky * cs);
     half_t *vd = vc + (size_t)pos * hd + (size_t)h * PA_HD + c;
-    vd[0] = v[0];
-    vd[half] = v[half];
-}
-
-// byte offset of 16-byte chunk ch (0..15) of row `row` in a [rows][128 fp16] LDS image
-GPTQ_DEV int pa_off(int row, int ch) { return 256 * row + 16 * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3))); }
-
-typedef short pa_short4 __attribute__((__vector_size__(4 * sizeof(short))));
-#define PA_LDS __attribute__((address_space(3)))
-
-GPTQ_DEV half8_t pa_row_read(const half_t *img, int off) { return *(const PA_LDS half8_t *)((const PA_LDS char *)img + off); }
-// ds_read_b64_tr_b16: per 16-lane group a block of 4 rows x 16 columns, lane i receives column i (row q in element q).  Every lane supplies
-// an address (EXEC must be full: only ever called under wave-uniform control flow).
-GPTQ_DEV half4_t pa_tr_read(const half_t *img, int off) {
-    return __builtin_bit_cast(half4_t, __builtin_amdgcn_ds_read_tr16_b64_v4i16((PA_LDS pa_short4 *)((PA_LDS char *)img + off)));
-}
-GPTQ_DEV float pa_max_halves(float v) {
-    const uint32_t u = __builtin_bit_cast(uint32_t, v);
-    auto a = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-    return fmaxf(__builtin_bit_cast(float, (uint32_t)a[0]), __builtin_bit_cast(float, (uint32_t)a[1]));
-}
-GPTQ_DEV float pa_sum_halves(float v) {
-    const uint32_t u = __builtin_bit_cast(uint32_t, v);
-    auto a = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-    return __builtin_bit_cast(float, (uint32_t)a[0]) + __builtin_bit_cast(float, (uint32_t)a[1]);
+    rope_kv_row(q, q + hd, q + 2 * hd, qd, kd, vd, half, cs, sn);
 }
 
 struct PromptAttnArgs {
@@ -172,9 +132,9 @@ __global__ void __launch_bounds__(PA_NW * 64) prompt_attn_kernel(const PromptAtt
     auto commit = [&]() {
 #pragma unroll
         for (int i = 0; i < 4; i++) {
-            const int off = pa_off(srow + 16 * i, sch);
-            *(PA_LDS u32x4 *)((PA_LDS char *)ks + off) = kreg[i];
-            *(PA_LDS u32x4 *)((PA_LDS char *)vs + off) = vreg[i];
+            const int off = attn_lds_off(srow + 16 * i, sch);
+            *(ATTN_LDS u32x4 *)((ATTN_LDS char *)ks + off) = kreg[i];
+            *(ATTN_LDS u32x4 *)((ATTN_LDS char *)vs + off) = vreg[i];
         }
     };
 
@@ -203,7 +163,7 @@ __global__ void __launch_bounds__(PA_NW * 64) prompt_attn_kernel(const PromptAtt
                 for (int r = 0; r < 16; r++) sc[b][r] = 0.f;
 #pragma unroll
                 for (int s = 0; s < 8; s++) {
-                    const half8_t kf = pa_row_read(ks, pa_off(32 * b + l31, 2 * s + hi));
+                    const half8_t kf = attn_row_read(ks, attn_lds_off(32 * b + l31, 2 * s + hi));
                     sc[b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[s], sc[b], 0, 0, 0);
                 }
             }
@@ -220,7 +180,7 @@ __global__ void __launch_bounds__(PA_NW * 64) prompt_attn_kernel(const PromptAtt
                     sc[b][r] = v;
                     mt = fmaxf(mt, v);
                 }
-            mt = pa_max_halves(mt);
+            mt = halves_max(mt);
             const float mn = fmaxf(m, mt);
             const float msub = mn == -INFINITY ? 0.f : mn;   // a row with nothing unmasked so far: exp2(-inf - 0) = 0, never -inf - -inf
             const float alpha = __builtin_amdgcn_exp2f(m - msub);
@@ -250,8 +210,8 @@ __global__ void __launch_bounds__(PA_NW * 64) prompt_attn_kernel(const PromptAtt
                     for (int s = 0; s < 2; s++) {
                         const int r0 = 32 * b + 16 * s + 4 * hi + tq;
                         const int ch = 4 * d + 2 * g1 + (tp >> 1);
-                        const half4_t lo = pa_tr_read(vs, pa_off(r0, ch) + 8 * (tp & 1));
-                        const half4_t up = pa_tr_read(vs, pa_off(r0 + 8, ch) + 8 * (tp & 1));
+                        const half4_t lo = attn_tr_read(vs, attn_lds_off(r0, ch) + 8 * (tp & 1));
+                        const half4_t up = attn_tr_read(vs, attn_lds_off(r0 + 8, ch) + 8 * (tp & 1));
                         const half8_t vf = half8_t{lo[0], lo[1], lo[2], lo[3], up[0], up[1], up[2], up[3]};
                         acc[d] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf[b][s], acc[d], 0, 0, 0);
                     }
@@ -264,7 +224,7 @@ __global__ void __launch_bounds__(PA_NW * 64) prompt_attn_kernel(const PromptAtt
     }
 
     // ---- out[query][32 d + 8 g + 4 hi + (0..3)] = O^T / l: four dims per register quad, one fp16 rounding ----------------------
-    l = pa_sum_halves(l);
+    l = halves_sum(l);
     if (qrow < rows) {
         const float inv = 1.0f / l;
         half_t *o = out + (size_t)qrow * a.ldo + (size_t)h * PA_HD + 4 * hi;
@@ -295,9 +255,8 @@ int prompt_attn_batch_launch(const half_t *qkv, int64_t ldq, const gptq_prompt_s
         rows += segs[i].rows;
         tiles += (segs[i].rows + PA_QT - 1) / PA_QT;
     }
-    const float inv_base = -2.0f * logf(base) / (float)PA_HD;   // reference fused_attn.py:91
-    hipLaunchKernelGGL(prompt_rope_kv_kernel, dim3(rows, heads), dim3(PA_HD / 2), 0, s, qkv, ldq, a.t, kc, vc, slot_stride, ws, heads, inv_base,
-                       (const float2 *)rope_table);
+    hipLaunchKernelGGL(prompt_rope_kv_kernel, dim3(rows, heads), dim3(PA_HD / 2), 0, s, qkv, ldq, a.t, kc, vc, slot_stride, ws, heads,
+                       rope_inv_base(base, PA_HD), (const float2 *)rope_table);
     a.q = ws; a.kc = kc; a.vc = vc; a.out = out;
     a.heads = heads; a.ldo = ldo; a.slot_stride = slot_stride;
     a.scale2 = scale * 1.44269504088896340736f;

@@ -15,7 +15,8 @@ amp = 8 wherever a dropped key or the scale must show (the needle then holds 0.4
 puts amp = 12, 16, 20 on key 0, which drives every later weight of the row into and below the fp16 subnormal range of P.
 
 The bar.  exact = sum_j w_j v_j in float64 on the fp16 values the kernel itself read (w = softmax(scale q . k) over the row's visible keys);
-A = sum_j w_j |v_j|.  Rounding points, as read in csrc/decode_attn.hip, csrc/prompt_attn.hip, csrc/chunk_attn.hip and csrc/attn_split.h:
+A = sum_j w_j |v_j|.  Rounding points, as read in csrc/decode_attn.hip, csrc/prompt_attn.hip, csrc/chunk_attn.hip, csrc/attn_device.h (the
+last arriver's merge) and csrc/attn_split.h:
 
   score   every kernel forms p_j = exp2(s_j - m), s_j = fp32(q . k_j) * scale2, scale2 = fp32(scale * log2 e), m some running maximum.  m is
           the SAME number in the numerator and in l, and the rescale alpha multiplies both: their errors cancel.  What does not cancel is a

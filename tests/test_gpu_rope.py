@@ -180,6 +180,28 @@ def test_rope_instances_agree_bit_for_bit(base):
     assert np.array_equal(results[8].view(np.uint16), results[1].view(np.uint16)), '<8> and <1> differ'
 
 
+@pytest.mark.parametrize('base', (1e4, 5e5))
+def test_rope_op_and_decode_rope_kv_agree_bit_for_bit(base):
+    """heads 2, head_dim 128, t_max 64, positions 0, 1 and 63: the q and k rows gptq_rope_f16 rotates in place (rope_kernel<8>) against the q row
+    gptq_decode_rope_kv_f16 rotates in place and the k row it appends to the cache -- both run the RoPE of csrc/attn_device.h under the same
+    flags, so the bits are the same."""
+    heads, hd, t_max = 2, 128, 64
+    lib = _native.lib()
+    for pos in (0, 1, 63):
+        qkv = torch.from_numpy(RC.qkv_inputs((), heads, hd, 900 + pos)).to(DEV)                    # [3, heads, hd]
+        p = torch.tensor([pos], dtype=torch.int64, device=DEV)
+        op = qkv.clone()
+        _native.check(lib.gptq_rope_f16(op.data_ptr(), 3 * heads * hd, p.data_ptr(), 1, 1, 1, heads, hd, float(base), _stream()), 'gptq_rope_f16')
+        kv, kc, vc = qkv.clone(), torch.zeros((t_max, heads * hd), dtype=torch.float16, device=DEV), torch.zeros((t_max, heads * hd), dtype=torch.float16, device=DEV)
+        _native.check(lib.gptq_decode_rope_kv_f16(kv.data_ptr(), p.data_ptr(), kc.data_ptr(), vc.data_ptr(), heads, hd, t_max, float(base), _stream()),
+                      'gptq_decode_rope_kv_f16')
+        torch.cuda.synchronize()
+        assert torch.equal(op[0], kv[0]), 'q differs at position %d, base %g' % (pos, base)
+        assert torch.equal(op[1].reshape(-1), kc[pos]), 'k differs at position %d, base %g' % (pos, base)
+        assert torch.equal(op[2], qkv[2]) and torch.equal(vc[pos], qkv[2].reshape(-1)), 'v at position %d' % pos
+        assert torch.equal(op[0], qkv[0]) == (pos == 0), 'position 0 is the identity, and only position 0'
+
+
 def test_rope_op_refuses_a_half_beyond_256_columns():
     """hd 514: half = 257 is odd, so only the scalar instance could take it, and that serves half <= 256: GPTQ_E_SHAPE, nothing launched"""
     heads, hd = 1, 514
