@@ -5,8 +5,8 @@
 //   gptq_kv_reorder_f16    cache row b of every layer continues row parent[b], in place, ONE launch.
 //
 // Launch A, one workgroup per row (passes 2 .. 4 are row_select.h's row_select, shared with logprobs.hip; what a bad row means and what is written
-// stay here): pass 1 finds the row's largest key and its first NaN / +inf; pass 2 sums exp(l - max) in fp32 -- eight
-// accumulators per thread added pairwise, a shuffle tree per wave, the 16 wave sums in a fixed tree: the same bits on every call -- and counts the
+// stay here): pass 1 (sample_common.h's row_top, shared with sampling) finds the row's largest key and its first NaN / +inf; pass 2 sums
+// exp(l - max) in fp32 -- eight accumulators per thread added pairwise, a shuffle tree per wave, the 16 wave sums in a fixed tree: the same bits on every call -- and counts the
 // high byte of the 16-bit order-preserving key (sample_common.h) into 256 bins; the wave's radix select finds the bin of the 2N-th largest element,
 // pass 3 counts the low byte inside that bin, the select gives the threshold key; pass 4 collects every element above the threshold and, of the
 // elements AT it, the ones with the lowest ids (all of them where they just fill the 2N places -- the usual case; otherwise a block-wide running
@@ -23,9 +23,12 @@
 // writes nothing.  A fixed grid walks the columns below len[0] (read from device memory: one captured launch serves every step).
 // Built with the strict flags: accurate expf / logf / powf and IEEE division.
 #include "../../include/gptq_mi355x.h"
+#include "gptq_internal.h"
 #include "row_select.h"
 
 namespace {
+
+using gptq::aligned;
 
 constexpr int BM_MAX = GPTQ_BEAM_MAX_BEAMS;          // beams, and the slots every per-beam array of the state block has
 constexpr float BM_DEAD = -1e9f;
@@ -46,33 +49,15 @@ __global__ __launch_bounds__(SM_NT) void beam_row_kernel(const uint16_t *logits,
     __shared__ u64 red64[SM_NW];
     __shared__ int red32[SM_NW];
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const uint16_t *row = logits + (int64_t)blockIdx.x * ld;
     uint32_t *rec = state + ST_REC + blockIdx.x * REC_WORDS;
 
-    // ---- 1: the largest key, the first NaN / +inf ----
-    uint32_t maxkey = 0;
-    int bad = SM_NONE;
-    scan_row(row, vocab, tid, [&](int i, uint32_t b) {
-        if (not_finite_above(b)) bad = min(bad, i);
-        maxkey = max(maxkey, key_of(b));
-    });
-    for (int d = 32; d > 0; d >>= 1) {
-        maxkey = max(maxkey, (uint32_t)__shfl_xor((int)maxkey, d, 64));
-        bad = min(bad, __shfl_xor(bad, d, 64));
-    }
-    if (lane == 0) {
-        red64[wave] = maxkey;
-        red32[wave] = bad;
-    }
+    // ---- 1: the largest key, the first NaN / +inf (sample_common.h's row_top; its barrier stands behind the clear) ----
     row_select_clear(L, tid);
-    __syncthreads();
-#pragma unroll
-    for (int w = 0; w < SM_NW; w++) {
-        maxkey = max(maxkey, (uint32_t)red64[w]);
-        bad = min(bad, red32[w]);
-    }
-    if (bad != SM_NONE || maxkey == key_of(0xFC00u)) {         // a NaN or +inf, or -inf only: ids in range, the update scores them DEAD
+    const RowTop t1 = row_top<false>(row, vocab, tid, red64, red32);
+    const uint32_t maxkey = t1.maxkey;
+    if (t1.bad != SM_NONE || maxkey == key_of(0xFC00u)) {         // a NaN or +inf, or -inf only: ids in range, the update scores them DEAD
         if (tid == 0) {
             rec[0] = 0;
             rec[1] = 0;
@@ -318,8 +303,6 @@ __global__ __launch_bounds__(RO_NT) void kv_reorder_kernel(uint16_t *k_cache, ui
             if (par[b] != b) *(u32x4 *)(base + b * row_stride) = reg[b];
     }
 }
-
-inline bool aligned(const void *p, size_t a) { return ((uintptr_t)p % a) == 0; }
 
 }  // namespace
 

@@ -19,8 +19,6 @@ static std::atomic<int> g_force_variant{-1};
 static std::atomic<int> g_force_split_k{-1};
 static std::atomic<void *> g_debug_buffer{nullptr};
 
-static bool aligned(const void *p, size_t a) { return ((uintptr_t)p % a) == 0; }
-
 struct Problem {
     const void *x;
     int64_t ldx;

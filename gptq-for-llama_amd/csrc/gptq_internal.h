@@ -12,6 +12,9 @@
 
 namespace gptq {
 
+// the alignment check of every C entry (a NULL pointer is aligned: an optional argument passes)
+inline bool aligned(const void *p, size_t a) { return ((uintptr_t)p % a) == 0; }
+
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) belongs to the DEVICE's copy of the code object and must never shrink under a
 // concurrent launch: one state per (kernel instantiation, device), raised monotonically under a mutex (round-2 advisor finding:
 // a per-process "configured" word let the second device of a multi-GPU process launch > 48 KB of LDS without the opt-in).

@@ -17,7 +17,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "gptq_internal.h"
+
 namespace {
+
+using gptq::aligned;
 
 constexpr int LP_NT = 256;            // thread j owns bias entry j and EOS entry j
 constexpr int LP_MAX_ROWS = GPTQ_LOGITS_PROCESS_MAX_ROWS;
@@ -112,8 +116,6 @@ __global__ __launch_bounds__(LP_NT) void logits_process_kernel(uint16_t *logits,
         if (v >= 0 && v < vocab) row[v] = 0xFC00u;
     }
 }
-
-inline bool aligned(const void *p, size_t a) { return ((uintptr_t)p % a) == 0; }
 
 }  // namespace
 

@@ -3,8 +3,8 @@
 //   gptq_logprobs_rows_f16   for each of 1 .. 128 rows of fp16 logits: the log-probability of one chosen token, its rank, and the row's first
 //                            `top` tokens with their log-probabilities, ONE launch, no workspace, no global atomics.
 //
-// One workgroup per row.  Pass 1 finds the row's largest key and its first NaN / +inf (what a bad row means is this file's); passes 2 .. 4 are
-// row_select.h's row_select, shared with beam.hip: the fp32 sum of exp(l - max) through a fixed tree -- the same bits on every call -- and the
+// One workgroup per row.  Pass 1 (sample_common.h's row_top, shared with sampling and beam.hip) finds the row's largest key and its first
+// NaN / +inf (what a bad row means is this file's); passes 2 .. 4 are row_select.h's row_select, shared with beam.hip: the fp32 sum of exp(l - max) through a fixed tree -- the same bits on every call -- and the
 // row's first n = max(top, 1) tokens in (key descending, id ascending) order.  The chosen token's key is known from the start (one load), so its
 // rank -- the tokens with a larger key, plus the ones with its key and a lower id -- is one more count in row_select's pass 3, per thread in a
 // register, summed over the wave by shuffles and over the 16 waves by thread 0: integers, no atomics.  Pass 5: log p of a token is a function of
@@ -12,9 +12,12 @@
 // The slot of the [steps][rows] outputs comes from device memory: one captured launch serves every step of a generation.
 // Built with the strict flags: accurate expf / logf.
 #include "../../include/gptq_mi355x.h"
+#include "gptq_internal.h"
 #include "row_select.h"
 
 namespace {
+
+using gptq::aligned;
 
 constexpr int LP_MAX_TOP = GPTQ_LOGPROBS_MAX_TOP, LP_MAX_ROWS = 128;
 static_assert(LP_MAX_TOP <= RS_MAX_N, "row_select's list holds a row's top entries");
@@ -40,29 +43,11 @@ __global__ __launch_bounds__(SM_NT) void logprobs_rows_kernel(const uint16_t *lo
     const int cid = known ? (int)cid64 : 0;
     const uint32_t cbits = (uint32_t)row[cid];
 
-    // ---- 1: the largest key, the first NaN / +inf ----
-    uint32_t maxkey = 0;
-    int bad = SM_NONE;
-    scan_row(row, vocab, tid, [&](int i, uint32_t b) {
-        if (not_finite_above(b)) bad = min(bad, i);
-        maxkey = max(maxkey, key_of(b));
-    });
-    for (int d = 32; d > 0; d >>= 1) {
-        maxkey = max(maxkey, (uint32_t)__shfl_xor((int)maxkey, d, 64));
-        bad = min(bad, __shfl_xor(bad, d, 64));
-    }
-    if (lane == 0) {
-        red64[wave] = maxkey;
-        red32[wave] = bad;
-    }
+    // ---- 1: the largest key, the first NaN / +inf (sample_common.h's row_top; its barrier stands behind the clear) ----
     row_select_clear(L, tid);
-    __syncthreads();
-#pragma unroll
-    for (int w = 0; w < SM_NW; w++) {
-        maxkey = max(maxkey, (uint32_t)red64[w]);
-        bad = min(bad, red32[w]);
-    }
-    if (bad != SM_NONE || maxkey == key_of(0xFC00u)) {         // a NaN or +inf, or -inf only: no distribution
+    const RowTop t1 = row_top<false>(row, vocab, tid, red64, red32);
+    const uint32_t maxkey = t1.maxkey;
+    if (t1.bad != SM_NONE || maxkey == key_of(0xFC00u)) {         // a NaN or +inf, or -inf only: no distribution
         if (tid == 0) {
             chosen[o] = nan;
             rank[o] = -1;
@@ -101,8 +86,6 @@ __global__ __launch_bounds__(SM_NT) void logprobs_rows_kernel(const uint16_t *lo
         olp[p] = (logit_of_key((uint32_t)(mine >> 32)) - lmax) - lse;
     }
 }
-
-inline bool aligned(const void *p, size_t a) { return ((uintptr_t)p % a) == 0; }
 
 }  // namespace
 

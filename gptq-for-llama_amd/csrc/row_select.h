@@ -2,13 +2,13 @@
 // logits and one workgroup of SM_NT threads, the fp32 sum of exp(l - max) through a fixed tree and the first n tokens of the row in (key
 // descending, id ascending) order -- sample_common.h's 16-bit order-preserving key, so -0 == +0 and -inf sorts below everything finite.
 //
-// What a bad row means (a NaN, +inf, -inf only) and what is written where stay with the caller: it finds the row's largest key first, and it gets
-// the n entries back unsorted, in LDS.  Pass 2 sums exp(l - max) in fp32 -- eight accumulators per thread added pairwise, a shuffle tree per wave,
-// the 16 wave sums in a fixed tree: the same bits on every call -- and counts the high byte of the key into 256 bins; the wave's radix select finds
-// the bin of the n-th largest element, pass 3 counts the low byte inside that bin, the select gives the threshold key; pass 4 collects every
-// element above the threshold and, of the elements AT it, the ones with the lowest ids (all of them where they just fill the n places -- the usual
-// case; otherwise a block-wide running count in ascending id hands out the places).  Only integer counts go through LDS atomics, so nothing
-// depends on the order they arrive in.
+// What a bad row means (a NaN, +inf, -inf only) and what is written where stay with the caller: it finds the row's largest key first (pass 1,
+// sample_common.h's row_top), and it gets the n entries back unsorted, in LDS.  Pass 2 sums exp(l - max) in fp32 -- eight accumulators per thread,
+// one per slot of the row walk (scan_row_slots), added pairwise, a shuffle tree per wave, the 16 wave sums in a fixed tree: the same bits on every
+// call -- and counts the high byte of the key into 256 bins; the wave's radix select finds the bin of the n-th largest element, pass 3 counts the
+// low byte inside that bin, the select gives the threshold key; pass 4 collects every element above the threshold and, of the elements AT it, the
+// ones with the lowest ids (all of them where they just fill the n places -- the usual case; otherwise a block-wide running count in ascending id,
+// sample_common.h's block_prefix, hands out the places).  Only integer counts go through LDS atomics, so nothing depends on the order they arrive in.
 #pragma once
 #include "sample_common.h"
 
@@ -25,7 +25,7 @@ struct RowSelectLds {
     uint32_t filled;
 };
 
-// before row_select, with a __syncthreads() between the two (the caller's first pass has one anyway)
+// before row_select, with a __syncthreads() between the two (row_top, the caller's pass 1, has one)
 GPTQ_DEV void row_select_clear(RowSelectLds &L, int tid) {
     if (tid < 256) {
         L.h1c[tid] = 0;
@@ -42,32 +42,13 @@ GPTQ_DEV float row_select(const uint16_t *row, int vocab, int tid, float lmax, i
     const int lane = tid & 63, wave = tid >> 6;
 
     // ---- 2: sum exp(l - max) through a fixed tree, and the level-1 histogram ----
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f, a4 = 0.f, a5 = 0.f, a6 = 0.f, a7 = 0.f;
-    auto one = [&](uint32_t b) -> float {
+    float a[8] = {};                                           // eight accumulators, one per slot of the walk
+    scan_row_slots(row, vocab, tid, [&](int, uint32_t b, int slot) {
         const uint32_t key = key_of(b);
         atomicAdd(&L.h1c[key >> 8], 1u);
-        return expf(logit_of_key(key) - lmax);                 // -inf gives 0
-    };
-    {
-        const int head = min(vocab, (int)(((16u - (uint32_t)((uintptr_t)row & 15u)) & 15u) >> 1));
-        if (tid < head) a0 += one((uint32_t)row[tid]);
-        const int nvec = (vocab - head) >> 3;
-        const u32x4 *v = (const u32x4 *)(row + head);
-        for (int i = tid; i < nvec; i += SM_NT) {
-            const u32x4 q = v[i];
-            a0 += one(q[0] & 0xFFFFu);
-            a1 += one(q[0] >> 16);
-            a2 += one(q[1] & 0xFFFFu);
-            a3 += one(q[1] >> 16);
-            a4 += one(q[2] & 0xFFFFu);
-            a5 += one(q[2] >> 16);
-            a6 += one(q[3] & 0xFFFFu);
-            a7 += one(q[3] >> 16);
-        }
-        const int t = head + nvec * 8 + tid;
-        if (t < vocab) a1 += one((uint32_t)row[t]);
-    }
-    float sum = ((a0 + a1) + (a2 + a3)) + ((a4 + a5) + (a6 + a7));
+        a[slot] += expf(logit_of_key(key) - lmax);             // -inf gives 0
+    });
+    float sum = ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
     for (int d = 32; d > 0; d >>= 1) sum += __shfl_xor(sum, d, 64);
     if (lane == 0) L.redf[wave] = sum;
     __syncthreads();
@@ -112,22 +93,8 @@ GPTQ_DEV float row_select(const uint16_t *row, int vocab, int tid, float lmax, i
             for (int j = 0; j < 8; j++)
                 if (i0 + j < vocab && key_of((uint32_t)row[i0 + j]) == fkey) mask |= 1u << j;
             const int c = __builtin_popcount(mask);
-            int incl = c;
-            for (int d = 1; d < 64; d <<= 1) {
-                const int o = __shfl_up(incl, d, 64);
-                if (lane >= d) incl += o;
-            }
-            if (lane == 63) L.wcnt[parity][wave] = incl;
-            __syncthreads();
-            int tot = 0, below = 0;
-#pragma unroll
-            for (int w = 0; w < SM_NW; w++) {
-                const int x = L.wcnt[parity][w];
-                below += w < wave ? x : 0;
-                tot += x;
-            }
-            parity ^= 1;
-            int rank = running + below + incl - c;
+            int tot;
+            int rank = running + block_prefix(c, tid, L.wcnt, parity, tot);
 #pragma unroll
             for (int j = 0; j < 8; j++)
                 if ((mask >> j) & 1u) {

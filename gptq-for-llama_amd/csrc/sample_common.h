@@ -1,12 +1,15 @@
-// sample_common.h -- the device code gptq_sample_rows_f16 (sample.hip) and gptq_spec_sample_rows_f16 (spec_sample.hip) share: the order-preserving
-// 16-bit key of an fp16 logit, the row scan that needs 2-byte alignment only, a token's integer mass, the 256-bin radix select of one wave, and --
-// for kernels that look at more than one row per workgroup -- the passes A .. D of sample.hip as a function (select_row) and its pass E as a
-// function of any mass (draw_row).  sample.hip states the method; its kernel keeps its own straight-line copy of the passes.  row_select.h
-// (beam.hip, logprobs.hip) takes the key, the row scan and the count-only select from here.
+// sample_common.h -- the row passes of the token-choice kernels, each written once: one workgroup of SM_NT threads walks one row of fp16 logits.
+// The order-preserving 16-bit key of an fp16 logit, the row walk that needs 2-byte alignment only (scan_row), pass 1 -- the largest key, its
+// first index, the first NaN / +inf (row_top) --, a token's integer mass, the 256-bin radix select of one wave, the block-wide running prefix
+// (block_prefix), and the passes of sample.hip as functions: A .. D as select_row, E as draw_row for any mass.  sample.hip states the method and
+// calls the two once per row; spec_sample.hip calls them for up to two rows and a residual mass.  row_select.h (beam.hip, logprobs.hip) takes
+// the key, the walk, pass 1, the prefix and the count-only select from here.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "gptq_device.h"
 
@@ -27,11 +30,13 @@ GPTQ_DEV float logit_of_key(uint32_t key) {
 }
 GPTQ_DEV bool not_finite_above(uint32_t b) { return (b & 0x7FFFu) > 0x7C00u || b == 0x7C00u; }   // NaN or +inf
 
-// f(token id, fp16 bits) for every element of the row, thread `tid` of SM_NT; a thread sees its ids in ascending order
+// f(token id, fp16 bits, slot) for every element of the row, thread `tid` of SM_NT; a thread sees its ids in ascending order.  Up to 7 leading and
+// 7 trailing elements are read one by one, everything between as 16-byte vectors.  slot: element j of a vector has slot j, a leading element
+// slot 0, a trailing one slot 1 -- a constant at every call once the loop is unrolled, so f may index registers with it.
 template <class F>
-GPTQ_DEV void scan_row(const uint16_t *row, int vocab, int tid, F f) {
+GPTQ_DEV void scan_row_slots(const uint16_t *row, int vocab, int tid, F f) {
     const int head = min(vocab, (int)(((16u - (uint32_t)((uintptr_t)row & 15u)) & 15u) >> 1));
-    if (tid < head) f(tid, (uint32_t)row[tid]);
+    if (tid < head) f(tid, (uint32_t)row[tid], 0);
     const int nvec = (vocab - head) >> 3;
     const u32x4 *v = (const u32x4 *)(row + head);
     for (int i = tid; i < nvec; i += SM_NT) {
@@ -39,12 +44,88 @@ GPTQ_DEV void scan_row(const uint16_t *row, int vocab, int tid, F f) {
         const int base = head + i * 8;
 #pragma unroll
         for (int j = 0; j < 4; j++) {
-            f(base + 2 * j, q[j] & 0xFFFFu);
-            f(base + 2 * j + 1, q[j] >> 16);
+            f(base + 2 * j, q[j] & 0xFFFFu, 2 * j);
+            f(base + 2 * j + 1, q[j] >> 16, 2 * j + 1);
         }
     }
     const int t = head + nvec * 8 + tid;
-    if (t < vocab) f(t, (uint32_t)row[t]);
+    if (t < vocab) f(t, (uint32_t)row[t], 1);
+}
+template <class F>
+GPTQ_DEV void scan_row(const uint16_t *row, int vocab, int tid, F f) {
+    scan_row_slots(row, vocab, tid, [&](int i, uint32_t b, int) { f(i, b); });
+}
+
+// pass 1: the row's largest key, with INDEX its first index (key << 32 | ~index: the maximum is the largest key at its lowest index), and the first
+// NaN / +inf (SM_NONE without one); the same values in every thread.  A shuffle tree per wave, the SM_NW wave results in red64 / red32, ONE
+// __syncthreads(): what the caller clears in LDS before the call is clear behind it.  What a bad row means stays with the caller.
+struct RowTop {
+    uint32_t maxkey;
+    int argmax, bad;
+};
+template <bool INDEX>
+GPTQ_DEV RowTop row_top(const uint16_t *row, int vocab, int tid, u64 *red64, int *red32) {
+    typedef typename std::conditional<INDEX, u64, uint32_t>::type best_t;
+    const int lane = tid & 63, wave = tid >> 6;
+    best_t best = 0;
+    int bad = SM_NONE;
+    scan_row(row, vocab, tid, [&](int i, uint32_t b) {
+        if (not_finite_above(b)) bad = min(bad, i);
+        best_t cand = key_of(b);
+        if constexpr (INDEX) cand = (cand << 32) | (uint32_t)~(uint32_t)i;
+        best = cand > best ? cand : best;
+    });
+    for (int d = 32; d > 0; d >>= 1) {
+        const best_t o = __shfl_xor(best, d, 64);
+        best = o > best ? o : best;
+        bad = min(bad, __shfl_xor(bad, d, 64));
+    }
+    if (lane == 0) {
+        red64[wave] = best;
+        red32[wave] = bad;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int w = 0; w < SM_NW; w++) {
+        const best_t o = (best_t)red64[w];
+        best = o > best ? o : best;
+        bad = min(bad, red32[w]);
+    }
+    RowTop t;
+    t.bad = bad;
+    if constexpr (INDEX) {
+        t.maxkey = (uint32_t)(best >> 32);
+        t.argmax = (int)~(uint32_t)best;
+    } else {
+        t.maxkey = best;
+        t.argmax = 0;
+    }
+    return t;
+}
+
+// the block-wide running prefix of one value per thread: returns the sum over the threads in front of this one and sets tot to the sum over all
+// -- an inclusive shuffle scan per wave, the wave totals in wsum[parity] (the parity flips per call, so ONE __syncthreads() per call is enough).
+// Every thread of the workgroup must call it.
+template <class T>
+GPTQ_DEV T block_prefix(T s, int tid, T (*wsum)[SM_NW], int &parity, T &tot) {
+    const int lane = tid & 63, wave = tid >> 6;
+    T incl = s;
+    for (int d = 1; d < 64; d <<= 1) {
+        const T o = __shfl_up(incl, d, 64);
+        if (lane >= d) incl += o;
+    }
+    if (lane == 63) wsum[parity][wave] = incl;
+    __syncthreads();
+    T below = 0;
+    tot = 0;
+#pragma unroll
+    for (int w = 0; w < SM_NW; w++) {
+        const T t = wsum[parity][w];
+        below += w < wave ? t : 0;
+        tot += t;
+    }
+    parity ^= 1;
+    return below + incl - s;
 }
 
 struct Weigher {
@@ -141,6 +222,9 @@ GPTQ_DEV void wave_select(const uint32_t *hc, uint32_t baseC, uint32_t k, Select
 // the exponent of the mass unit: masses are integer multiples of 2^-40, of 2^-(62 - ceil(log2 vocab)) above 2^22 tokens (no sum overflows 64 bits)
 GPTQ_DEV int mass_exponent(int vocab) { return min(40, 62 - (32 - __builtin_clz((uint32_t)max(vocab - 1, 1)))); }
 
+// the uniform of a draw, into [0, 1): NaN and negatives draw the first kept token, 1 and above the last
+GPTQ_DEV float clamp_u(float u) { return isnan(u) || u < 0.f ? 0.f : (u >= 1.f ? 0x1.fffffep-1f : u); }
+
 // ---- the passes as functions -------------------------------------------------------------------------------------------------------------
 struct SelectLds {
     uint32_t h1c[256], h2c[256];
@@ -161,42 +245,20 @@ struct RowDist {
     __device__ __forceinline__ u64 mass(uint32_t key) const { return key >= fkey ? wq(key) : 0; }
 };
 
-// passes A .. D of sample.hip: the same operations on the same integers, so fkey, W and every mass are the bits that kernel computes.
-// A COPY of sample_rows_kernel's passes: an edit to either must be mirrored in the other (tests/test_gpu_spec_sample.py holds the last row of a
-// step bit-equal to gptq_sample_rows_f16).
+// passes A .. D of sample.hip
 GPTQ_DEV RowDist select_row(const uint16_t *row, int vocab, int tid, float T, int kraw, float praw, SelectLds &L) {
-    const int lane = tid & 63, wave = tid >> 6;
+    const int lane = tid & 63;
     RowDist D;
     __syncthreads();               // (L may still be read by the previous call's last pass)
-    u64 best = 0;                  // key << 32 | ~index: the maximum is the largest key at its lowest index
-    int bad = SM_NONE;
-    scan_row(row, vocab, tid, [&](int i, uint32_t b) {
-        if (not_finite_above(b)) bad = min(bad, i);
-        const u64 cand = ((u64)key_of(b) << 32) | (uint32_t)~(uint32_t)i;
-        best = cand > best ? cand : best;
-    });
-    for (int d = 32; d > 0; d >>= 1) {
-        const u64 o = __shfl_xor(best, d, 64);
-        best = o > best ? o : best;
-        bad = min(bad, __shfl_xor(bad, d, 64));
-    }
-    if (lane == 0) {
-        L.red64[wave] = best;
-        L.red32[wave] = bad;
-    }
     if (tid < 256) {
         L.h1c[tid] = 0;
         L.h1m[tid] = 0;
     }
-    __syncthreads();
-#pragma unroll
-    for (int w = 0; w < SM_NW; w++) {
-        best = L.red64[w] > best ? L.red64[w] : best;
-        bad = min(bad, L.red32[w]);
-    }
+    const RowTop top = row_top<true>(row, vocab, tid, L.red64, L.red32);
+    const int bad = top.bad;
     D.bad = bad;
-    D.argmax = (int)~(uint32_t)best;
-    const uint32_t maxkey = (uint32_t)(best >> 32);
+    D.argmax = top.argmax;
+    const uint32_t maxkey = top.maxkey;
     const bool greedy = !(T > 0.f) || isinf(T);
     D.point = greedy || maxkey == key_of(0xFC00u);
     D.fkey = 0;
@@ -291,34 +353,21 @@ GPTQ_DEV RowDist select_row(const uint16_t *row, int vocab, int tid, float T, in
 }
 
 // pass E of sample.hip for any integer mass(token id, fp16 bits of row[id]) of sum `total` > 0: the first id, ascending, whose running mass exceeds
-// floor(uu total), written to *tok by the thread that holds it.  *tok must hold the fallback (an id in range) before the call; the caller puts a
-// __syncthreads() between this call and its read of *tok.  The id found does not depend on how the row is split over threads and rounds.
-template <class M>
-GPTQ_DEV void draw_row(const uint16_t *row, int vocab, int tid, u64 total, float uu, M mass, u64 (*wsum)[SM_NW], int *tok) {
-    const int lane = tid & 63, wave = tid >> 6;
+// floor(uu total), written to *tok (an int in LDS, an int64_t of the result) by the thread that holds it.  *tok must hold the fallback (an id in
+// range) before the call; the caller puts a __syncthreads() between this call and its read of *tok.  The id found does not depend on how the
+// row is split over threads and rounds.  The walk is scan_row's, kept as rounds: every thread reaches every barrier, all leave in the same round.
+template <class M, class O>
+GPTQ_DEV void draw_row(const uint16_t *row, int vocab, int tid, u64 total, float uu, M mass, u64 (*wsum)[SM_NW], O *tok) {
     const u64 target = (u64)((double)uu * (double)total);
     u64 running = 0;
     int parity = 0;
     // one round: m[j] = the mass of token base + j of this thread (0: none); rounds cover ascending, thread-contiguous id ranges
     auto round = [&](const u64(&m)[8], int base) -> bool {
         const u64 s = m[0] + m[1] + m[2] + m[3] + m[4] + m[5] + m[6] + m[7];
-        u64 incl = s;
-        for (int d = 1; d < 64; d <<= 1) {
-            const u64 o = __shfl_up(incl, d, 64);
-            if (lane >= d) incl += o;
-        }
-        if (lane == 63) wsum[parity][wave] = incl;
-        __syncthreads();
-        u64 tot = 0, below = 0;
-#pragma unroll
-        for (int w = 0; w < SM_NW; w++) {
-            const u64 t = wsum[parity][w];
-            below += w < wave ? t : 0;
-            tot += t;
-        }
-        parity ^= 1;
+        u64 tot;
+        const u64 before = block_prefix(s, tid, wsum, parity, tot);
         if (running + tot > target) {
-            u64 c = running + below + incl - s;          // the mass in front of this thread's tokens
+            u64 c = running + before;                    // the mass in front of this thread's tokens
             if (c <= target && target < c + s) {
                 int pick = 0;
                 bool found = false;

@@ -6,7 +6,7 @@
 //
 // Row i of the target logits is the distribution p after ids[0 .. i]; ids[i + 1] = d is the token drafted for that place, from q: row i of the draft
 // logits under the row's own setting, or a point mass at d without draft logits.  p and q are the kept sets and integer masses of sample.hip
-// (sample_common.h: the same passes, so the last row's plain draw is that kernel's to the bit).  The two rows have different totals; a token's mass
+// (sample_common.h: select_row and draw_row, the functions that kernel calls, so the last row's plain draw is its draw to the bit).  The two rows have different totals; a token's mass
 // goes onto a common scale by one double multiplication with the row's factor c_p = 2^S / W_p (ONE IEEE division per row; S = the exponent of the
 // mass unit): P(x) = floor(m_p(x) c_p + 1/2), Q(x) likewise, which are integers again (a division per token made the reject path slower):
 //   accept    u_accept Q(d) < P(d)                     (doubles of integers below 2^41: one rounding, in the product)
@@ -20,15 +20,16 @@
 // Idle sequences (t_max > 0, the batch entry): sequence b is active iff 0 <= pos[b] < t_max, the rule of chunk_attn.hip.  The workgroups of an idle
 // sequence return at once: no logits read, no ticket, nothing written.
 #include "../../include/gptq_mi355x.h"
+#include "gptq_internal.h"
 #include "sample_common.h"
 
 namespace {
 
+using gptq::aligned;
+
 // the row's factor onto the common scale 2^sh, and a mass on that scale, rounded to an integer; m <= W
 GPTQ_DEV double scale_of(u64 W, int sh) { return ldexp(1.0, sh) / (double)W; }
 GPTQ_DEV u64 scaled(u64 m, double c) { return (u64)((double)m * c + 0.5); }
-
-GPTQ_DEV float clamp_u(float u) { return isnan(u) || u < 0.f ? 0.f : (u >= 1.f ? 0x1.fffffep-1f : u); }
 
 __global__ __launch_bounds__(SM_NT) void spec_sample_rows_kernel(const uint16_t *logits, int64_t ld, const uint16_t *qlogits, int64_t ldq, int rows,
                                                                  int vocab, const int64_t *ids, const float *temperature, const int32_t *top_k,
@@ -137,8 +138,6 @@ __global__ __launch_bounds__(SM_NT) void spec_sample_rows_kernel(const uint16_t 
     for (int j = tid; j <= rows; j += SM_NT) out[j] = j == 0 ? (int64_t)a : (j <= a ? ids[j] : ta);
     if (tid == 0) *pos += a + 1;
 }
-
-inline bool aligned(const void *p, size_t a) { return ((uintptr_t)p % a) == 0; }
 
 }  // namespace
 
