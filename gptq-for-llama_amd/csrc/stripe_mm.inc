@@ -52,24 +52,59 @@ struct MMArgs {
     int rowmajor;   // round 6 (one row tile, one set): the slices' partials as [S][16][N] fp32 rows -- the combine launch owns whole rows (slices_combine_norm_launch)
 };
 
-// distinct magic offsets of a width and the class of pair p of a lane block (stripe_unpack.inc pair_off_block)
-constexpr int MM_NOFFC = SB == 8 ? 1 : (SB == 4 ? 2 : (SB == 3 ? 3 : 5));
-__host__ __device__ constexpr int mm_off_class(int p) {
-    if (SB == 8) return 0;
-    if (SB == 4) return p & 1;
-    if (SB == 3) return p == 15 ? 0 : (p % 5) % 3;    // offsets 1024, 128, 16, 1024, 128 per word; the spare-bit pair 1024
-    constexpr int c2[8] = {0, 1, 2, 3, 4, 2, 3, 4};    // 1024, 256, 64, 16, 4, 64, 16, 4
-    return c2[p & 7];
-}
-__host__ __device__ constexpr float mm_class_off(int c) {
-    if (SB == 8) return 1024.f;
-    if (SB == 4) return c ? 64.f : 1024.f;
-    if (SB == 3) return c == 0 ? 1024.f : (c == 1 ? 128.f : 16.f);
-    constexpr float o2[5] = {1024.f, 256.f, 64.f, 16.f, 4.f};
-    return o2[c];
+// -OFF of every offset class (stripe_unpack.inc), both halves: built once per kernel, ahead of the K loop
+GPTQ_DEV void neg_offsets(half2_t (&negoff)[NOFFC]) {
+#pragma unroll
+    for (int o = 0; o < NOFFC; o++) negoff[o] = half2_t{(half_t)(-class_off(o)), (half_t)(-class_off(o))};
 }
 
-// lane = column, rows 16 t + 4 rq + r of the accumulators -> y (SiLU pair / bias / fp16 rounding)
+// THE dequantiser of this file: a lane's share of one row block (WPL packed words) -> its PPB B fragments of v_mfma_f32_16x16x32_f16, the exact
+// integers q - z: one v_pk_add_f16 per pair subtracts OFF + zero + 1 (cz = negoff - zz, exact).  Returns the fp32 group scale of the table word
+// {scale, zero + 1} for the accumulator, zero when !valid (a clamped re-read past K or past the slice).  (The prescale form -- every pair times the
+// lane block's fp16 scale -- exists only at the hand-written sites of stripe_mm_kernel and stripe_gemm_kernel, see the note above mm_epilogue.)
+template <typename WV>
+GPTQ_DEV float dequant_block(const WV &w, uint32_t table_word, bool valid, const half2_t (&negoff)[NOFFC], const UnpackConsts &uc, mm_h8_t (&B)[PPB]) {
+    const half2_t e = as_half2(table_word);
+    const half2_t zz = {e[1], e[1]};
+    half2_t cz[NOFFC];
+#pragma unroll
+    for (int o = 0; o < NOFFC; o++) cz[o] = negoff[o] - zz;   // -(OFF + zero + 1), exact
+    uint32_t t[NPB], d[NPB];
+    unpack_block(w, uc, t);
+#pragma unroll
+    for (int q = 0; q < NPB; q++) d[q] = as_u32(as_half2(t[q]) + cz[off_class(q)]);   // q - z, exact
+#pragma unroll
+    for (int b = 0; b < PPB; b++) B[b] = __builtin_bit_cast(mm_h8_t, u32x4{d[4 * b], d[4 * b + 1], d[4 * b + 2], d[4 * b + 3]});
+    return valid ? (float)e[0] : 0.f;
+}
+
+// THE output epilogue of this file: one row tile of one stripe.  lane = column n = 16 stripe + col; rows row0 + 4 rq + r of the tile's fp32 sums
+// (a float4 per weight set) -> SiLU(gate) * up for a pair -> fp16 -> + bias (ldb == 0) or + the residual row (ldb != 0) on the ROUNDED value
+// -> y, rows below M only.
+template <int NS>
+GPTQ_DEV void finish_tile(const float4_t (&tot)[NS], const MMArgs &a, int stripe, int row0, int rq, int col) {
+    const int n = stripe * 16 + col;
+    const float bv = (a.bias && !a.ldb) ? (float)a.bias[n] : 0.f;
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+        const int row = row0 + 4 * rq + r;
+        float v = tot[0][r];
+        if constexpr (NS == 2) v = v * (1.0f / (1.0f + __expf(-v))) * tot[1][r];   // silu on the fp32 accumulator (fused_mlp.py:160-164)
+        if (row < a.M) {
+            half_t h = (half_t)v;
+            if (a.bias) h = (half_t)((float)h + (a.ldb ? (float)a.bias[(size_t)row * a.ldb + n] : bv));
+            a.y[(size_t)row * a.ldy + n] = h;
+        }
+    }
+}
+
+// Three kernels keep their HAND-WRITTEN dequantiser and epilogue, the text of dequant_block / finish_tile written out at the site: stripe_mm_kernel
+// (with mm_epilogue, below), stripe_mm2_kernel and stripe_gemm_kernel.  Through the functions the compiler gave their K loops another schedule -- more
+// waits in most instances, six v_perm_b32 in the 256-row tile GEMM, the occupancy line of seven kernels moved
+// (profiles/stripe_dequant_once/README.md) -- and the rule of this file is that such a kernel keeps its site.  A change to the dequantiser or
+// the epilogue is made in dequant_block / finish_tile AND at these three sites.
+
+// the TM row tiles a wave of stripe_mm_kernel holds for one stripe: lane = column, rows 16 t + 4 rq + r (hand-written, see above)
 template <int TM, int NS>
 GPTQ_DEV void mm_epilogue(const float4_t (&yacc)[NS][TM], const MMArgs &a, int stripe, bool has, int rq, int col) {
     if (!has) return;
@@ -148,9 +183,9 @@ __global__ void __launch_bounds__(STRIPE_NW * 64) stripe_mm_kernel(const MMArgs 
     for (int s = 0; s < NS; s++)
 #pragma unroll
         for (int t = 0; t < TM; t++) yacc[s][t] = float4_t{0.f, 0.f, 0.f, 0.f};
-    half2_t negoff[MM_NOFFC];
+    half2_t negoff[NOFFC];
 #pragma unroll
-    for (int o = 0; o < MM_NOFFC; o++) negoff[o] = half2_t{(half_t)(-mm_class_off(o)), (half_t)(-mm_class_off(o))};
+    for (int o = 0; o < NOFFC; o++) negoff[o] = half2_t{(half_t)(-class_off(o)), (half_t)(-class_off(o))};
 
     auto step = [&](int i, int u, bool refill) {
         const bool valid = rb0 + u < rb1;
@@ -158,19 +193,19 @@ __global__ void __launch_bounds__(STRIPE_NW * 64) stripe_mm_kernel(const MMArgs 
         mm_h8_t B[NS][PPB];
         float scale[NS];
 #pragma unroll
-        for (int s = 0; s < NS; s++) {
+        for (int s = 0; s < NS; s++) {      // (hand-written dequant_block, with the prescale: see the note above mm_epilogue)
             const half2_t e = as_half2(tw[i][s]);
             scale[s] = valid ? (float)e[0] : 0.f;
             const half2_t zz = {e[1], e[1]};
             const half2_t s2 = valid ? half2_t{e[0], e[0]} : half2_t{(half_t)0.f, (half_t)0.f};
-            half2_t cz[MM_NOFFC];
+            half2_t cz[NOFFC];
 #pragma unroll
-            for (int o = 0; o < MM_NOFFC; o++) cz[o] = negoff[o] - zz;   // -(OFF + zero + 1), exact
+            for (int o = 0; o < NOFFC; o++) cz[o] = negoff[o] - zz;   // -(OFF + zero + 1), exact
             uint32_t t[NPB], d[NPB];
             unpack_block(w[i][s], uc, t);
 #pragma unroll
             for (int q = 0; q < NPB; q++) {
-                half2_t v = as_half2(t[q]) + cz[mm_off_class(q)];          // q - z, exact
+                half2_t v = as_half2(t[q]) + cz[off_class(q)];          // q - z, exact
                 if constexpr (PS) v = v * s2;                              // ... times the lane block's own scale: one fp16 rounding
                 d[q] = as_u32(v);
             }
@@ -266,19 +301,7 @@ __global__ void __launch_bounds__(STRIPE_NW * 64) stripe_mm_reduce_kernel(const 
             }
     }
     if (stripe >= a.nstripes) return;
-    const int rq = lane >> 4, col = lane & 15, n = stripe * 16 + col;
-    const float bv = (a.bias && !a.ldb) ? (float)a.bias[n] : 0.f;
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-        const int row = row0 + 16 * t + 4 * rq + r;
-        float v = acc[0][r];
-        if constexpr (NS == 2) v = v * (1.0f / (1.0f + __expf(-v))) * acc[1][r];
-        if (row < a.M) {
-            half_t h = (half_t)v;
-            if (a.bias) h = (half_t)((float)h + (a.ldb ? (float)a.bias[(size_t)row * a.ldb + n] : bv));
-            a.y[(size_t)row * a.ldy + n] = h;
-        }
-    }
+    finish_tile<NS>(acc, a, stripe, row0 + 16 * t, lane >> 4, lane & 15);
 }
 
 // ---- single-launch variant: one stripe (16 columns) x WHOLE K per workgroup, x streamed through LDS ----
@@ -295,7 +318,6 @@ __global__ void __launch_bounds__(STRIPE_NW * 64, PF == 2 ? 4 : 1) stripe_mm1_ke
     constexpr int NW = STRIPE_NW, T = NW * 64, TG = TM == 1 ? 1 : (TM == 2 ? 2 : 4), NRB = NW / TG;
     constexpr int ROWS = 16 * TM, CK = NRB * BK, XS = CK + 8, CP = CK / 8, NPC = ROWS * CP, XPF = (NPC + T - 1) / T;
     constexpr int RD = 4, BUF = ROWS * XS;   // halves per LDS buffer
-    constexpr int NOFF = SB == 8 ? 1 : 2;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     half_t *xl = (half_t *)smem;   // [2][ROWS][XS]; reused for the output partials
     const int tid = threadIdx.x, lane = tid & 63;
@@ -346,9 +368,8 @@ __global__ void __launch_bounds__(STRIPE_NW * 64, PF == 2 ? 4 : 1) stripe_mm1_ke
     float4_t yacc[NS];
 #pragma unroll
     for (int s = 0; s < NS; s++) yacc[s] = float4_t{0.f, 0.f, 0.f, 0.f};
-    half2_t negoff[NOFF];
-#pragma unroll
-    for (int o = 0; o < NOFF; o++) negoff[o] = half2_t{(half_t)(-pair_off(o)), (half_t)(-pair_off(o))};
+    half2_t negoff[NOFFC];
+    neg_offsets(negoff);
 
     for (int c0 = 0; c0 < nchunk; c0 += RD) {
 #pragma unroll
@@ -361,24 +382,7 @@ __global__ void __launch_bounds__(STRIPE_NW * 64, PF == 2 ? 4 : 1) stripe_mm1_ke
             mm_h8_t B[NS][PPB];
             float scale[NS];
 #pragma unroll
-            for (int s = 0; s < NS; s++) {
-                const half2_t e = as_half2(tw[i][s]);
-                scale[s] = valid ? (float)e[0] : 0.f;
-                const half2_t zz = {e[1], e[1]};
-                half2_t cz[NOFF];
-#pragma unroll
-                for (int o = 0; o < NOFF; o++) cz[o] = negoff[o] - zz;
-                uint32_t d[4 * NPAIR];
-#pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    uint32_t t[NPAIR];
-                    unpack_word(w[i][s][j], uc, t);
-#pragma unroll
-                    for (int q = 0; q < NPAIR; q++) d[j * NPAIR + q] = as_u32(as_half2(t[q]) + cz[SB == 8 ? 0 : (q & 1)]);
-                }
-#pragma unroll
-                for (int b = 0; b < PPB; b++) B[s][b] = __builtin_bit_cast(mm_h8_t, u32x4{d[4 * b], d[4 * b + 1], d[4 * b + 2], d[4 * b + 3]});
-            }
+            for (int s = 0; s < NS; s++) scale[s] = dequant_block(w[i][s], tw[i][s], valid, negoff, uc, B[s]);
             if (c + RD < nchunk) issue(i, c + RD);   // wave-uniform
             const half_t *xa = xl + buf * BUF + (16 * min(tg, TM - 1) + col) * XS + kb * BK + LK * rq;
             float4_t acc[NS];
@@ -411,19 +415,7 @@ __global__ void __launch_bounds__(STRIPE_NW * 64, PF == 2 ? 4 : 1) stripe_mm1_ke
 #pragma unroll
             for (int k2 = 0; k2 < NRB; k2++) tot[s] += red[((tg * NRB + k2) * NS + s) * 64 + lane];
         }
-        const int n = stripe * 16 + col;
-        const float bv = (a.bias && !a.ldb) ? (float)a.bias[n] : 0.f;
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-            const int row = 16 * tg + 4 * rq + r;
-            float v = tot[0][r];
-            if constexpr (NS == 2) v = v * (1.0f / (1.0f + __expf(-v))) * tot[1][r];
-            if (row < a.M) {
-                half_t h = (half_t)v;
-                if (a.bias) h = (half_t)((float)h + (a.ldb ? (float)a.bias[(size_t)row * a.ldb + n] : bv));
-                a.y[(size_t)row * a.ldy + n] = h;
-            }
-        }
+        finish_tile<NS>(tot, a, stripe, 16 * tg, rq, col);
     }
 }
 
@@ -532,6 +524,7 @@ __global__ void __launch_bounds__(STRIPE_NW * 64) stripe_mm2_kernel(const MMArgs
 #pragma unroll
         for (int s = 0; s < NS; s++) {
             const u32x4 wv = *(const u32x4 *)(st + XBYTES + (kb * NS + s) * 1024 + lane * 16);
+            // (hand-written, in the WORD form this kernel was built in: see the note above mm_epilogue.  4 and 8 bits only -- WPL == 4, the class of pair q of a word is q & 1)
             const half2_t e = as_half2(tabl[(s * a.G + g) * 16 + col]);
             scale[s] = valid ? (float)e[0] : 0.f;
             const half2_t zz = {e[1], e[1]};
@@ -705,9 +698,8 @@ __global__ void __launch_bounds__(NWV * 64) stripe_mm3_kernel(const MMArgs a) {
     for (int s = 0; s < NSC; s++)
 #pragma unroll
         for (int t = 0; t < TM; t++) yacc[s][t] = float4_t{0.f, 0.f, 0.f, 0.f};
-    half2_t negoff[MM_NOFFC];
-#pragma unroll
-    for (int o = 0; o < MM_NOFFC; o++) negoff[o] = half2_t{(half_t)(-mm_class_off(o)), (half_t)(-mm_class_off(o))};
+    half2_t negoff[NOFFC];
+    neg_offsets(negoff);
 
     // the weights of segment 0 go first (HBM: the longest latency), then the first PF sub-slots of x
     // C == 1: the packed words of a whole segment (NQ row blocks) are requested at once, one segment ahead.  C > 1: a ring of WD = 2 row
@@ -758,18 +750,7 @@ __global__ void __launch_bounds__(NWV * 64) stripe_mm3_kernel(const MMArgs a) {
             const bool valid = (seg * NW + wave) * NQ + q < a.nrb;
             // exact q - z fragments of weight set s of this row block + its scale (16 VGPRs per set)
             auto unpack_set = [&](int s, mm_h8_t (&Bs)[PPB]) __attribute__((always_inline)) -> float {
-                const half2_t e = as_half2(tw[q % WD][s]);
-                const half2_t zz = {e[1], e[1]};
-                half2_t cz[MM_NOFFC];
-#pragma unroll
-                for (int o = 0; o < MM_NOFFC; o++) cz[o] = negoff[o] - zz;   // -(OFF + zero + 1), exact
-                uint32_t t[NPB], d[NPB];
-                unpack_block(w[q % WD][s], uc, t);
-#pragma unroll
-                for (int p2 = 0; p2 < NPB; p2++) d[p2] = as_u32(as_half2(t[p2]) + cz[mm_off_class(p2)]);   // q - z, exact
-#pragma unroll
-                for (int b = 0; b < PPB; b++) Bs[b] = __builtin_bit_cast(mm_h8_t, u32x4{d[4 * b], d[4 * b + 1], d[4 * b + 2], d[4 * b + 3]});
-                return valid ? (float)e[0] : 0.f;
+                return dequant_block(w[q % WD][s], tw[q % WD][s], valid, negoff, uc, Bs);
             };
             if constexpr (SPLIT) {
                 // the PAIR with C stripes per workgroup (round 5): 2 C weight streams per wave -- their B fragments together (96 VGPRs at C = 3) spill,
@@ -878,19 +859,7 @@ __global__ void __launch_bounds__(NWV * 64) stripe_mm3_kernel(const MMArgs a) {
         }
         const int stripe = stripe0 + c;
         if (stripe >= a.nstripes) continue;     // (wave-uniform)
-        const int n = stripe * 16 + col;
-        const float bv = (a.bias && !a.ldb) ? (float)a.bias[n] : 0.f;
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-            const int row = 16 * t + 4 * rq + r;
-            float v = tot[0][r];
-            if constexpr (NS == 2) v = v * (1.0f / (1.0f + __expf(-v))) * tot[1][r];   // silu on the fp32 accumulator (fused_mlp.py:160-164)
-            if (row < a.M) {
-                half_t h = (half_t)v;
-                if (a.bias) h = (half_t)((float)h + (a.ldb ? (float)a.bias[(size_t)row * a.ldb + n] : bv));
-                a.y[(size_t)row * a.ldy + n] = h;
-            }
-        }
+        finish_tile<NS>(tot, a, stripe, 16 * t, rq, col);
     }
 }
 
@@ -1083,9 +1052,8 @@ __global__ void __launch_bounds__(STRIPE_NW * 64) stripe_mmr_kernel(const MMArgs
 #pragma unroll
         for (int c = 0; c < C; c++) stripe_of[c] = min(stripe0 + c, a.nstripes - 1);
         const uint32_t woff = lane * WPL;
-        half2_t negoff[MM_NOFFC];
-#pragma unroll
-        for (int o = 0; o < MM_NOFFC; o++) negoff[o] = half2_t{(half_t)(-mm_class_off(o)), (half_t)(-mm_class_off(o))};
+        half2_t negoff[NOFFC];
+        neg_offsets(negoff);
         wvec_t wn[C];
         uint32_t twn[C];
         auto wload = [&](int rb, int st) {     // the image: [stripe][row block][set][64 lanes] words, [stripe][set][group][16] table entries
@@ -1115,18 +1083,7 @@ __global__ void __launch_bounds__(STRIPE_NW * 64) stripe_mmr_kernel(const MMArgs
                     float scale[C];
 #pragma unroll
                     for (int c = 0; c < C; c++) {
-                        const half2_t e = as_half2(twn[c]);
-                        const half2_t zz = {e[1], e[1]};
-                        half2_t cz[MM_NOFFC];
-#pragma unroll
-                        for (int o = 0; o < MM_NOFFC; o++) cz[o] = negoff[o] - zz;
-                        uint32_t t[NPB], d[NPB];
-                        unpack_block(wn[c], uc, t);
-#pragma unroll
-                        for (int p2 = 0; p2 < NPB; p2++) d[p2] = as_u32(as_half2(t[p2]) + cz[mm_off_class(p2)]);
-#pragma unroll
-                        for (int b = 0; b < PPB; b++) B[c][b] = __builtin_bit_cast(mm_h8_t, u32x4{d[4 * b], d[4 * b + 1], d[4 * b + 2], d[4 * b + 3]});
-                        scale[c] = (float)e[0];
+                        scale[c] = dequant_block(wn[c], twn[c], true, negoff, uc, B[c]);      // (rb < nrbl: every row block here is inside the slice)
                         __builtin_amdgcn_sched_barrier(0);
                     }
                     if (sw + 1 < NSW) wload(rb, st + 1);
@@ -1225,18 +1182,7 @@ __global__ void __launch_bounds__(STRIPE_NW * 64) stripe_mmr_kernel(const MMArgs
                 continue;
             }
         }
-        const float bv = (a.bias && !a.ldb) ? (float)a.bias[n] : 0.f;
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-            const int row = 16 * t + 4 * rq + r;
-            float v = tot[0][r];
-            if constexpr (NS == 2) v = v * (1.0f / (1.0f + __expf(-v))) * tot[1][r];   // silu on the fp32 accumulator (fused_mlp.py:160-164)
-            if (row < a.M) {
-                half_t h = (half_t)v;
-                if (a.bias) h = (half_t)((float)h + (a.ldb ? (float)a.bias[(size_t)row * a.ldb + n] : bv));
-                a.y[(size_t)row * a.ldy + n] = h;
-            }
-        }
+        finish_tile<NS>(tot, a, stripe, 16 * t, rq, col);
     }
 }
 
@@ -1491,27 +1437,27 @@ __global__ void __launch_bounds__(STRIPE_NW * 64) stripe_gemm_kernel(const MMArg
     for (int i = 0; i < NSW; i++)
 #pragma unroll
         for (int t = 0; t < RT; t++) yacc[i][t] = float4_t{0.f, 0.f, 0.f, 0.f};
-    half2_t negoff[MM_NOFFC];
+    half2_t negoff[NOFFC];
 #pragma unroll
-    for (int o = 0; o < MM_NOFFC; o++) negoff[o] = half2_t{(half_t)(-mm_class_off(o)), (half_t)(-mm_class_off(o))};
+    for (int o = 0; o < NOFFC; o++) negoff[o] = half2_t{(half_t)(-class_off(o)), (half_t)(-class_off(o))};
 
     // ---- prologue: weights of the first PFW chunks, x chunk 0 into LDS, x chunk 1 into registers ----
     // B fragments + scales of one chunk from its packed words: exact q - z (VALU only)
     auto unpack = [&](int j, bool valid, mm_h8_t (&B)[NSW][PPB], float2_t (&scale)[NSW]) {
 #pragma unroll
-        for (int i = 0; i < NSW; i++) {
+        for (int i = 0; i < NSW; i++) {      // (hand-written dequant_block, with the prescale: see the note above mm_epilogue)
             const half2_t e = as_half2(tw[j][i]);
             const float sc1 = valid ? (float)e[0] : 0.f;   // chunks past K (clamped loads) carry a zero scale
             scale[i] = float2_t{sc1, sc1};
             const half2_t zz = {e[1], e[1]};
-            half2_t cz[MM_NOFFC];
+            half2_t cz[NOFFC];
 #pragma unroll
-            for (int o = 0; o < MM_NOFFC; o++) cz[o] = negoff[o] - zz;   // -(OFF + zero + 1), exact
+            for (int o = 0; o < NOFFC; o++) cz[o] = negoff[o] - zz;   // -(OFF + zero + 1), exact
             uint32_t t32[NPB], d[NPB];
             unpack_block(w[j][i], uc, t32);
 #pragma unroll
             for (int q = 0; q < NPB; q++) {
-                half2_t v = as_half2(t32[q]) + cz[mm_off_class(q)];   // q - z, exact
+                half2_t v = as_half2(t32[q]) + cz[off_class(q)];   // q - z, exact
                 if constexpr (PS) v = v * half2_t{valid ? e[0] : (half_t)0.f, valid ? e[0] : (half_t)0.f};   // ... times the group scale: one fp16 rounding
                 d[q] = as_u32(v);
             }
@@ -1631,7 +1577,7 @@ __global__ void __launch_bounds__(STRIPE_NW * 64) stripe_gemm_kernel(const MMArg
         }
         return;
     }
-    // ---- epilogue: lane = column, rows 4 rq + r of each row tile ----
+    // ---- epilogue: lane = column, rows 4 rq + r of each row tile (hand-written finish_tile: see the note above mm_epilogue) ----
 #pragma unroll
     for (int i = 0; i < (NS == 1 ? NSW : 1); i++) {
         if (sstripe[i] >= a.nstripes) continue;

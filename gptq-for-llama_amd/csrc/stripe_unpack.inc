@@ -39,10 +39,15 @@ GPTQ_DEV float wave_sum_all(float v) {
     return fold_rows(v);
 }
 
-// fp16 offset the magic of pair i of a packed row carries (the field value is OFF + q).  Selects, NOT a constant table: indexed with a
-// run-time pair number a table becomes a global load from .rodata, and its s_waitcnt vmcnt(0) -- in the staging phase, or (act-order) in
-// every K-loop iteration -- also waits for every weight load in flight (found in round 4.  3-bit 4096 x 4096 at M = 1: 4.27 -> 3.86 us, 11008 x 4096: 6.76 -> 5.90 us; with act-order 10.0 -> 6.9 us)
-__host__ __device__ constexpr float pair_off(int i) {
+// The fp16 magic offsets of a lane block.  pair_off_block(p) is the offset the magic of pair p (natural k order, NPB pairs) carries -- the field
+// value is OFF + q; the decode kernels' x staging calls it with a run-time pair.  The MFMA kernels (dequant_block, stripe_mm.inc) need the same
+// fact as CLASSES: NOFFC distinct offsets, off_class(p) the class of pair p, class_off(c) its offset -- and class c IS the magic g[c] of
+// unpack_consts() (MAGIC<c>).  The static_assert below ties the three together: every pair's offset is its class's, every magic decodes to its
+// class's offset.
+// Selects, NOT constant tables: indexed with a run-time pair number a table becomes a global load from .rodata, and its s_waitcnt vmcnt(0)
+// -- in the staging phase, or (act-order) in every K-loop iteration -- also waits for every weight load in flight (found in round 4.  3-bit
+// 4096 x 4096 at M = 1: 4.27 -> 3.86 us, 11008 x 4096: 6.76 -> 5.90 us; with act-order 10.0 -> 6.9 us)
+__host__ __device__ constexpr float pair_off(int i) {   // ... of pair i of a packed WORD
     if (SB == 8) return 1024.f;
     if (SB == 4) return (i & 1) ? 64.f : 1024.f;
     if (SB == 3) {   // 1024 128 16 1024 128
@@ -54,35 +59,69 @@ __host__ __device__ constexpr float pair_off(int i) {
     const int c = r >= 5 ? r - 5 : r - 2;
     return c == 0 ? 64.f : (c == 1 ? 16.f : 4.f);
 }
-// ... of pair p of a LANE BLOCK (NPB pairs, natural k order)
 __host__ __device__ constexpr float pair_off_block(int p) {
-    if (SB == 3) return p == 15 ? 1024.f : pair_off(p % 5);
+    if (SB == 3) return p == 15 ? 1024.f : pair_off(p % 5);   // (pair 15: k 30 / k 31 from the spare bits)
     return pair_off(p % NPAIR);
 }
+constexpr int NOFFC = SB == 8 ? 1 : (SB == 4 ? 2 : (SB == 3 ? 3 : 5));   // distinct offsets of a width
+__host__ __device__ constexpr int off_class(int p) {
+    if (SB == 8) return 0;
+    if (SB == 4) return p & 1;
+    if (SB == 3) return p == 15 ? 0 : (p % 5) % 3;    // offsets 1024, 128, 16, 1024, 128 per word; the spare-bit pair 1024
+    const int r = p & 7;                               // 1024, 256, 64, 16, 4, 64, 16, 4 per word
+    return r < 5 ? r : r - 3;
+}
+__host__ __device__ constexpr float class_off(int c) {
+    if (SB == 8) return 1024.f;
+    if (SB == 4) return c ? 64.f : 1024.f;
+    if (SB == 3) return c == 0 ? 1024.f : (c == 1 ? 128.f : 16.f);
+    return c == 0 ? 1024.f : (c == 1 ? 256.f : (c == 2 ? 64.f : (c == 3 ? 16.f : 4.f)));
+}
+// the magic of an offset: fp16 OFF (a power of two 2^e, 0 <= e <= 15: bits (e + 15) << 10, zero mantissa) in both halves; OR-ing a field into
+// its mantissa gives OFF + q.  Anything that is no such power of two gives 0, which the static_assert below refuses.
+__host__ __device__ constexpr uint32_t off_magic(float off) {
+    for (int e = 0; e <= 15; e++)
+        if ((float)(1 << e) == off) return (uint32_t)((e + 15) << 10) * 0x10001u;
+    return 0u;
+}
+// ... and back: the fp16 value both halves of a magic carry (0 if they differ or the mantissa is not empty)
+__host__ __device__ constexpr float magic_off(uint32_t m) {
+    const uint32_t h = m & 0xFFFFu, e = h >> 10;
+    return ((m >> 16) != h || (h & 0x3FFu) || e < 15 || e > 30) ? 0.f : (float)(1 << (e - 15));
+}
+constexpr bool magics_match() {      // every class's magic decodes back to the class's offset, and every pair's offset is its class's
+    for (int c = 0; c < NOFFC; c++)
+        if (magic_off(off_magic(class_off(c))) != class_off(c)) return false;
+    for (int p = 0; p < NPB; p++)
+        if (off_class(p) < 0 || off_class(p) >= NOFFC || class_off(off_class(p)) != pair_off_block(p)) return false;
+    return true;
+}
+static_assert(magics_match(), "pair_off_block() <-> offset classes <-> magics of unpack_consts()");
+template <int C> constexpr uint32_t MAGIC = off_magic(class_off(C < NOFFC ? C : 0));   // of class C.  1024: 0x6400, 256: 0x5C00, 128: 0x5800, 64: 0x5400, 16: 0x4C00, 4: 0x4400
 
 struct UnpackConsts {
-    uint32_t m[5], g[5];   // masks in SGPRs, magics in VGPRs: (w & m) | g is ONE v_and_or_b32
+    uint32_t m[5], g[5];   // masks in SGPRs, magics in VGPRs: (w & m) | g is ONE v_and_or_b32; g[c] = MAGIC<c>, the magic of offset class c
 };
 GPTQ_DEV UnpackConsts unpack_consts() {
     UnpackConsts c{};
     if constexpr (SB == 8) {
-        c.m[0] = sreg_const(0x00FF00FFu); c.g[0] = vreg_const(0x64006400u);
+        c.m[0] = sreg_const(0x00FF00FFu); c.g[0] = vreg_const(MAGIC<0>);
     } else if constexpr (SB == 4) {
-        c.m[0] = sreg_const(0x000F000Fu); c.g[0] = vreg_const(0x64006400u);   // bits [3:0]  -> 1024 + q
-        c.m[1] = sreg_const(0x00F000F0u); c.g[1] = vreg_const(0x54005400u);   // bits [7:4]  ->   64 + q
+        c.m[0] = sreg_const(0x000F000Fu); c.g[0] = vreg_const(MAGIC<0>);   // bits [3:0]  -> 1024 + q
+        c.m[1] = sreg_const(0x00F000F0u); c.g[1] = vreg_const(MAGIC<1>);   // bits [7:4]  ->   64 + q
     } else if constexpr (SB == 3) {
-        c.m[0] = sreg_const(0x00070007u); c.g[0] = vreg_const(0x64006400u);   // bits [2:0]  -> 1024 + q
-        c.m[1] = sreg_const(0x00380038u); c.g[1] = vreg_const(0x58005800u);   // bits [5:3]  ->  128 + q
-        c.m[2] = sreg_const(0x01C001C0u); c.g[2] = vreg_const(0x4C004C00u);   // bits [8:6]  ->   16 + q
+        c.m[0] = sreg_const(0x00070007u); c.g[0] = vreg_const(MAGIC<0>);   // bits [2:0]  -> 1024 + q
+        c.m[1] = sreg_const(0x00380038u); c.g[1] = vreg_const(MAGIC<1>);   // bits [5:3]  ->  128 + q
+        c.m[2] = sreg_const(0x01C001C0u); c.g[2] = vreg_const(MAGIC<2>);   // bits [8:6]  ->   16 + q
         c.m[3] = sreg_const(0x00010001u);                                     // the spare bits, shifted down to [0], [1], [2]
         c.m[4] = sreg_const(0x00020002u);
         c.g[4] = sreg_const(0x00040004u);                                     // (third spare mask parked in g[4]: an SGPR like the others)
     } else {
-        c.m[0] = sreg_const(0x00030003u); c.g[0] = vreg_const(0x64006400u);   // [1:0] -> 1024 + q
-        c.m[1] = sreg_const(0x000C000Cu); c.g[1] = vreg_const(0x5C005C00u);   // [3:2] ->  256 + q
-        c.m[2] = sreg_const(0x00300030u); c.g[2] = vreg_const(0x54005400u);   // [5:4] ->   64 + q
-        c.m[3] = sreg_const(0x00C000C0u); c.g[3] = vreg_const(0x4C004C00u);   // [7:6] ->   16 + q
-        c.m[4] = sreg_const(0x03000300u); c.g[4] = vreg_const(0x44004400u);   // [9:8] ->    4 + q
+        c.m[0] = sreg_const(0x00030003u); c.g[0] = vreg_const(MAGIC<0>);   // [1:0] -> 1024 + q
+        c.m[1] = sreg_const(0x000C000Cu); c.g[1] = vreg_const(MAGIC<1>);   // [3:2] ->  256 + q
+        c.m[2] = sreg_const(0x00300030u); c.g[2] = vreg_const(MAGIC<2>);   // [5:4] ->   64 + q
+        c.m[3] = sreg_const(0x00C000C0u); c.g[3] = vreg_const(MAGIC<3>);   // [7:6] ->   16 + q
+        c.m[4] = sreg_const(0x03000300u); c.g[4] = vreg_const(MAGIC<4>);   // [9:8] ->    4 + q
     }
     return c;
 }

@@ -210,6 +210,31 @@ def pow2_layer(bits, groupsize, K, N, act_order=False, seed=0):
     return L
 
 
+def exact_domain_case(bits, groupsize, K, N, M, nsets=1, act_order=False, seed=0, x_max=4, scale_exps=(-7, -6, -5)):
+    """Data on which a quantised matmul has ONE right answer whatever the order of its fp32 sums: make_random_layer with every scale a power
+    of two drawn per (group, column) from 2^scale_exps, and x integer-valued in [-x_max, x_max] as fp16.  Every product x (q - z) s -- and
+    x q s, x z s, which the decode kernels sum separately -- is a multiple of the granule 2^min(scale_exps) (the bound below allows 2^-3 of
+    it, the grid of a bias of eighths), so every partial sum in any order is exact in fp32 while it stays below 2^24 granules.  That is
+    asserted here in float64, with the largest output below the fp16 maximum: a cap on the data, not a tolerance.
+    Returns (list of nsets layers, x [M, K] fp16)."""
+    from oracle import oracle
+    rng = np.random.default_rng(seed + 7919)
+    x = rng.integers(-x_max, x_max + 1, size=(M, K)).astype(np.float16)
+    granule = 2.0 ** min(scale_exps) * 2.0 ** -3
+    Ls = []
+    for i in range(nsets):
+        L = make_random_layer(bits, groupsize, K, N, act_order=act_order, seed=seed + i)
+        L['scales'] = (2.0 ** rng.choice(np.asarray(scale_exps, dtype=np.float64), size=L['scales'].shape)).astype(np.float16)
+        w = oracle.dequant(L['qweight'], L['qzeros'], L['scales'], L['g_idx'], bits, faithful=False).astype(np.float64)              # (q - z) s, exact
+        zs = -oracle.dequant(np.zeros_like(L['qweight']), L['qzeros'], L['scales'], L['g_idx'], bits, faithful=False).astype(np.float64)   # z s
+        assert np.all(w == np.round(w / granule) * granule)
+        bound = (np.abs(x.astype(np.float64)) @ (np.abs(w + zs) + zs)).max()         # sum |x| (q + z) s >= sum |x| |q - z| s
+        assert bound / granule < 2.0 ** 24, ('exact_domain_case: a partial sum may leave the exact range of fp32', bits, K, N, M, bound / granule)
+        assert np.abs(x.astype(np.float64) @ w).max() < FP16_MAX
+        Ls.append(L)
+    return Ls, x
+
+
 def rows_excess_over_reference(hip, faithful, exact, extra_ulp=1.0):
     """how far the worst row of ``hip`` is further from ``exact`` than ``faithful`` beyond assert_not_worse_than_reference's per-row
     slack, relative to that row's max|exact| (0 where every row passes that check)"""
