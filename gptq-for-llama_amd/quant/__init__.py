@@ -5,7 +5,7 @@ exactly as with the reference tree: every public name of the reference's ``quant
 re-exported below from the sub-module of the same file name, plus the two spellings of the old-cuda
 branch that ``BASELINE.json``'s north_star uses (``make_quant``, ``autotune_warmup``).
 """
-from . import layer, quantizer, quant_linear, fused_attn, fused_mlp, triton_norm, tensor_parallel, decode  # noqa: F401
+from . import layer, quantizer, quant_linear, fused_attn, fused_mlp, triton_norm, tensor_parallel, decode, constrain  # noqa: F401
 
 _PUBLIC = {
     quantizer: ('Quantizer', ),

@@ -186,6 +186,10 @@ _SIGNATURES = {
     # (csrc/logits_process.hip)
     'gptq_logits_process_f16': [c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
                                 c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p],
+    # constrained decoding: advance every row's automaton state by the token consumed and mask what the new state bans, grid (B)
+    # (csrc/constrain.hip)
+    'gptq_constrain_rows_f16': [c_void_p, c_int64, c_int, c_int, c_void_p, c_int64, c_int, c_int, c_void_p, c_int64, c_int, c_void_p, c_void_p,
+                                c_void_p, c_void_p, c_int64, c_int64, c_void_p],
     # beam search: one step on N rows of logits with all bookkeeping in one device block, and the in-place move of K/V histories between cache
     # rows (csrc/beam.hip)
     'gptq_beam_state_bytes': [c_int, c_int],

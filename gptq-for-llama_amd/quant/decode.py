@@ -181,6 +181,7 @@ MAX_BATCH = 16         # rows of a decode batch one engine serves (the LM head k
 MAX_CHUNK_ROWS = 128   # rows of a batched verify step (batch x batch_chunk): what gptq_layer_decode_f16 and the batched chunk attention take
 MAX_PROCESS_EOS, MAX_PROCESS_BIAS, MAX_PROCESS_VOCAB = 8, 256, 131072      # GPTQ_LOGITS_PROCESS_MAX_EOS / _BIAS / _VOCAB
 MAX_BEAMS = 16         # GPTQ_BEAM_MAX_BEAMS
+MAX_CONSTRAIN_STATES, MAX_CONSTRAIN_CLASSES = 32767, 16384                 # GPTQ_CONSTRAIN_MAX_STATES / _CLASSES
 BEAM_DEAD = -1e9
 MAX_LOGPROBS, MAX_LOGPROBS_ROWS = 32, 128      # GPTQ_LOGPROBS_MAX_TOP, the rows of one gptq_logprobs_rows_f16 launch
 # gptq_beam_select_f16's state block in 4-byte words (gptq_mi355x.h "beam search")
@@ -219,8 +220,16 @@ def lm_head_logits(eng, x, logits, s, h=None):
 class DecodeEngine:
 
     def __init__(self, model, t_max=2048, fuse_norm=True, fuse_attn=True, batch=1, chunk=0, batch_chunk=0, spec_sample=False, logits_process=False, beam_search=False,
-                 logprobs=None):
-        """logprobs = K (0 .. 32) makes every self-feeding step (capture_greedy_rows, capture_sample_native, capture_sample_rows) RECORD the
+                 logprobs=None, constrain=None):
+        """constrain = True (dict(states=4096, classes=1024)) or a dict of those two capacities adds CONSTRAINED DECODING for regular languages
+        (gptq_constrain_rows_f16, gptq_mi355x.h "constrained decoding"; quant/constrain.py builds the automata): c_next int16 [states, classes]
+        filled with -1, c_cls int16 [B, vocab] -- one class-map slot per row --, c_map int32 [B], c_state int32 [B], all -1 (unconstrained).  One
+        more launch per step, directly behind the processors' and ahead of the draw: it advances every row's state by the token the step
+        consumed and sets the logits of the tokens the new state bans to -inf (set_constraint, reset_constraint, constrain_logits).  Every
+        pointer and capacity is fixed here: a captured graph serves any automaton set later.  None (the default) allocates nothing and adds no
+        launch.  ValueError together with chunk, batch_chunk or beam_search: constraints under speculation (a verify step has R rows per
+        sequence and needs the state chain per row) and for beams are not built yet.
+        logprobs = K (0 .. 32) makes every self-feeding step (capture_greedy_rows, capture_sample_native, capture_sample_rows) RECORD the
         log-probability of the token it chose, that token's rank and the row's K most probable tokens (gptq_logprobs_rows_f16, gptq_mi355x.h
         "token log-probabilities": one more launch per step, no host round trip): lp_chosen float [t_max + 1, B], lp_rank int32 [t_max + 1, B],
         lp_top_ids int32 / lp_top float [t_max + 1, B, K]; row n belongs to row n of stream_rows.  The logits are the ones the draw sees:
@@ -286,6 +295,21 @@ class DecodeEngine:
                 raise ValueError('DecodeEngine: logprobs together with chunk / batch_chunk / beam_search is not built yet (records of a verify '
                                  'step, of a beam)')
         self.logprobs = logprobs
+        if constrain is None or constrain is False:
+            self.constrain = None
+        else:
+            cap = dict(states=4096, classes=1024)
+            if constrain is not True:
+                if not isinstance(constrain, dict) or set(constrain) - set(cap):
+                    raise ValueError('DecodeEngine: constrain must be None, True or a dict with the keys states, classes, not %r' % (constrain,))
+                cap.update(constrain)
+            for k, most in (('states', MAX_CONSTRAIN_STATES), ('classes', MAX_CONSTRAIN_CLASSES)):
+                if isinstance(cap[k], bool) or not isinstance(cap[k], int) or not 1 <= cap[k] <= most:
+                    raise ValueError('DecodeEngine: constrain %s must be an int in 1 .. %d, not %r' % (k, most, cap[k]))
+            if self.chunk or self.batch_chunk or self.beam_search:
+                raise ValueError('DecodeEngine: constrain together with chunk / batch_chunk / beam_search is not built yet (the state chain of a '
+                                 'verify step, of a beam)')
+            self.constrain = cap
         self.fuse_norm, self.fuse_attn = bool(fuse_norm), bool(fuse_attn)
         self.native = _native
         self.lib = _native.lib()
@@ -352,6 +376,13 @@ class DecodeEngine:
             self.bias_ids = torch.zeros(MAX_PROCESS_BIAS, dtype=torch.int32, device=dev)
             self.bias_vals = torch.zeros(MAX_PROCESS_BIAS, dtype=torch.float32, device=dev)
             self.n_eos, self.n_bias = 0, 0                  # launch arguments: a captured step holds the counts it was captured with
+        if self.constrain is not None:
+            # gptq_constrain_rows_f16: the stacked automata, every row's class map and state, read by the kernel at every replay (set_constraint)
+            self.c_next = torch.full((self.constrain['states'], self.constrain['classes']), -1, dtype=torch.int16, device=dev)
+            self.c_cls = torch.zeros((B, self.logits.shape[1]), dtype=torch.int16, device=dev)
+            self.c_map = torch.arange(B, dtype=torch.int32, device=dev)
+            self.c_state = torch.full((B,), -1, dtype=torch.int32, device=dev)
+            self._c_dfas, self._c_start = [None] * B, [-1] * B       # the rows' automata and start states, as set_constraint left them
         nl = len(self.layers)
         self.kcb = torch.zeros((nl, B, self.t_max, H), **f16)          # [layer][row][t][heads * head_dim]
         self.vcb = torch.zeros((nl, B, self.t_max, H), **f16)
@@ -701,6 +732,7 @@ class DecodeEngine:
         and the choice is appended to stream_out[pos] (pos = number of tokens consumed so far)."""
         self._step()                                   # consumes self.ids, advances pos
         self._process_step()
+        self._constrain_step()
         torch.argmax(self.logits, dim=-1, out=self.ids)
         self.stream_out.index_copy_(0, self.pos, self.ids)
 
@@ -729,7 +761,7 @@ class DecodeEngine:
 
     def capture_greedy(self):
         """capture the self-feeding greedy step (engine_generate): a replay needs no host input at all."""
-        self.greedy_graph = self._capture(self._greedy_step, (self.pos, self.ids))
+        self.greedy_graph = self._capture(self._greedy_step, (self.pos, self.ids) + self._constrain_state())
         return self
 
     def _stream_buffers(self):
@@ -794,15 +826,16 @@ class DecodeEngine:
         """_capture for the steps that append to stream_rows: the step counter starts at 0, and is 0 again afterwards"""
         self._stream_buffers()
         self.stepc.zero_()
-        return self._capture(step, (self.pos, self.ids, self.stepc), keep_rng)
+        return self._capture(step, (self.pos, self.ids, self.stepc) + self._constrain_state(), keep_rng)
 
     def _self_feeding_step(self, choose):
-        """THE self-feeding step, for any batch: one decode step, the processors (nothing without the flag), choose() puts every row's next input
+        """THE self-feeding step, for any batch: one decode step, the processors and the constraint (nothing without their flags), choose() puts every row's next input
         token into self.ids, the logprobs record of the choices (nothing without the flag), and the choices of step n become row n of stream_rows
         (n = stepc, a device counter the step advances itself)"""
         self._stream_buffers()
         self._step()
         self._process_step()
+        self._constrain_step()
         choose()
         self._logprobs_step()
         self.stream_rows.index_copy_(0, self.stepc, self.ids.unsqueeze(0))
@@ -1010,6 +1043,105 @@ class DecodeEngine:
         if last is not None and (last.dtype != torch.int64 or last.device != self.ids.device or last.shape != (n,) or not last.is_contiguous()):
             raise ValueError('DecodeEngine.process_logits: last must be a contiguous int64 [%d] on %s' % (n, self.dev))
         self._process_launch(rows, n, last, 0)
+        return logits
+
+    # -- constrained decoding: gptq_constrain_rows_f16 (csrc/constrain.hip) on the rows' automaton states, every table in device memory ----------
+    def _need_constrain(self, what):
+        if self.constrain is None:
+            raise ValueError('DecodeEngine.%s: the engine was built without constrain=' % what)
+
+    def _constrain_state(self):
+        """what a capture must put back behind its warm-up run and behind the capture itself: both run the step, and the step moves c_state"""
+        return () if self.constrain is None else (self.c_state,)
+
+    def set_constraint(self, dfa):
+        """the rows' automata: a quant.constrain.TokenDFA, None (unconstrained), or a list of `batch` of either -- it may differ per row.  The
+        automata are stacked into c_next, each at a state offset, their transitions shifted on upload, so c_state holds absolute indices; rows
+        that pass the same object share its states and its class map.  Every row is put to its automaton's start (None: -1).  Only the static
+        device buffers change: a captured graph serves the new automata at its next replay, and no graph is dropped.  ValueError before
+        anything changes when the automata do not fit the capacities or a vocabulary differs from the head's."""
+        from .constrain import TokenDFA
+        self._need_constrain('set_constraint')
+        what, B, V = 'DecodeEngine.set_constraint', self.batch, self.logits.shape[1]
+        dfas = list(dfa) if isinstance(dfa, (list, tuple)) else [dfa] * B
+        if len(dfas) != B or any(d is not None and not isinstance(d, TokenDFA) for d in dfas):
+            raise ValueError('%s: needs a TokenDFA, None or a list of %d of either' % (what, B))
+        distinct = []
+        for d in dfas:
+            if d is not None and not any(d is e for e in distinct):
+                distinct.append(d)
+        for d in distinct:
+            if d.vocab != V:
+                raise ValueError('%s: an automaton over %d tokens for a head of %d' % (what, d.vocab, V))
+        states, classes = sum(d.n_states for d in distinct), max([d.n_classes for d in distinct] + [1])
+        if states > self.constrain['states'] or classes > self.constrain['classes']:
+            raise ValueError('%s: the automata need %d states and %d classes, the engine was built for %d and %d' % (
+                what, states, classes, self.constrain['states'], self.constrain['classes']))
+        with torch.no_grad():
+            offset, first_row, start, maps = 0, {}, [], []
+            self.c_next.fill_(-1)
+            for b, d in enumerate(dfas):
+                if d is None:
+                    start.append(-1)
+                    maps.append(b)
+                    continue
+                if id(d) not in first_row:                           # its states at `offset`, its class map in the slot of its first row
+                    nxt = d.next.astype(np.int32)
+                    nxt[nxt >= 0] += offset
+                    self.c_next[offset:offset + d.n_states, :d.n_classes].copy_(torch.from_numpy(nxt.astype(np.int16)))
+                    self.c_cls[b].copy_(torch.from_numpy(d.cls.copy()))        # (a copy: the automaton's arrays are read-only)
+                    first_row[id(d)] = (b, offset)
+                    offset += d.n_states
+                maps.append(first_row[id(d)][0])
+                start.append(first_row[id(d)][1])
+            self.c_map.copy_(torch.tensor(maps, dtype=torch.int32))
+            self._c_dfas, self._c_start = dfas, start
+            self.c_state.copy_(torch.tensor(start, dtype=torch.int32))
+        return self
+
+    def reset_constraint(self, rows=None):
+        """the rows (None: all; an int or a list of ints) back to the start states of their automata"""
+        self._need_constrain('reset_constraint')
+        rows = range(self.batch) if rows is None else ([rows] if isinstance(rows, int) else list(rows))
+        if any(isinstance(r, bool) or not isinstance(r, int) or not 0 <= r < self.batch for r in rows):
+            raise ValueError('DecodeEngine.reset_constraint: rows must lie in the batch of %d' % self.batch)
+        state = self.c_state.tolist()
+        for r in rows:
+            state[r] = self._c_start[r]
+        with torch.no_grad():
+            self.c_state.copy_(torch.tensor(state, dtype=torch.int32))
+        return self
+
+    def _constrain_launch(self, logits, n, last, len_add):
+        with self.native.on_device(self.dev):
+            rc = self.lib.gptq_constrain_rows_f16(
+                logits.data_ptr(), logits.stride(0) if n > 1 else logits.shape[1], n, logits.shape[1], self.c_next.data_ptr(), self.c_next.stride(0),
+                self.c_next.shape[0], self.c_next.shape[1], self.c_cls.data_ptr(), self.c_cls.stride(0), self.batch, self.c_map.data_ptr(),
+                self.c_state.data_ptr(), self.native.ptr(last), self.pos.data_ptr(), len_add, self.t_max - (0 if last is None else 1),
+                self.native.stream_ptr(self.dev))
+        self.native.check(rc, 'gptq_constrain_rows_f16')
+
+    def _constrain_step(self):
+        """behind _process_step() (pos is advanced already: len_add = -1): every row's state advances by the token this step consumed (self.ids)
+        and self.logits is masked under the new state, in ONE launch -- the processors act first, then the mask.  A row idling at a negative
+        position, or past the cache, is left alone, as the processors leave it.  Nothing without the flag."""
+        if self.constrain is not None:
+            self._constrain_launch(self.logits, self.batch, self.ids, -1)
+
+    def constrain_logits(self, logits, last=None):
+        """the eager entry, with the shape rules of process_logits: rows 0 .. n - 1 of `logits` ([n, vocab] or [vocab] fp16 on the engine's
+        device, unit column stride, n <= batch) are masked IN PLACE under those rows' states -- what the first token after a prompt needs.
+        last: int64 [n] on the device, tokens the rows consume first: the states advance by them, and a token its state bans puts the row at
+        -2 (it has left its automaton: its logits are left alone from then on).  Returns logits."""
+        self._need_constrain('constrain_logits')
+        rows = logits.unsqueeze(0) if logits.dim() == 1 else logits
+        n = rows.shape[0] if rows.dim() == 2 else 0
+        if not 1 <= n <= self.batch or rows.dtype != torch.float16 or rows.device != self.ids.device or rows.stride(1) != 1 or \
+                rows.shape[1] != self.logits.shape[1]:
+            raise ValueError('DecodeEngine.constrain_logits: logits must be fp16 [n <= %d, vocab] with unit column stride on %s' % (self.batch, self.dev))
+        if last is not None and (last.dtype != torch.int64 or last.device != self.ids.device or last.shape != (n,) or not last.is_contiguous()):
+            raise ValueError('DecodeEngine.constrain_logits: last must be a contiguous int64 [%d] on %s' % (n, self.dev))
+        self._constrain_launch(rows, n, last, 0)
         return logits
 
     # -- beam search: the N rows are the running beams; gptq_beam_select_f16 + gptq_kv_reorder_f16 (csrc/beam.hip) behind the batch step ---------
@@ -1690,7 +1822,8 @@ class DecodeEngine:
 
     def decode(self, token):
         """one token per row in ([batch] ids), logits [batch, vocab] out (the static buffer: clone it to keep it).  An engine built with
-        logits_process=True returns the PROCESSED logits (set_logits_process) and appends the tokens to its history."""
+        logits_process=True returns the PROCESSED logits (set_logits_process) and appends the tokens to its history; one built with constrain
+        advances the rows' automata by the tokens and returns the logits MASKED under the new states (set_constraint)."""
         if torch.is_tensor(token):
             self.ids.copy_(token.reshape(self.batch))
         else:
@@ -1701,6 +1834,7 @@ class DecodeEngine:
             else:
                 self._step()
             self._process_step()
+            self._constrain_step()
         return self.logits
 
 
@@ -2067,7 +2201,31 @@ def _logprobs_setting(what, logprobs, speculate, engine):
     return logprobs
 
 
-def _generate_rows(what, eng, prompts, into, max_new_tokens, eos_token_id, settings, proc, spec, one_prompt=False, logprobs=None):
+def _constrain_setting(what, constrain, n, speculate, engine):
+    """the constrain= argument of `what` (engine_generate / engine_generate_batch), validated: None, or one automaton (or None) per prompt.
+    ValueError under speculate= and for an engine passed in without the flag"""
+    if constrain is None:
+        return None
+    from .constrain import TokenDFA
+    dfas = list(constrain) if isinstance(constrain, (list, tuple)) else [constrain] * n
+    if len(dfas) != n or any(d is not None and not isinstance(d, TokenDFA) for d in dfas):
+        raise ValueError('%s: constrain must be a TokenDFA or a list of %d of them (None: that prompt is unconstrained)' % (what, n))
+    if speculate is not None:
+        raise ValueError('%s: constrain together with speculate is not built yet (a verify step needs the state chain per row)' % what)
+    if engine is not None and engine.constrain is None:
+        raise ValueError('%s: constrain needs an engine built with constrain=' % what)
+    return dfas
+
+
+def _constrain_capacity(dfas):
+    """the constrain= argument of a DecodeEngine that holds exactly these automata (None: no flag)"""
+    if dfas is None:
+        return None
+    distinct = {id(d): d for d in dfas if d is not None}.values()
+    return dict(states=max(1, sum(d.n_states for d in distinct)), classes=max([d.n_classes for d in distinct] + [1]))
+
+
+def _generate_rows(what, eng, prompts, into, max_new_tokens, eos_token_id, settings, proc, spec, one_prompt=False, logprobs=None, dfas=None):
     """THE generation driver behind engine_generate (one prompt) and engine_generate_batch: prompts are n = eng.batch 1-D id tensors,
     into(engine) puts them into that engine's cache from position 0 and returns the [n, vocab] logits behind their last tokens.  In this order:
     the settings go into the engine; every graph the run will need is taken from graph_for, while no prompt is in the cache yet; the prompts
@@ -2080,6 +2238,8 @@ def _generate_rows(what, eng, prompts, into, max_new_tokens, eos_token_id, setti
         if spec is not None:
             return _speculate_rows(what, eng, prompts, into, max_new_tokens, eos_token_id, *spec)
         record = None
+        if eng.constrain is not None:                            # (an engine passed in with the flag, no automata: its rows are unconstrained)
+            eng.set_constraint(dfas)                             # validates before anything changes; every row at its start state
         if settings is not None:
             eng.set_sampling(**settings)
             if eng.logits_process:                               # (an engine passed in with the flag, neutral keys: its processors are switched off)
@@ -2091,16 +2251,27 @@ def _generate_rows(what, eng, prompts, into, max_new_tokens, eos_token_id, setti
         else:
             graph = eng.graph_for('greedy_rows')
         logits = into(eng)
+        if dfas is not None:                                     # the first token under the start states (behind the processors, ahead of the draw)
+            logits = logits.to(torch.float16).contiguous()
         if settings is None:
+            if dfas is not None:
+                eng.constrain_logits(logits)
             first = logits.argmax(dim=-1)
         else:
             logits = logits.to(torch.float16).contiguous()
             if eng.logits_process:
                 eng.process_logits(logits)
+            if dfas is not None:
+                eng.constrain_logits(logits)
             first = eng.sample_logits(logits)
         if logprobs is not None:                                 # the first token's record, from the logits it was drawn from
             head = eng.token_logprobs(logits.to(torch.float16).contiguous(), first, top=logprobs)
         gen = _self_feeding_tail(eng, graph, first, max_new_tokens, eos_token_id, record).t()      # [row][step]
+        if dfas is not None:                                     # ONE look at the states: a row that consumed a token its state bans is at -2
+            left = [b for b, s in enumerate(eng.c_state.tolist()) if s == -2]
+            if left:
+                raise RuntimeError('%s: row %s left its automaton: every token its state allows was banned by another setting (logit_bias, '
+                                   'min_new_tokens), so the draw fell on a banned one' % (what, ', '.join(str(b) for b in left)))
         gens = [_cut_after_eos(g, eos_token_id) for g in gen]
         if logprobs is None:
             return gens
@@ -2113,7 +2284,7 @@ def _generate_rows(what, eng, prompts, into, max_new_tokens, eos_token_id, setti
 
 
 def engine_generate(model, input_ids, max_new_tokens, eos_token_id=None, engine=None, t_max=2048, prefill='hf', sample=None, speculate=None,
-                    logprobs=None):
+                    logprobs=None, constrain=None):
     """Generation for ONE prompt ([1, T] ids) on the DecodeEngine: the prompt enters the engine's static cache, the first token is chosen from
     its logits, and every further token is ONE hipGraph replay of a self-feeding step; the host looks at the stream every 16 tokens only.
     Returns the full sequence [1, prompt + generated], cut after the first eos_token_id.  The reference equivalent is
@@ -2152,6 +2323,18 @@ def engine_generate(model, input_ids, max_new_tokens, eos_token_id=None, engine=
     gptq_logprobs_rows_f16, one more launch per step of the captured graph (DecodeEngine(logprobs=K)).  The probabilities are the MODEL's,
     from the logits the draw sees: behind the logit processors, before temperature / top-k / top-p.  Greedy, sample= and the processor keys
     all record; an engine passed in must have been built with logprobs >= K.
+    constrain = a quant.constrain.TokenDFA (from_regex, from_sequences, from_table) makes the GENERATED tokens a word of its language -- the
+    prompt is not part of the constrained text --: DecodeEngine.set_constraint puts the row at the start state, constrain_logits masks the first
+    logits behind the processors and ahead of argmax / sample_logits, and every replay of the usual graphs advances the state by the token it
+    consumes and masks its logits in one more launch (gptq_constrain_rows_f16).  An automaton whose accepting states lead eos to a FINAL state
+    that allows only eos (from_regex, from_sequences) emits eos there, and the sequence is cut as always when that is eos_token_id.
+    engine=None builds the engine with capacities taken from the automaton; an engine passed in must have been built with constrain= and hold
+    it.  With logprobs, the records are those of the constrained distribution: banned tokens have -inf.  After the run the states are read
+    once: RuntimeError naming the row that left its automaton (-2) -- the CALLER's error: logit_bias or min_new_tokens banned every token its
+    state allowed, so the draw fell on a banned one.  None (the default) is exactly the call without the argument -- and on an engine passed
+    in that was built with constrain= it means UNCONSTRAINED: the call replaces whatever automata an earlier set_constraint left on that
+    engine by none (every row at -1), as the processor keys left out switch the processors off; set them again afterwards, or pass them
+    here.  ValueError together with speculate= (not built yet) and for an engine without the flag.
     ValueError: logprobs together with speculate, on a beam-search engine, outside 0 .. 32, or on an engine built with a smaller K or none;
     speculate together with the sample ARGUMENT; k outside 1 .. 15; an engine passed in whose chunk is not k + 1 or whose batch is
     not 1; unknown keys; draft together with draft_model; a draft model of another vocabulary size; a prompt that is not [1, T]; prompt +
@@ -2161,6 +2344,7 @@ def engine_generate(model, input_ids, max_new_tokens, eos_token_id=None, engine=
         raise ValueError("engine_generate: prefill must be 'hf' or 'engine', not %r" % (prefill,))
     settings, proc, spec = _generation_settings(what, model, sample, speculate, engine)
     logprobs = _logprobs_setting(what, logprobs, speculate, engine)
+    dfas = _constrain_setting(what, constrain, 1, speculate, engine)
     if spec is not None and engine is not None and (engine.batch != 1 or engine.chunk != spec[0] + 1):
         raise ValueError('engine_generate: speculate k = %d needs an engine of batch 1 with chunk = %d (this one: batch %d, chunk %d)' % (
             spec[0], spec[0] + 1, engine.batch, engine.chunk))
@@ -2171,7 +2355,7 @@ def engine_generate(model, input_ids, max_new_tokens, eos_token_id=None, engine=
     elif spec is not None:
         eng = DecodeEngine(model, t_max=t_max, chunk=spec[0] + 1)
     else:
-        eng = DecodeEngine(model, t_max=t_max, logits_process=proc is not None, logprobs=logprobs)
+        eng = DecodeEngine(model, t_max=t_max, logits_process=proc is not None, logprobs=logprobs, constrain=_constrain_capacity(dfas))
     if input_ids.shape[1] + max_new_tokens > eng.t_max:
         raise ValueError('engine_generate: prompt + max_new_tokens exceeds the engine cache (%d)' % eng.t_max)
     if settings is not None and eng.batch != 1:
@@ -2179,7 +2363,8 @@ def engine_generate(model, input_ids, max_new_tokens, eos_token_id=None, engine=
 
     def into(e):                                                 # (a draft model's engine takes the prompt by its own prefill)
         return _prompt_into_engine(model, input_ids, e, prefill if e is eng else 'engine').reshape(1, -1)
-    out = _generate_rows(what, eng, [input_ids[0]], into, max_new_tokens, eos_token_id, settings, proc, spec, one_prompt=True, logprobs=logprobs)
+    out = _generate_rows(what, eng, [input_ids[0]], into, max_new_tokens, eos_token_id, settings, proc, spec, one_prompt=True, logprobs=logprobs,
+                         dfas=dfas)
     gen = (out if logprobs is None else out[0])[0]
     if spec is not None:                                         # one sequence: emitted as an int, accepted as the flat per-step list
         eng.spec_stats = dict(eng.spec_stats, emitted=eng.spec_stats['emitted'][0], accepted=eng.spec_stats['accepted'][0])
@@ -2189,7 +2374,8 @@ def engine_generate(model, input_ids, max_new_tokens, eos_token_id=None, engine=
     return seq, {k: v.to(input_ids.device) for k, v in out[1][0].items()}
 
 
-def engine_generate_batch(model, prompts, max_new_tokens, eos_token_id=None, engine=None, t_max=2048, sample=None, speculate=None, logprobs=None):
+def engine_generate_batch(model, prompts, max_new_tokens, eos_token_id=None, engine=None, t_max=2048, sample=None, speculate=None, logprobs=None,
+                          constrain=None):
     """engine_generate for a LIST of prompts of different lengths (1-D id tensors): the same driver, arguments and ValueErrors, and what differs:
     all prompts enter through ONE DecodeEngine.prefill_batch (there is no prefill= route: nothing of `transformers` is involved, and the
     prompts are pad-free, so every row's history is its own prompt and tokens); a step is one replay for all rows, and a row that has emitted
@@ -2203,11 +2389,15 @@ def engine_generate_batch(model, prompts, max_new_tokens, eos_token_id=None, eng
     spec_sample=True (capture_verify_sample_batch: gptq_spec_sample_batch_f16 on all sequences in one launch).
     logprobs = K: returns (list of sequences, list of info dicts), one dict per prompt as engine_generate's, each as long as that row's generated
     tokens.
+    constrain = one TokenDFA for all prompts or a list with one per prompt, None for a prompt that stays unconstrained: rows that pass the same
+    object share its states.  A row that has reached its FINAL state keeps emitting eos and disturbs no other row.  As in engine_generate,
+    the call REPLACES the automata of an engine passed in, also by none where constrain is None.
     ValueError also: an engine passed in whose batch is not len(prompts) or whose batch_chunk is not k + 1, or that lacks spec_sample where it
     is needed; an empty list or prompt; max_new_tokens below 1."""
     what = 'engine_generate_batch'
     settings, proc, spec = _generation_settings(what, model, sample, speculate, engine)
     logprobs = _logprobs_setting(what, logprobs, speculate, engine)
+    dfas = _constrain_setting(what, constrain, len(prompts), speculate, engine)
     sampled = spec is not None and (spec[3] is not None or spec[4] is not None)
     if sampled and engine is not None and not engine.spec_sample:
         raise ValueError('engine_generate_batch: speculate with sample or draft_model needs an engine built with spec_sample=True')
@@ -2225,13 +2415,13 @@ def engine_generate_batch(model, prompts, max_new_tokens, eos_token_id=None, eng
     elif spec is not None:
         eng = DecodeEngine(model, t_max=t_max, batch=n, batch_chunk=spec[0] + 1, spec_sample=sampled)
     else:
-        eng = DecodeEngine(model, t_max=t_max, batch=n, logits_process=proc is not None, logprobs=logprobs)
+        eng = DecodeEngine(model, t_max=t_max, batch=n, logits_process=proc is not None, logprobs=logprobs, constrain=_constrain_capacity(dfas))
     if eng.batch != n:
         raise ValueError('engine_generate_batch: %d prompts for an engine of batch %d' % (n, eng.batch))
     if max(int(p.numel()) for p in prompts) + max_new_tokens > eng.t_max:
         raise ValueError('engine_generate_batch: prompt + max_new_tokens exceeds the engine cache (%d)' % eng.t_max)
     out = _generate_rows(what, eng, prompts, lambda e: e.prefill_batch(prompts, starts=[0] * n), max_new_tokens, eos_token_id, settings, proc, spec,
-                         logprobs=logprobs)
+                         logprobs=logprobs, dfas=dfas)
     gens = out if logprobs is None else out[0]
     seqs = [torch.cat([p, g.to(device=p.device, dtype=p.dtype)]) for p, g in zip(prompts, gens)]
     if logprobs is None:
@@ -2240,7 +2430,7 @@ def engine_generate_batch(model, prompts, max_new_tokens, eos_token_id=None, eng
 
 
 def engine_generate_beam(model, input_ids, max_new_tokens, num_beams=4, eos_token_id=None, length_penalty=1.0, early_stopping=False,
-                         num_return_sequences=1, engine=None, t_max=2048, prefill='engine'):
+                         num_return_sequences=1, engine=None, t_max=2048, prefill='engine', constrain=None):
     """Beam search for ONE prompt ([1, T] ids) on the DecodeEngine, by HF's rule (`generate(num_beams=N, do_sample=False)` with at most one EOS id
     and no logit processors; gptq_mi355x.h "beam search"): the prompt enters cache row 0 (prefill: 'engine' or 'hf', as engine_generate), beam_begin
     chooses the N first tokens and replicates the prompt's cache rows, and every further step is ONE replay of the capture_beam_step graph -- the
@@ -2249,8 +2439,11 @@ def engine_generate_beam(model, input_ids, max_new_tokens, num_beams=4, eos_toke
     length-penalised scores (HF's sequences_scores).  engine=None builds DecodeEngine(model, t_max, batch=num_beams, beam_search=True).
     ValueError: a prompt that is not [1, T]; num_beams outside 2 .. 16; an engine whose batch is not num_beams or that lacks beam_search;
     num_return_sequences outside 1 .. num_beams; more than one EOS id; prompt + max_new_tokens beyond the cache; a vocabulary below 2 num_beams;
-    a row of logits that was not finite (the state's status word) -- raised after the run."""
+    a row of logits that was not finite (the state's status word) -- raised after the run; constrain= other than None: constraints for beams
+    are not built yet (a beam's state would have to move with its cache row)."""
     what = 'engine_generate_beam'
+    if constrain is not None:
+        raise ValueError('%s: constrain together with beam search is not built yet' % what)
     if prefill not in ('hf', 'engine'):
         raise ValueError("%s: prefill must be 'hf' or 'engine', not %r" % (what, prefill))
     if input_ids.dim() != 2 or input_ids.shape[0] != 1 or input_ids.shape[1] < 1:

@@ -813,6 +813,45 @@ int gptq_logits_process_f16(void *logits, int64_t ld, int seqs, int rows, int vo
                             const float *presence_penalty, const int32_t *min_new_tokens, const int32_t *eos_ids, int n_eos,
                             const int32_t *bias_ids, const float *bias_vals, int n_bias, gptq_stream_t stream);
 
+/* ---- constrained decoding: a deterministic automaton over TOKENS in device memory, one state word per sequence, and ONE launch per step
+ * (csrc/constrain.hip), grid (B), one workgroup per sequence b, that advances state[b] by the token the step consumed and sets the logits of every
+ * token the NEW state does not allow to fp16 -inf (0xFC00), IN PLACE, ahead of the draw.  Every table is in device memory at a fixed address: a
+ * captured graph serves any automaton.  No arithmetic, no atomics, no workspace: the same inputs give the same bits on every call.
+ * (tests/constrain_ref.py restates the rules in numpy; quant/constrain.py builds the tables.)
+ *   logits [B, vocab] (ld)        fp16, in place; 2-byte alignment only, ld >= vocab; elements vocab .. ld - 1 of a row are never touched.  Rows
+ *                                 whose base is 16-byte aligned -- together with their class map's row -- are swept with 16-byte accesses
+ *   next [n_states, n_classes]    device int16 (ld_next >= n_classes): next[s][c] = the state behind a token of class c in state s; an entry
+ *                                 outside [0, n_states) -- -1 by convention -- says the token is not allowed
+ *   cls [n_maps, vocab]           device int16 (ld_cls >= vocab): class maps; cls[m][v] = the class of token v; a class outside [0, n_classes)
+ *                                 says the token is never allowed
+ *   map_of                        device int32 [B]: the class map of sequence b
+ *   state                         device int32 [B], read AND written: >= 0 a state, -1 the row is unconstrained, -2 the row has LEFT its automaton
+ *   last                          device int64 [B] or NULL: the tokens consumed by THIS step
+ *   len, len_add, t_limit         device int64 [B] and two scalars: n_b = len[b] + len_add
+ * The rules of row b, in order:
+ *   1 idle         n_b < 0 or n_b > t_limit: nothing is written, and neither the logits nor the tables are read (finished rows of a batch, an
+ *                  exhausted cache: the rule of the logit processors)
+ *   2 switched off s = state[b] < 0: nothing is written, the row keeps its bits
+ *   3 advance      with `last`: s' = next[s][cls[map_of[b]][last[b]]]
+ *   4 left         s' = -2 when last[b] lies outside [0, vocab), its class outside [0, n_classes), or the entry outside [0, n_states); also --
+ *                  with or without `last` -- when s >= n_states or map_of[b] lies outside [0, n_maps).  state[b] = -2 is stored and the row's
+ *                  logits are left untouched: garbage in the tables, or a garbage token, never causes an out-of-range read
+ *   5 no token     without `last`: s' = s, and state[b] is not written
+ *   6 publish      with `last`: state[b] = s'
+ *   7 mask         every v in [0, vocab) whose class lies outside [0, n_classes), or whose entry next[s'][class] lies outside [0, n_states),
+ *                  becomes 0xFC00; every other element keeps its bits exactly (NaN, +-inf and -0.0 included)
+ * One workgroup per sequence because it reads and writes state[b]: no second workgroup may read the word this one stores.
+ * Validated before the launch: GPTQ_E_NULL first (any pointer but `last`), GPTQ_E_SHAPE (B < 1, B > GPTQ_CONSTRAIN_MAX_SEQS, vocab < 1,
+ * ld < vocab, n_states outside 1 .. GPTQ_CONSTRAIN_MAX_STATES, n_classes outside 1 .. GPTQ_CONSTRAIN_MAX_CLASSES -- the staged row is 32 KiB of
+ * LDS there --, ld_next < n_classes, ld_cls < vocab, n_maps < 1), GPTQ_E_ALIGN (logits and the int16 tables 2 bytes, int32 arrays 4, int64
+ * arrays 8). */
+#define GPTQ_CONSTRAIN_MAX_SEQS 65535
+#define GPTQ_CONSTRAIN_MAX_STATES 32767
+#define GPTQ_CONSTRAIN_MAX_CLASSES 16384
+int gptq_constrain_rows_f16(void *logits, int64_t ld, int seqs, int vocab, const int16_t *next, int64_t ld_next, int n_states, int n_classes,
+                            const int16_t *cls, int64_t ld_cls, int n_maps, const int32_t *map_of, int32_t *state, const int64_t *last,
+                            const int64_t *len, int64_t len_add, int64_t t_limit, gptq_stream_t stream);
+
 /* ---- beam search: one step of HF's `_beam_search` (one prompt, do_sample=False, at most one EOS id, no logit processors) on N = `beams` rows
  * of fp16 logits, every piece of bookkeeping in ONE device block, and the in-place move of K/V histories between cache rows (csrc/beam.hip;
  * tests/beam_ref.py restates the rule in float64).
