@@ -971,6 +971,40 @@ int gptq_decode_attn_splits(int batch, int heads, int head_dim, int t_max) {
     return decode_attn_grid_splits(heads, t_max, batch);
 }
 
+/* the fp8 KV cache (csrc/decode_attn_kv8.hip): gptq_decode_attn_batch_f16 over e4m3 bytes + one exponent per (token, head), and the conversion of
+ * fp16 cache rows into that format.  Checks in the order of the siblings: NULL, SHAPE, ALIGN (, WORKSPACE). */
+int gptq_decode_attn_batch_kv8_f16(const void *qkv, int64_t ldq, const int64_t *positions, void *k8, void *v8, void *kexp, void *vexp, void *out,
+                                   int64_t ldo, void *workspace, size_t workspace_bytes, int batch, int heads, int head_dim, int t_max, float base,
+                                   float scale, const float *rope_table, const int32_t *out_perm, int tokens_per_split, gptq_stream_t stream) {
+    if (!qkv || !positions || !k8 || !v8 || !kexp || !vexp || !out || !workspace) return GPTQ_E_NULL;
+    if (out_perm && !aligned(out_perm, 4)) return GPTQ_E_ALIGN;
+    if (batch <= 0 || batch > 65535 || heads <= 0 || head_dim != 128 || t_max <= 0 || ldq < 3 * (int64_t)heads * head_dim || ldo < (int64_t)heads * head_dim ||
+        ((int64_t)t_max + 1024) * heads * head_dim > INT32_MAX)        // byte offsets of a slice (two tiles past its end included) are 32-bit
+        return GPTQ_E_SHAPE;
+    if (!aligned(qkv, 16) || !aligned(k8, 16) || !aligned(v8, 16) || !aligned(workspace, 16) || (rope_table && !aligned(rope_table, 8)) || ldq % 8 != 0 ||
+        ldo % 8 != 0 || !aligned(out, 2) || !aligned(positions, 8))
+        return GPTQ_E_ALIGN;
+    if (workspace_bytes < decode_attn_ws_bytes(heads, t_max, batch)) return GPTQ_E_WORKSPACE;
+    return decode_attn_kv8_launch((const half_t *)qkv, positions, (uint8_t *)k8, (uint8_t *)v8, (int8_t *)kexp, (int8_t *)vexp, (half_t *)out,
+                                  (float *)workspace, heads, t_max, base, scale, rope_table, (hipStream_t)stream, batch, ldq, ldo, out_perm,
+                                  tokens_per_split);
+}
+
+int gptq_kv8_store_f16(const void *k16, const void *v16, int64_t slot_stride, const gptq_prompt_seg_t *segs, int nseq, void *k8, void *v8, void *kexp,
+                       void *vexp, int heads, int head_dim, int t_max, gptq_stream_t stream) {
+    if (!k16 || !v16 || !segs || !k8 || !v8 || !kexp || !vexp) return GPTQ_E_NULL;
+    if (nseq < 1 || nseq > GPTQ_PROMPT_ATTN_MAX_SEQS || heads <= 0 || heads > 65535 || head_dim != 128 || t_max <= 0 ||
+        slot_stride < (int64_t)t_max * heads * head_dim)
+        return GPTQ_E_SHAPE;
+    for (int i = 0; i < nseq; i++) {
+        const gptq_prompt_seg_t &a = segs[i];
+        if (a.rows <= 0 || a.start < 0 || (int64_t)a.start + a.rows > t_max || a.slot < 0) return GPTQ_E_SHAPE;
+    }
+    if (!aligned(k16, 16) || !aligned(v16, 16) || !aligned(k8, 16) || !aligned(v8, 16) || slot_stride % 8 != 0) return GPTQ_E_ALIGN;
+    return kv8_store_launch((const half_t *)k16, (const half_t *)v16, slot_stride, segs, nseq, (uint8_t *)k8, (uint8_t *)v8, (int8_t *)kexp,
+                            (int8_t *)vexp, heads, t_max, (hipStream_t)stream);
+}
+
 /* a PROMPT chunk: `rows` consecutive tokens of one sequence at positions start .. start + rows - 1 (csrc/prompt_attn.hip).  start is a host value:
  * prefill is not graph-captured.  rows may exceed t_max: the packed rows of gptq_prompt_attn_batch_f16 are those of up to 16 sequences. */
 size_t gptq_prompt_attn_workspace_bytes(int rows, int heads, int head_dim, int t_max) {

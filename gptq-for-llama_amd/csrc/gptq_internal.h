@@ -262,6 +262,15 @@ int decode_attn_grid_splits(int heads, int t_max, int batch);   // S of the laun
 int decode_attn_tps(bool rec);                                  // default tokens per split of the mode
 int rope_table_launch(float *table, int t_max, int head_dim, float base, hipStream_t s);
 
+// decode_attn_kv8.hip: decode_attn_fused_launch (rec = false) over the fp8 cache k8 / v8 [batch][t_max][heads * 128] e4m3 bytes with kexp / vexp
+// [batch][t_max][heads] exponents; the same workspace.  tps <= 0: the default of the non-record mode
+int decode_attn_kv8_launch(const half_t *qkv, const int64_t *pos, uint8_t *k8, uint8_t *v8, int8_t *kexp, int8_t *vexp, half_t *out, float *ws,
+                           int heads, int t_max, float base, float scale, const float *rope_table, hipStream_t s, int batch, int64_t ldq,
+                           int64_t ldo, const int32_t *out_perm, int tps);
+// rows [start, start + rows) of slot `slot` of every segment (HOST array, copied into the launch arguments): fp16 cache -> fp8 cache, one launch
+int kv8_store_launch(const half_t *k16, const half_t *v16, int64_t slot_stride, const gptq_prompt_seg_t *segs, int nseq, uint8_t *k8, uint8_t *v8,
+                     int8_t *kexp, int8_t *vexp, int heads, int t_max, hipStream_t s);
+
 // prompt_attn.hip: RoPE + cache append of `rows` tokens at positions start .. start + rows - 1, then causal attention over cache rows [0, start + rows);
 // ws = prompt_attn_ws_bytes(rows, heads) bytes (the rotated q)
 size_t prompt_attn_ws_bytes(int rows, int heads);

@@ -159,6 +159,12 @@ _SIGNATURES = {
     # ... of up to 16 segments (a HOST array of PromptSeg) of one packed qkv / out and one cache allocation
     'gptq_prompt_attn_batch_f16': [c_void_p, c_int64, c_int, ctypes.POINTER(PromptSeg), c_int, c_void_p, c_void_p, c_int64, c_void_p, c_int64,
                                    c_void_p, c_size_t, c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p],
+    # fp8 KV cache: the batch decode attention over e4m3 bytes + per-(token, head) exponents, and fp16 cache rows -> that format for the
+    # segments of a prompt call (csrc/decode_attn_kv8.hip)
+    'gptq_decode_attn_batch_kv8_f16': [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_size_t,
+                                       c_int, c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p, c_int, c_void_p],
+    'gptq_kv8_store_f16': [c_void_p, c_void_p, c_int64, ctypes.POINTER(PromptSeg), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                           c_void_p],
     # speculative decoding: a chunk of consecutive tokens of one sequence, the position in device memory (csrc/chunk_attn.hip)
     'gptq_decode_attn_chunk_workspace_bytes': [c_int, c_int, c_int, c_int],
     'gptq_decode_attn_chunk_splits': [c_int, c_int, c_int, c_int],

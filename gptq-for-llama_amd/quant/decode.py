@@ -220,8 +220,19 @@ def lm_head_logits(eng, x, logits, s, h=None):
 class DecodeEngine:
 
     def __init__(self, model, t_max=2048, fuse_norm=True, fuse_attn=True, batch=1, chunk=0, batch_chunk=0, spec_sample=False, logits_process=False, beam_search=False,
-                 logprobs=None, constrain=None):
-        """constrain = True (dict(states=4096, classes=1024)) or a dict of those two capacities adds CONSTRAINED DECODING for regular languages
+                 logprobs=None, constrain=None, kv_cache='fp16'):
+        """kv_cache = 'fp8' keeps the K/V cache in the FP8 format of gptq_mi355x.h "fp8 KV cache": k8b / v8b uint8 [layers, B, t_max, H] (OCP
+        e4m3fn bytes) with kexpb / vexpb int8 [layers, B, t_max, heads] (one power-of-two exponent per token and head) -- half the bytes a decode
+        step streams at depth, half the memory; kcb / vcb do not exist.  Every batch size, 1 included, steps through _step_rows with
+        gptq_decode_attn_batch_kv8_f16, which rotates, quantises, attends to and appends the new token in one launch; the batch-1 route whose
+        attention records are merged by o_proj's kernel is not built for fp8 (profiles/kv_fp8/README.md has what that costs at short context).
+        prefill / prefill_batch run the fp16 prompt attention on ONE layer's worth of fp16 staging (kst / vst [B, t_max, H]) -- the prompt
+        attends to its unquantised rows -- and gptq_kv8_store_f16 converts the rows they appended, layer by layer.  Everything behind the logits
+        (greedy, sampling, processors, log-probabilities, constraints, every capture helper) is unchanged.  ValueError('... not built yet')
+        before anything is allocated: together with chunk, batch_chunk, beam_search or fuse_attn=False; and, before anything changes, from
+        prefill / prefill_batch with a start other than 0 or a prompt that needs more than one max_rows pass, and from score / score_batch.
+        'fp16' (the default) allocates and launches exactly what it always did.
+        constrain = True (dict(states=4096, classes=1024)) or a dict of those two capacities adds CONSTRAINED DECODING for regular languages
         (gptq_constrain_rows_f16, gptq_mi355x.h "constrained decoding"; quant/constrain.py builds the automata): c_next int16 [states, classes]
         filled with -1, c_cls int16 [B, vocab] -- one class-map slot per row --, c_map int32 [B], c_state int32 [B], all -1 (unconstrained).  One
         more launch per step, directly behind the processors' and ahead of the draw: it advances every row's state by the token the step
@@ -311,6 +322,12 @@ class DecodeEngine:
                                  'verify step, of a beam)')
             self.constrain = cap
         self.fuse_norm, self.fuse_attn = bool(fuse_norm), bool(fuse_attn)
+        if kv_cache not in ('fp16', 'fp8'):
+            raise ValueError("DecodeEngine: kv_cache must be 'fp16' or 'fp8', not %r" % (kv_cache,))
+        self.kv_cache = kv_cache
+        if kv_cache == 'fp8' and (self.chunk or self.batch_chunk or self.beam_search or not self.fuse_attn):
+            raise ValueError("DecodeEngine: kv_cache='fp8' together with chunk / batch_chunk / beam_search / fuse_attn=False is not built yet (the "
+                             "fp8 cache has the fused decode attention and the prompt store, nothing else)")
         self.native = _native
         self.lib = _native.lib()
         self.model = model
@@ -384,9 +401,15 @@ class DecodeEngine:
             self.c_state = torch.full((B,), -1, dtype=torch.int32, device=dev)
             self._c_dfas, self._c_start = [None] * B, [-1] * B       # the rows' automata and start states, as set_constraint left them
         nl = len(self.layers)
-        self.kcb = torch.zeros((nl, B, self.t_max, H), **f16)          # [layer][row][t][heads * head_dim]
-        self.vcb = torch.zeros((nl, B, self.t_max, H), **f16)
-        self.kc, self.vc = self.kcb[:, 0], self.vcb[:, 0]              # row 0 = THE cache of a batch-1 engine ([layer][t][H] views)
+        if self.kv_cache == 'fp8':
+            u8, i8 = dict(dtype=torch.uint8, device=dev), dict(dtype=torch.int8, device=dev)
+            self.k8b, self.v8b = torch.zeros((nl, B, self.t_max, H), **u8), torch.zeros((nl, B, self.t_max, H), **u8)      # e4m3fn bytes
+            self.kexpb, self.vexpb = torch.zeros((nl, B, self.t_max, self.heads), **i8), torch.zeros((nl, B, self.t_max, self.heads), **i8)
+            self.kst, self.vst = torch.zeros((B, self.t_max, H), **f16), torch.zeros((B, self.t_max, H), **f16)          # ONE layer of fp16 staging
+        else:
+            self.kcb = torch.zeros((nl, B, self.t_max, H), **f16)          # [layer][row][t][heads * head_dim]
+            self.vcb = torch.zeros((nl, B, self.t_max, H), **f16)
+            self.kc, self.vc = self.kcb[:, 0], self.vcb[:, 0]              # row 0 = THE cache of a batch-1 engine ([layer][t][H] views)
         self.attn_ws = torch.zeros(self.lib.gptq_decode_attn_batch_workspace_bytes(B, self.heads, self.head_dim, self.t_max),
                                    dtype=torch.uint8, device=dev)
         self.ws = _native.workspace(dev)
@@ -407,10 +430,10 @@ class DecodeEngine:
         self.scratch = None
         self._rope_tabs, self._prefill_bufs, self._nll_ws = {}, None, None      # filled on first use: _rope_table, _prefill_buffers, _nll_rows
         # batch 1: the attention's splits are merged by o_proj's decode kernel when every o_proj can (trivial g_idx, an image, no bias next to the residual)
-        self.attn_records = bool(ATTN_RECORDS and self.fuse_attn and B == 1 and all(
+        self.attn_records = bool(ATTN_RECORDS and self.fuse_attn and B == 1 and self.kv_cache == 'fp16' and all(
             L['o']['st'] is not None and L['o']['bias'] is None and
             self.lib.gptq_layer_decode_attn_supported(L['o']['_keep'].handle, 1, self.heads, self.head_dim) == 1 for L in self.layers))
-        if B > 1:
+        if B > 1 or self.kv_cache == 'fp8':                        # (an fp8 engine steps through _step_rows at every batch size)
             self.scratch = self._rows_scratch('batch', (B,))
         self.verify_graph, self.verify_sample_graphs, self.spec_stats = None, {}, None
         self.draft_graph, self._draft_engine = None, None          # capture_draft_step (a draft engine) / (draft model, its engine) of a target engine
@@ -651,18 +674,28 @@ class DecodeEngine:
         lm_head_logits(self, x, logits, s, h)
 
     def _step_batch(self):
-        """a decode batch: _step_rows at M = batch, gptq_decode_attn_batch_f16 on every row's own cache slice and position"""
+        """a decode batch: _step_rows at M = batch, gptq_decode_attn_batch_f16 on every row's own cache slice and position (an fp8 engine:
+        gptq_decode_attn_batch_kv8_f16 on its bytes and exponents, at every batch size)"""
+        def attn8(li, L, qkvb, ab, tab, s):
+            rc = self.lib.gptq_decode_attn_batch_kv8_f16(qkvb.data_ptr(), qkvb.stride(0), self.pos.data_ptr(), self.k8b[li].data_ptr(),
+                                                         self.v8b[li].data_ptr(), self.kexpb[li].data_ptr(), self.vexpb[li].data_ptr(),
+                                                         ab.data_ptr(), ab.stride(0), self.attn_ws.data_ptr(), self.attn_ws.numel(), self.batch,
+                                                         self.heads, self.head_dim, self.t_max, L['theta'], self.scale, self.native.ptr(tab), None,
+                                                         0, s)
+            self.native.check(rc, 'gptq_decode_attn_batch_kv8_f16')
+
         def attn(li, L, qkvb, ab, tab, s):
             rc = self.lib.gptq_decode_attn_batch_f16(qkvb.data_ptr(), qkvb.stride(0), self.pos.data_ptr(), self.kcb[li].data_ptr(),
                                                      self.vcb[li].data_ptr(), ab.data_ptr(), ab.stride(0), self.attn_ws.data_ptr(),
                                                      self.attn_ws.numel(), self.batch, self.heads, self.head_dim, self.t_max, L['theta'],
                                                      self.scale, self.native.ptr(tab), None, s)
             self.native.check(rc, 'gptq_decode_attn_batch_f16')
-        self._step_rows(dict(x=self.x, x2=self.x2, h=self.h, qkv=self.qkvb, ab=self.ab, cb=self.cb), self.ids, attn, self.logits)
+        self._step_rows(dict(x=self.x, x2=self.x2, h=self.h, qkv=self.qkvb, ab=self.ab, cb=self.cb), self.ids,
+                        attn8 if self.kv_cache == 'fp8' else attn, self.logits)
         self.pos.add_(1)
 
     def _step(self):
-        if self.batch > 1:
+        if self.batch > 1 or self.kv_cache == 'fp8':
             return self._step_batch()
         lib, ptr = self.lib, self.native.ptr
         s = torch.cuda.current_stream(self.dev).cuda_stream
@@ -1309,6 +1342,15 @@ class DecodeEngine:
         self.pos.index_copy_(0, rows_t, torch.tensor(pos, dtype=torch.int64, device=self.dev))
         return self.logits[rows_t]
 
+    def _kv8_store(self, li, table, nseq, s):
+        """an fp8 engine: the rows of the segments `table` (a PromptSeg array: rows start .. start + rows - 1 of cache row slot) of the fp16 staging
+        cache kst / vst -> layer li of the fp8 cache (gptq_kv8_store_f16, one launch)"""
+        with self.native.on_device(self.dev):
+            rc = self.lib.gptq_kv8_store_f16(self.kst.data_ptr(), self.vst.data_ptr(), self.kst.stride(0), table, nseq, self.k8b[li].data_ptr(),
+                                             self.v8b[li].data_ptr(), self.kexpb[li].data_ptr(), self.vexpb[li].data_ptr(), self.heads,
+                                             self.head_dim, self.t_max, s)
+        self.native.check(rc, 'gptq_kv8_store_f16')
+
     def prefill(self, input_ids, row=0, start=None):
         """Feed T tokens of ONE sequence (input_ids: int64, 1-D or [1, T]) into cache row `row` at positions start .. start + T - 1 and return
         the logits after the last of them (self.logits[row], the static buffer: clone it to keep it -- the contract of decode()).
@@ -1326,15 +1368,23 @@ class DecodeEngine:
         start = int(self.pos[row]) if start is None else int(start)
         if start < 0 or start + T > self.t_max:
             raise ValueError('DecodeEngine.prefill: positions %d .. %d do not fit the engine cache (%d)' % (start, start + T - 1, self.t_max))
+        fp8 = self.kv_cache == 'fp8'
+        if fp8 and start != 0:
+            raise ValueError("DecodeEngine.prefill: start = %d on a kv_cache='fp8' engine is not built yet (the prompt attention reads fp16 rows: "
+                             "only a whole prompt from position 0)" % start)
         with torch.no_grad(), torch.cuda.device(self.dev):
             s = self.native.stream_ptr(self.dev)
             self._prefill_buffers(T)
+            table = (self.native.PromptSeg * 1)(self.native.PromptSeg(0, T, start, row)) if fp8 else None
 
             def attn(li, L, qkv, ab, ws, tab):
-                rc = self.lib.gptq_prompt_attn_f16(qkv.data_ptr(), qkv.stride(0), T, start, self.kcb[li, row].data_ptr(), self.vcb[li, row].data_ptr(),
+                kc, vc = (self.kst[row], self.vst[row]) if fp8 else (self.kcb[li, row], self.vcb[li, row])
+                rc = self.lib.gptq_prompt_attn_f16(qkv.data_ptr(), qkv.stride(0), T, start, kc.data_ptr(), vc.data_ptr(),
                                                    ab.data_ptr(), ab.stride(0), ws.data_ptr(), ws.numel(), self.heads, self.head_dim, self.t_max,
                                                    L['theta'], self.scale, self.native.ptr(tab), s)
                 self.native.check(rc, 'gptq_prompt_attn_f16')
+                if fp8:
+                    self._kv8_store(li, table, 1, s)
             ids = ids.to(device=self.dev, dtype=torch.int64)
             x, _ = self._prompt_layers(ids, attn, s)
             if self.logits_process:
@@ -1372,6 +1422,12 @@ class DecodeEngine:
             raise ValueError('DecodeEngine.%s: max_rows must be positive' % what)
         total = sum(lens)
         offs = [sum(lens[:i]) for i in range(n)]                                    # first packed row of prompt i
+        fp8 = self.kv_cache == 'fp8'
+        if fp8 and (score or any(st != 0 for st in starts) or total > max_rows):
+            raise ValueError("DecodeEngine.%s on a kv_cache='fp8' engine is not built yet: %s" % (what, (
+                'scoring' if score else 'a start other than 0' if any(st != 0 for st in starts) else
+                '%d packed rows need more than one pass of max_rows = %d' % (total, max_rows)) +
+                ' (the prompt attention reads fp16 rows: only whole prompts from position 0 in one pass)'))
         if score:
             vocab = min(self.embed.shape[0], self.lm_head.shape[0])
             host = torch.cat([p.detach().reshape(-1).to(device='cpu', dtype=torch.int64) for p in prompts])      # a copy, not a launch
@@ -1390,7 +1446,7 @@ class DecodeEngine:
             else:
                 ids = torch.cat([p.to(device=self.dev, dtype=torch.int64) for p in prompts])
             last = torch.empty((n, self.hidden), dtype=torch.float16, device=self.dev)      # the final hidden row of every prompt
-            slot_stride = self.kcb.stride(1)
+            slot_stride = self.kst.stride(0) if fp8 else self.kcb.stride(1)
             for p0 in range(0, total, max_rows):
                 M = min(total, p0 + max_rows) - p0
                 # the part of every prompt inside packed rows [p0, p0 + M): ONE segment per prompt and pass (never two of the same cache row)
@@ -1404,11 +1460,14 @@ class DecodeEngine:
                 table = (self.native.PromptSeg * len(segs))(*segs)
 
                 def attn(li, L, qkv, ab, ws, tab):
-                    rc = self.lib.gptq_prompt_attn_batch_f16(qkv.data_ptr(), qkv.stride(0), M, table, len(segs), self.kcb[li].data_ptr(),
-                                                             self.vcb[li].data_ptr(), slot_stride, ab.data_ptr(), ab.stride(0), ws.data_ptr(),
+                    kc, vc = (self.kst, self.vst) if fp8 else (self.kcb[li], self.vcb[li])
+                    rc = self.lib.gptq_prompt_attn_batch_f16(qkv.data_ptr(), qkv.stride(0), M, table, len(segs), kc.data_ptr(),
+                                                             vc.data_ptr(), slot_stride, ab.data_ptr(), ab.stride(0), ws.data_ptr(),
                                                              ws.numel(), self.heads, self.head_dim, self.t_max, L['theta'], self.scale,
                                                              self.native.ptr(tab), s)
                     self.native.check(rc, 'gptq_prompt_attn_batch_f16')
+                    if fp8:
+                        self._kv8_store(li, table, len(segs), s)
                 x, h = self._prompt_layers(ids[p0:p0 + M], attn, s)
                 if ends:
                     dst = torch.tensor([i for i, _ in ends], dtype=torch.int64, device=self.dev)
@@ -1888,10 +1947,16 @@ def _prompt_into_engine(model, input_ids, eng, prefill):
     from transformers.cache_utils import DynamicCache
     cache = DynamicCache(config=model.config)
     out = model(input_ids, past_key_values=cache, use_cache=True)
+    fp8 = eng.kv_cache == 'fp8'
+    if fp8:                                                      # the module cache goes through the staging layer, as the engine's own prefill does
+        table, s = (eng.native.PromptSeg * 1)(eng.native.PromptSeg(0, T, 0, 0)), eng.native.stream_ptr(eng.dev)
     for li in range(len(eng.layers)):
         k, v = _cache_layer_kv(cache, li)
-        eng.kc[li, :T].copy_(k[0].transpose(0, 1).reshape(T, -1))
-        eng.vc[li, :T].copy_(v[0].transpose(0, 1).reshape(T, -1))
+        kc, vc = (eng.kst[0], eng.vst[0]) if fp8 else (eng.kc[li], eng.vc[li])
+        kc[:T].copy_(k[0].transpose(0, 1).reshape(T, -1))
+        vc[:T].copy_(v[0].transpose(0, 1).reshape(T, -1))
+        if fp8:
+            eng._kv8_store(li, table, 1, s)
     eng.pos.fill_(T)
     if eng.logits_process:
         eng.set_history(0, input_ids[0])
@@ -2217,6 +2282,17 @@ def _constrain_setting(what, constrain, n, speculate, engine):
     return dfas
 
 
+def _kv_cache_setting(what, kv_cache, speculate, engine):
+    """the kv_cache= argument of `what` (engine_generate / engine_generate_batch), validated: 'fp16' or 'fp8'; ValueError for 'fp8' under
+    speculate= and for an engine passed in of the other kind"""
+    if kv_cache not in ('fp16', 'fp8'):
+        raise ValueError("%s: kv_cache must be 'fp16' or 'fp8', not %r" % (what, kv_cache))
+    if kv_cache == 'fp8' and speculate is not None:
+        raise ValueError("%s: kv_cache='fp8' together with speculate is not built yet (the verify step's chunk attention reads an fp16 cache)" % what)
+    if engine is not None and engine.kv_cache != kv_cache:
+        raise ValueError('%s: kv_cache=%r for an engine built with kv_cache=%r' % (what, kv_cache, engine.kv_cache))
+
+
 def _constrain_capacity(dfas):
     """the constrain= argument of a DecodeEngine that holds exactly these automata (None: no flag)"""
     if dfas is None:
@@ -2284,7 +2360,7 @@ def _generate_rows(what, eng, prompts, into, max_new_tokens, eos_token_id, setti
 
 
 def engine_generate(model, input_ids, max_new_tokens, eos_token_id=None, engine=None, t_max=2048, prefill='hf', sample=None, speculate=None,
-                    logprobs=None, constrain=None):
+                    logprobs=None, constrain=None, kv_cache='fp16'):
     """Generation for ONE prompt ([1, T] ids) on the DecodeEngine: the prompt enters the engine's static cache, the first token is chosen from
     its logits, and every further token is ONE hipGraph replay of a self-feeding step; the host looks at the stream every 16 tokens only.
     Returns the full sequence [1, prompt + generated], cut after the first eos_token_id.  The reference equivalent is
@@ -2345,6 +2421,7 @@ def engine_generate(model, input_ids, max_new_tokens, eos_token_id=None, engine=
     settings, proc, spec = _generation_settings(what, model, sample, speculate, engine)
     logprobs = _logprobs_setting(what, logprobs, speculate, engine)
     dfas = _constrain_setting(what, constrain, 1, speculate, engine)
+    _kv_cache_setting(what, kv_cache, speculate, engine)
     if spec is not None and engine is not None and (engine.batch != 1 or engine.chunk != spec[0] + 1):
         raise ValueError('engine_generate: speculate k = %d needs an engine of batch 1 with chunk = %d (this one: batch %d, chunk %d)' % (
             spec[0], spec[0] + 1, engine.batch, engine.chunk))
@@ -2355,7 +2432,8 @@ def engine_generate(model, input_ids, max_new_tokens, eos_token_id=None, engine=
     elif spec is not None:
         eng = DecodeEngine(model, t_max=t_max, chunk=spec[0] + 1)
     else:
-        eng = DecodeEngine(model, t_max=t_max, logits_process=proc is not None, logprobs=logprobs, constrain=_constrain_capacity(dfas))
+        eng = DecodeEngine(model, t_max=t_max, logits_process=proc is not None, logprobs=logprobs, constrain=_constrain_capacity(dfas),
+                           kv_cache=kv_cache)
     if input_ids.shape[1] + max_new_tokens > eng.t_max:
         raise ValueError('engine_generate: prompt + max_new_tokens exceeds the engine cache (%d)' % eng.t_max)
     if settings is not None and eng.batch != 1:
@@ -2375,7 +2453,7 @@ def engine_generate(model, input_ids, max_new_tokens, eos_token_id=None, engine=
 
 
 def engine_generate_batch(model, prompts, max_new_tokens, eos_token_id=None, engine=None, t_max=2048, sample=None, speculate=None, logprobs=None,
-                          constrain=None):
+                          constrain=None, kv_cache='fp16'):
     """engine_generate for a LIST of prompts of different lengths (1-D id tensors): the same driver, arguments and ValueErrors, and what differs:
     all prompts enter through ONE DecodeEngine.prefill_batch (there is no prefill= route: nothing of `transformers` is involved, and the
     prompts are pad-free, so every row's history is its own prompt and tokens); a step is one replay for all rows, and a row that has emitted
@@ -2392,12 +2470,14 @@ def engine_generate_batch(model, prompts, max_new_tokens, eos_token_id=None, eng
     constrain = one TokenDFA for all prompts or a list with one per prompt, None for a prompt that stays unconstrained: rows that pass the same
     object share its states.  A row that has reached its FINAL state keeps emitting eos and disturbs no other row.  As in engine_generate,
     the call REPLACES the automata of an engine passed in, also by none where constrain is None.
+    kv_cache = 'fp8': as in engine_generate (the prompts enter through prefill_batch's fp16 staging and gptq_kv8_store_f16).
     ValueError also: an engine passed in whose batch is not len(prompts) or whose batch_chunk is not k + 1, or that lacks spec_sample where it
     is needed; an empty list or prompt; max_new_tokens below 1."""
     what = 'engine_generate_batch'
     settings, proc, spec = _generation_settings(what, model, sample, speculate, engine)
     logprobs = _logprobs_setting(what, logprobs, speculate, engine)
     dfas = _constrain_setting(what, constrain, len(prompts), speculate, engine)
+    _kv_cache_setting(what, kv_cache, speculate, engine)
     sampled = spec is not None and (spec[3] is not None or spec[4] is not None)
     if sampled and engine is not None and not engine.spec_sample:
         raise ValueError('engine_generate_batch: speculate with sample or draft_model needs an engine built with spec_sample=True')
@@ -2415,7 +2495,8 @@ def engine_generate_batch(model, prompts, max_new_tokens, eos_token_id=None, eng
     elif spec is not None:
         eng = DecodeEngine(model, t_max=t_max, batch=n, batch_chunk=spec[0] + 1, spec_sample=sampled)
     else:
-        eng = DecodeEngine(model, t_max=t_max, batch=n, logits_process=proc is not None, logprobs=logprobs, constrain=_constrain_capacity(dfas))
+        eng = DecodeEngine(model, t_max=t_max, batch=n, logits_process=proc is not None, logprobs=logprobs, constrain=_constrain_capacity(dfas),
+                           kv_cache=kv_cache)
     if eng.batch != n:
         raise ValueError('engine_generate_batch: %d prompts for an engine of batch %d' % (n, eng.batch))
     if max(int(p.numel()) for p in prompts) + max_new_tokens > eng.t_max:

@@ -595,6 +595,37 @@ int gptq_layer_decode_attn_f16(const gptq_layer_t *layer, const void *attn_works
                                int heads, int head_dim, int t_max, int tokens_per_split, void *y, int64_t ldy, const void *residual, int64_t ldr,
                                gptq_stream_t stream);
 
+/* ---- fp8 KV cache: the decode attention over e4m3 rows with one power-of-two exponent per (token, head) (csrc/decode_attn_kv8.hip) -------------
+ * At depth a decode step is the stream of the K/V cache (the reference grows it by torch.cat and reads all of it per token, quant/fused_attn.py:
+ * 142-155); this format halves those bytes.  One cache (K or V) of `slots` sequences is two arrays:
+ *     k8 / v8       uint8 [slot][t_max][heads * 128]   OCP e4m3fn bytes q_i
+ *     kexp / vexp   int8  [slot][t_max][heads]         one exponent e per (token, head); the stored head row means q_i * 2^e
+ * Quantising a head row r[0 .. 128) of fp16 values (for K: the bits the fp16 cache would hold -- rotated, rounded to fp16):
+ *     amax = max |r_i|;  e = 0 when amax == 0, else the smallest integer with amax * 2^-e <= 448 -- with amax = m * 2^x, m in [0.5, 1): e = x - 9
+ *     when m <= 0.875, else x - 8 -- so e lies in [-32, 8] and amax * 2^-e in (224, 448];
+ *     q_i = RNE_e4m3(r_i * 2^-e): the scaling is exact, the rounding is to nearest even (subnormals of e4m3 included) and never overflows.
+ * In PyTorch on the CPU: torch.ldexp(r.float(), -e).to(torch.float8_e4m3fn) -- that restatement (tests/kv8_ref.py) is the specification.  Rows
+ * with NaN / inf are outside the contract; they cannot fault (no index depends on data).
+ *
+ * gptq_decode_attn_batch_kv8_f16   gptq_decode_attn_batch_f16 on such a cache: out[b, h] = softmax(scale q^ K^T) V^ over rows 0 .. positions[b],
+ *     q^ the rotated fp16 query, K^ / V^ the dequantised rows INCLUDING row positions[b]: the new token is rotated, quantised, attended to in
+ *     its quantised form and appended (bytes and exponents), so a step is a function of the cache alone.  Everything else -- idle rows
+ *     (positions[b] < 0 or >= t_max: nothing read or written), the run-time split count, the deterministic merge, out_perm, the workspace of
+ *     gptq_decode_attn_batch_workspace_bytes -- is that entry's.  tokens_per_split <= 0: the library's default (one split up to 768 tokens).
+ *     Validated before the launch: GPTQ_E_NULL (any pointer but rope_table / out_perm), GPTQ_E_SHAPE (batch outside 1 .. 65535, heads < 1,
+ *     head_dim != 128, t_max < 1, (t_max + 1024) heads 128 >= 2^31, ldq < 3 heads 128, ldo < heads 128), GPTQ_E_ALIGN (qkv / k8 / v8 / workspace
+ *     16 bytes, positions and rope_table 8, out_perm 4, out 2, ldq / ldo multiples of 8), GPTQ_E_WORKSPACE.
+ * gptq_kv8_store_f16               for each of nseq <= 16 segments {row0 (ignored), rows, start, slot}: rows start .. start + rows - 1 of slot
+ *     `slot` of an fp16 cache k16 / v16 ([t_max][heads 128] per slot, slots slot_stride ELEMENTS apart) -> the same rows of the same slot of
+ *     the fp8 cache ([slot][t_max][..] dense), by the rule above.  One launch, no atomics; nothing outside the segments is written.  What the
+ *     prompt paths run behind gptq_prompt_attn_f16 / gptq_prompt_attn_batch_f16 on an fp16 staging cache.  `segs` is a HOST array, passed by
+ *     value.  GPTQ_E_NULL (any pointer), GPTQ_E_SHAPE (nseq outside 1 .. 16, heads < 1, head_dim != 128, t_max < 1, slot_stride < t_max heads
+ *     128, a segment with rows <= 0, start < 0, start + rows > t_max or slot < 0), GPTQ_E_ALIGN (k16 / v16 / k8 / v8 16 bytes, slot_stride a
+ *     multiple of 8). */
+int gptq_decode_attn_batch_kv8_f16(const void *qkv, int64_t ldq, const int64_t *positions, void *k8, void *v8, void *kexp, void *vexp, void *out,
+                                   int64_t ldo, void *workspace, size_t workspace_bytes, int batch, int heads, int head_dim, int t_max, float base,
+                                   float scale, const float *rope_table, const int32_t *out_perm, int tokens_per_split, gptq_stream_t stream);
+
 /* ---- prompt prefill: causal attention of a chunk of tokens over the decode engine's own cache (csrc/prompt_attn.hip) ----------------------------
  * Replaces, for a prompt, what QuantLlamaAttention.forward does between qkv_proj and o_proj (quant/fused_attn.py:126-158: triton_rotate_half_ on q and
  * k, torch.cat onto the past, F.scaled_dot_product_attention with is_causal) on the cache layout of the decode entries above: `rows` consecutive
@@ -628,6 +659,9 @@ typedef struct { int32_t row0, rows, start, slot; } gptq_prompt_seg_t;
 int gptq_prompt_attn_batch_f16(const void *qkv, int64_t ldq, int total_rows, const gptq_prompt_seg_t *segs, int nseq, void *k_cache,
                                void *v_cache, int64_t slot_stride, void *out, int64_t ldo, void *workspace, size_t workspace_bytes, int heads,
                                int head_dim, int t_max, float base, float scale, const float *rope_table, gptq_stream_t stream);
+/* ("fp8 KV cache" above: the rows such a call appended to an fp16 staging cache, converted into the fp8 cache) */
+int gptq_kv8_store_f16(const void *k16, const void *v16, int64_t slot_stride, const gptq_prompt_seg_t *segs, int nseq, void *k8, void *v8,
+                       void *kexp, void *vexp, int heads, int head_dim, int t_max, gptq_stream_t stream);
 
 /* ---- speculative decoding: attention of a CHUNK of a decoding sequence with the position in device memory (csrc/chunk_attn.hip) ----------------
  * Replaces what HF generate's one-token loop (llama_inference.py:109-115) does R times between qkv_proj and o_proj: `rows` (1 .. 16, a host value: it
