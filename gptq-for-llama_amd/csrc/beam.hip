@@ -2,7 +2,9 @@
 // restates the rule in float64):
 //   gptq_beam_select_f16   one beam step on N = 2 .. 16 rows of fp16 logits, TWO launches whose only hand-off is the kernel boundary -- no tickets,
 //                          no flags, no global atomics;
-//   gptq_kv_reorder_f16    cache row b of every layer continues row parent[b], in place, ONE launch.
+//   gptq_kv_reorder_f16    cache row b of every layer continues row parent[b], in place, ONE launch;
+//   gptq_beam_src_update_u8  the alternative that moves nothing: row b of the ancestry table continues row parent[b] (beam_attn.hip reads the
+//                          histories through the table), ONE workgroup.
 //
 // Launch A, one workgroup per row (passes 2 .. 4 are row_select.h's row_select, shared with logprobs.hip; what a bad row means and what is written
 // stay here): pass 1 (sample_common.h's row_top, shared with sampling) finds the row's largest key and its first NaN / +inf; pass 2 sums
@@ -304,7 +306,64 @@ __global__ __launch_bounds__(RO_NT) void kv_reorder_kernel(uint16_t *k_cache, ui
     }
 }
 
+// ---- the ancestry table of the indirect beam cache (beam_attn.hip reads it) ------------------------------------------------------------------
+// src'[b][t] = src[parent[b]][t] for t < len[0], in place, by the reorder's trick on bytes: one thread owns column t across ALL rows, loads its N
+// bytes and stores only the ones that changed -- swaps and cycles need no order.  The same ONE workgroup counts the leading columns in which all
+// N new entries are equal: every thread keeps the first column it saw that is not uniform, an LDS tree takes the minimum -- integers in a fixed
+// tree, no global atomics.
+constexpr int SU_NT = 1024;
+
+__global__ __launch_bounds__(SU_NT) void beam_src_update_kernel(uint8_t *src, int rows, int t_max, const int32_t *parent, const int64_t *len,
+                                                                int32_t *common_out) {
+    __shared__ int first[SU_NT];
+    const int n = (int)min(max(len[0], (int64_t)0), (int64_t)t_max);
+    int par[BM_MAX];
+#pragma unroll
+    for (int b = 0; b < BM_MAX; b++) {
+        int p = b < rows ? parent[b] : b;
+        if (p < 0 || p >= rows) p = b;                         // (never from gptq_beam_select_f16; no row outside the table is ever read)
+        par[b] = p;
+    }
+    int mine = n;                                              // the first column of this thread that is not uniform (columns ascend)
+    for (int t = threadIdx.x; t < n; t += SU_NT) {
+        uint8_t old[BM_MAX], now[BM_MAX];
+#pragma unroll
+        for (int b = 0; b < BM_MAX; b++) old[b] = b < rows ? src[(size_t)b * t_max + t] : 0;
+        bool same = true;
+#pragma unroll
+        for (int b = 0; b < BM_MAX; b++) {
+            uint8_t v = old[0];
+#pragma unroll
+            for (int q = 1; q < BM_MAX; q++) v = par[b] == q ? old[q] : v;      // (selects: old[] stays in registers)
+            now[b] = v;
+        }
+#pragma unroll
+        for (int b = 0; b < BM_MAX; b++)
+            if (b < rows) {
+                same = same && now[b] == now[0];
+                if (now[b] != old[b]) src[(size_t)b * t_max + t] = now[b];
+            }
+        if (!same) mine = min(mine, t);
+    }
+    first[threadIdx.x] = mine;
+    __syncthreads();
+    for (int d = SU_NT / 2; d > 0; d >>= 1) {
+        if ((int)threadIdx.x < d) first[threadIdx.x] = min(first[threadIdx.x], first[threadIdx.x + d]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) common_out[0] = first[0];
+}
+
 }  // namespace
+
+extern "C" int gptq_beam_src_update_u8(void *src, int beams, int t_max, const int32_t *parent, const int64_t *len, int32_t *common_out,
+                                       gptq_stream_t stream) {
+    if (!src || !parent || !len || !common_out) return GPTQ_E_NULL;
+    if (beams < 1 || beams > BM_MAX || t_max < 1) return GPTQ_E_SHAPE;
+    if (!aligned(parent, 4) || !aligned(len, 8) || !aligned(common_out, 4)) return GPTQ_E_ALIGN;
+    hipLaunchKernelGGL(beam_src_update_kernel, dim3(1), dim3(SU_NT), 0, (hipStream_t)stream, (uint8_t *)src, beams, t_max, parent, len, common_out);
+    return (int)hipGetLastError();
+}
 
 extern "C" size_t gptq_beam_state_bytes(int beams, int t_max) {
     if (beams < 2 || beams > BM_MAX || t_max < 1) return 0;

@@ -1103,6 +1103,35 @@ int gptq_decode_attn_chunk_batch_f16(const void *qkv, int64_t ldq, int seqs, int
                                    workspace, heads, t_max, base, scale, rope_table, (hipStream_t)stream);
 }
 
+/* the beams of ONE beam search at one device position, their histories read through the ancestry table (csrc/beam_attn.hip; the table's update
+ * is gptq_beam_src_update_u8, csrc/beam.hip) */
+size_t gptq_decode_attn_beam_ws_bytes(int beams, int heads, int t_max) {
+    if (beams < 1 || beams > 16 || heads <= 0 || heads > 65535 || t_max <= 0) return 0;
+    return beam_attn_ws_bytes(beams, heads, t_max);
+}
+
+int gptq_decode_attn_beam_splits(int heads, int head_dim, int t_max, int len) {
+    if (heads <= 0 || heads > 65535 || head_dim != 128 || t_max <= 0 || len < 1 || len > t_max) return GPTQ_E_SHAPE;
+    return beam_attn_active_splits(heads, t_max, len);
+}
+
+int gptq_decode_attn_beam_f16(const void *qkv, int64_t ldq, int beams, const int64_t *position, void *k_cache, void *v_cache, int64_t slot_stride,
+                              void *src, const int32_t *common, void *out, int64_t ldo, const int32_t *out_perm, void *workspace,
+                              size_t workspace_bytes, int heads, int head_dim, int t_max, float base, float scale, const float *rope_table,
+                              gptq_stream_t stream) {
+    if (!qkv || !position || !k_cache || !v_cache || !src || !common || !out || !workspace) return GPTQ_E_NULL;
+    if (beams < 1 || beams > 16 || heads <= 0 || heads > 65535 || head_dim != 128 || t_max <= 0 || ldq < 3 * (int64_t)heads * head_dim ||
+        ldo < (int64_t)heads * head_dim || slot_stride < (int64_t)t_max * heads * head_dim)
+        return GPTQ_E_SHAPE;
+    if (!aligned(qkv, 16) || !aligned(position, 8) || !aligned(k_cache, 16) || !aligned(v_cache, 16) || !aligned(workspace, 16) ||
+        (rope_table && !aligned(rope_table, 8)) || !aligned(common, 4) || (out_perm && !aligned(out_perm, 4)) || ldq % 8 != 0 || ldo % 8 != 0 ||
+        slot_stride % 8 != 0 || !aligned(out, 16))
+        return GPTQ_E_ALIGN;
+    if (workspace_bytes < beam_attn_ws_bytes(beams, heads, t_max)) return GPTQ_E_WORKSPACE;
+    return beam_attn_launch((const half_t *)qkv, ldq, beams, position, (half_t *)k_cache, (half_t *)v_cache, slot_stride, (uint8_t *)src, common,
+                            (half_t *)out, ldo, out_perm, workspace, heads, t_max, base, scale, rope_table, (hipStream_t)stream);
+}
+
 /* scoring (csrc/gemm8.hip, cross-entropy epilogue): everything is checked here, before the first launch */
 size_t gptq_lm_head_nll_workspace_bytes(int M, int N) {
     if (M <= 0 || N <= 0) return 0;

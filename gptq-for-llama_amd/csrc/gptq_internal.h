@@ -295,4 +295,12 @@ int chunk_attn_batch_launch(const half_t *qkv, int64_t ldq, int seqs, int rows, 
                             half_t *out, int64_t ldo, void *ws, int heads, int t_max, float base, float scale, const float *rope_table,
                             hipStream_t s);
 
+// beam_attn.hip: RoPE + append + attention of the `beams` (1..16) beams of one search at position *pos, histories read through the ancestry table
+// src [beams][t_max] (keys below *common once for all beams); ws = beam_attn_ws_bytes(beams, heads, t_max), no state
+size_t beam_attn_ws_bytes(int beams, int heads, int t_max);
+int beam_attn_active_splits(int heads, int t_max, int len);       // splits a call with len = *pos + 1 keys uses
+int beam_attn_launch(const half_t *qkv, int64_t ldq, int beams, const int64_t *pos, half_t *kc, half_t *vc, int64_t slot_stride, uint8_t *src,
+                     const int32_t *common, half_t *out, int64_t ldo, const int32_t *out_perm, void *ws, int heads, int t_max, float base,
+                     float scale, const float *rope_table, hipStream_t s);
+
 }  // namespace gptq

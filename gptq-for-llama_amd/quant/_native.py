@@ -201,6 +201,12 @@ _SIGNATURES = {
     'gptq_beam_state_bytes': [c_int, c_int],
     'gptq_beam_select_f16': [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p],
     'gptq_kv_reorder_f16': [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p],
+    # beam cache indirection: the ancestry table's update (csrc/beam.hip) and the beams' attention through the table (csrc/beam_attn.hip)
+    'gptq_beam_src_update_u8': [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
+    'gptq_decode_attn_beam_ws_bytes': [c_int, c_int, c_int],
+    'gptq_decode_attn_beam_splits': [c_int, c_int, c_int, c_int],
+    'gptq_decode_attn_beam_f16': [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
+                                  c_void_p, c_size_t, c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p],
     # token log-probabilities: the chosen token's log p and rank and the row's top K, into slot step[0] of a record ring (csrc/logprobs.hip)
     'gptq_logprobs_rows_f16': [c_void_p, c_int64, c_int, c_int, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
 }
@@ -247,6 +253,7 @@ def lib():
             L.gptq_spec_sample_workspace_bytes.restype = c_size_t
             L.gptq_spec_sample_batch_workspace_bytes.restype = c_size_t
             L.gptq_beam_state_bytes.restype = c_size_t
+            L.gptq_decode_attn_beam_ws_bytes.restype = c_size_t
             L.gptq_layer_destroy.restype = None
             L.gptq_strerror.argtypes = [c_int]
             L.gptq_strerror.restype = ctypes.c_char_p

@@ -220,8 +220,17 @@ def lm_head_logits(eng, x, logits, s, h=None):
 class DecodeEngine:
 
     def __init__(self, model, t_max=2048, fuse_norm=True, fuse_attn=True, batch=1, chunk=0, batch_chunk=0, spec_sample=False, logits_process=False, beam_search=False,
-                 logprobs=None, constrain=None, kv_cache='fp16'):
-        """kv_cache = 'fp8' keeps the K/V cache in the FP8 format of gptq_mi355x.h "fp8 KV cache": k8b / v8b uint8 [layers, B, t_max, H] (OCP
+                 logprobs=None, constrain=None, kv_cache='fp16', beam_cache='reorder'):
+        """beam_cache = 'indirect' (with beam_search=True) reads the beams' histories through an ANCESTRY TABLE instead of moving them between
+        cache rows (gptq_mi355x.h "beam cache indirection"): beam_src uint8 [N, t_max] -- beam_src[b, t] = the cache row that holds position t
+        of beam b's history --, beam_common int32 [1] -- the columns below it are equal in all rows -- and the workspace of
+        gptq_decode_attn_beam_f16, which every layer of the beam step calls instead of the batch attention (the shared trunk is streamed once
+        for all beams); _beam_advance calls gptq_beam_src_update_u8 instead of the reorder, beam_begin zeroes the table and replicates no
+        prompt row.  kcb / vcb rows are never moved -- so from beam_begin on ONLY the beam step (_beam_step, capture_beam_step) reads a beam's
+        history: rows other than row 0 are not self-contained, and _step(), decode() and the greedy / sampling captures of such an engine,
+        which attend to each row's own physical history, give meaningless results until the next prompt call.  'reorder' (the default) allocates and launches exactly what it always did.  ValueError
+        for another value, and for 'indirect' without beam_search.
+        kv_cache = 'fp8' keeps the K/V cache in the FP8 format of gptq_mi355x.h "fp8 KV cache": k8b / v8b uint8 [layers, B, t_max, H] (OCP
         e4m3fn bytes) with kexpb / vexpb int8 [layers, B, t_max, heads] (one power-of-two exponent per token and head) -- half the bytes a decode
         step streams at depth, half the memory; kcb / vcb do not exist.  Every batch size, 1 included, steps through _step_rows with
         gptq_decode_attn_batch_kv8_f16, which rotates, quantises, attends to and appends the new token in one launch; the batch-1 route whose
@@ -299,6 +308,11 @@ class DecodeEngine:
         if self.beam_search and (self.logits_process or self.chunk or self.batch_chunk or not 2 <= self.batch <= MAX_BEAMS):
             raise ValueError('DecodeEngine: beam_search needs batch = 2 .. %d beams and combines with neither logits_process, chunk nor batch_chunk'
                              % MAX_BEAMS)
+        if beam_cache not in ('reorder', 'indirect'):
+            raise ValueError("DecodeEngine: beam_cache must be 'reorder' or 'indirect', not %r" % (beam_cache,))
+        if beam_cache == 'indirect' and not self.beam_search:
+            raise ValueError("DecodeEngine: beam_cache='indirect' needs beam_search=True")
+        self.beam_cache = beam_cache
         if logprobs is not None:
             if isinstance(logprobs, bool) or not isinstance(logprobs, int) or not 0 <= logprobs <= MAX_LOGPROBS:
                 raise ValueError('DecodeEngine: logprobs must be None or an int in 0 .. %d, not %r' % (MAX_LOGPROBS, logprobs))
@@ -427,6 +441,11 @@ class DecodeEngine:
             self.beam_parent = self.beam_state[BEAM_W_PARENT:BEAM_W_PARENT + B]
             self.beam_token = self.beam_state[BEAM_W_TOKEN:BEAM_W_TOKEN + 2 * B].view(torch.int64)
             self.set_beam_search(self.t_max)
+            if self.beam_cache == 'indirect':
+                # the ancestry table, its common-prefix length and the workspace of gptq_decode_attn_beam_f16 (gptq_mi355x.h "beam cache indirection")
+                self.beam_src = torch.zeros((B, self.t_max), dtype=torch.uint8, device=dev)
+                self.beam_common = torch.zeros(1, dtype=torch.int32, device=dev)
+                self.beam_attn_ws = torch.zeros(self.lib.gptq_decode_attn_beam_ws_bytes(B, self.heads, self.t_max), dtype=torch.uint8, device=dev)
         self.scratch = None
         self._rope_tabs, self._prefill_bufs, self._nll_ws = {}, None, None      # filled on first use: _rope_table, _prefill_buffers, _nll_rows
         # batch 1: the attention's splits are merged by o_proj's decode kernel when every o_proj can (trivial g_idx, an image, no bias next to the residual)
@@ -673,9 +692,10 @@ class DecodeEngine:
                 normed = False
         lm_head_logits(self, x, logits, s, h)
 
-    def _step_batch(self):
+    def _step_batch(self, beam=False):
         """a decode batch: _step_rows at M = batch, gptq_decode_attn_batch_f16 on every row's own cache slice and position (an fp8 engine:
-        gptq_decode_attn_batch_kv8_f16 on its bytes and exponents, at every batch size)"""
+        gptq_decode_attn_batch_kv8_f16 on its bytes and exponents, at every batch size).  beam: the step of an indirect beam engine -- the rows
+        are beams at pos[0] and attend through beam_src (gptq_decode_attn_beam_f16); every other step of such an engine is the plain batch step"""
         def attn8(li, L, qkvb, ab, tab, s):
             rc = self.lib.gptq_decode_attn_batch_kv8_f16(qkvb.data_ptr(), qkvb.stride(0), self.pos.data_ptr(), self.k8b[li].data_ptr(),
                                                          self.v8b[li].data_ptr(), self.kexpb[li].data_ptr(), self.vexpb[li].data_ptr(),
@@ -690,6 +710,16 @@ class DecodeEngine:
                                                      self.attn_ws.numel(), self.batch, self.heads, self.head_dim, self.t_max, L['theta'],
                                                      self.scale, self.native.ptr(tab), None, s)
             self.native.check(rc, 'gptq_decode_attn_batch_f16')
+
+        def attn_beam(li, L, qkvb, ab, tab, s):                 # beam_cache='indirect': the rows are beams at ONE position, read through beam_src
+            rc = self.lib.gptq_decode_attn_beam_f16(qkvb.data_ptr(), qkvb.stride(0), self.batch, self.pos.data_ptr(), self.kcb[li].data_ptr(),
+                                                    self.vcb[li].data_ptr(), self.kcb.stride(1), self.beam_src.data_ptr(),
+                                                    self.beam_common.data_ptr(), ab.data_ptr(), ab.stride(0), None, self.beam_attn_ws.data_ptr(),
+                                                    self.beam_attn_ws.numel(), self.heads, self.head_dim, self.t_max, L['theta'], self.scale,
+                                                    self.native.ptr(tab), s)
+            self.native.check(rc, 'gptq_decode_attn_beam_f16')
+        if beam:
+            attn = attn_beam
         self._step_rows(dict(x=self.x, x2=self.x2, h=self.h, qkv=self.qkvb, ab=self.ab, cb=self.cb), self.ids,
                         attn8 if self.kv_cache == 'fp8' else attn, self.logits)
         self.pos.add_(1)
@@ -1238,29 +1268,51 @@ class DecodeEngine:
                                               self.native.stream_ptr(self.dev))
         self.native.check(rc, 'gptq_kv_reorder_f16')
 
+    def _beam_src_update(self):
+        """beam_cache='indirect': row b of the ancestry table continues row beam_parent[b] at columns [0, pos[0]), and beam_common <- the number
+        of leading columns all rows share (gptq_beam_src_update_u8: in place, one launch for all layers -- no cache row moves)"""
+        with self.native.on_device(self.dev):
+            rc = self.lib.gptq_beam_src_update_u8(self.beam_src.data_ptr(), self.batch, self.t_max, self.beam_parent.data_ptr(),
+                                                  self.pos.data_ptr(), self.beam_common.data_ptr(), self.native.stream_ptr(self.dev))
+        self.native.check(rc, 'gptq_beam_src_update_u8')
+
     def _beam_advance(self, logits):
         self.beam_select(logits)
-        self._beam_reorder()
+        if self.beam_cache == 'indirect':
+            self._beam_src_update()
+        else:
+            self._beam_reorder()
         self.ids.copy_(self.beam_token)
 
     def beam_begin(self, first_logits):
         """the first step of a search whose prompt sits in cache row 0 (prefill; pos[0] = its length): the one row of prompt logits stands for all
-        N beams -- only beam 0 is alive --, select, the reorder replicates row 0's prompt into every row, ids <- the N first tokens"""
+        N beams -- only beam 0 is alive --, select, the reorder replicates row 0's prompt into every row, ids <- the N first tokens.
+        beam_cache='indirect': the table is zeroed -- every beam's history IS row 0's prompt -- and nothing is replicated"""
         self._need_beam_search('beam_begin')
         with torch.no_grad():
             rows = first_logits.reshape(1, -1).to(device=self.dev, dtype=torch.float16).expand(self.batch, -1).contiguous()
             self.pos.copy_(self.pos[:1].clone().expand(self.batch))
+            if self.beam_cache == 'indirect':
+                self.beam_src.zero_()
+                self.beam_common.copy_(self.pos[:1])
             self._beam_advance(rows)
 
     def _beam_step(self):
-        """one step of the search: the batch step on the beams' tokens, select on its logits, the reorder, ids <- the step's tokens"""
-        self._step()
+        """one step of the search: the batch step on the beams' tokens, select on its logits, the reorder (or the table update), ids <- the
+        step's tokens"""
+        if self.beam_cache == 'indirect':
+            self._step_batch(beam=True)
+        else:
+            self._step()
         self._beam_advance(self.logits)
 
     def capture_beam_step(self):
         """capture _beam_step ONCE: settings and state are device memory, so set_beam_search never re-captures"""
         self._need_beam_search('capture_beam_step')
-        self.beam_graph = self._capture(self._beam_step, (self.pos, self.ids, self.beam_state))
+        state = (self.pos, self.ids, self.beam_state)
+        if self.beam_cache == 'indirect':
+            state += (self.beam_src, self.beam_common)
+        self.beam_graph = self._capture(self._beam_step, state)
         return self.beam_graph
 
     def beam_result(self, num_return_sequences=1):
@@ -2511,7 +2563,7 @@ def engine_generate_batch(model, prompts, max_new_tokens, eos_token_id=None, eng
 
 
 def engine_generate_beam(model, input_ids, max_new_tokens, num_beams=4, eos_token_id=None, length_penalty=1.0, early_stopping=False,
-                         num_return_sequences=1, engine=None, t_max=2048, prefill='engine', constrain=None):
+                         num_return_sequences=1, engine=None, t_max=2048, prefill='engine', constrain=None, beam_cache='reorder'):
     """Beam search for ONE prompt ([1, T] ids) on the DecodeEngine, by HF's rule (`generate(num_beams=N, do_sample=False)` with at most one EOS id
     and no logit processors; gptq_mi355x.h "beam search"): the prompt enters cache row 0 (prefill: 'engine' or 'hf', as engine_generate), beam_begin
     chooses the N first tokens and replicates the prompt's cache rows, and every further step is ONE replay of the capture_beam_step graph -- the
@@ -2521,8 +2573,15 @@ def engine_generate_beam(model, input_ids, max_new_tokens, num_beams=4, eos_toke
     ValueError: a prompt that is not [1, T]; num_beams outside 2 .. 16; an engine whose batch is not num_beams or that lacks beam_search;
     num_return_sequences outside 1 .. num_beams; more than one EOS id; prompt + max_new_tokens beyond the cache; a vocabulary below 2 num_beams;
     a row of logits that was not finite (the state's status word) -- raised after the run; constrain= other than None: constraints for beams
-    are not built yet (a beam's state would have to move with its cache row)."""
+    are not built yet (a beam's state would have to move with its cache row).
+    beam_cache = 'indirect': the engine reads the beams' histories through its ancestry table instead of reordering the cache (DecodeEngine's
+    beam_cache); results, scores, EOS handling and the status word are the same.  ValueError for another value and for an engine passed in that
+    was built with the other one."""
     what = 'engine_generate_beam'
+    if beam_cache not in ('reorder', 'indirect'):
+        raise ValueError("%s: beam_cache must be 'reorder' or 'indirect', not %r" % (what, beam_cache))
+    if engine is not None and getattr(engine, 'beam_cache', 'reorder') != beam_cache:
+        raise ValueError('%s: the engine was built with beam_cache=%r, not %r' % (what, getattr(engine, 'beam_cache', 'reorder'), beam_cache))
     if constrain is not None:
         raise ValueError('%s: constrain together with beam search is not built yet' % what)
     if prefill not in ('hf', 'engine'):
@@ -2540,7 +2599,7 @@ def engine_generate_beam(model, input_ids, max_new_tokens, num_beams=4, eos_toke
         raise ValueError('%s: max_new_tokens must be positive' % what)
     if model.lm_head.weight.shape[0] < 2 * num_beams:
         raise ValueError('%s: %d beams need a vocabulary of at least %d' % (what, num_beams, 2 * num_beams))
-    eng = engine if engine is not None else DecodeEngine(model, t_max=t_max, batch=num_beams, beam_search=True)
+    eng = engine if engine is not None else DecodeEngine(model, t_max=t_max, batch=num_beams, beam_search=True, beam_cache=beam_cache)
     if input_ids.shape[1] + max_new_tokens > eng.t_max:
         raise ValueError('%s: prompt + max_new_tokens exceeds the engine cache (%d)' % (what, eng.t_max))
     with torch.no_grad():

@@ -936,6 +936,43 @@ int gptq_beam_select_f16(const void *logits, int64_t ld, int beams, int vocab, v
 int gptq_kv_reorder_f16(void *k_cache, void *v_cache, int layers, int rows, int t_max, int row_elems, int64_t layer_stride, const int32_t *parent,
                         const int64_t *len, gptq_stream_t stream);
 
+/* ---- beam cache indirection: the beams' histories read through an ancestry table instead of being moved between cache rows (csrc/beam.hip,
+ * csrc/beam_attn.hip).  The alternative to gptq_kv_reorder_f16; a caller uses one or the other for a whole search.
+ *
+ * The table: src, uint8 [beams][t_max], ONE per search (ancestry is the same in every layer).  INVARIANT: src[b][t] is the cache slot (row) that
+ * physically holds position t of beam b's history, for every t below the beams' common position; the token a beam appends at position p is
+ * written to (slot b, p) and src[b][p] = b.  Physical rows are never moved.  A prompt that sits in slot 0 is src[:, :T] = 0.
+ *
+ * gptq_beam_src_update_u8: after a select, src'[b][t] = src[parent[b]][t] for t < len[0] -- in place, swaps and cycles included (one thread owns
+ * column t across all rows and stores only what changed); columns at and past len are untouched; a parent outside [0, beams) leaves its row
+ * alone.  The same launch (ONE workgroup, an LDS reduction, no global atomics: the same bits every call) writes common_out[0] = the number of
+ * leading columns t < len[0] in which all `beams` new entries are equal -- ancestry is a tree, so those are exactly the shared columns.  parent
+ * (int32 [beams]), len (int64 [1], clamped into [0, t_max]) and common_out (int32 [1]) are DEVICE memory: a captured launch serves every step.
+ * Validated before the launch: GPTQ_E_NULL (src, parent, len, common_out), GPTQ_E_SHAPE (beams outside 1 .. 16, t_max < 1), GPTQ_E_ALIGN
+ * (parent and common_out 4 bytes, len 8).
+ *
+ * gptq_decode_attn_beam_f16: the attention step of the `beams` (1 .. 16) running beams at ONE position p = position[0] (device memory), in TWO
+ * launches for any number of beams.  Row b of qkv (ldq apart: q | k | v of the beam's new token) is rotated (the RoPE of every other entry),
+ * k / v are appended at (slot b, p) with the bits a token-by-token feed writes, src[b][p] = b, and out row b (ldo apart) = softmax attention of
+ * the rotated q over keys t = 0 .. p read from (slot src[b][t], t); slot s is k_cache / v_cache + s slot_stride elements ([t_max][heads 128]).
+ * common[0] (device int32, clamped into [0, p]) promises that columns t < common of the table are equal in all rows: those keys are streamed
+ * ONCE per head for all beams (from slot src[0][t]); the rest is gathered per beam.  A value below the true common prefix gives the same
+ * result up to rounding; a value above it is the caller's error.  Table bytes are clamped to beams - 1 before they address the cache.
+ * out_perm (NULL or int32 [heads 128]): element k of an output row is stored at column out_perm[k], as gptq_decode_attn_batch_f16 does.
+ * The same inputs give the same bits on every call.  p < 0 or p >= t_max: nothing is read or written.
+ * The workspace (gptq_decode_attn_beam_ws_bytes; 0 for unsupported shapes) is pure scratch.  gptq_decode_attn_beam_splits: the number of active
+ * key splits of a call with len = p + 1 keys (tests pick positions with 1 .. max splits), or GPTQ_E_SHAPE.
+ * Validated before anything is launched: GPTQ_E_NULL (qkv, position, k_cache, v_cache, src, common, out, workspace); GPTQ_E_SHAPE (beams outside
+ * 1 .. 16, heads < 1, head_dim != 128, t_max < 1, ldq < 3 heads 128, ldo < heads 128, slot_stride < t_max heads 128); GPTQ_E_ALIGN (qkv / caches
+ * / workspace / out 16 bytes, position and rope_table 8, common and out_perm 4, ldq / ldo / slot_stride multiples of 8); GPTQ_E_WORKSPACE. */
+int gptq_beam_src_update_u8(void *src, int beams, int t_max, const int32_t *parent, const int64_t *len, int32_t *common_out, gptq_stream_t stream);
+size_t gptq_decode_attn_beam_ws_bytes(int beams, int heads, int t_max);
+int gptq_decode_attn_beam_splits(int heads, int head_dim, int t_max, int len);
+int gptq_decode_attn_beam_f16(const void *qkv, int64_t ldq, int beams, const int64_t *position, void *k_cache, void *v_cache, int64_t slot_stride,
+                              void *src, const int32_t *common, void *out, int64_t ldo, const int32_t *out_perm, void *workspace,
+                              size_t workspace_bytes, int heads, int head_dim, int t_max, float base, float scale, const float *rope_table,
+                              gptq_stream_t stream);
+
 /* ---- token log-probabilities: how probable the chosen token of a row of fp16 logits was, where it ranks, and the row's first `top` tokens
  * (csrc/logprobs.hip; tests/logprobs_ref.py restates the rule in float64).  ONE launch, one workgroup per row, rows = 1 .. 128, no workspace.
  *

@@ -11,9 +11,16 @@ greedy step of the same engine, and engine_generate_beam against the only route 
            max_new_tokens=128) through the installed hook (which switches itself off for beams: the eager module chain), alternating in one
            process; tokens of the best hypothesis per second, (t(129 tokens) - t(1 token)) / 128.
 
+  table 5, indirect attention: gptq_decode_attn_beam_f16 (csrc/beam_attn.hip) alone, 32 heads, N in {4, 16}, the new token at position 16 / 512 /
+           2047, a short tail of 4 keys (common = p - 3), tails of 64 and 256 keys, and no shared trunk (common = 0), against gptq_decode_attn_batch_f16 on the same N rows.
+  table 6, the indirect step: the table-3 model; DecodeEngine(batch=N, beam_search=True, beam_cache='indirect') against the 'reorder' engine and
+           against the reorder engine's capture_greedy_rows graph, N in {4, 16}, 16 / 512 / 2027 tokens (every beam window starts as the step
+           after a prompt of that many tokens: table zeroed, common = context, so the tails grow to 16 over a window); then
+           engine_generate_beam(num_beams=4), 16 + 128 tokens, with either cache.
+
 Device events around a synchronised window (wall clock end to end), everything warmed up, REPEATS alternating repeats, medians and max - min
 spreads (raw repeats printed too).  Every table is a child process under its own `timeout`; at most 16 CPU threads.
-    python tools/bench_beam.py [--markdown FILE] [--only select|reorder|engine]"""
+    python tools/bench_beam.py [--markdown FILE] [--only select|reorder|engine|attn|indirect]"""
 import json
 import os
 import subprocess
@@ -28,7 +35,7 @@ T_MAX = 2048
 LAYERS, H = 32, 4096
 WINDOW = 16
 NEW = 128
-STEP_TIMEOUT = {'select': 200, 'reorder': 200, 'engine': 900}
+STEP_TIMEOUT = {'select': 200, 'reorder': 200, 'engine': 900, 'attn': 200, 'indirect': 900}
 
 
 def _timed(fn, inner):
@@ -112,17 +119,7 @@ def step_engine():
     import time
     import torch
     from quant import decode as D
-    torch.set_num_threads(min(16, torch.get_num_threads()))
-    fill = D.fill_random_quant_
-
-    def small(layer, gen):                               # bench.py's sampling leg: finite logits
-        fill(layer, gen)
-        layer.scales.mul_(0.05)
-    D.fill_random_quant_ = small
-    try:
-        model = D.build_random_llama('cuda:0', seed=0)
-    finally:
-        D.fill_random_quant_ = fill
+    model = _small_model()
     dev = torch.device('cuda:0')
     N = 4
     eng = D.DecodeEngine(model, t_max=T_MAX, batch=N, beam_search=True)
@@ -171,7 +168,123 @@ def step_engine():
     return res
 
 
-STEPS = dict(select=step_select, reorder=step_reorder, engine=step_engine)
+def _small_model():
+    import torch
+    from quant import decode as D
+    torch.set_num_threads(min(16, torch.get_num_threads()))
+    fill = D.fill_random_quant_
+
+    def small(layer, gen):                               # bench.py's sampling leg: finite logits
+        fill(layer, gen)
+        layer.scales.mul_(0.05)
+    D.fill_random_quant_ = small
+    try:
+        return D.build_random_llama('cuda:0', seed=0)
+    finally:
+        D.fill_random_quant_ = fill
+
+
+def step_attn():
+    import torch
+    from quant import _native
+    lib, dev = _native.lib(), torch.device('cuda:0')
+    s = _native.stream_ptr(dev)
+    heads, hd = H // 128, 128
+    cands = {}
+    for N in (4, 16):
+        g = torch.Generator(device=dev).manual_seed(N)
+        qkv = torch.randn((N, 3 * H), device=dev, generator=g).half()
+        k = (torch.randn((N, T_MAX, H), device=dev, generator=g) * 0.5).half()
+        v = torch.randn((N, T_MAX, H), device=dev, generator=g).half()
+        out = torch.zeros((N, H), dtype=torch.float16, device=dev)
+        ws_b = torch.zeros(lib.gptq_decode_attn_beam_ws_bytes(N, heads, T_MAX), dtype=torch.uint8, device=dev)
+        ws_r = torch.zeros(lib.gptq_decode_attn_batch_workspace_bytes(N, heads, hd, T_MAX), dtype=torch.uint8, device=dev)
+        for p in (16, 512, 2047):
+            pos = torch.full((N,), p, dtype=torch.int64, device=dev)
+            for tail, common in (('short', p - 3), ('t64', p - 63), ('t256', p - 255), ('none', 0)):
+                if common < 0:
+                    continue
+                src = (torch.arange(T_MAX, device=dev) % N).to(torch.uint8).repeat(N, 1)      # a trunk whose slot changes with every key
+                src[:, common:] = torch.arange(N, device=dev, dtype=torch.uint8)[:, None]
+                cm = torch.tensor([common], dtype=torch.int32, device=dev)
+
+                def beam(N=N, qkv=qkv, k=k, v=v, out=out, ws=ws_b, pos=pos, src=src, cm=cm):
+                    rc = lib.gptq_decode_attn_beam_f16(qkv.data_ptr(), 3 * H, N, pos.data_ptr(), k.data_ptr(), v.data_ptr(), T_MAX * H, src.data_ptr(),
+                                                       cm.data_ptr(), out.data_ptr(), H, None, ws.data_ptr(), ws.numel(), heads, hd, T_MAX, 10000.0,
+                                                       0.0884, None, s)
+                    assert rc == 0, rc
+                cands['beam_%s_N%d_%d' % (tail, N, p)] = beam
+
+            def rows(N=N, qkv=qkv, k=k, v=v, out=out, ws=ws_r, pos=pos):
+                rc = lib.gptq_decode_attn_batch_f16(qkv.data_ptr(), 3 * H, pos.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), H, ws.data_ptr(),
+                                                    ws.numel(), N, heads, hd, T_MAX, 10000.0, 0.0884, None, None, s)
+                assert rc == 0, rc
+            cands['rows_N%d_%d' % (N, p)] = rows
+    for fn in cands.values():
+        for _ in range(5):
+            fn()
+    times = {name: [] for name in cands}
+    for _ in range(REPEATS):
+        for name, fn in cands.items():
+            times[name].append(_timed(fn, 200))
+    return dict(step='attn', us=times)
+
+
+def step_indirect():
+    import time
+    import torch
+    from quant import decode as D
+    model = _small_model()
+    dev = torch.device('cuda:0')
+    gen = torch.Generator(device=dev).manual_seed(1)
+    prompt = torch.randint(1, VOCAB, (1, 16), device=dev, generator=gen)
+    times, rates = {}, {}
+    for N in (4, 16):
+        engs = {c: D.DecodeEngine(model, t_max=T_MAX, batch=N, beam_search=True, beam_cache=c) for c in ('reorder', 'indirect')}
+        for e in engs.values():
+            e.graph_for('beam')
+        engs['reorder'].graph_for('greedy_rows')
+
+        def window(kind, ctx):
+            eng = engs['indirect' if kind == 'indirect' else 'reorder']
+            eng.set_beam_search(T_MAX)
+            eng.pos.fill_(ctx)
+            eng.ids.copy_(torch.arange(1, N + 1, device=dev))
+            if kind == 'greedy':
+                eng.stepc.zero_()
+                return _timed(eng.greedy_rows_graph.replay, WINDOW)
+            if kind == 'indirect':
+                eng.beam_src.zero_()
+                eng.beam_common.fill_(ctx)
+            return _timed(eng.beam_graph.replay, WINDOW)
+        cands = [(kind, ctx) for ctx in (16, 512, 2027) for kind in ('greedy', 'reorder', 'indirect')]
+        for c in cands:
+            window(*c)
+        for c in cands:
+            times['%s_N%d_%d' % (c[0], N, c[1])] = []
+        for _ in range(REPEATS):
+            for c in cands:
+                times['%s_N%d_%d' % (c[0], N, c[1])].append(window(*c))
+        if N == 4:
+            def route(cache, n):
+                torch.cuda.synchronize(); t0 = time.perf_counter()
+                seqs, _ = D.engine_generate_beam(model, prompt, n, num_beams=N, engine=engs[cache], beam_cache=cache)
+                torch.cuda.synchronize()
+                return time.perf_counter() - t0, seqs[0].numel() - prompt.shape[1]
+            rates = {c: [] for c in engs}
+            for c in engs:
+                route(c, 4)
+            for _ in range(REPEATS):
+                for c in engs:
+                    (tn, got), (t1, _) = route(c, NEW + 1), route(c, 1)
+                    assert got == NEW + 1, (c, got)
+                    rates[c].append(NEW / (tn - t1))
+        del engs
+        torch.cuda.empty_cache()
+    return dict(step='indirect', window=WINDOW, us_per_replay=times, tokens_per_s=rates)
+
+
+STEPS = dict(select=step_select, reorder=step_reorder, engine=step_engine, attn=step_attn, indirect=step_indirect)
 
 
 def _median(v):
@@ -223,6 +336,31 @@ def main():
         lines += ['', '### End to end: 4 beams, 16 + %d tokens, tokens of the best hypothesis per second: %s' % (NEW, head), '',
                   '| model.generate(num_beams=4) through the hook (the parent\'s route) | engine_generate_beam | engine / parent |', '|---|---|---|',
                   '| %s | %s | %.2f |' % (cell(q['hf']), cell(q['engine']), _median(q['engine']) / _median(q['hf']))]
+    if 'attn' in results:
+        t = results['attn']['us']
+        lines += ['', '### gptq_decode_attn_beam_f16 alone (two launches), 32 heads, us per call against gptq_decode_attn_batch_f16 on the same N rows: '
+                  + head + '; beam columns by tail length (keys from `common` to p), with rows / beam in brackets', '',
+                  '| N | position | batch rows | tail 4 | tail 64 | tail 256 | nothing shared (common = 0) |', '|---|---|---|---|---|---|---|']
+        for N in (4, 16):
+            for p in (16, 512, 2047):
+                r = t['rows_N%d_%d' % (N, p)]
+                cols = [t.get('beam_%s_N%d_%d' % (k, N, p)) for k in ('short', 't64', 't256', 'none')]
+                lines.append('| %d | %d | %s | %s |' % (N, p, cell(r), ' | '.join(
+                    '-' if c is None else '%s [%.2f]' % (cell(c), _median(r) / _median(c)) for c in cols)))
+    if 'indirect' in results:
+        r = results['indirect']
+        t, q = r['us_per_replay'], r['tokens_per_s']
+        lines += ['', '### The beam step, 7B-shaped random model, us per replay over %d replays: %s' % (r['window'], head), '',
+                  "| N | context | capture_greedy_rows | beam step, 'reorder' | beam step, 'indirect' | indirect / reorder | indirect / greedy |",
+                  '|---|---|---|---|---|---|---|']
+        for N in (4, 16):
+            for ctx in (16, 512, 2027):
+                g, o, i = (t['%s_N%d_%d' % (k, N, ctx)] for k in ('greedy', 'reorder', 'indirect'))
+                lines.append('| %d | %d | %s | %s | %s | %.3f | %.3f |' % (N, ctx, cell(g), cell(o), cell(i), _median(i) / _median(o),
+                                                                           _median(i) / _median(g)))
+        lines += ['', '### End to end: engine_generate_beam(num_beams=4), 16 + %d tokens, tokens of the best hypothesis per second: %s' % (NEW, head),
+                  '', "| 'reorder' | 'indirect' | indirect / reorder |", '|---|---|---|',
+                  '| %s | %s | %.3f |' % (cell(q['reorder']), cell(q['indirect']), _median(q['indirect']) / _median(q['reorder']))]
     lines += ['', '### Raw repeats', '', '```'] + [json.dumps(r) for r in results.values()] + ['```', '']
     text = '\n'.join(lines)
     print(text)
