@@ -1,10 +1,11 @@
-// attn_device.h -- the device-side pieces the attention entries share (decode_attn.hip, chunk_attn.hip, prompt_attn.hip; the RoPE also
-// elementwise.hip), each written ONCE: the engine promises that a K/V cache row has the same bits whichever entry appended it, and that
-// promise rests on every entry running the same instructions -- so they come from one place.
+// attn_device.h -- the device-side pieces the attention entries share (decode_attn.hip, decode_attn_kv8.hip, chunk_attn.hip, beam_attn.hip,
+// prompt_attn.hip; the RoPE also elementwise.hip), each written ONCE: the engine promises that a K/V cache row has the same bits whichever
+// entry appended it, and that promise rests on every entry running the same instructions -- so they come from one place.
 //   1. RoPE: rope_inv_base / rope_cos_sin / rope_rotate / rope_kv_row.  The accurate libm exp / cos / sin and two roundings per product: a
 //      translation unit that includes this header for the RoPE is built with CXXFLAGS_STRICT (see the Makefile).
 //   2. the LDS image of a K or V tile: 256-byte rows with a chunk swizzle, row reads and transposed reads.
-//   3. the hand-off between the splits of one (row, head): arrival ticket + the last arriver's merge of the records.
+//   3. the ending of a split of the MFMA kernels: attn_waves_meet (partial states -> the split's {M, den, o}) and attn_split_finish (one split stores;
+//      several publish their records, take the arrival ticket, and the last arriver merges and stores).
 // The wave reductions (row_sum16, rows_sum, halves_sum, ...) live in gptq_device.h; the split rule, the merge arithmetic and the
 // workspace layouts in attn_split.h.
 #pragma once
@@ -120,6 +121,63 @@ GPTQ_DEV void attn_merge_records(const float *rmd, size_t mstride, const T *ro, 
         for (int i = 0; i < ATT_MAX_SPLITS; i++) oj[i] = __builtin_bit_cast(halves_t, oi[i])[j];
         res[j] = attn_round_f16(attn_merge_value(oj, c));
     }
+}
+
+// The meeting of the NSRC partial online-softmax states of a split (the waves'; for the beams also the tail's), behind the barrier that made
+// them visible: M of source w at mw[w * ms], its l at lw[w * ms], this thread's W partial sums at part(w).  Gives {Mx, den} of the split and
+// o = num / den rounded to fp16; a row that saw no key (den = 0) leaves zeros, which merge with weight 0.
+template <int NSRC, int W, class PART>
+GPTQ_DEV void attn_waves_meet(const float *mw, const float *lw, int ms, PART part, float &Mx, float &den, half_t (&o)[W]) {
+    Mx = mw[0];
+#pragma unroll
+    for (int w = 1; w < NSRC; w++) Mx = fmaxf(Mx, mw[w * ms]);
+    float num[W];
+#pragma unroll
+    for (int j = 0; j < W; j++) num[j] = 0.f;
+    den = 0.f;
+#pragma unroll
+    for (int w = 0; w < NSRC; w++) {
+        const float e = __builtin_amdgcn_exp2f(mw[w * ms] - Mx);
+        den = __builtin_fmaf(e, lw[w * ms], den);
+        const float *src = part(w);
+#pragma unroll
+        for (int j = 0; j < W; j++) num[j] = __builtin_fmaf(e, src[j], num[j]);
+    }
+    const float rden = den > 0.f ? __builtin_amdgcn_rcpf(den) : 0.f;
+#pragma unroll
+    for (int j = 0; j < W; j++) o[j] = attn_round_f16(num[j] * rden);
+}
+
+// What a split does with its result when no later launch merges the records.  Called by every thread of the workgroup.  o: this thread's W
+// adjacent outputs; ro / rmd: where they and {M, den} go in the record of split 0 (as attn_merge_records takes them); live: the thread holds a
+// row that exists; md_writer: it is the one that writes the row's {M, den}.  One active split stores o.  Several publish with system-scope stores,
+// and the last arriver merges the records in split order and stores that.  store(const half_t (&)[W]) knows the output's address (and out_perm).
+template <int W, typename T, class STORE>
+GPTQ_DEV void attn_split_finish(const half_t (&o)[W], float Mx, float den, T *ro, size_t ostride, float *rmd, size_t mstride, unsigned *ticket,
+                                int *last_flag, int nsp, int s, bool live, bool md_writer, STORE store) {
+    constexpr int NT = W * sizeof(half_t) / sizeof(T);
+    typedef T words_t __attribute__((ext_vector_type(NT)));
+    typedef half_t halves_t __attribute__((ext_vector_type(W)));
+    if (nsp == 1) {          // this workgroup is the whole head
+        if (live) store(o);
+        return;
+    }
+    if (live) {
+        halves_t oh;
+#pragma unroll
+        for (int j = 0; j < W; j++) oh[j] = o[j];
+        const words_t ow = __builtin_bit_cast(words_t, oh);
+#pragma unroll
+        for (int j = 0; j < NT; j++) __hip_atomic_store(ro + (size_t)s * ostride + j, ow[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        if (md_writer) {
+            __hip_atomic_store(rmd + (size_t)s * mstride, Mx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            __hip_atomic_store(rmd + (size_t)s * mstride + 1, den, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+    }
+    if (!attn_ticket_last(ticket, nsp, last_flag) || !live) return;
+    half_t res[W];
+    attn_merge_records(rmd, mstride, (const T *)ro, ostride, nsp, res);
+    store(res);
 }
 
 }  // namespace gptq

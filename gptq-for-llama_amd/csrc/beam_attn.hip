@@ -307,57 +307,26 @@ __global__ void __launch_bounds__(BA_NW * 64) beam_attn_kernel(const BeamAttnArg
     }
     __syncthreads();
 
-    // ================================ the four trunk states and the tail of a beam -> {Mx, den, num} of the split ================================
+    // ================================ the four trunk states and the tail of a beam -> {Mx, den, o} of the split ================================
     const int qq = tid >> 4, d0 = (tid & 15) * 8;          // this thread's beam and its eight dims
-    float Mx = mw[0][qq];
-#pragma unroll
-    for (int w = 1; w <= BA_NW; w++) Mx = fmaxf(Mx, mw[w][qq]);
-    float num[8], den = 0.f;
-#pragma unroll
-    for (int j = 0; j < 8; j++) num[j] = 0.f;
-#pragma unroll
-    for (int w = 0; w <= BA_NW; w++) {
-        const float e = __builtin_amdgcn_exp2f(mw[w][qq] - Mx);
-        den = __builtin_fmaf(e, lw[w][qq], den);
-        const float *part = (w < BA_NW ? (const float *)vs[w] + qq * BA_HD : &ta[qq][0]) + d0;
-#pragma unroll
-        for (int j = 0; j < 8; j++) num[j] = __builtin_fmaf(e, part[j], num[j]);
-    }
-    const float rden = den > 0.f ? __builtin_amdgcn_rcpf(den) : 0.f;   // (den = 0 only for the padding rows qq >= N)
-    half8_t o;
-#pragma unroll
-    for (int j = 0; j < 8; j++) o[j] = attn_round_f16(num[j] * rden);
+    float Mx, den;                                         // (den = 0 only for the padding rows qq >= N)
+    half_t o[8];
+    attn_waves_meet<BA_NW + 1, 8>(&mw[0][qq], &lw[0][qq], BA_QR,
+                                        [&](int w) { return (w < BA_NW ? (const float *)vs[w] + qq * BA_HD : &ta[qq][0]) + d0; }, Mx, den, o);
     half_t *const orow = a.out + (size_t)qq * a.ldo;
-    auto store = [&](const half8_t r) {                    // out_perm: element k of the row goes to column out_perm[k] (the batch entry's map)
+    auto store = [&](const half_t (&r)[8]) {               // out_perm: element k of the row goes to column out_perm[k] (the batch entry's map)
         if (a.out_perm) {
 #pragma unroll
             for (int j = 0; j < 8; j++) orow[a.out_perm[h * BA_HD + d0 + j]] = r[j];
         } else {
-            *(half8_t *)(orow + (size_t)h * BA_HD + d0) = r;
+            *(half8_t *)(orow + (size_t)h * BA_HD + d0) = half8_t{r[0], r[1], r[2], r[3], r[4], r[5], r[6], r[7]};
         }
     };
-    if (sp.nsp == 1) {       // this workgroup is the whole head
-        if (qq < N) store(o);
-        return;
-    }
-    // ---- several splits: system-scope records, arrival ticket, the last split merges them in split order ----
     const size_t rstride = (size_t)N * hd / 2;             // uint32 words per split
     const size_t mstride = (size_t)a.heads * N * 2;
     uint32_t *const ro = a.o16 + ((size_t)qq * hd + (size_t)h * BA_HD + d0) / 2;
     float *const rmd = a.md + ((size_t)h * N + qq) * 2;
-    if (qq < N) {
-        const u32x4 ow4 = __builtin_bit_cast(u32x4, o);
-#pragma unroll
-        for (int j = 0; j < 4; j++) __hip_atomic_store(ro + (size_t)s * rstride + j, ow4[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        if ((tid & 15) == 0) {
-            __hip_atomic_store(rmd + (size_t)s * mstride, Mx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            __hip_atomic_store(rmd + (size_t)s * mstride + 1, den, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-    }
-    if (!attn_ticket_last(a.tickets + h, sp.nsp, &last_flag) || qq >= N) return;
-    half_t res[8];
-    attn_merge_records(rmd, mstride, ro, rstride, sp.nsp, res);
-    store(half8_t{res[0], res[1], res[2], res[3], res[4], res[5], res[6], res[7]});
+    attn_split_finish(o, Mx, den, ro, rstride, rmd, mstride, a.tickets + h, &last_flag, sp.nsp, s, qq < N, (tid & 15) == 0, store);
 }
 
 // the workspace is the chunk attention's for one sequence of N rows (attn_split.h): rotated q | records | {M, den} | tickets; S of the grid likewise

@@ -213,48 +213,16 @@ __global__ void __launch_bounds__(CA_NW * 64) chunk_attn_kernel(const ChunkAttnA
     }
     __syncthreads();
     const int qq = tid >> 4, d0 = (tid & 15) * 8;          // this thread's query row and its eight dims
-    float Mx = mw[0][qq];
-#pragma unroll
-    for (int w = 1; w < CA_NW; w++) Mx = fmaxf(Mx, mw[w][qq]);
-    float num[8], den = 0.f;
-#pragma unroll
-    for (int j = 0; j < 8; j++) num[j] = 0.f;
-#pragma unroll
-    for (int w = 0; w < CA_NW; w++) {
-        const float e = __builtin_amdgcn_exp2f(mw[w][qq] - Mx);
-        den = __builtin_fmaf(e, lw[w][qq], den);
-        const float *src = (const float *)vs[w] + qq * CA_HD + d0;
-#pragma unroll
-        for (int j = 0; j < 8; j++) num[j] = __builtin_fmaf(e, src[j], num[j]);
-    }
-    // the split's normalised output; a row that saw no key of this split (den = 0: its keys end below t0) leaves zeros, which merge with weight 0
-    const float rden = den > 0.f ? __builtin_amdgcn_rcpf(den) : 0.f;
-    half8_t o;
-#pragma unroll
-    for (int j = 0; j < 8; j++) o[j] = attn_round_f16(num[j] * rden);
+    float Mx, den;
+    half_t o[8];
+    attn_waves_meet<CA_NW, 8>(&mw[0][qq], &lw[0][qq], CA_QR, [&](int w) { return (const float *)vs[w] + qq * CA_HD + d0; }, Mx, den, o);
     half_t *const orow = a.out + ((size_t)b * a.rows + qq) * a.ldo + (size_t)h * CA_HD + d0;
-    if (sp.nsp == 1) {       // this workgroup is the whole head
-        if (qq < nr) *(half8_t *)orow = o;
-        return;
-    }
-    // ---- several splits: system-scope records, arrival ticket, the last split merges them in split order ----
     const size_t rstride = (size_t)a.rows * hd / 2;        // uint32 words per split
     const size_t mstride = (size_t)a.heads * a.rows * 2;
     uint32_t *const ro = a.o16 + (size_t)b * S * rstride + ((size_t)qq * hd + (size_t)h * CA_HD + d0) / 2;
     float *const rmd = a.md + (size_t)b * S * mstride + ((size_t)h * a.rows + qq) * 2;
-    if (qq < nr) {
-        const u32x4 ow4 = __builtin_bit_cast(u32x4, o);
-#pragma unroll
-        for (int j = 0; j < 4; j++) __hip_atomic_store(ro + (size_t)s * rstride + j, ow4[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        if ((tid & 15) == 0) {
-            __hip_atomic_store(rmd + (size_t)s * mstride, Mx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            __hip_atomic_store(rmd + (size_t)s * mstride + 1, den, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-    }
-    if (!attn_ticket_last(a.tickets + (size_t)b * a.heads + h, sp.nsp, &last_flag) || qq >= nr) return;
-    half_t res[8];
-    attn_merge_records(rmd, mstride, ro, rstride, sp.nsp, res);
-    *(half8_t *)orow = half8_t{res[0], res[1], res[2], res[3], res[4], res[5], res[6], res[7]};
+    attn_split_finish(o, Mx, den, ro, rstride, rmd, mstride, a.tickets + (size_t)b * a.heads + h, &last_flag, sp.nsp, s, qq < nr, (tid & 15) == 0,
+                      [&](const half_t (&r)[8]) { *(half8_t *)orow = half8_t{r[0], r[1], r[2], r[3], r[4], r[5], r[6], r[7]}; });
 }
 
 // S of the launch's grid: as the decode attention of one row (heads x S <= 256 workgroups, at most ATT_MAX_SPLITS, one split per tile of tokens)
