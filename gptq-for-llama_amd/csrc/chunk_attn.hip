@@ -28,6 +28,15 @@
 // Several sequences (batched speculative decoding): both grids get the sequence b as blockIdx.z -- its packed rows b rows .. of qkv / out, its cache
 // slot, its position pos[b], its part of the workspace, its tickets -- and nothing else changes: per sequence the same instructions on the same
 // values as a single-sequence call (which is the seqs = 1 case), hence the same bits; still two launches for any number of sequences.
+//
+// A draft tree (tree_attn_launch, the TREE instances of both kernels; single sequence): the rows are the NODES of a tree rooted in the last accepted
+// token, in topological order, described by anc[16] in device memory -- bit j of anc[r]: node j is node r or an ancestor of it (anc[0] = 1).
+// Node r has depth d_r = popcount(anc[r]) - 1; it is rotated at position p + d_r and stored in cache row p + r: the slot is by node, the angle by
+// depth, so the rows of an accepted root-to-leaf path hold, once gptq_kv_tree_compact_f16 has moved them to p + depth, what a token-by-token
+// feed writes.  Launch 2 differs in ONE select: row r sees key t iff t < p or bit t - p of anc[r]; a lane keeps its row's mask in a register for
+// the walk, and only a tile that reaches key p tests it (a wave-uniform branch) -- a tile of the history runs the instructions of the chunk
+// instance; the same tiles stage a node's non-finite v values as +0 (0 x NaN would pass the mask).  A node with p + r >= t_max is skipped, and by the topological order so is everything below it.  The chain anc[r] = (2 << r) - 1
+// gives the bits of the chunk instance.
 #include <algorithm>
 
 #include "attn_device.h"
@@ -41,10 +50,12 @@ constexpr int CA_KT = 32;      // keys per wave tile (two 16-key MFMA blocks)
 constexpr int CA_QR = 16;      // query rows of the MFMA (rows padded to it)
 constexpr int CA_TPS = 256;    // tokens a split owns at least: 8 splits from 1793 tokens on (32 heads x 8 = one workgroup per CU at 2047)
 
+// TREE: row r is NODE r of a draft tree (the header of this file, "A draft tree"): the slot is by node index, the angle by depth
+template <bool TREE>
 __global__ void __launch_bounds__(64) chunk_rope_kv_kernel(const half_t *__restrict__ qkv, int64_t ldq, const int64_t *__restrict__ pos_ptr,
                                                            half_t *__restrict__ kc, half_t *__restrict__ vc, int64_t slot_stride,
                                                            half_t *__restrict__ qrot, unsigned *__restrict__ tickets, int heads, int t_max,
-                                                           float inv_base, const float2 *__restrict__ tab) {
+                                                           float inv_base, const float2 *__restrict__ tab, const uint32_t *__restrict__ anc) {
     const int h = blockIdx.y, c = threadIdx.x, half = CA_HD / 2;
     const int r = blockIdx.x, b = blockIdx.z, rows = gridDim.x;      // sequence b: packed rows b rows .., cache slot b, position pos_ptr[b]
     if (r == 0 && c == 0) tickets[(size_t)b * heads + h] = 0u;
@@ -53,13 +64,22 @@ __global__ void __launch_bounds__(64) chunk_rope_kv_kernel(const half_t *__restr
     const int64_t pos = p + r;
     if (pos >= t_max) return;
     float cs, sn;
-    rope_cos_sin(tab, pos, c, half, inv_base, cs, sn);
+    if constexpr (TREE)
+        rope_cos_sin(tab, p + (__builtin_popcount(anc[r] & 0xffffu) - 1), c, half, inv_base, cs, sn);   // depth <= r: inside the table
+    else
+        rope_cos_sin(tab, pos, c, half, inv_base, cs, sn);
     const int hd = heads * CA_HD;
     const half_t *q = qkv + ((size_t)b * rows + r) * ldq + (size_t)h * CA_HD + c;
     half_t *qd = qrot + ((size_t)b * rows + r) * hd + (size_t)h * CA_HD + c;
     half_t *kd = kc + (size_t)b * slot_stride + (size_t)pos * hd + (size_t)h * CA_HD + c;
     half_t *vd = vc + (size_t)b * slot_stride + (size_t)pos * hd + (size_t)h * CA_HD + c;
     rope_kv_row(q, q + hd, q + 2 * hd, qd, kd, vd, half, cs, sn);
+}
+
+// two fp16: a non-finite one (exponent all ones) becomes +0, a finite one keeps its bits
+GPTQ_DEV uint32_t finite_pair(uint32_t w) {
+    const uint32_t f = ((w & 0x7c007c00u) + 0x04000400u) & 0x80008000u;      // bit 15 of a half: it is not finite
+    return w & ~((f << 1) - (f >> 15));
 }
 
 struct ChunkAttnArgs {
@@ -73,8 +93,10 @@ struct ChunkAttnArgs {
     int heads, rows, t_max;
     int64_t ldo, slot_stride;
     float scale2;                // softmax scale x log2(e)
+    const uint32_t *anc;         // TREE only: [16] ancestor masks, bit j of anc[r]: node j is node r or above it
 };
 
+template <bool TREE>
 __global__ void __launch_bounds__(CA_NW * 64) chunk_attn_kernel(const ChunkAttnArgs a) {
     // the waves' V tiles [32 keys][128] fp16; at the end the waves' O [16 rows][128] fp32 (the same 8 KB each)
     __shared__ __attribute__((aligned(16))) half_t vs[CA_NW][CA_KT * CA_HD];
@@ -136,10 +158,25 @@ __global__ void __launch_bounds__(CA_NW * 64) chunk_attn_kernel(const ChunkAttnA
 #pragma unroll
     for (int d = 0; d < 8; d++) acc[d] = float4_t{0.f, 0.f, 0.f, 0.f};
     const int qpos = p + qi;                               // the last key this lane's query row sees
+    uint32_t mask = 0;                                     // TREE: the keys p + j this lane's query row sees, for the whole walk
+    if constexpr (TREE) mask = a.anc[qi] & 0xffffu;
 
     auto tile = [&](const u32x4 (&K)[2][4], const u32x4 (&V)[8], int tb) {
+        // TREE: a tile that reaches the nodes (keys >= p: the last 16 of the launch) -- wave-uniform, EXEC stays full; every tile below p runs
+        // the chunk instance's instructions.  A node's v is staged with its non-finite values as +0: P = 0 times a NaN would carry a node
+        // that the mask excludes into every row of the tile.
+        const bool nodes = TREE && tb + CA_KT > p;
+        if (nodes) {
 #pragma unroll
-        for (int i = 0; i < 8; i++) *(ATTN_LDS u32x4 *)((ATTN_LDS char *)img + attn_lds_off(vrow + 4 * i, vch)) = V[i];
+            for (int i = 0; i < 8; i++) {
+                u32x4 v = V[i];
+                if (tb + vrow + 4 * i >= p) v = u32x4{finite_pair(v[0]), finite_pair(v[1]), finite_pair(v[2]), finite_pair(v[3])};
+                *(ATTN_LDS u32x4 *)((ATTN_LDS char *)img + attn_lds_off(vrow + 4 * i, vch)) = v;
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < 8; i++) *(ATTN_LDS u32x4 *)((ATTN_LDS char *)img + attn_lds_off(vrow + 4 * i, vch)) = V[i];
+        }
         float4_t sc[2];
 #pragma unroll
         for (int b = 0; b < 2; b++) {
@@ -149,16 +186,30 @@ __global__ void __launch_bounds__(CA_NW * 64) chunk_attn_kernel(const ChunkAttnA
                 sc[b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8_t, K[b][ks]), qf[ks], sc[b], 0, 0, 0);
         }
         float mt = -INFINITY;
+        // the nodes' tile selects by the mask; every tile below p takes the causal select, which passes every key there
+        if (nodes) {
 #pragma unroll
-        for (int b = 0; b < 2; b++)
+            for (int b = 0; b < 2; b++)
 #pragma unroll
-            for (int r = 0; r < 4; r++) {
-                const int key = tb + 16 * b + kreg0 + r;
-                float v = sc[b][r] * a.scale2;
-                if (key > qpos || key >= t_end) v = -INFINITY;
-                sc[b][r] = v;
-                mt = fmaxf(mt, v);
-            }
+                for (int r = 0; r < 4; r++) {
+                    const int key = tb + 16 * b + kreg0 + r;
+                    float v = sc[b][r] * a.scale2;
+                    if (key >= t_end || (key >= p && !((mask >> ((key - p) & 15)) & 1u))) v = -INFINITY;   // (key < t_end <= p + 16)
+                    sc[b][r] = v;
+                    mt = fmaxf(mt, v);
+                }
+        } else {
+#pragma unroll
+            for (int b = 0; b < 2; b++)
+#pragma unroll
+                for (int r = 0; r < 4; r++) {
+                    const int key = tb + 16 * b + kreg0 + r;
+                    float v = sc[b][r] * a.scale2;
+                    if (key > qpos || key >= t_end) v = -INFINITY;
+                    sc[b][r] = v;
+                    mt = fmaxf(mt, v);
+                }
+        }
         mt = rows_max(mt);
         const float Mn = fmaxf(M, mt);                     // finite: M starts at the floor
         const float alpha = __builtin_amdgcn_exp2f(M - Mn);
@@ -238,27 +289,41 @@ size_t chunk_attn_ws_bytes(int rows, int heads, int t_max) { return chunk_attn_b
 // seqs sequences of `rows` rows each -- packed rows b rows .. b rows + rows - 1 of qkv / out, cache slot b (slot_stride elements apart), position
 // pos[b] on the device -- in the same two launches: the sequence is blockIdx.z of both kernels, everything else is per sequence what it is for one
 // (the same attn_split() cut from the same grid split count S, tickets per (sequence, head))
-int chunk_attn_batch_launch(const half_t *qkv, int64_t ldq, int seqs, int rows, const int64_t *pos, half_t *kc, half_t *vc, int64_t slot_stride,
-                            half_t *out, int64_t ldo, void *ws, int heads, int t_max, float base, float scale, const float *rope_table,
-                            hipStream_t s) {
+template <bool TREE>
+static int chunk_attn_launch_as(const half_t *qkv, int64_t ldq, int seqs, int rows, const int64_t *pos, half_t *kc, half_t *vc, int64_t slot_stride,
+                                half_t *out, int64_t ldo, void *ws, int heads, int t_max, float base, float scale, const float *rope_table,
+                                const uint32_t *anc, hipStream_t s) {
     const ChunkAttnWs w = chunk_attn_ws(seqs, rows, heads, t_max);
     half_t *qrot = (half_t *)((char *)ws + w.qrot);
     ChunkAttnArgs a{};
     a.o16 = (uint32_t *)((char *)ws + w.o16);
     a.md = (float *)((char *)ws + w.md);
     a.tickets = (unsigned *)((char *)ws + w.tickets);
-    hipLaunchKernelGGL(chunk_rope_kv_kernel, dim3(rows, heads, seqs), dim3(CA_HD / 2), 0, s, qkv, ldq, pos, kc, vc, slot_stride, qrot, a.tickets, heads,
-                       t_max, rope_inv_base(base, CA_HD), (const float2 *)rope_table);
+    hipLaunchKernelGGL(chunk_rope_kv_kernel<TREE>, dim3(rows, heads, seqs), dim3(CA_HD / 2), 0, s, qkv, ldq, pos, kc, vc, slot_stride, qrot, a.tickets,
+                       heads, t_max, rope_inv_base(base, CA_HD), (const float2 *)rope_table, anc);
     a.q = qrot; a.pos = pos; a.kc = kc; a.vc = vc; a.out = out;
     a.heads = heads; a.rows = rows; a.t_max = t_max; a.ldo = ldo; a.slot_stride = slot_stride;
     a.scale2 = scale * 1.44269504088896340736f;
-    hipLaunchKernelGGL(chunk_attn_kernel, dim3(heads, w.S, seqs), dim3(CA_NW * 64), 0, s, a);
+    a.anc = anc;
+    hipLaunchKernelGGL(chunk_attn_kernel<TREE>, dim3(heads, w.S, seqs), dim3(CA_NW * 64), 0, s, a);
     return (int)hipGetLastError();
+}
+
+int chunk_attn_batch_launch(const half_t *qkv, int64_t ldq, int seqs, int rows, const int64_t *pos, half_t *kc, half_t *vc, int64_t slot_stride,
+                            half_t *out, int64_t ldo, void *ws, int heads, int t_max, float base, float scale, const float *rope_table,
+                            hipStream_t s) {
+    return chunk_attn_launch_as<false>(qkv, ldq, seqs, rows, pos, kc, vc, slot_stride, out, ldo, ws, heads, t_max, base, scale, rope_table, nullptr, s);
 }
 
 int chunk_attn_launch(const half_t *qkv, int64_t ldq, int rows, const int64_t *pos, half_t *kc, half_t *vc, half_t *out, int64_t ldo, void *ws,
                       int heads, int t_max, float base, float scale, const float *rope_table, hipStream_t s) {
     return chunk_attn_batch_launch(qkv, ldq, 1, rows, pos, kc, vc, 0, out, ldo, ws, heads, t_max, base, scale, rope_table, s);
+}
+
+// the `rows` NODES of a draft tree of one sequence (anc: 16 masks in device memory), in the workspace of chunk_attn_launch
+int tree_attn_launch(const half_t *qkv, int64_t ldq, int rows, const int64_t *pos, const uint32_t *anc, half_t *kc, half_t *vc, half_t *out,
+                     int64_t ldo, void *ws, int heads, int t_max, float base, float scale, const float *rope_table, hipStream_t s) {
+    return chunk_attn_launch_as<true>(qkv, ldq, 1, rows, pos, kc, vc, 0, out, ldo, ws, heads, t_max, base, scale, rope_table, anc, s);
 }
 
 }  // namespace gptq

@@ -294,6 +294,10 @@ size_t chunk_attn_batch_ws_bytes(int seqs, int rows, int heads, int t_max);
 int chunk_attn_batch_launch(const half_t *qkv, int64_t ldq, int seqs, int rows, const int64_t *pos, half_t *kc, half_t *vc, int64_t slot_stride,
                             half_t *out, int64_t ldo, void *ws, int heads, int t_max, float base, float scale, const float *rope_table,
                             hipStream_t s);
+// ... of the `rows` (1..16) NODES of a draft tree of one sequence: anc [16] ancestor masks in DEVICE memory; node r rotated at *pos + depth,
+// stored in cache row *pos + r, attending to the history and its ancestors; ws = chunk_attn_ws_bytes(rows, heads, t_max)
+int tree_attn_launch(const half_t *qkv, int64_t ldq, int rows, const int64_t *pos, const uint32_t *anc, half_t *kc, half_t *vc, half_t *out,
+                     int64_t ldo, void *ws, int heads, int t_max, float base, float scale, const float *rope_table, hipStream_t s);
 
 // beam_attn.hip: RoPE + append + attention of the `beams` (1..16) beams of one search at position *pos, histories read through the ancestry table
 // src [beams][t_max] (keys below *common once for all beams); ws = beam_attn_ws_bytes(beams, heads, t_max), no state

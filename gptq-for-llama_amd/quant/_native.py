@@ -170,6 +170,11 @@ _SIGNATURES = {
     'gptq_decode_attn_chunk_splits': [c_int, c_int, c_int, c_int],
     'gptq_decode_attn_chunk_f16': [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_size_t, c_int, c_int, c_int,
                                    c_float, c_float, c_void_p, c_void_p],
+    # ... of the nodes of a draft TREE (ancestor masks in device memory), the greedy accept walk and the accepted path's compaction (csrc/tree.hip)
+    'gptq_decode_attn_tree_f16': [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_size_t, c_int, c_int,
+                                  c_int, c_float, c_float, c_void_p, c_void_p],
+    'gptq_tree_accept_greedy': [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
+    'gptq_kv_tree_compact_f16': [c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p],
     # ... of up to 16 sequences in the same two launches: packed rows, one cache slot and one device position per sequence
     'gptq_decode_attn_chunk_batch_workspace_bytes': [c_int, c_int, c_int, c_int, c_int],
     'gptq_decode_attn_chunk_batch_f16': [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_size_t,

@@ -220,8 +220,16 @@ def lm_head_logits(eng, x, logits, s, h=None):
 class DecodeEngine:
 
     def __init__(self, model, t_max=2048, fuse_norm=True, fuse_attn=True, batch=1, chunk=0, batch_chunk=0, spec_sample=False, logits_process=False, beam_search=False,
-                 logprobs=None, constrain=None, kv_cache='fp16', beam_cache='reorder'):
-        """beam_cache = 'indirect' (with beam_search=True) reads the beams' histories through an ANCESTRY TABLE instead of moving them between
+                 logprobs=None, constrain=None, kv_cache='fp16', beam_cache='reorder', tree=False):
+        """tree = True (with chunk = R: batch 1, fp16 cache, greedy) makes the R rows of the verify step the NODES of a draft TREE
+        (gptq_mi355x.h "tree speculative decoding"): tree_anc uint32 [16] -- the ancestor masks gptq_decode_attn_tree_f16 reads --, tree_parent
+        int32 [R], tree_path int32 [16], and tree_tok, which IS chunk_ids (the nodes' tokens).  set_tree uploads a tree, verify_tree is the eager
+        step, capture_verify_tree_greedy the graph: the chunk step with the tree attention per layer, the rows' argmax, gptq_tree_accept_greedy
+        and gptq_kv_tree_compact_f16 for all layers; engine_generate(speculate=dict(tree=...)) drives it.  Such an engine verifies trees only:
+        verify / verify_sample and their captures raise (a chain is the tree whose node r hangs below node r - 1).  False (the default)
+        allocates nothing and adds no launch.  ValueError without chunk = R; batch_chunk, beams, the fp8 cache, processors, log-probabilities
+        and constraints are refused together with chunk already.
+        beam_cache = 'indirect' (with beam_search=True) reads the beams' histories through an ANCESTRY TABLE instead of moving them between
         cache rows (gptq_mi355x.h "beam cache indirection"): beam_src uint8 [N, t_max] -- beam_src[b, t] = the cache row that holds position t
         of beam b's history --, beam_common int32 [1] -- the columns below it are equal in all rows -- and the workspace of
         gptq_decode_attn_beam_f16, which every layer of the beam step calls instead of the batch attention (the shared trunk is streamed once
@@ -301,6 +309,9 @@ class DecodeEngine:
         if spec_sample and not (self.chunk or self.batch_chunk):
             raise ValueError('DecodeEngine: spec_sample needs batch_chunk = R (a chunk engine always samples speculatively)')
         self.spec_sample = bool(spec_sample or self.chunk)
+        self.tree = bool(tree)
+        if self.tree and not self.chunk:
+            raise ValueError('DecodeEngine: tree needs chunk = R (one sequence; batched trees are not built yet)')
         self.logits_process = bool(logits_process)
         if self.logits_process and (self.chunk or self.batch_chunk):
             raise ValueError('DecodeEngine: logits_process together with chunk / batch_chunk is not built yet (processors under speculation)')
@@ -459,6 +470,12 @@ class DecodeEngine:
         self.chunk_rows = self.chunk or self.batch_chunk           # R of the verify step, whichever argument asked for it (0: none)
         if self.chunk_rows:
             self._chunk_buffers()
+        if self.tree:
+            self.tree_anc = torch.ones(MAX_BATCH, dtype=torch.int32, device=dev)     # (uint32 bits: every node its own root until set_tree)
+            self.tree_parent = torch.full((self.chunk,), -1, dtype=torch.int32, device=dev)
+            self.tree_path = torch.zeros(MAX_BATCH, dtype=torch.int32, device=dev)
+            self.tree_tok = self.chunk_ids
+            self.tree_graph = None
 
     verify_batch_graph = property(lambda self: self.verify_graph, doc='the ONE verify-greedy graph under the name capture_verify_greedy_batch stores it')
 
@@ -1629,7 +1646,8 @@ class DecodeEngine:
         self.spec_ws = torch.zeros(self.lib.gptq_spec_sample_batch_workspace_bytes(B, R) // 8, dtype=torch.int64, device=dev)
 
     def _step_chunk(self):
-        """_step_rows at M = B R: row b R + r is token r of sequence b (chunk_ids[b, r] at position pos[b] + r); gptq_decode_attn_chunk_batch_f16 on
+        """(a tree engine: the R rows are the nodes of the tree in tree_anc, through gptq_decode_attn_tree_f16 -- nothing else differs)
+        _step_rows at M = B R: row b R + r is token r of sequence b (chunk_ids[b, r] at position pos[b] + r); gptq_decode_attn_chunk_batch_f16 on
         kcb[li] / vcb[li] with pos as the DEVICE positions (pos[b] < 0: sequence b idles), the LM head for B R rows into chunk_logits (above 16
         rows: the stand-alone norm + the library matmul of lm_head_logits).  Does not advance pos."""
         slot_stride = self.kcb.stride(1)
@@ -1640,11 +1658,21 @@ class DecodeEngine:
                                                            self.chunk_attn_ws.data_ptr(), self.chunk_attn_ws.numel(), self.heads, self.head_dim,
                                                            self.t_max, L['theta'], self.scale, self.native.ptr(tab), s)
             self.native.check(rc, 'gptq_decode_attn_chunk_batch_f16')
-        self._step_rows(self.chunk_bufs, self.chunk_ids.view(-1), attn, self.chunk_logits)
 
-    def _need_chunk(self, what, batched=False):
+        def attn_tree(li, L, qkvb, ab, tab, s):
+            rc = self.lib.gptq_decode_attn_tree_f16(qkvb.data_ptr(), qkvb.stride(0), self.chunk, self.pos.data_ptr(), self.tree_anc.data_ptr(),
+                                                    self.kc[li].data_ptr(), self.vc[li].data_ptr(), ab.data_ptr(), ab.stride(0),
+                                                    self.chunk_attn_ws.data_ptr(), self.chunk_attn_ws.numel(), self.heads, self.head_dim,
+                                                    self.t_max, L['theta'], self.scale, self.native.ptr(tab), s)
+            self.native.check(rc, 'gptq_decode_attn_tree_f16')
+        self._step_rows(self.chunk_bufs, self.chunk_ids.view(-1), attn_tree if self.tree else attn, self.chunk_logits)
+
+    def _need_chunk(self, what, batched=False, tree=False):
         if not (self.batch_chunk if batched else self.chunk):
             raise ValueError('DecodeEngine.%s: the engine was built without %s=R' % (what, 'batch_chunk' if batched else 'chunk'))
+        if self.tree != tree:
+            raise ValueError('DecodeEngine.%s: %s' % (what, 'the engine was built without tree=True' if tree else
+                                                      'an engine built with tree=True verifies trees only (set_tree, verify_tree)'))
 
     def _chunks_fit(self, what, active=None):
         """ValueError unless positions pos[b] .. pos[b] + R - 1 fit the cache for every sequence b -- of `active` (a list of B flags) when given,
@@ -1761,6 +1789,74 @@ class DecodeEngine:
         """batch_chunk = R.  capture_verify_greedy for the B sequences -- the same step, the same stored graph (verify_batch_graph reads it) --
         where only an active sequence's warm-up chunk has to fit; engine_generate_batch captures at pos = 0, in front of the prefill."""
         self.verify_graph = self._capture_verify('capture_verify_greedy_batch', self._verify_greedy_step, batched=True)
+        return self
+
+    # -- a draft TREE in the R rows of the verify step (tree=True): the nodes' attention masks in tree_anc, the accept walk and the compaction of the
+    # -- accepted path on the device -----------------------------------------------------------------------------------------------------------
+    def set_tree(self, tokens, parents):
+        """tokens: 1 .. R ids, node 0 the last accepted token (the root), the others drafts; parents: as many ints, parents[r] the node whose
+        continuation node r is -- parents[0] = -1 and 0 <= parents[r] < r (topological order).  Uploads chunk_ids, tree_parent and the ancestor
+        masks tree_anc; unused rows are copies of the root that nothing descends from.  ValueError, with nothing uploaded, for anything else."""
+        self._need_chunk('set_tree', tree=True)
+        R = self.chunk
+        tok = [int(t) for t in (tokens.reshape(-1).tolist() if torch.is_tensor(tokens) else list(tokens))]
+        par = [int(q) for q in (parents.reshape(-1).tolist() if torch.is_tensor(parents) else list(parents))]
+        if not 1 <= len(tok) <= R or len(par) != len(tok):
+            raise ValueError('DecodeEngine.set_tree: 1 .. %d tokens and as many parents, not %d and %d' % (R, len(tok), len(par)))
+        if par[0] != -1 or any(not 0 <= q < r for r, q in enumerate(par) if r):
+            raise ValueError('DecodeEngine.set_tree: parents[0] must be -1 and 0 <= parents[r] < r (topological order), not %r' % (par,))
+        anc = [1] * MAX_BATCH
+        for r in range(1, len(tok)):
+            anc[r] = anc[par[r]] | (1 << r)
+        pad = R - len(tok)
+        with torch.no_grad():
+            self.chunk_ids.copy_(torch.tensor(tok + [tok[0]] * pad, dtype=torch.int64))
+            self.tree_parent.copy_(torch.tensor(par + [-1] * pad, dtype=torch.int32))
+            self.tree_anc.copy_(torch.tensor(anc, dtype=torch.int32))
+        return self
+
+    def verify_tree(self):
+        """the eager verify step of the tree set_tree uploaded: node r at cache row pos + r, rotated at pos + its depth, attending to the
+        history and its ancestors.  Returns chunk_logits (the static buffer: clone it to keep it): row r is the distribution after the path
+        from the root to node r.  pos is unchanged and no cache row moves: accept_tree does both.  ValueError, with nothing launched, when the
+        R rows do not fit the cache."""
+        self._need_chunk('verify_tree', tree=True)
+        self._chunks_fit('verify_tree')
+        with torch.no_grad(), torch.cuda.device(self.dev):
+            self._step_chunk()
+        return self.chunk_logits
+
+    def _tree_accept(self):
+        """the rows' argmax, gptq_tree_accept_greedy -- tree_path, verify_out = [a, the a + 1 tokens the step emits, copies], pos += a + 1 -- and
+        gptq_kv_tree_compact_f16: the accepted path's cache rows of every layer become rows pos .. pos + a"""
+        best = torch.argmax(self.chunk_logits, dim=-1)
+        s = self.native.stream_ptr(self.dev)
+        with self.native.on_device(self.dev):
+            rc = self.lib.gptq_tree_accept_greedy(self.chunk_ids.data_ptr(), self.tree_parent.data_ptr(), best.data_ptr(), self.chunk,
+                                                  self.pos.data_ptr(), self.verify_out.data_ptr(), self.tree_path.data_ptr(), s)
+            self.native.check(rc, 'gptq_tree_accept_greedy')
+            rc = self.lib.gptq_kv_tree_compact_f16(self.kc.data_ptr(), self.vc.data_ptr(), self.kc.shape[0], self.t_max, self.hidden, self.kcb.stride(0),
+                                                   self.pos.data_ptr(), self.verify_out.data_ptr(), self.tree_path.data_ptr(), s)
+            self.native.check(rc, 'gptq_kv_tree_compact_f16')
+
+    def accept_tree(self):
+        """behind verify_tree: the greedy accept walk and the compaction, eagerly.  Returns verify_out (the static buffer)"""
+        self._need_chunk('accept_tree', tree=True)
+        with torch.no_grad(), torch.cuda.device(self.dev):
+            self._tree_accept()
+        return self.verify_out
+
+    def _verify_tree_greedy_step(self):
+        self._step_chunk()
+        self._tree_accept()
+
+    def capture_verify_tree_greedy(self):
+        """capture_verify_greedy for a tree engine: ONE hipGraph (tree_graph) of the chunk step with the tree attention per layer, the rows'
+        argmax, the accept walk and the compaction.  tree_anc, tree_parent and chunk_ids are read on the device: a replay verifies whatever
+        set_tree uploaded last, at the device position, and advances it; the host downloads verify_out once per step."""
+        self._need_chunk('capture_verify_tree_greedy', tree=True)
+        self._chunks_fit('capture_verify_tree_greedy')
+        self.tree_graph = self._capture(self._verify_tree_greedy_step, (self.pos, self.chunk_ids))
         return self
 
     # -- speculative SAMPLING: the verify step followed by the accept / resample rule of gptq_spec_sample_batch_f16 (csrc/spec_sample.hip), for the
@@ -1911,7 +2007,7 @@ class DecodeEngine:
 
     def graph_for(self, kind, draft_logits=False):
         """THE place that hands out the graphs of the generation drivers: the captured graph of `kind` -- 'greedy' (batch 1: capture_greedy),
-        'greedy_rows', 'sample_native', 'verify_greedy', 'verify_sample' (draft_logits: the one that reads the draft model's logits rows), 'beam' --,
+        'greedy_rows', 'sample_native', 'verify_greedy', 'verify_tree_greedy', 'verify_sample' (draft_logits: the one that reads the draft model's logits rows), 'beam' --,
         captured by the public capture_* method on first use.  A capture warms up with a real step, which writes the cache rows at pos: pos is
         put to 0 first, so that the step fits whatever an earlier sequence left there.  A driver therefore asks for EVERY graph it will need
         BEFORE its prompt enters the cache: behind a prompt, the warm-up step at position 0 would overwrite the prompt's first cache row, and
@@ -1922,6 +2018,7 @@ class DecodeEngine:
             'greedy_rows': (lambda: self.greedy_rows_graph, self.capture_greedy_rows),
             'sample_native': (lambda: self.sample_native_graph, self.capture_sample_native),
             'verify_greedy': (lambda: self.verify_graph, self.capture_verify_greedy_batch if self.batch_chunk else self.capture_verify_greedy),
+            'verify_tree_greedy': (lambda: self.tree_graph, self.capture_verify_tree_greedy),
             'verify_sample': (lambda: self.verify_sample_graphs.get(with_q), lambda: (
                 self.capture_verify_sample_batch if self.batch_chunk else self.capture_verify_sample)(draft_logits=with_q)),
             'beam': (lambda: self.beam_graph, self.capture_beam_step),
@@ -2083,11 +2180,66 @@ def prompt_lookup_draft(tokens, k, max_ngram=3):
     return out
 
 
+def prompt_lookup_tree_draft(tokens, nodes, max_ngram=3, width=3):
+    """Draft a TREE for speculative decoding from the sequence itself: the longest suffix of n <= max_ngram tokens that occurred earlier, up to
+    `width` of its earlier occurrences with distinct continuations (most recent first), and those continuations merged into a trie below the
+    last token -- longest continuation first, ties to the more recent one, level by level so that every branch gets its share of the at most
+    nodes - 1 drafts.  Returns (draft tokens, parents): draft i is node i + 1 of the tree, parents[i] its parent's node (0: the root, the last
+    token), in topological order; what DecodeEngine.set_tree takes behind the root.  With fewer than two such continuations it is the chain of
+    prompt_lookup_draft(tokens, nodes - 1, max_ngram).  Pure host code."""
+    seq = list(tokens) if isinstance(tokens, list) else [int(t) for t in (tokens.tolist() if hasattr(tokens, 'tolist') else tokens)]
+    k, max_ngram, width = int(nodes) - 1, int(max_ngram), int(width)
+    if not seq or k < 0 or max_ngram < 1 or width < 1:
+        raise ValueError('prompt_lookup_tree_draft: needs a non-empty sequence, nodes >= 1, max_ngram >= 1 and width >= 1')
+    L, runs = len(seq), []
+    for n in range(min(max_ngram, L - 1), 0, -1):
+        tail = seq[L - n:]
+        for e in range(L - 1, n - 1, -1):                        # e: one behind the occurrence's last token, most recent first
+            if seq[e - n:e] == tail and seq[e:e + k] not in runs:
+                runs.append(seq[e:e + k])
+                if len(runs) == width:
+                    break
+        if runs:
+            break
+    if len(runs) < 2 or k < 2:
+        return prompt_lookup_draft(seq, k, max_ngram), list(range(k))
+    runs.sort(key=len, reverse=True)                             # (stable: the more recent of two equally long ones stays in front)
+    toks, parents, at = [], [], [0] * len(runs)                  # at[b]: the node run b has reached
+    for d in range(k):
+        for b, run in enumerate(runs):
+            if d < len(run) and len(toks) < k:
+                kids = [i + 1 for i, q in enumerate(parents) if q == at[b] and toks[i] == run[d]]
+                if not kids:
+                    toks.append(run[d])
+                    parents.append(at[b])
+                    kids = [len(toks)]
+                at[b] = kids[0]
+            elif d < len(run):
+                at[b] = -1                                       # the budget ended above this run's next node: nothing hangs below it
+    return toks, parents
+
+
+def _speculate_tree(speculate, what):
+    """the key `tree` of `speculate`: None, or dict(width=3) -- prompt_lookup_tree_draft's width; a `draft` callable may then return (tokens,
+    parents) as that function does"""
+    tree = speculate.get('tree')
+    if tree is None:
+        return None
+    if tree is True:
+        tree = {}
+    width = tree.get('width', 3) if isinstance(tree, dict) and not set(tree) - {'width'} else None
+    if isinstance(width, bool) or not isinstance(width, int) or width < 1:
+        raise ValueError('%s: speculate tree must be True or dict(width=<positive int>), not %r' % (what, speculate.get('tree')))
+    if speculate.get('sample') is not None or speculate.get('draft_model') is not None:
+        raise ValueError('%s: speculate tree together with sample or draft_model is not built yet (greedy, host drafts)' % what)
+    return dict(width=width)
+
+
 def _speculate_settings(speculate, what='engine_generate'):
     """the `speculate` argument of `what` (engine_generate / engine_generate_batch): (k, max_ngram, draft) -- every key optional"""
     if not isinstance(speculate, dict):
         raise ValueError('%s: speculate must be None or a dict with the keys k, max_ngram, draft' % what)
-    unknown = sorted(set(speculate) - {'k', 'max_ngram', 'draft', 'sample', 'draft_model'})
+    unknown = sorted(set(speculate) - {'k', 'max_ngram', 'draft', 'sample', 'draft_model', 'tree'})
     if unknown:
         raise ValueError('%s: unknown speculation keys %r' % (what, unknown))
     k, max_ngram, draft = speculate.get('k', 4), speculate.get('max_ngram', 3), speculate.get('draft')
@@ -2118,7 +2270,8 @@ def _speculate_sampling(speculate, model, what):
 
 def _generation_settings(what, model, sample, speculate, engine):
     """what the arguments sample= / speculate= / engine= of `what` (engine_generate / engine_generate_batch) ask for, validated ONCE for both:
-    (sampling settings or None, processor settings or None, (k, max_ngram, draft, sampling settings or None, draft model or None) or None)"""
+    (sampling settings or None, processor settings or None, (k, max_ngram, draft, sampling settings or None, draft model or None, tree settings
+    or None) or None)"""
     settings = None if sample is None else _sampling_settings(what, sample)
     proc = None if sample is None else _process_settings(sample)
     spec = None
@@ -2126,7 +2279,7 @@ def _generation_settings(what, model, sample, speculate, engine):
         if sample is not None:
             raise ValueError('%s: speculate and the sample argument exclude each other (speculative sampling: the key sample inside '
                              'speculate)' % what)
-        spec = _speculate_settings(speculate, what) + _speculate_sampling(speculate, model, what)
+        spec = _speculate_settings(speculate, what) + _speculate_sampling(speculate, model, what) + (_speculate_tree(speculate, what),)
     if engine is not None and proc is not None and not engine.logits_process:
         raise ValueError('%s: %s need an engine built with logits_process=True' % (what, ', '.join(sorted(proc))))
     return settings, proc, spec
@@ -2167,6 +2320,21 @@ def _host_drafts(what, eng, k, max_ngram, draft):
                 raise ValueError('%s: the draft returned %d ids for k = %d' % (what, len(d), k))
             ids.append([0 if idle else seq[-1]] + d)
         eng.chunk_ids.view(len(seqs), k + 1).copy_(torch.tensor(ids, dtype=torch.int64))
+    return fill
+
+
+def _tree_drafts(what, eng, k, max_ngram, draft, width):
+    """the draft source of a TREE engine (one sequence): draft(tokens_so_far, k) -> (at most k draft tokens, their parents) as
+    prompt_lookup_tree_draft returns them (the default), or k ids, a chain; DecodeEngine.set_tree validates and uploads"""
+    if draft is None:
+        draft = lambda toks, m: prompt_lookup_tree_draft(toks, m + 1, max_ngram, width)
+
+    def fill(seqs, done):
+        d = draft(seqs[0], k)
+        toks, parents = d if isinstance(d, tuple) else (d, list(range(len(d))))
+        if len(toks) > k:
+            raise ValueError('%s: the draft returned %d ids for k = %d' % (what, len(toks), k))
+        eng.set_tree([seqs[0][-1]] + [int(t) for t in toks], [-1] + [int(q) for q in parents])
     return fill
 
 
@@ -2266,15 +2434,18 @@ def _generate_speculative(eng, prompts, first, max_new_tokens, eos_token_id, k, 
     return gens, stats
 
 
-def _speculate_rows(what, eng, prompts, into, max_new_tokens, eos_token_id, k, max_ngram, draft, settings, draft_model):
+def _speculate_rows(what, eng, prompts, into, max_new_tokens, eos_token_id, k, max_ngram, draft, settings, draft_model, tree=None):
     """_generate_rows with speculation: what _generate_speculative needs for the n sequences of a chunk (n = 1) or batch_chunk engine.
     settings None: the verify-greedy graph, the first tokens by argmax, the capture_greedy_rows graph for the tail.  settings (one value for all
     or one per prompt): the verify-sample graph -- with the draft model's logits rows when a draft model is given, point-mass drafts otherwise
-    --, the first tokens by sample_logits, the tail by the capture_sample_native graph.
+    --, the first tokens by sample_logits, the tail by the capture_sample_native graph.  tree (dict(width)): the verify-tree-greedy graph of a
+    tree engine, fed by _tree_drafts.
     draft_model: _model_drafts on a DecodeEngine of this batch, under the same settings (greedily without them); else _host_drafts.
     Afterwards every position is that of the sequence's last token, the one not consumed yet, and eng.spec_stats describes the run."""
     n = len(prompts)
-    if settings is None:
+    if tree is not None:                                         # (greedy, host drafts: _speculate_tree refused the rest)
+        graph, tail = eng.graph_for('verify_tree_greedy'), eng.graph_for('greedy_rows')
+    elif settings is None:
         graph, tail = eng.graph_for('verify_greedy'), eng.graph_for('greedy_rows')
     else:
         eng.set_sampling(**settings)                             # (validates before anything changes)
@@ -2285,6 +2456,8 @@ def _speculate_rows(what, eng, prompts, into, max_new_tokens, eos_token_id, k, m
     if deng is not None:
         into(deng)
         drafts = _model_drafts(eng, deng, k, [int(p.numel()) for p in prompts])
+    elif tree is not None:
+        drafts = _tree_drafts(what, eng, k, max_ngram, draft, tree['width'])
     else:
         drafts = _host_drafts(what, eng, k, max_ngram, draft)
 
@@ -2444,6 +2617,11 @@ def engine_generate(model, input_ids, max_new_tokens, eos_token_id=None, engine=
     processors under speculation are not built yet.  speculate=dict(..., draft_model=<fused model of the same vocabulary>) drafts with a MODEL:
     a DecodeEngine of its own (kept on the engine) draws the k tokens under the same setting and hands its logits rows to the verify step;
     without `sample` it drafts greedily and the verify-greedy graph checks it.
+    speculate=dict(k, tree=dict(width=3)) verifies a draft TREE of up to k nodes per step on an engine with chunk = k + 1 and tree=True:
+    prompt_lookup_tree_draft merges the continuations of up to `width` earlier occurrences of the suffix into a trie, the
+    capture_verify_tree_greedy graph verifies every branch in the one pass, walks the greedy accept rule down the tree and makes the accepted
+    branch's cache rows contiguous; `draft` may return (tokens, parents) as that function does.  Same tokens, return value and stats.  Greedy,
+    host drafts, one prompt: ValueError together with sample or draft_model, and from engine_generate_batch.
     logprobs = K (0 .. 32; None, the default: the call as it always was) returns (sequences, info): info is a dict on the device of the returned
     ids with, for the n generated tokens -- the first one included, cut after the first eos exactly as the tokens are, the eos entry kept --,
     token_logprobs float [n] (the log-probability of each token), ranks int32 [n] (its 0-based place among the vocabulary by (logit
@@ -2477,12 +2655,14 @@ def engine_generate(model, input_ids, max_new_tokens, eos_token_id=None, engine=
     if spec is not None and engine is not None and (engine.batch != 1 or engine.chunk != spec[0] + 1):
         raise ValueError('engine_generate: speculate k = %d needs an engine of batch 1 with chunk = %d (this one: batch %d, chunk %d)' % (
             spec[0], spec[0] + 1, engine.batch, engine.chunk))
+    if spec is not None and engine is not None and engine.tree != (spec[5] is not None):
+        raise ValueError('engine_generate: speculate with tree= needs an engine built with tree=True, and one without needs one built without')
     if input_ids.dim() != 2 or input_ids.shape[0] != 1:
         raise ValueError('engine_generate: batch 1 only')
     if engine is not None:
         eng = engine
     elif spec is not None:
-        eng = DecodeEngine(model, t_max=t_max, chunk=spec[0] + 1)
+        eng = DecodeEngine(model, t_max=t_max, chunk=spec[0] + 1, tree=spec[5] is not None)
     else:
         eng = DecodeEngine(model, t_max=t_max, logits_process=proc is not None, logprobs=logprobs, constrain=_constrain_capacity(dfas),
                            kv_cache=kv_cache)
@@ -2530,6 +2710,8 @@ def engine_generate_batch(model, prompts, max_new_tokens, eos_token_id=None, eng
     logprobs = _logprobs_setting(what, logprobs, speculate, engine)
     dfas = _constrain_setting(what, constrain, len(prompts), speculate, engine)
     _kv_cache_setting(what, kv_cache, speculate, engine)
+    if spec is not None and spec[5] is not None:
+        raise ValueError('engine_generate_batch: speculate tree= is not built yet for several prompts (engine_generate takes it)')
     sampled = spec is not None and (spec[3] is not None or spec[4] is not None)
     if sampled and engine is not None and not engine.spec_sample:
         raise ValueError('engine_generate_batch: speculate with sample or draft_model needs an engine built with spec_sample=True')

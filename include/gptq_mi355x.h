@@ -710,6 +710,42 @@ int gptq_decode_attn_chunk_batch_f16(const void *qkv, int64_t ldq, int seqs, int
                                      int64_t slot_stride, void *out, int64_t ldo, void *workspace, size_t workspace_bytes, int heads, int head_dim,
                                      int t_max, float base, float scale, const float *rope_table, gptq_stream_t stream);
 
+/* ---- tree speculative decoding: the verify step of a draft TREE (csrc/chunk_attn.hip TREE instances, csrc/tree.hip) --------------------------------
+ * gptq_decode_attn_tree_f16: the contract, workspace, split rule and validation of gptq_decode_attn_chunk_f16 for one sequence, with one more DEVICE
+ * argument.  The `rows` (1 .. 16) rows are the NODES of a tree: node 0 is the root (the last accepted token), the others are drafts in TOPOLOGICAL
+ * order (an ancestor's index is below its descendant's).  anc [16] uint32 in device memory: bit j of anc[r] is set iff node j is node r or an
+ * ancestor of it (anc[0] = 1; bits 16 .. 31 are ignored; all 16 words are read, entries at and beyond rows mean nothing).  Node r has depth
+ * d_r = popcount(anc[r] & 0xffff) - 1.  Its q and k are rotated at position p + d_r and its k / v go to cache row p + r -- the slot is by node, the
+ * angle by depth --; out[r] = softmax over the history [0, p) and the cache rows p + j of the set bits j of anc[r].  Nothing of a node outside
+ * anc[r] reaches row r -- not its NaN either: a node's non-finite v values are read as +0 (weight 0 times NaN would pass the mask).  anc and *position are read on the device: one captured graph serves every tree shape and position.
+ * The chain anc[r] = (2 << r) - 1 gives cache rows and output rows bit-identical to gptq_decode_attn_chunk_f16.
+ * p < 0 or p >= t_max: an idle call.  A node with p + r >= t_max is skipped, and so, by the topological order, are its descendants; the nodes
+ * that fit are served.  Validated like the chunk entry, anc among GPTQ_E_NULL and aligned to 8 bytes.
+ *
+ * gptq_tree_accept_greedy (one wave, no atomics: the same inputs give the same bits): tokens [rows] int64 the nodes' tokens, parent [rows] int32
+ * their parents (parent[0] is not read), best [rows] int64 the argmax of every node's logits row.  From the root, at node n the walk takes the
+ * LOWEST-INDEX child c (parent[c] == n, c > n) with tokens[c] == best[n] and ends where there is none, after a accepted drafts.  Written:
+ * path [16] int32 -- the node per accepted depth, path[0] = 0, -1 beyond a --; out [rows + 1] int64 = [a, best[path[0]], .., best[path[a]],
+ * copies of the last] -- the row the chain's verify step gives: the a + 1 tokens the step emits are the accepted drafts and the bonus token --;
+ * *position += a + 1.  GPTQ_E_NULL (any pointer), GPTQ_E_SHAPE (rows outside 1 .. 16), GPTQ_E_ALIGN (int64 arrays 8 bytes, int32 arrays 4).
+ *
+ * gptq_kv_tree_compact_f16: the accepted path becomes a contiguous sequence.  Caches [layers][t_max][row_elems] fp16 of one sequence (layer l at
+ * + l layer_stride elements).  *position is the position BEHIND the accept, a = *accepted (out[0] of the accept) and path as the accept wrote
+ * them, all read on the device: the root sits at row p = *position - a - 1, and for i = 1 .. a cache row p + path[i] moves to row p + i, K and V,
+ * every layer, in ONE launch.  One thread owns a 16-byte column of the rows: it loads every row that moves and then stores them; path[i] >= i,
+ * so no row is read behind its overwrite.  A chain (path[i] = i) or a = 0 stores nothing.  Afterwards rows p + 1 .. p + a hold what a
+ * token-by-token feed of the accepted tokens writes (a node's rotation was by its depth, which is its final position).  A record the accept
+ * cannot have written (a outside 0 .. 15, a path that does not ascend, a row outside the cache) moves nothing.  GPTQ_E_NULL (any pointer),
+ * GPTQ_E_SHAPE (layers < 1, t_max < 1, row_elems not a positive multiple of 8, layer_stride < t_max row_elems or not a multiple of 8),
+ * GPTQ_E_ALIGN (caches 16 bytes, position / accepted 8, path 4). */
+int gptq_decode_attn_tree_f16(const void *qkv, int64_t ldq, int rows, const int64_t *position, const uint32_t *anc, void *k_cache, void *v_cache,
+                              void *out, int64_t ldo, void *workspace, size_t workspace_bytes, int heads, int head_dim, int t_max, float base,
+                              float scale, const float *rope_table, gptq_stream_t stream);
+int gptq_tree_accept_greedy(const int64_t *tokens, const int32_t *parent, const int64_t *best, int rows, int64_t *position, int64_t *out,
+                            int32_t *path, gptq_stream_t stream);
+int gptq_kv_tree_compact_f16(void *k_cache, void *v_cache, int layers, int t_max, int row_elems, int64_t layer_stride, const int64_t *position,
+                             const int64_t *accepted, const int32_t *path, gptq_stream_t stream);
+
 /* ---- scoring: the LM head of MANY rows with the cross-entropy inside (reference llama.py:241-258: lm_head over all rows of a segment, shifted
  * labels, CrossEntropyLoss) -- the [M, N] logits never exist in memory.
  *   x [M, K] (ldx)       fp16, the already normalised hidden rows
