@@ -1920,4 +1920,17 @@ int gptq_solver_block_f32(const float *W, int64_t ldw, const float *Hinv, int64_
                              (hipStream_t)stream);
 }
 
+// ---- GPTQ solver: the calibration Hessian of one batch (hessian.hip) ----
+int gptq_hessian_update_f16(const void *x, int64_t ldx, int tokens, int k, float *H, int64_t ldh, float decay, float weight, gptq_stream_t stream) {
+    if (!x || !H) return GPTQ_E_NULL;
+    if (tokens < 1 || k < 8 || k % 8 != 0 || ldx < k || ldh < k) return GPTQ_E_SHAPE;
+    int64_t xspan, hspan;                                        // the kernel's offsets are int64; its grid is 8 ceil(tiles / 8) workgroups
+    if (__builtin_mul_overflow((int64_t)tokens, ldx, &xspan) || __builtin_mul_overflow((int64_t)k, ldh, &hspan)) return GPTQ_E_SHAPE;
+    if (xspan > INT64_MAX / 2 || hspan > INT64_MAX / 4) return GPTQ_E_SHAPE;   // ... of bytes
+    const int64_t nt = ((int64_t)k + 127) / 128;
+    if (nt * (nt + 1) / 2 + 7 > INT_MAX) return GPTQ_E_SHAPE;
+    if (!aligned(x, 16) || !aligned(H, 16) || ldx % 8 != 0 || ldh % 4 != 0) return GPTQ_E_ALIGN;
+    return hessian_update_launch((const half_t *)x, ldx, tokens, k, H, ldh, decay, weight, (hipStream_t)stream);
+}
+
 }  // extern "C"

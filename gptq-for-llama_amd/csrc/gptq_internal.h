@@ -248,6 +248,9 @@ int gptq_block_launch(const float *W, int64_t ldw, const float *Hinv, int64_t ld
                       const float *scale, const float *zero, int64_t ldg, float *Q, int64_t ldq, float *Err, int64_t lde, float *loss_rows,
                       hipStream_t s);
 
+// hessian.hip: H <- decay H + weight X^T X in place (x fp16 [tokens][k], H fp32 [k][k] symmetric; the tiles i <= j are read, both triangles written)
+int hessian_update_launch(const half_t *x, int64_t ldx, int tokens, int k, float *H, int64_t ldh, float decay, float weight, hipStream_t s);
+
 int decode_rope_kv_launch(half_t *qkv, const int64_t *pos, half_t *kc, half_t *vc, int heads, int head_dim, int t_max, float base,
                           hipStream_t s);
 int decode_attn_launch(const half_t *q, const half_t *kc, const half_t *vc, const int64_t *pos, half_t *out, float *ws, int heads,

@@ -3,7 +3,11 @@
 unchanged.  It is the caller that produces the integer weights ``QuantLinear.pack`` packs.
 
 What runs where:
-  * Hessian accumulation (reference gptq.py:71-96): one fp32 GEMM per calibration batch on the GPU (torch).
+  * Hessian accumulation (reference gptq.py:71-96): fp16 activations of an ``nn.Linear`` whose width is a multiple of 8 -- what
+    ``llama.py``'s hooks deliver -- take ONE hand-written HIP launch per calibration batch (``gptq_hessian_update_f16``,
+    csrc/hessian.hip): H <- n/(n+b) H + 2/(n+b) X^T X in place, exact fp16 products on the matrix core, only the tiles on and above
+    the diagonal computed and mirrored (H is bit-symmetric), no upcast or transposed copy of X.  Every other input (fp32 or bf16
+    activations, Conv2d / Conv1D layers, odd widths) keeps the reference's route: one fp32 GEMM per batch (torch).
   * damping + Hinv = chol(chol_inv(chol(H)), upper) (gptq.py:157-163): torch.linalg (rocSOLVER).
   * the sequential quantise / error-feedback loop over the columns of a block (gptq.py:177-199) -- ~10 dependent
     torch launches per column in the reference -- is ONE hand-written HIP launch per block
@@ -106,11 +110,25 @@ class GPTQ:
         else:
             if inp.dim() == 3:
                 inp = inp.reshape((-1, inp.shape[-1]))
+            if (isinstance(self.layer, nn.Linear) and inp.dtype == torch.float16 and inp.is_cuda and inp.dim() == 2
+                    and inp.shape[0] > 0 and inp.shape[1] % 8 == 0):
+                self._add_batch_native(inp, batch)
+                return
             inp = inp.t()
         self.H *= self.nsamples / (self.nsamples + batch)
         self.nsamples += batch
         x = math.sqrt(2 / self.nsamples) * inp.float()
         self.H.addmm_(x, x.t())
+
+    def _add_batch_native(self, x, batch):
+        """the same running mean in one launch: H <- n/(n+b) H + 2/(n+b) X^T X on the fp16 rows x [tokens, columns]"""
+        x = x.contiguous()
+        n = self.nsamples
+        with _native.on_device(self.dev):
+            rc = _native.lib().gptq_hessian_update_f16(x.data_ptr(), x.shape[1], x.shape[0], x.shape[1], self.H.data_ptr(), self.columns,
+                                                       n / (n + batch), 2 / (n + batch), _native.stream_ptr(self.dev))
+        _native.check(rc, 'gptq_hessian_update_f16')
+        self.nsamples = n + batch
 
     # -----------------------------------------------------------------------------------------
     def _report(self, name, q_weight, weight_error, seconds):

@@ -99,6 +99,8 @@ _SIGNATURES = {
                              c_float, c_void_p],
     'gptq_solver_block_f32': [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int64,
                               c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p],
+    # ... and its calibration Hessian: H <- decay H + weight X^T X for one fp16 batch, the upper tiles only, mirrored (csrc/hessian.hip)
+    'gptq_hessian_update_f16': [c_void_p, c_int64, c_int, c_int, c_void_p, c_int64, c_float, c_float, c_void_p],
     'gptq_stripe_bytes': [c_int, c_int, c_int, c_int, c_int],
     'gptq_stripe_repack': [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_int,
                            c_void_p],

@@ -1047,6 +1047,18 @@ int gptq_solver_block_f32(const float *W, int64_t ldw, const float *Hinv, int64_
                           int groupsize, int maxq, const float *scale, const float *zero, int64_t ldg, float *Q, int64_t ldq,
                           float *Err, int64_t lde, float *loss_rows, gptq_stream_t stream);
 
+/* The calibration Hessian of one batch (reference gptq.py:71-96): H <- decay H + weight X^T X, in place.
+ *   x [tokens, k] fp16 (ldx)  the activations of the batch as the layer saw them, tokens >= 1, k >= 8 and a multiple of 8
+ *   H [k, k] fp32 (ldh)       symmetric on entry (only its 128 x 128 tiles with i <= j are read; decay == 0 reads nothing) and bit-symmetric
+ *                             on exit: both triangles are written and H[j][i] has the bits of H[i][j]
+ * The running mean of 2 X^T X over n + b samples is decay = n / (n + b), weight = 2 / (n + b).  Products of fp16 values are exact in the
+ * fp32 accumulators (v_mfma_f32_32x32x16_f16); the scale is applied once, to the sum.  One launch, no workspace, no atomics, the same
+ * bits on every call.  Elements of a row of H beyond k (ldh > k) are not touched.
+ * Validated before the launch: GPTQ_E_NULL (x, H), GPTQ_E_SHAPE (tokens < 1, k < 8, k % 8 != 0, ldx < k, ldh < k, tokens ldx or k ldh
+ * beyond int64, more tiles than a grid holds), GPTQ_E_ALIGN (x / H 16 bytes, ldx a multiple of 8, ldh a multiple of 4). */
+int gptq_hessian_update_f16(const void *x, int64_t ldx, int tokens, int k, float *H, int64_t ldh, float decay, float weight,
+                            gptq_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
