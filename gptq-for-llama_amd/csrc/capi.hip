@@ -1933,4 +1933,17 @@ int gptq_hessian_update_f16(const void *x, int64_t ldx, int tokens, int k, float
     return hessian_update_launch((const half_t *)x, ldx, tokens, k, H, ldh, decay, weight, (hipStream_t)stream);
 }
 
+// ---- GPTQ solver: the inverse Hessian factor (hinv_factor.hip) ----
+int gptq_hinv_factor_f32(float *A, int64_t lda, int n, float *U, int64_t ldu, int32_t *info, gptq_stream_t stream) {
+    if (!A || !U || !info) return GPTQ_E_NULL;
+    if (n < 128 || n % 128 != 0 || lda < n || ldu < n) return GPTQ_E_SHAPE;
+    int64_t aspan, uspan;                                        // the kernels' offsets are int64; the trailing grid is 8 ceil(tiles / 8) workgroups
+    if (__builtin_mul_overflow((int64_t)n, lda, &aspan) || __builtin_mul_overflow((int64_t)n, ldu, &uspan)) return GPTQ_E_SHAPE;
+    if (aspan > INT64_MAX / 4 || uspan > INT64_MAX / 4) return GPTQ_E_SHAPE;   // ... of bytes
+    const int64_t nb = n / 128;
+    if (nb * (nb + 1) / 2 + 7 > INT_MAX) return GPTQ_E_SHAPE;
+    if (!aligned(A, 16) || !aligned(U, 16) || lda % 4 != 0 || ldu % 4 != 0 || !aligned(info, 4)) return GPTQ_E_ALIGN;
+    return hinv_factor_launch(A, lda, n, U, ldu, info, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -251,6 +251,9 @@ int gptq_block_launch(const float *W, int64_t ldw, const float *Hinv, int64_t ld
 // hessian.hip: H <- decay H + weight X^T X in place (x fp16 [tokens][k], H fp32 [k][k] symmetric; the tiles i <= j are read, both triangles written)
 int hessian_update_launch(const half_t *x, int64_t ldx, int tokens, int k, float *H, int64_t ldh, float decay, float weight, hipStream_t s);
 
+// hinv_factor.hip: U upper triangular with U^T U = A^-1 (A fp32 [n][n], upper triangle read, destroyed; n a multiple of 128; *info as LAPACK's)
+int hinv_factor_launch(float *A, int64_t lda, int n, float *U, int64_t ldu, int32_t *info, hipStream_t s);
+
 int decode_rope_kv_launch(half_t *qkv, const int64_t *pos, half_t *kc, half_t *vc, int heads, int head_dim, int t_max, float base,
                           hipStream_t s);
 int decode_attn_launch(const half_t *q, const half_t *kc, const half_t *vc, const int64_t *pos, half_t *out, float *ws, int heads,

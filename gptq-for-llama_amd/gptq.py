@@ -8,7 +8,11 @@ What runs where:
     csrc/hessian.hip): H <- n/(n+b) H + 2/(n+b) X^T X in place, exact fp16 products on the matrix core, only the tiles on and above
     the diagonal computed and mirrored (H is bit-symmetric), no upcast or transposed copy of X.  Every other input (fp32 or bf16
     activations, Conv2d / Conv1D layers, odd widths) keeps the reference's route: one fp32 GEMM per batch (torch).
-  * damping + Hinv = chol(chol_inv(chol(H)), upper) (gptq.py:157-163): torch.linalg (rocSOLVER).
+  * damping (torch, one line) + Hinv = chol(chol_inv(chol(H)), upper) (gptq.py:157-163): for a width that is a multiple of 128 (every
+    LLaMA / OPT / NeoX linear) one hand-written HIP sweep (``gptq_hinv_factor_f32``, csrc/hinv_factor.hip) instead of the three library
+    factorisations: the damped Hessian is factored from the last column backwards, A = R R^T, and Hinv = R^-1 -- the same matrix, from
+    2/3 n^3 flops on the fp32 matrix instruction, with no dense inverse in between.  A pivot that is not positive raises
+    ``torch.linalg.LinAlgError`` like the library.  Other widths keep torch.linalg (rocSOLVER).
   * the sequential quantise / error-feedback loop over the columns of a block (gptq.py:177-199) -- ~10 dependent
     torch launches per column in the reference -- is ONE hand-written HIP launch per block
     (``gptq_solver_block_f32``, csrc/gptq_solver.hip): a wave per weight row, the block's columns in registers,
@@ -36,6 +40,7 @@ except Exception:  # pragma: no cover
     _Conv1D = ()
 
 KERNEL_MAX_BLOCK = 128   # columns the block kernel keeps in registers (two per lane)
+FACTOR_BLOCK = 128       # block edge of the inverse-factor sweep: it serves widths that are multiples of it
 
 
 class Observer:
@@ -75,10 +80,27 @@ def _weight_matrix(layer):
 
 
 def _inverse_factor(hess, percdamp):
-    """upper Cholesky factor of (H + percdamp * mean(diag H) * I)^-1, via rocSOLVER (reference gptq.py:157-163)."""
+    """upper Cholesky factor U of (H + percdamp * mean(diag H) * I)^-1 (reference gptq.py:157-163); ``hess`` is damped in place, as upstream.
+    A ROCm fp32 Hessian whose width is a multiple of 128 takes the HIP sweep (``gptq_hinv_factor_f32``: A = R R^T from the last column
+    backwards, U = R^-1); every other input the reference's three library factorisations."""
     hess.diagonal().add_(percdamp * hess.diagonal().mean())
-    lower = torch.linalg.cholesky(hess)
-    return torch.linalg.cholesky(torch.cholesky_inverse(lower), upper=True).contiguous()
+    n = hess.shape[0]
+    if not (hess.is_cuda and hess.dtype == torch.float32 and hess.dim() == 2 and n >= FACTOR_BLOCK and n % FACTOR_BLOCK == 0):
+        lower = torch.linalg.cholesky(hess)
+        return torch.linalg.cholesky(torch.cholesky_inverse(lower), upper=True).contiguous()
+    # the sweep destroys its input (it is the storage of R): it works on a copy, so a caller that keeps the damped Hessian (observe=True
+    # leaves it in GPTQ.H) still holds it afterwards, as with the library route.  One n^2 copy against 2/3 n^3 flops.
+    work = hess.clone(memory_format=torch.contiguous_format)
+    factor = torch.zeros((n, n), device=hess.device, dtype=torch.float32)
+    info = torch.zeros(1, device=hess.device, dtype=torch.int32)
+    with _native.on_device(hess.device):
+        rc = _native.lib().gptq_hinv_factor_f32(work.data_ptr(), n, n, factor.data_ptr(), n, info.data_ptr(), _native.stream_ptr(hess.device))
+    _native.check(rc, 'gptq_hinv_factor_f32')
+    bad = int(info.item())                                  # read once, behind the whole sweep
+    if bad:
+        raise torch.linalg.LinAlgError('gptq_hinv_factor_f32: the damped Hessian is not positive definite (the pivot of column %d is not '
+                                       'positive)' % (bad - 1))
+    return factor
 
 
 class GPTQ:

@@ -1059,6 +1059,22 @@ int gptq_solver_block_f32(const float *W, int64_t ldw, const float *Hinv, int64_
 int gptq_hessian_update_f16(const void *x, int64_t ldx, int tokens, int k, float *H, int64_t ldh, float decay, float weight,
                             gptq_stream_t stream);
 
+/* ---- GPTQ solver: the inverse Hessian factor (csrc/hinv_factor.hip) ------------------------------------------------------------------------
+ * U upper triangular with U^T U = A^-1 -- the matrix chol(chol_inv(chol(A)), upper) of the reference (gptq.py:157-163) -- from ONE
+ * factorisation and one triangular inverse: A = R R^T factored from the last column backwards (R upper triangular), U = R^-1.
+ *   A    fp32 [n][lda]  the damped Hessian.  Only its upper triangle (i <= j) is read, and A is DESTROYED: it is the working storage of R and
+ *                       of the running Schur complement.
+ *   U    fp32 [n][ldu]  on exit the factor on and above the diagonal and exact +0 below it
+ *   info one device word: 0, or 1 + the index of the first column whose pivot was <= 0 or not finite (LAPACK's convention; the columns are
+ *                       met from the last backwards).  Written by plain stores; read it after the stream has passed the call.  A bad pivot is
+ *                       a handled numerical condition: the sweep completes, U then holds NaN.
+ * Blocked on 128 columns: per block one single-workgroup launch (reversed Cholesky and inverse of the diagonal block in LDS and registers, IEEE
+ * division and square root), one launch of panel and row tiles and one of trailing tiles on v_mfma_f32_32x32x2_f32; 3 n / 128 - 1 launches, no
+ * host synchronisation, no workspace, no atomics, the same bits on every call.  Elements of a row beyond n (lda, ldu > n) are not touched.
+ * Validated before any launch: GPTQ_E_NULL (A, U, info), GPTQ_E_SHAPE (n < 128, n % 128 != 0, lda < n, ldu < n, n lda or n ldu beyond int64,
+ * more tiles than a grid holds), GPTQ_E_ALIGN (A / U 16 bytes, lda / ldu multiples of 4, info 4 bytes).  Returns the first launch error. */
+int gptq_hinv_factor_f32(float *A, int64_t lda, int n, float *U, int64_t ldu, int32_t *info, gptq_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
