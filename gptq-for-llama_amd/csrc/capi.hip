@@ -1920,6 +1920,23 @@ int gptq_solver_block_f32(const float *W, int64_t ldw, const float *Hinv, int64_
                              (hipStream_t)stream);
 }
 
+// ---- GPTQ solver: the whole layer in one launch, grid fit and trailing update included (gptq_solver.hip) ----
+int gptq_solver_layer_f32(float *W, int64_t ldw, const float *Hinv, int64_t ldh, int rows, int cols, int groupsize, int maxq, int sym, int fit,
+                          float *scale, float *zero, int64_t ldg, float *Q, int64_t ldq, float *loss_rows, gptq_stream_t stream) {
+    if (!W || !Hinv || !scale || !zero || !Q || !loss_rows) return GPTQ_E_NULL;
+    if (rows < 1 || cols < 128 || cols % 128 != 0 || groupsize < 1 || maxq < 1) return GPTQ_E_SHAPE;
+    if (ldw < cols || ldh < cols || ldq < cols || ldg < ((int64_t)cols + groupsize - 1) / groupsize) return GPTQ_E_SHAPE;
+    int64_t wspan, hspan, qspan, gspan;                          // the kernel's offsets are int64
+    if (__builtin_mul_overflow((int64_t)rows, ldw, &wspan) || __builtin_mul_overflow((int64_t)cols, ldh, &hspan) ||
+        __builtin_mul_overflow((int64_t)rows, ldq, &qspan) || __builtin_mul_overflow((int64_t)rows, ldg, &gspan))
+        return GPTQ_E_SHAPE;
+    if (wspan > INT64_MAX / 4 || hspan > INT64_MAX / 4 || qspan > INT64_MAX / 4 || gspan > INT64_MAX / 4) return GPTQ_E_SHAPE;   // ... of bytes
+    if (!aligned(W, 16) || !aligned(Hinv, 16) || !aligned(Q, 16) || ldw % 4 != 0 || ldh % 4 != 0 || ldq % 4 != 0) return GPTQ_E_ALIGN;
+    if (!aligned(scale, 4) || !aligned(zero, 4) || !aligned(loss_rows, 4)) return GPTQ_E_ALIGN;
+    return solver_layer_launch(W, ldw, Hinv, ldh, rows, cols, groupsize, maxq, sym != 0, fit != 0, scale, zero, ldg, Q, ldq, loss_rows,
+                               (hipStream_t)stream);
+}
+
 // ---- GPTQ solver: the calibration Hessian of one batch (hessian.hip) ----
 int gptq_hessian_update_f16(const void *x, int64_t ldx, int tokens, int k, float *H, int64_t ldh, float decay, float weight, gptq_stream_t stream) {
     if (!x || !H) return GPTQ_E_NULL;

@@ -248,6 +248,10 @@ int gptq_block_launch(const float *W, int64_t ldw, const float *Hinv, int64_t ld
                       const float *scale, const float *zero, int64_t ldg, float *Q, int64_t ldq, float *Err, int64_t lde, float *loss_rows,
                       hipStream_t s);
 
+// gptq_solver.hip: the whole layer in one launch (cols a multiple of 128; W destroyed; fit != 0: the grids are fitted in the kernel and written)
+int solver_layer_launch(float *W, int64_t ldw, const float *Hinv, int64_t ldh, int rows, int cols, int groupsize, int maxq, int sym, int fit,
+                        float *scale, float *zero, int64_t ldg, float *Q, int64_t ldq, float *loss_rows, hipStream_t s);
+
 // hessian.hip: H <- decay H + weight X^T X in place (x fp16 [tokens][k], H fp32 [k][k] symmetric; the tiles i <= j are read, both triangles written)
 int hessian_update_launch(const half_t *x, int64_t ldx, int tokens, int k, float *H, int64_t ldh, float decay, float weight, hipStream_t s);
 

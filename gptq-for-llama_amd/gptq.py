@@ -13,14 +13,17 @@ What runs where:
     factorisations: the damped Hessian is factored from the last column backwards, A = R R^T, and Hinv = R^-1 -- the same matrix, from
     2/3 n^3 flops on the fp32 matrix instruction, with no dense inverse in between.  A pivot that is not positive raises
     ``torch.linalg.LinAlgError`` like the library.  Other widths keep torch.linalg (rocSOLVER).
-  * the sequential quantise / error-feedback loop over the columns of a block (gptq.py:177-199) -- ~10 dependent
-    torch launches per column in the reference -- is ONE hand-written HIP launch per block
-    (``gptq_solver_block_f32``, csrc/gptq_solver.hip): a wave per weight row, the block's columns in registers,
-    the reference's fp32 operations one by one.
-  * the grid of a group is fitted with ``quant.Quantizer.find_params`` on the global W before the block, exactly where
-    the reference fits it (gptq.py:181-183: it reads ``W``, not the in-block clone), so ``sym`` / ``mse`` behave
-    as upstream;
-  * trailing update W[:, i2:] -= Err1 . Hinv[i1:i2, i2:] (gptq.py:204): one GEMM per block (torch / hipBLASLt).
+  * the solve step (gptq.py:171-208), ``blocksize`` 128, a width that is a multiple of 128, a min/max quantiser (``mse=False``; per-channel when there are groups) -- every
+    LLaMA / OPT / NeoX linear as ``llama.py`` quantises it: ONE hand-written HIP launch for the layer (``_solve_layer`` ->
+    ``gptq_solver_layer_f32``, csrc/gptq_solver.hip).  A workgroup owns 16 weight rows and walks the blocks: per block it fits the grids
+    of the groups that start there to W as it stands then (where the reference fits them, gptq.py:181-183; ``sym`` as upstream), runs the
+    column loop below, keeps Err1 in LDS and applies W[:, i2:] -= Err1 . Hinv[i1:i2, i2:] (gptq.py:204) on the fp32 matrix instruction.
+  * every other call (other block sizes, other widths, ``mse=True`` whose search stays in torch, and groups with ``perchannel=False``,
+    where all weight rows share one grid per group while the kernel fits one per row) keeps ``_solve_blocks``: per block the
+    grids with ``quant.Quantizer.find_params`` on the global W (torch), the sequential quantise / error-feedback loop over the columns
+    (gptq.py:177-199; ~10 dependent torch launches per column in the reference) as ONE hand-written HIP launch
+    (``gptq_solver_block_f32``: a wave per weight row, the block's columns in registers, the reference's fp32 operations one by one --
+    the same device function the layer kernel calls), and the trailing update as one GEMM (torch / hipBLASLt).
 There is no CPU path: the layer must live on a ROCm device (the CPU restatement used for parity and as the
 reported-only baseline is oracle/gptq_solver.py, which this module never imports).
 """
@@ -40,6 +43,7 @@ except Exception:  # pragma: no cover
     _Conv1D = ()
 
 KERNEL_MAX_BLOCK = 128   # columns the block kernel keeps in registers (two per lane)
+LAYER_BLOCK = 128        # block edge of the one-launch layer solver: it serves blocksize 128 on widths that are multiples of it
 FACTOR_BLOCK = 128       # block edge of the inverse-factor sweep: it serves widths that are multiples of it
 
 
@@ -101,6 +105,44 @@ def _inverse_factor(hess, percdamp):
         raise torch.linalg.LinAlgError('gptq_hinv_factor_f32: the damped Hessian is not positive definite (the pivot of column %d is not '
                                        'positive)' % (bad - 1))
     return factor
+
+
+def _solve_blocks(W, Hinv, quantizer, blocksize, groupsize, gs, maxq, scale_all, zero_all, Q, loss_rows):
+    """the solve step block by block from the host (reference gptq.py:171-208): per block the grids of the groups that start in it
+    (``quantizer.find_params``, torch), ONE launch of the column loop (``gptq_solver_block_f32``) and one library GEMM for the trailing
+    update.  Serves every block size, every width and ``mse=True``.  ``W`` is updated in place."""
+    lib = _native.lib()
+    rows, cols = W.shape
+    n_groups = scale_all.shape[1]
+    Err = torch.empty((rows, KERNEL_MAX_BLOCK), device=W.device)
+    stream = _native.stream_ptr(W.device)
+    for i1 in range(0, cols, blocksize):
+        i2 = min(i1 + blocksize, cols)
+        if groupsize != -1:
+            # grids of the groups that START inside this block, fitted to W as it is now (gptq.py:181-183)
+            first = -(-i1 // gs) * gs
+            for c in range(first, i2, gs):
+                quantizer.find_params(W[:, c:c + gs], weight=True)
+                scale_all[:, c // gs] = quantizer.scale.reshape(-1)
+                zero_all[:, c // gs] = quantizer.zero.reshape(-1)
+        for j1 in range(i1, i2, KERNEL_MAX_BLOCK):   # the kernel keeps <= 128 columns in registers
+            j2 = min(j1 + KERNEL_MAX_BLOCK, i2)
+            rc = lib.gptq_solver_block_f32(W.data_ptr(), cols, Hinv.data_ptr(), cols, rows, cols, j1, j2 - j1, gs, maxq,
+                                           scale_all.data_ptr(), zero_all.data_ptr(), n_groups, Q.data_ptr(), cols,
+                                           Err.data_ptr(), KERNEL_MAX_BLOCK, loss_rows.data_ptr(), stream)
+            _native.check(rc, 'gptq_solver_block_f32')
+            if j2 < cols:
+                W[:, j2:] -= Err[:, :j2 - j1].matmul(Hinv[j1:j2, j2:])
+
+
+def _solve_layer(W, Hinv, gs, maxq, sym, fit, scale_all, zero_all, Q, loss_rows):
+    """the same solve step in ONE launch (``gptq_solver_layer_f32``): 128-column blocks, the min/max grid fitted in the kernel when ``fit``
+    (``scale_all`` / ``zero_all`` are then outputs), Err1 in LDS, the trailing update on the fp32 matrix instruction.  ``W`` is destroyed."""
+    rows, cols = W.shape
+    rc = _native.lib().gptq_solver_layer_f32(W.data_ptr(), cols, Hinv.data_ptr(), cols, rows, cols, gs, maxq, int(sym), int(fit),
+                                             scale_all.data_ptr(), zero_all.data_ptr(), scale_all.shape[1], Q.data_ptr(), cols,
+                                             loss_rows.data_ptr(), _native.stream_ptr(W.device))
+    _native.check(rc, 'gptq_solver_layer_f32')
 
 
 class GPTQ:
@@ -173,15 +215,21 @@ class GPTQ:
     def fasterquant(self, blocksize=128, percdamp=.01, groupsize=-1, actorder=False, name=''):
         if self.dev.type != 'cuda':
             raise RuntimeError('GPTQ.fasterquant: layer is on %s -- the MI355X solver has no CPU path' % self.dev)
-        lib = _native.lib()
+        _native.lib()
         self.layer.to(self.dev)
         W = _weight_matrix(self.layer).float().contiguous()
         tick = time.time()
         if int(self.quantizer.maxq) < 0:
             raise NotImplementedError('ternary grids (trits) are not supported by the HIP block solver')
         maxq = int(self.quantizer.maxq)
+        # one launch for the layer where the kernel serves it: its blocks are 128 columns and its grid fit is the min/max rule, one grid
+        # per weight row and group (perchannel=True; a per-tensor quantiser shares one grid per group among all rows and keeps the block route)
+        layer_route = (maxq > 0 and blocksize == LAYER_BLOCK and self.columns % LAYER_BLOCK == 0 and not self.quantizer.mse
+                       and (groupsize == -1 or self.quantizer.perchannel))
 
-        if not self.quantizer.ready():                      # whole-row grid; the only one without groups (gptq.py:139-140)
+        # whole-row grid; the only one without groups (gptq.py:139-140).  With groups every grid is fitted again per group, in the kernel
+        # on the layer route: nothing reads this one
+        if not self.quantizer.ready() and not (layer_route and groupsize != -1):
             self.quantizer.find_params(W, weight=True)
 
         hess = self.H
@@ -208,28 +256,15 @@ class GPTQ:
             scale_all[:, 0] = self.quantizer.scale.reshape(-1)
             zero_all[:, 0] = self.quantizer.zero.reshape(-1)
         Q = torch.zeros_like(W)
-        Err = torch.empty((rows, KERNEL_MAX_BLOCK), device=self.dev)
         loss_rows = torch.zeros(rows, device=self.dev)
-        stream = _native.stream_ptr(self.dev)
-
         with torch.cuda.device(self.dev):
-            for i1 in range(0, cols, blocksize):
-                i2 = min(i1 + blocksize, cols)
-                if groupsize != -1:
-                    # grids of the groups that START inside this block, fitted to W as it is now (gptq.py:181-183)
-                    first = -(-i1 // gs) * gs
-                    for c in range(first, i2, gs):
-                        self.quantizer.find_params(W[:, c:c + gs], weight=True)
-                        scale_all[:, c // gs] = self.quantizer.scale.reshape(-1)
-                        zero_all[:, c // gs] = self.quantizer.zero.reshape(-1)
-                for j1 in range(i1, i2, KERNEL_MAX_BLOCK):   # the kernel keeps <= 128 columns in registers
-                    j2 = min(j1 + KERNEL_MAX_BLOCK, i2)
-                    rc = lib.gptq_solver_block_f32(W.data_ptr(), cols, Hinv.data_ptr(), cols, rows, cols, j1, j2 - j1, gs, maxq,
-                                                   scale_all.data_ptr(), zero_all.data_ptr(), n_groups, Q.data_ptr(), cols,
-                                                   Err.data_ptr(), KERNEL_MAX_BLOCK, loss_rows.data_ptr(), stream)
-                    _native.check(rc, 'gptq_solver_block_f32')
-                    if j2 < cols:
-                        W[:, j2:] -= Err[:, :j2 - j1].matmul(Hinv[j1:j2, j2:])
+            if layer_route:
+                _solve_layer(W, Hinv, gs, maxq, bool(self.quantizer.sym), groupsize != -1, scale_all, zero_all, Q, loss_rows)
+                if groupsize != -1:                         # the quantiser is left as the last per-group fit leaves it
+                    self.quantizer.maxq = self.quantizer.maxq.to(self.dev)
+                    self.quantizer.scale, self.quantizer.zero = scale_all[:, -1:].clone(), zero_all[:, -1:].clone()
+            else:
+                _solve_blocks(W, Hinv, self.quantizer, blocksize, groupsize, gs, maxq, scale_all, zero_all, Q, loss_rows)
             torch.cuda.synchronize()
         error = float(loss_rows.double().sum().item())
 

@@ -99,6 +99,9 @@ _SIGNATURES = {
                              c_float, c_void_p],
     'gptq_solver_block_f32': [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int64,
                               c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p],
+    # ... the whole layer in one launch: grid fit, column loop and trailing update of every block (csrc/gptq_solver.hip)
+    'gptq_solver_layer_f32': [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int64,
+                              c_void_p, c_int64, c_void_p, c_void_p],
     # ... and its calibration Hessian: H <- decay H + weight X^T X for one fp16 batch, the upper tiles only, mirrored (csrc/hessian.hip)
     'gptq_hessian_update_f16': [c_void_p, c_int64, c_int, c_int, c_void_p, c_int64, c_float, c_float, c_void_p],
     # ... and the inverse Hessian factor U, U^T U = A^-1: reversed blocked Cholesky + triangular inverse in one sweep (csrc/hinv_factor.hip)

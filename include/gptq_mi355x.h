@@ -1047,6 +1047,28 @@ int gptq_solver_block_f32(const float *W, int64_t ldw, const float *Hinv, int64_
                           int groupsize, int maxq, const float *scale, const float *zero, int64_t ldg, float *Q, int64_t ldq,
                           float *Err, int64_t lde, float *loss_rows, gptq_stream_t stream);
 
+/* The WHOLE layer in one launch (reference gptq.py:171-208): for every 128-column block, left to right, the grid fit, the column loop of
+ * gptq_solver_block_f32 (the same device function: the same bits) and the trailing update W[:, i2:] -= Err1 . Hinv[i1:i2, i2:]
+ * (v_mfma_f32_16x16x4_f32, true fp32 operands; Err1 never leaves LDS).  A workgroup owns 16 weight rows for the whole layer; rows never interact.
+ *   W [rows, cols] (ldw)    the caller's scratch copy of the weights, DESTROYED: it carries the running error feedback
+ *   Hinv [cols, cols] (ldh) upper Cholesky factor of the inverse damped Hessian; only i <= j is read
+ *   scale, zero [rows, ldg] grid of row r, group g = column / groupsize (groupsize = cols: no groups).
+ *                           fit != 0: OUTPUTS.  The grid of a group is fitted when the sweep reaches the block the group STARTS in, to
+ *                           W[r, c .. min(c + groupsize, cols)) as it stands then -- behind the trailing updates of all earlier blocks, before
+ *                           that block's column loop (gptq.py:181-183); a group may reach into later blocks.  The rule is the min/max
+ *                           quantiser's (quantizer.py find_params, mse = False), in fp32: lo = min(min, 0), hi = max(max, 0); sym != 0:
+ *                           hi = max(|lo|, hi) and lo = -hi where lo < 0; lo = hi = 0 becomes (-1, +1); scale = (hi - lo) / maxq;
+ *                           zero = (maxq + 1) / 2 (sym) or rint(-lo / scale).
+ *                           fit == 0: INPUTS, read as gptq_solver_block_f32 reads them; sym is ignored.
+ *   Q [rows, cols] (ldq)    out: quantised (de-quantised, fp32) weights, all columns
+ *   loss_rows [rows]        out: sum over the blocks, in order, of (block's sum of (w - q)^2 / d^2) * 0.5 (gptq.py:194,202)
+ * One launch, no workspace, no atomics; a row's result depends on that row alone, wherever it sits; the same bits on every call.
+ * Validated before the launch: GPTQ_E_NULL (any pointer), GPTQ_E_SHAPE (rows < 1, cols < 128, cols % 128 != 0, groupsize < 1, maxq < 1,
+ * ldw / ldh / ldq < cols, ldg < ceil(cols / groupsize), a span beyond int64), GPTQ_E_ALIGN (W / Hinv / Q 16 bytes and ldw / ldh / ldq multiples
+ * of 4; scale / zero / loss_rows 4 bytes). */
+int gptq_solver_layer_f32(float *W, int64_t ldw, const float *Hinv, int64_t ldh, int rows, int cols, int groupsize, int maxq, int sym, int fit,
+                          float *scale, float *zero, int64_t ldg, float *Q, int64_t ldq, float *loss_rows, gptq_stream_t stream);
+
 /* The calibration Hessian of one batch (reference gptq.py:71-96): H <- decay H + weight X^T X, in place.
  *   x [tokens, k] fp16 (ldx)  the activations of the batch as the layer saw them, tokens >= 1, k >= 8 and a multiple of 8
  *   H [k, k] fp32 (ldh)       symmetric on entry (only its 128 x 128 tiles with i <= j are read; decay == 0 reads nothing) and bit-symmetric
