@@ -172,6 +172,10 @@ _SIGNATURES = {
                                        c_int, c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p, c_int, c_void_p],
     'gptq_kv8_store_f16': [c_void_p, c_void_p, c_int64, ctypes.POINTER(PromptSeg), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                            c_void_p],
+    # grouped-query models: the batch decode attention with kv_heads < heads, one K/V stream per group of query heads (csrc/decode_attn_gqa.hip)
+    'gptq_decode_attn_batch_gqa_workspace_bytes': [c_int, c_int, c_int, c_int, c_int],
+    'gptq_decode_attn_batch_gqa_f16': [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_size_t, c_int, c_int, c_int, c_int,
+                                       c_int, c_float, c_float, c_void_p, c_void_p, c_void_p],
     # speculative decoding: a chunk of consecutive tokens of one sequence, the position in device memory (csrc/chunk_attn.hip)
     'gptq_decode_attn_chunk_workspace_bytes': [c_int, c_int, c_int, c_int],
     'gptq_decode_attn_chunk_splits': [c_int, c_int, c_int, c_int],
@@ -258,6 +262,7 @@ def lib():
             L.gptq_layer_fallback_scratch_bytes.restype = c_size_t
             L.gptq_layer_decode_scratch_bytes.restype = c_size_t
             L.gptq_decode_attn_batch_workspace_bytes.restype = c_size_t
+            L.gptq_decode_attn_batch_gqa_workspace_bytes.restype = c_size_t
             L.gptq_prompt_attn_workspace_bytes.restype = c_size_t
             L.gptq_lm_head_nll_workspace_bytes.restype = c_size_t
             L.gptq_decode_attn_chunk_workspace_bytes.restype = c_size_t

@@ -367,6 +367,19 @@ class DecodeEngine:
         self.eps = float(cfg.rms_norm_eps)
         if self.head_dim != 128:
             raise NotImplementedError('DecodeEngine: head_dim must be 128')
+        # grouped-query models (num_key_value_heads < num_attention_heads): caches and the k / v parts of the qkv row are kv_heads wide, and every
+        # batch size steps through _step_rows with gptq_decode_attn_batch_gqa_f16.  The grouped prompt, chunk, tree, beam and fp8 attention are
+        # not built yet: refused here, before anything is allocated.
+        self.kv_heads = int(getattr(cfg, 'num_key_value_heads', None) or self.heads)
+        self.grouped = self.kv_heads != self.heads
+        if self.grouped:
+            if self.chunk or self.batch_chunk or self.tree or self.beam_search or kv_cache == 'fp8' or not self.fuse_attn:
+                raise ValueError("DecodeEngine: a grouped-query model (%d query heads on %d K/V heads) together with chunk / batch_chunk / tree / "
+                                 "beam_search / kv_cache='fp8' / fuse_attn=False is not built yet (the grouped decode attention is the only "
+                                 "grouped kernel)" % (self.heads, self.kv_heads))
+            if self.heads % self.kv_heads != 0 or self.heads // self.kv_heads > 16:
+                raise ValueError('DecodeEngine: %d query heads on %d K/V heads is not built yet (groups of 2 .. 16 query heads)' % (
+                    self.heads, self.kv_heads))
         self.embed = model.model.embed_tokens.weight
         self.lm_head = model.lm_head.weight
         self.lm_head_bias = getattr(model.lm_head, 'bias', None)
@@ -382,13 +395,14 @@ class DecodeEngine:
                 qkv=self._pack(attn.qkv_proj), o=self._pack(attn.o_proj), down=self._pack(mlp.down_proj),
                 gate=gpack, up=upack, theta=float(attn.rope_theta)))
         H, I, B = self.hidden, cfg.intermediate_size, self.batch
+        KV = self.kv_heads * self.head_dim                             # columns of a cache row and of the k / v parts of a qkv row (ungrouped: H)
         f16 = dict(dtype=torch.float16, device=dev)
         self.ids = torch.zeros(B, dtype=torch.int64, device=dev)
         self.pos = torch.zeros(B, dtype=torch.int64, device=dev)       # per row: tokens consumed so far = the position of the next one
         self.x = torch.zeros((B, H), **f16)
         self.x2 = torch.zeros((B, H), **f16)
         self.h = torch.zeros((B, H), **f16)
-        self.qkvb = torch.zeros((B, 3 * H), **f16)
+        self.qkvb = torch.zeros((B, H + 2 * KV), **f16)
         self.ab = torch.zeros((B, H), **f16)
         self.cb = torch.zeros((B, I), **f16)
         # sized from the head itself (a resized / padded lm_head has rows != config.vocab_size: ADVICE r4)
@@ -432,11 +446,14 @@ class DecodeEngine:
             self.kexpb, self.vexpb = torch.zeros((nl, B, self.t_max, self.heads), **i8), torch.zeros((nl, B, self.t_max, self.heads), **i8)
             self.kst, self.vst = torch.zeros((B, self.t_max, H), **f16), torch.zeros((B, self.t_max, H), **f16)          # ONE layer of fp16 staging
         else:
-            self.kcb = torch.zeros((nl, B, self.t_max, H), **f16)          # [layer][row][t][heads * head_dim]
-            self.vcb = torch.zeros((nl, B, self.t_max, H), **f16)
-            self.kc, self.vc = self.kcb[:, 0], self.vcb[:, 0]              # row 0 = THE cache of a batch-1 engine ([layer][t][H] views)
-        self.attn_ws = torch.zeros(self.lib.gptq_decode_attn_batch_workspace_bytes(B, self.heads, self.head_dim, self.t_max),
-                                   dtype=torch.uint8, device=dev)
+            self.kcb = torch.zeros((nl, B, self.t_max, KV), **f16)         # [layer][row][t][kv_heads * head_dim]
+            self.vcb = torch.zeros((nl, B, self.t_max, KV), **f16)
+            self.kc, self.vc = self.kcb[:, 0], self.vcb[:, 0]              # row 0 = THE cache of a batch-1 engine ([layer][t][KV] views)
+        if self.grouped:
+            ws_bytes = self.lib.gptq_decode_attn_batch_gqa_workspace_bytes(B, self.heads, self.kv_heads, self.head_dim, self.t_max)
+        else:
+            ws_bytes = self.lib.gptq_decode_attn_batch_workspace_bytes(B, self.heads, self.head_dim, self.t_max)
+        self.attn_ws = torch.zeros(ws_bytes, dtype=torch.uint8, device=dev)
         self.ws = _native.workspace(dev)
         self.graph = None
         self.beam_graph = None
@@ -460,10 +477,10 @@ class DecodeEngine:
         self.scratch = None
         self._rope_tabs, self._prefill_bufs, self._nll_ws = {}, None, None      # filled on first use: _rope_table, _prefill_buffers, _nll_rows
         # batch 1: the attention's splits are merged by o_proj's decode kernel when every o_proj can (trivial g_idx, an image, no bias next to the residual)
-        self.attn_records = bool(ATTN_RECORDS and self.fuse_attn and B == 1 and self.kv_cache == 'fp16' and all(
+        self.attn_records = bool(ATTN_RECORDS and self.fuse_attn and B == 1 and self.kv_cache == 'fp16' and not self.grouped and all(
             L['o']['st'] is not None and L['o']['bias'] is None and
             self.lib.gptq_layer_decode_attn_supported(L['o']['_keep'].handle, 1, self.heads, self.head_dim) == 1 for L in self.layers))
-        if B > 1 or self.kv_cache == 'fp8':                        # (an fp8 engine steps through _step_rows at every batch size)
+        if B > 1 or self.kv_cache == 'fp8' or self.grouped:        # (an fp8 and a grouped engine step through _step_rows at every batch size)
             self.scratch = self._rows_scratch('batch', (B,))
         self.verify_graph, self.verify_sample_graphs, self.spec_stats = None, {}, None
         self.draft_graph, self._draft_engine = None, None          # capture_draft_step (a draft engine) / (draft model, its engine) of a target engine
@@ -735,14 +752,22 @@ class DecodeEngine:
                                                     self.beam_attn_ws.numel(), self.heads, self.head_dim, self.t_max, L['theta'], self.scale,
                                                     self.native.ptr(tab), s)
             self.native.check(rc, 'gptq_decode_attn_beam_f16')
+        def attn_gqa(li, L, qkvb, ab, tab, s):                  # a grouped-query model: kv_heads K/V streams serve heads query heads
+            rc = self.lib.gptq_decode_attn_batch_gqa_f16(qkvb.data_ptr(), qkvb.stride(0), self.pos.data_ptr(), self.kcb[li].data_ptr(),
+                                                         self.vcb[li].data_ptr(), ab.data_ptr(), ab.stride(0), self.attn_ws.data_ptr(),
+                                                         self.attn_ws.numel(), self.batch, self.heads, self.kv_heads, self.head_dim, self.t_max,
+                                                         L['theta'], self.scale, self.native.ptr(tab), None, s)
+            self.native.check(rc, 'gptq_decode_attn_batch_gqa_f16')
         if beam:
             attn = attn_beam
+        elif self.grouped:
+            attn = attn_gqa
         self._step_rows(dict(x=self.x, x2=self.x2, h=self.h, qkv=self.qkvb, ab=self.ab, cb=self.cb), self.ids,
                         attn8 if self.kv_cache == 'fp8' else attn, self.logits)
         self.pos.add_(1)
 
     def _step(self):
-        if self.batch > 1 or self.kv_cache == 'fp8':
+        if self.batch > 1 or self.kv_cache == 'fp8' or self.grouped:
             return self._step_batch()
         lib, ptr = self.lib, self.native.ptr
         s = torch.cuda.current_stream(self.dev).cuda_stream
@@ -1420,6 +1445,11 @@ class DecodeEngine:
                                              self.head_dim, self.t_max, s)
         self.native.check(rc, 'gptq_kv8_store_f16')
 
+    def _need_ungrouped(self, what):
+        if self.grouped:
+            raise ValueError('DecodeEngine.%s on a grouped-query model is not built yet (there is no grouped prompt attention: feed the prompt '
+                             "through the model, engine_generate(prefill='hf'))" % what)
+
     def prefill(self, input_ids, row=0, start=None):
         """Feed T tokens of ONE sequence (input_ids: int64, 1-D or [1, T]) into cache row `row` at positions start .. start + T - 1 and return
         the logits after the last of them (self.logits[row], the static buffer: clone it to keep it -- the contract of decode()).
@@ -1427,6 +1457,7 @@ class DecodeEngine:
         launches: gptq_rmsnorm_f16, the layer's PreparedLayer (gptq_layer_forward: the derived copy the modules and the decode step share; any
         bit width, act-order included), gptq_prompt_attn_f16 (RoPE + cache append + causal attention on kcb[li, row] / vcb[li, row]),
         gptq_add_rows_f16; only the last row goes through the LM head.  Nothing of `transformers` is involved; not graph-captured."""
+        self._need_ungrouped('prefill')
         ids = input_ids.reshape(-1) if (input_ids.dim() == 1 or (input_ids.dim() == 2 and input_ids.shape[0] == 1)) else None
         if ids is None or ids.numel() == 0:
             raise ValueError('DecodeEngine.prefill: input_ids must be a non-empty 1-D or [1, T] tensor')
@@ -1467,6 +1498,7 @@ class DecodeEngine:
         behind every pass the final norm and _nll_rows run over all its rows -- the targets are the packed ids shifted by one, so the last row
         of a pass is scored against the first token of the next, and the last row of every prompt gives 0.  Validates everything (ValueError)
         before the first launch.  Returns (logits[rows], nll [sum T] float32 or None, offs, lens)."""
+        self._need_ungrouped(what)
         n = len(prompts)
         if not 1 <= n <= self.batch:
             raise ValueError('DecodeEngine.%s: %d prompts for an engine of batch %d' % (what, n, self.batch))
@@ -2078,6 +2110,12 @@ def perplexity(model, input_ids, seqlen=2048, engine=None, batch=1):
     return dict(nll_sum=nll_sum, tokens=tokens, ppl=math.exp(nll_sum / tokens), ppl_reference=math.exp(reference))
 
 
+def _grouped_model(model):
+    """num_key_value_heads < num_attention_heads: what DecodeEngine serves with the grouped decode attention only"""
+    cfg = model.config
+    return (getattr(cfg, 'num_key_value_heads', None) or cfg.num_attention_heads) != cfg.num_attention_heads
+
+
 def _cache_layer_kv(cache, li):
     """(keys, values) [1, heads, T, head_dim] of layer li from a transformers cache (5.x: cache.layers[li].keys)."""
     layers = getattr(cache, 'layers', None)
@@ -2648,6 +2686,9 @@ def engine_generate(model, input_ids, max_new_tokens, eos_token_id=None, engine=
     what = 'engine_generate'
     if prefill not in ('hf', 'engine'):
         raise ValueError("engine_generate: prefill must be 'hf' or 'engine', not %r" % (prefill,))
+    if prefill == 'engine' and _grouped_model(model):
+        raise ValueError("engine_generate: prefill='engine' on a grouped-query model is not built yet (there is no grouped prompt attention: "
+                         "prefill='hf')")
     settings, proc, spec = _generation_settings(what, model, sample, speculate, engine)
     logprobs = _logprobs_setting(what, logprobs, speculate, engine)
     dfas = _constrain_setting(what, constrain, 1, speculate, engine)
@@ -2706,6 +2747,9 @@ def engine_generate_batch(model, prompts, max_new_tokens, eos_token_id=None, eng
     ValueError also: an engine passed in whose batch is not len(prompts) or whose batch_chunk is not k + 1, or that lacks spec_sample where it
     is needed; an empty list or prompt; max_new_tokens below 1."""
     what = 'engine_generate_batch'
+    if _grouped_model(model):
+        raise ValueError('engine_generate_batch on a grouped-query model is not built yet (its prompts enter through prefill_batch, and there is '
+                         'no grouped prompt attention)')
     settings, proc, spec = _generation_settings(what, model, sample, speculate, engine)
     logprobs = _logprobs_setting(what, logprobs, speculate, engine)
     dfas = _constrain_setting(what, constrain, len(prompts), speculate, engine)

@@ -91,6 +91,8 @@ def _eligible_model(model):
             if type(layer.self_attn) is not QuantLlamaAttention or type(layer.mlp) is not QuantLlamaMLP:
                 return False
         a = layers[0].self_attn
+        if a.num_heads // a.num_kv_heads > 16:          # grouped-query layers: the engine serves groups of up to 16 query heads
+            return False
         return a.head_dim == 128 and a.qkv_proj.qweight.is_cuda and model.lm_head.weight.is_cuda and not model.training
     except AttributeError:
         return False
@@ -114,8 +116,8 @@ def _sync_back(st, upto=None):
         return
     npad = st.npad if st.npad is not None else [0] * eng.batch
     for li in range(len(eng.layers)):
-        k = torch.stack([eng.kcb[li, r, a - n:b - n].view(b - a, eng.heads, eng.head_dim).transpose(0, 1) for r, n in enumerate(npad)])
-        v = torch.stack([eng.vcb[li, r, a - n:b - n].view(b - a, eng.heads, eng.head_dim).transpose(0, 1) for r, n in enumerate(npad)])
+        k = torch.stack([eng.kcb[li, r, a - n:b - n].view(b - a, eng.kv_heads, eng.head_dim).transpose(0, 1) for r, n in enumerate(npad)])
+        v = torch.stack([eng.vcb[li, r, a - n:b - n].view(b - a, eng.kv_heads, eng.head_dim).transpose(0, 1) for r, n in enumerate(npad)])
         cache.update(k.contiguous(), v.contiguous(), li)
     st.hf_len = b
 

@@ -42,14 +42,21 @@ def hip_rotate_half_(qk, position_ids, base=10000.0):
 
 triton_rotate_half_ = hip_rotate_half_   # reference name
 
+_SDPA_ENABLE_GQA = 'enable_gqa' in (F.scaled_dot_product_attention.__doc__ or '')      # torch >= 2.5
+
 
 class QuantLlamaAttention(nn.Module):
     """Multi-headed attention from 'Attention Is All You Need' paper"""
 
-    def __init__(self, hidden_size, num_heads, qkv_proj, o_proj, layer_idx=None, rope_theta=10000.0):
+    def __init__(self, hidden_size, num_heads, qkv_proj, o_proj, layer_idx=None, rope_theta=10000.0, num_kv_heads=None):
         super().__init__()
         self.hidden_size = hidden_size
         self.num_heads = num_heads
+        # grouped-query attention: num_kv_heads < num_heads K/V heads, query head h attends over K/V head h // (num_heads // num_kv_heads);
+        # the fused projection then has (num_heads + 2 num_kv_heads) head_dim columns, q | k | v.  None: num_heads
+        self.num_kv_heads = num_heads if num_kv_heads is None else num_kv_heads
+        if self.num_kv_heads < 1 or num_heads % self.num_kv_heads != 0:
+            raise ValueError(f"num_heads must be a multiple of num_kv_heads (got {num_heads} and {self.num_kv_heads}).")
         self.head_dim = hidden_size // num_heads
         if (self.head_dim * num_heads) != self.hidden_size:
             raise ValueError(f"hidden_size must be divisible by num_heads (got `hidden_size`: {self.hidden_size}"
@@ -65,8 +72,10 @@ class QuantLlamaAttention(nn.Module):
         bsz, q_len, _ = hidden_states.size()
         new_api = (past_key_values is not None and hasattr(past_key_values, 'update')) or position_embeddings is not None
 
+        grouped = self.num_kv_heads != self.num_heads
         qkv_states = self.qkv_proj(hidden_states)
-        qkv_states = qkv_states.view(bsz, q_len, 3, self.num_heads, self.head_dim)
+        if not grouped:
+            qkv_states = qkv_states.view(bsz, q_len, 3, self.num_heads, self.head_dim)
 
         if new_api and past_key_values is not None:
             past_len = past_key_values.get_seq_length(self.layer_idx)
@@ -86,9 +95,22 @@ class QuantLlamaAttention(nn.Module):
             position_ids = position_ids.contiguous()
 
         # This updates the query and key states in-place, saving VRAM.
-        hip_rotate_half_(qkv_states[:, :, :2], position_ids, self.rope_theta)
-
-        query_states, key_states, value_states = (qkv_states[:, :, i].transpose(1, 2) for i in range(3))
+        if grouped:
+            # the row is [heads q | kv k | kv v]: RoPE treats the n = heads + kv leading heads alike, then the row is split by widths.
+            # gptq_rope_f16 rotates PAIRS of heads: an odd n (8 heads on 1 K/V head) rotates its last k head together with the first v head,
+            # whose values are put back
+            hd, n = self.head_dim, self.num_heads + self.num_kv_heads
+            nq, nkv = self.num_heads * hd, self.num_kv_heads * hd
+            hip_rotate_half_(qkv_states[:, :, :(n & ~1) * hd].unflatten(-1, (2, n // 2, hd)), position_ids, self.rope_theta)
+            if n & 1:
+                v0 = qkv_states[:, :, n * hd:(n + 1) * hd].clone()
+                hip_rotate_half_(qkv_states[:, :, (n - 1) * hd:(n + 1) * hd].unflatten(-1, (2, 1, hd)), position_ids, self.rope_theta)
+                qkv_states[:, :, n * hd:(n + 1) * hd] = v0
+            query_states, key_states, value_states = (t.unflatten(-1, (-1, self.head_dim)).transpose(1, 2)
+                                                      for t in qkv_states.split([nq, nkv, nkv], dim=-1))
+        else:
+            hip_rotate_half_(qkv_states[:, :, :2], position_ids, self.rope_theta)
+            query_states, key_states, value_states = (qkv_states[:, :, i].transpose(1, 2) for i in range(3))
         del qkv_states
 
         if new_api:
@@ -105,16 +127,21 @@ class QuantLlamaAttention(nn.Module):
             past_key_value = (key_states, value_states) if use_cache else None
 
         kv_len = key_states.shape[-2]
+        gqa = {}
+        if grouped and _SDPA_ENABLE_GQA:      # SDPA on grouped K/V: every query head of a group reads its K/V head
+            gqa = dict(enable_gqa=True)
+        elif grouped:                         # a torch without enable_gqa: K and V repeated per group (a copy of G x their bytes)
+            key_states, value_states = (t.repeat_interleave(self.num_heads // self.num_kv_heads, dim=1) for t in (key_states, value_states))
         mask = None
         if attention_mask is not None and attention_mask.dim() == 4:
             mask = attention_mask[:, :, :, :kv_len]
         if mask is not None:
-            attn_output = F.scaled_dot_product_attention(query_states, key_states, value_states, attn_mask=mask)
+            attn_output = F.scaled_dot_product_attention(query_states, key_states, value_states, attn_mask=mask, **gqa)
         elif q_len > 1 and kv_len > q_len:
             causal = torch.ones(q_len, kv_len, dtype=torch.bool, device=query_states.device).tril(kv_len - q_len)
-            attn_output = F.scaled_dot_product_attention(query_states, key_states, value_states, attn_mask=causal)
+            attn_output = F.scaled_dot_product_attention(query_states, key_states, value_states, attn_mask=causal, **gqa)
         else:
-            attn_output = F.scaled_dot_product_attention(query_states, key_states, value_states, is_causal=q_len > 1)
+            attn_output = F.scaled_dot_product_attention(query_states, key_states, value_states, is_causal=q_len > 1, **gqa)
         del query_states, key_states, value_states
 
         attn_output = attn_output.transpose(1, 2).reshape(bsz, q_len, self.hidden_size)
@@ -147,8 +174,9 @@ def _attn_geometry(m):
 
 def make_quant_attn(model):
     """Replace all LlamaAttention modules with QuantLlamaAttention modules, fusing the q, k, v
-    projections (buffers concatenated along N; reference :164-204).  Grouped-query attention
-    layers are left untouched (the reference's fused layout assumes num_kv_heads == num_heads)."""
+    projections (buffers concatenated along N; reference :164-204).  A grouped-query layer (num_key_value_heads < num_attention_heads) is
+    fused too: its qkv_proj has (heads + 2 kv_heads) head_dim columns and the module is built with num_kv_heads (the reference's fused
+    layout assumes num_kv_heads == num_heads)."""
     from transformers.models.llama.modeling_llama import LlamaAttention
 
     for name, m in list(model.named_modules()):
@@ -158,9 +186,6 @@ def make_quant_attn(model):
         if not all(isinstance(p, QuantLinear) for p in (q_proj, k_proj, v_proj)):
             continue
         hidden, heads, kv_heads, layer_idx, theta = _attn_geometry(m)
-        if kv_heads != heads:
-            continue
-
         qweights = torch.cat([q_proj.qweight, k_proj.qweight, v_proj.qweight], dim=1)
         qzeros = torch.cat([q_proj.qzeros, k_proj.qzeros, v_proj.qzeros], dim=1)
         scales = torch.cat([q_proj.scales, k_proj.scales, v_proj.scales], dim=1)
@@ -175,7 +200,8 @@ def make_quant_attn(model):
         qkv_layer.g_idx = g_idx     # length 3K like the reference; the kernels read the first K
         qkv_layer.bias = bias
 
-        attn = QuantLlamaAttention(hidden, heads, qkv_layer, m.o_proj, layer_idx=layer_idx, rope_theta=theta)
+        attn = QuantLlamaAttention(hidden, heads, qkv_layer, m.o_proj, layer_idx=layer_idx, rope_theta=theta,
+                                   num_kv_heads=kv_heads)
 
         if '.' in name:
             parent_name, child_name = name.rsplit('.', 1)

@@ -203,6 +203,8 @@ class TPDecodeEngine:
             cfg = config
             self.dev = torch.device(device if device is not None else 'cuda:%d' % torch.cuda.current_device())
             shards = _CheckpointShards(checkpoint, config, bits, groupsize, self.dev)
+        if (getattr(cfg, 'num_key_value_heads', None) or cfg.num_attention_heads) != cfg.num_attention_heads:
+            raise ValueError('TPDecodeEngine: a grouped-query model is not built yet (the shards cut q | k | v at the same head columns)')
         self.source = getattr(shards, 'src', None)
         self.t_max = int(t_max)
         self.hidden, self.heads = cfg.hidden_size, cfg.num_attention_heads

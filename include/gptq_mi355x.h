@@ -626,6 +626,28 @@ int gptq_decode_attn_batch_kv8_f16(const void *qkv, int64_t ldq, const int64_t *
                                    int64_t ldo, void *workspace, size_t workspace_bytes, int batch, int heads, int head_dim, int t_max, float base,
                                    float scale, const float *rope_table, const int32_t *out_perm, int tokens_per_split, gptq_stream_t stream);
 
+/* ---- grouped-query decode attention: one K/V stream per group of query heads (csrc/decode_attn_gqa.hip) -----------------------------------------
+ * Llama-2-70B, Llama-3, Mistral and Qwen2 keep kv_heads < heads K/V heads; query head h attends over K/V head h / G, G = heads / kv_heads (HF's
+ * repeat_kv in front of F.scaled_dot_product_attention).  The entry below is gptq_decode_attn_batch_f16 for such a layer WITHOUT the repeat: one
+ * workgroup streams a K/V head's history once for the G query heads of its group (MFMA tiles whose 16 query columns are the group).
+ *
+ * gptq_decode_attn_batch_gqa_f16   qkv row b at qkv + b ldq is [heads 128 q | kv_heads 128 k | kv_heads 128 v] (left untouched); cache slice b is
+ *     k_cache / v_cache + b t_max kv_heads 128, [t_max][kv_heads 128]; out row b at out + b ldo is [heads 128].  For every row with 0 <=
+ *     positions[b] < t_max: q and k are rotated at positions[b] (the RoPE of every other entry: the k row is bit-identical to what
+ *     gptq_decode_attn_batch_f16 appends for that head and position), k and v are appended ONCE per K/V head at cache row positions[b], and
+ *     out[b, h] = softmax(scale q_h K^T) V over rows 0 .. positions[b] of K/V head h / G, the new row included.  Any other position idles the row:
+ *     nothing of it is read, neither its cache slice nor its out row is written.  out_perm != NULL: element n of an output row is stored at
+ *     out_perm[n].  Two launches (RoPE + append, then attention); the run-time split count and the deterministic merge are those of the other
+ *     decode entries: the same inputs give the same bits on every call.  The workspace needs no initialisation.
+ *     Validated before any launch: GPTQ_E_NULL (any pointer but rope_table / out_perm), GPTQ_E_SHAPE (head_dim != 128, kv_heads < 1, heads not a
+ *     multiple of kv_heads, G = 1 -- gptq_decode_attn_batch_f16 serves it -- or G > 16, batch outside 1 .. 16, t_max < 1, ldq < (heads + 2 kv_heads)
+ *     128, ldo < heads 128), GPTQ_E_ALIGN (qkv / k_cache / v_cache / out / workspace 16 bytes, positions and rope_table 8, out_perm 4, ldq / ldo
+ *     multiples of 8), GPTQ_E_WORKSPACE (fewer than gptq_decode_attn_batch_gqa_workspace_bytes(), which is 0 for a shape that is not served). */
+size_t gptq_decode_attn_batch_gqa_workspace_bytes(int batch, int heads, int kv_heads, int head_dim, int t_max);
+int gptq_decode_attn_batch_gqa_f16(const void *qkv, int64_t ldq, const int64_t *positions, void *k_cache, void *v_cache, void *out, int64_t ldo,
+                                   void *workspace, size_t workspace_bytes, int batch, int heads, int kv_heads, int head_dim, int t_max, float base,
+                                   float scale, const float *rope_table, const int32_t *out_perm, gptq_stream_t stream);
+
 /* ---- prompt prefill: causal attention of a chunk of tokens over the decode engine's own cache (csrc/prompt_attn.hip) ----------------------------
  * Replaces, for a prompt, what QuantLlamaAttention.forward does between qkv_proj and o_proj (quant/fused_attn.py:126-158: triton_rotate_half_ on q and
  * k, torch.cat onto the past, F.scaled_dot_product_attention with is_causal) on the cache layout of the decode entries above: `rows` consecutive
