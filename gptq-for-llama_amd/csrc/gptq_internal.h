@@ -281,6 +281,14 @@ int decode_attn_kv8_launch(const half_t *qkv, const int64_t *pos, uint8_t *k8, u
 int kv8_store_launch(const half_t *k16, const half_t *v16, int64_t slot_stride, const gptq_prompt_seg_t *segs, int nseq, uint8_t *k8, uint8_t *v8,
                      int8_t *kexp, int8_t *vexp, int heads, int t_max, hipStream_t s);
 
+// decode_attn_kv4.hip: the same two over the int4 cache k4 / v4 [batch][t_max][heads * 64] code bytes with kmeta / vmeta [batch][t_max][heads][4][2]
+// fp16 {d, m} per group of 32 values
+int decode_attn_kv4_launch(const half_t *qkv, const int64_t *pos, uint8_t *k4, uint8_t *v4, half_t *kmeta, half_t *vmeta, half_t *out, float *ws,
+                           int heads, int t_max, float base, float scale, const float *rope_table, hipStream_t s, int batch, int64_t ldq,
+                           int64_t ldo, const int32_t *out_perm, int tps);
+int kv4_store_launch(const half_t *k16, const half_t *v16, int64_t slot_stride, const gptq_prompt_seg_t *segs, int nseq, uint8_t *k4, uint8_t *v4,
+                     half_t *kmeta, half_t *vmeta, int heads, int t_max, hipStream_t s);
+
 // prompt_attn.hip: RoPE + cache append of `rows` tokens at positions start .. start + rows - 1, then causal attention over cache rows [0, start + rows);
 // ws = prompt_attn_ws_bytes(rows, heads) bytes (the rotated q)
 size_t prompt_attn_ws_bytes(int rows, int heads);

@@ -172,6 +172,11 @@ _SIGNATURES = {
                                        c_int, c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p, c_int, c_void_p],
     'gptq_kv8_store_f16': [c_void_p, c_void_p, c_int64, ctypes.POINTER(PromptSeg), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                            c_void_p],
+    # int4 KV cache: the same two over 4-bit codes + an fp16 {d, m} per group of 32 values (csrc/decode_attn_kv4.hip)
+    'gptq_decode_attn_batch_kv4_f16': [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_size_t,
+                                       c_int, c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p, c_int, c_void_p],
+    'gptq_kv4_store_f16': [c_void_p, c_void_p, c_int64, ctypes.POINTER(PromptSeg), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                           c_void_p],
     # grouped-query models: the batch decode attention with kv_heads < heads, one K/V stream per group of query heads (csrc/decode_attn_gqa.hip)
     'gptq_decode_attn_batch_gqa_workspace_bytes': [c_int, c_int, c_int, c_int, c_int],
     'gptq_decode_attn_batch_gqa_f16': [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_size_t, c_int, c_int, c_int, c_int,

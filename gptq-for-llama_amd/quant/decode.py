@@ -183,6 +183,17 @@ MAX_PROCESS_EOS, MAX_PROCESS_BIAS, MAX_PROCESS_VOCAB = 8, 256, 131072      # GPT
 MAX_BEAMS = 16         # GPTQ_BEAM_MAX_BEAMS
 MAX_CONSTRAIN_STATES, MAX_CONSTRAIN_CLASSES = 32767, 16384                 # GPTQ_CONSTRAIN_MAX_STATES / _CLASSES
 BEAM_DEAD = -1e9
+# The quantised K/V cache formats of gptq_mi355x.h ("fp8 KV cache", "int4 KV cache"): the decode attention entry, the entry that converts staged
+# fp16 prompt rows, and the engine's arrays behind [layers, B, t_max] -- (names of the K and the V array, dtype, trailing shape for `heads`), in
+# the order both entries take them.  Everything else about such an engine is one path (DecodeEngine.kvq).
+KV_QUANT = {
+    'fp8': dict(attn='gptq_decode_attn_batch_kv8_f16', store='gptq_kv8_store_f16',
+                arrays=((('k8b', 'v8b'), torch.uint8, lambda heads: (heads * 128,)),           # e4m3fn bytes
+                        (('kexpb', 'vexpb'), torch.int8, lambda heads: (heads,)))),            # one exponent per (token, head)
+    'int4': dict(attn='gptq_decode_attn_batch_kv4_f16', store='gptq_kv4_store_f16',
+                 arrays=((('k4b', 'v4b'), torch.uint8, lambda heads: (heads * 64,)),           # 4-bit codes, two per byte
+                         (('kmetab', 'vmetab'), torch.float16, lambda heads: (heads, 4, 2)))),  # {d, m} per group of 32 values
+}
 MAX_LOGPROBS, MAX_LOGPROBS_ROWS = 32, 128      # GPTQ_LOGPROBS_MAX_TOP, the rows of one gptq_logprobs_rows_f16 launch
 # gptq_beam_select_f16's state block in 4-byte words (gptq_mi355x.h "beam search")
 (BEAM_W_EOS, BEAM_W_MAX_NEW, BEAM_W_LP, BEAM_W_ES, BEAM_W_T_CAP, BEAM_W_BEAMS, BEAM_W_T, BEAM_W_OPEN, BEAM_W_DONE, BEAM_W_STATUS) = range(10)
@@ -248,6 +259,10 @@ class DecodeEngine:
         (greedy, sampling, processors, log-probabilities, constraints, every capture helper) is unchanged.  ValueError('... not built yet')
         before anything is allocated: together with chunk, batch_chunk, beam_search or fuse_attn=False; and, before anything changes, from
         prefill / prefill_batch with a start other than 0 or a prompt that needs more than one max_rows pass, and from score / score_batch.
+        kv_cache = 'int4' is the same engine on the format of gptq_mi355x.h "int4 KV cache": k4b / v4b uint8 [layers, B, t_max, heads * 64]
+        (4-bit codes) with kmetab / vmetab fp16 [layers, B, t_max, heads, 4, 2] ({d, m} per group of 32 values) -- 80 bytes per (token, head)
+        and array against 256; gptq_decode_attn_batch_kv4_f16 steps, gptq_kv4_store_f16 converts the staged prompt rows.  It is ONE path with
+        fp8 (KV_QUANT, self.kvq): the same staging, the same refusals with the same messages.
         'fp16' (the default) allocates and launches exactly what it always did.
         constrain = True (dict(states=4096, classes=1024)) or a dict of those two capacities adds CONSTRAINED DECODING for regular languages
         (gptq_constrain_rows_f16, gptq_mi355x.h "constrained decoding"; quant/constrain.py builds the automata): c_next int16 [states, classes]
@@ -347,12 +362,13 @@ class DecodeEngine:
                                  'verify step, of a beam)')
             self.constrain = cap
         self.fuse_norm, self.fuse_attn = bool(fuse_norm), bool(fuse_attn)
-        if kv_cache not in ('fp16', 'fp8'):
-            raise ValueError("DecodeEngine: kv_cache must be 'fp16' or 'fp8', not %r" % (kv_cache,))
+        if kv_cache != 'fp16' and kv_cache not in KV_QUANT:
+            raise ValueError("DecodeEngine: kv_cache must be 'fp16', 'fp8' or 'int4', not %r" % (kv_cache,))
         self.kv_cache = kv_cache
-        if kv_cache == 'fp8' and (self.chunk or self.batch_chunk or self.beam_search or not self.fuse_attn):
-            raise ValueError("DecodeEngine: kv_cache='fp8' together with chunk / batch_chunk / beam_search / fuse_attn=False is not built yet (the "
-                             "fp8 cache has the fused decode attention and the prompt store, nothing else)")
+        self.kvq = KV_QUANT.get(kv_cache)              # a quantised cache's entries and arrays; None: the fp16 cache
+        if self.kvq and (self.chunk or self.batch_chunk or self.beam_search or not self.fuse_attn):
+            raise ValueError("DecodeEngine: kv_cache='%s' together with chunk / batch_chunk / beam_search / fuse_attn=False is not built yet (the "
+                             "%s cache has the fused decode attention and the prompt store, nothing else)" % (kv_cache, kv_cache))
         self.native = _native
         self.lib = _native.lib()
         self.model = model
@@ -373,7 +389,7 @@ class DecodeEngine:
         self.kv_heads = int(getattr(cfg, 'num_key_value_heads', None) or self.heads)
         self.grouped = self.kv_heads != self.heads
         if self.grouped:
-            if self.chunk or self.batch_chunk or self.tree or self.beam_search or kv_cache == 'fp8' or not self.fuse_attn:
+            if self.chunk or self.batch_chunk or self.tree or self.beam_search or self.kvq or not self.fuse_attn:
                 raise ValueError("DecodeEngine: a grouped-query model (%d query heads on %d K/V heads) together with chunk / batch_chunk / tree / "
                                  "beam_search / kv_cache='fp8' / fuse_attn=False is not built yet (the grouped decode attention is the only "
                                  "grouped kernel)" % (self.heads, self.kv_heads))
@@ -440,10 +456,14 @@ class DecodeEngine:
             self.c_state = torch.full((B,), -1, dtype=torch.int32, device=dev)
             self._c_dfas, self._c_start = [None] * B, [-1] * B       # the rows' automata and start states, as set_constraint left them
         nl = len(self.layers)
-        if self.kv_cache == 'fp8':
-            u8, i8 = dict(dtype=torch.uint8, device=dev), dict(dtype=torch.int8, device=dev)
-            self.k8b, self.v8b = torch.zeros((nl, B, self.t_max, H), **u8), torch.zeros((nl, B, self.t_max, H), **u8)      # e4m3fn bytes
-            self.kexpb, self.vexpb = torch.zeros((nl, B, self.t_max, self.heads), **i8), torch.zeros((nl, B, self.t_max, self.heads), **i8)
+        if self.kvq:
+            # the format's four arrays [layers, B, t_max, ...] under their own names (fp8: k8b / v8b / kexpb / vexpb; int4: k4b / v4b / kmetab /
+            # vmetab), and in the order the C entries take them
+            self.kvq_bufs = []
+            for names, dtype, tail in self.kvq['arrays']:
+                for name in names:
+                    setattr(self, name, torch.zeros((nl, B, self.t_max) + tail(self.heads), dtype=dtype, device=dev))
+                    self.kvq_bufs.append(getattr(self, name))
             self.kst, self.vst = torch.zeros((B, self.t_max, H), **f16), torch.zeros((B, self.t_max, H), **f16)          # ONE layer of fp16 staging
         else:
             self.kcb = torch.zeros((nl, B, self.t_max, KV), **f16)         # [layer][row][t][kv_heads * head_dim]
@@ -480,7 +500,7 @@ class DecodeEngine:
         self.attn_records = bool(ATTN_RECORDS and self.fuse_attn and B == 1 and self.kv_cache == 'fp16' and not self.grouped and all(
             L['o']['st'] is not None and L['o']['bias'] is None and
             self.lib.gptq_layer_decode_attn_supported(L['o']['_keep'].handle, 1, self.heads, self.head_dim) == 1 for L in self.layers))
-        if B > 1 or self.kv_cache == 'fp8' or self.grouped:        # (an fp8 and a grouped engine step through _step_rows at every batch size)
+        if B > 1 or self.kvq or self.grouped:        # (a quantised-cache and a grouped engine step through _step_rows at every batch size)
             self.scratch = self._rows_scratch('batch', (B,))
         self.verify_graph, self.verify_sample_graphs, self.spec_stats = None, {}, None
         self.draft_graph, self._draft_engine = None, None          # capture_draft_step (a draft engine) / (draft model, its engine) of a target engine
@@ -730,13 +750,12 @@ class DecodeEngine:
         """a decode batch: _step_rows at M = batch, gptq_decode_attn_batch_f16 on every row's own cache slice and position (an fp8 engine:
         gptq_decode_attn_batch_kv8_f16 on its bytes and exponents, at every batch size).  beam: the step of an indirect beam engine -- the rows
         are beams at pos[0] and attend through beam_src (gptq_decode_attn_beam_f16); every other step of such an engine is the plain batch step"""
-        def attn8(li, L, qkvb, ab, tab, s):
-            rc = self.lib.gptq_decode_attn_batch_kv8_f16(qkvb.data_ptr(), qkvb.stride(0), self.pos.data_ptr(), self.k8b[li].data_ptr(),
-                                                         self.v8b[li].data_ptr(), self.kexpb[li].data_ptr(), self.vexpb[li].data_ptr(),
-                                                         ab.data_ptr(), ab.stride(0), self.attn_ws.data_ptr(), self.attn_ws.numel(), self.batch,
-                                                         self.heads, self.head_dim, self.t_max, L['theta'], self.scale, self.native.ptr(tab), None,
-                                                         0, s)
-            self.native.check(rc, 'gptq_decode_attn_batch_kv8_f16')
+        def attnq(li, L, qkvb, ab, tab, s):                     # a quantised cache: the format's entry on its four arrays (one argument list)
+            rc = getattr(self.lib, self.kvq['attn'])(qkvb.data_ptr(), qkvb.stride(0), self.pos.data_ptr(), *[t[li].data_ptr() for t in self.kvq_bufs],
+                                                     ab.data_ptr(), ab.stride(0), self.attn_ws.data_ptr(), self.attn_ws.numel(), self.batch,
+                                                     self.heads, self.head_dim, self.t_max, L['theta'], self.scale, self.native.ptr(tab), None,
+                                                     0, s)
+            self.native.check(rc, self.kvq['attn'])
 
         def attn(li, L, qkvb, ab, tab, s):
             rc = self.lib.gptq_decode_attn_batch_f16(qkvb.data_ptr(), qkvb.stride(0), self.pos.data_ptr(), self.kcb[li].data_ptr(),
@@ -763,11 +782,11 @@ class DecodeEngine:
         elif self.grouped:
             attn = attn_gqa
         self._step_rows(dict(x=self.x, x2=self.x2, h=self.h, qkv=self.qkvb, ab=self.ab, cb=self.cb), self.ids,
-                        attn8 if self.kv_cache == 'fp8' else attn, self.logits)
+                        attnq if self.kvq else attn, self.logits)
         self.pos.add_(1)
 
     def _step(self):
-        if self.batch > 1 or self.kv_cache == 'fp8' or self.grouped:
+        if self.batch > 1 or self.kvq or self.grouped:
             return self._step_batch()
         lib, ptr = self.lib, self.native.ptr
         s = torch.cuda.current_stream(self.dev).cuda_stream
@@ -1436,14 +1455,13 @@ class DecodeEngine:
         self.pos.index_copy_(0, rows_t, torch.tensor(pos, dtype=torch.int64, device=self.dev))
         return self.logits[rows_t]
 
-    def _kv8_store(self, li, table, nseq, s):
-        """an fp8 engine: the rows of the segments `table` (a PromptSeg array: rows start .. start + rows - 1 of cache row slot) of the fp16 staging
-        cache kst / vst -> layer li of the fp8 cache (gptq_kv8_store_f16, one launch)"""
+    def _kvq_store(self, li, table, nseq, s):
+        """a quantised-cache engine: the rows of the segments `table` (a PromptSeg array: rows start .. start + rows - 1 of cache row slot) of the
+        fp16 staging cache kst / vst -> layer li of the cache in its format (gptq_kv8_store_f16 / gptq_kv4_store_f16, one launch)"""
         with self.native.on_device(self.dev):
-            rc = self.lib.gptq_kv8_store_f16(self.kst.data_ptr(), self.vst.data_ptr(), self.kst.stride(0), table, nseq, self.k8b[li].data_ptr(),
-                                             self.v8b[li].data_ptr(), self.kexpb[li].data_ptr(), self.vexpb[li].data_ptr(), self.heads,
-                                             self.head_dim, self.t_max, s)
-        self.native.check(rc, 'gptq_kv8_store_f16')
+            rc = getattr(self.lib, self.kvq['store'])(self.kst.data_ptr(), self.vst.data_ptr(), self.kst.stride(0), table, nseq,
+                                                      *[t[li].data_ptr() for t in self.kvq_bufs], self.heads, self.head_dim, self.t_max, s)
+        self.native.check(rc, self.kvq['store'])
 
     def _need_ungrouped(self, what):
         if self.grouped:
@@ -1468,10 +1486,10 @@ class DecodeEngine:
         start = int(self.pos[row]) if start is None else int(start)
         if start < 0 or start + T > self.t_max:
             raise ValueError('DecodeEngine.prefill: positions %d .. %d do not fit the engine cache (%d)' % (start, start + T - 1, self.t_max))
-        fp8 = self.kv_cache == 'fp8'
+        fp8 = bool(self.kvq)                 # (any quantised cache: the prompt goes through the fp16 staging layer and the format's store)
         if fp8 and start != 0:
-            raise ValueError("DecodeEngine.prefill: start = %d on a kv_cache='fp8' engine is not built yet (the prompt attention reads fp16 rows: "
-                             "only a whole prompt from position 0)" % start)
+            raise ValueError("DecodeEngine.prefill: start = %d on a kv_cache='%s' engine is not built yet (the prompt attention reads fp16 rows: "
+                             "only a whole prompt from position 0)" % (start, self.kv_cache))
         with torch.no_grad(), torch.cuda.device(self.dev):
             s = self.native.stream_ptr(self.dev)
             self._prefill_buffers(T)
@@ -1484,7 +1502,7 @@ class DecodeEngine:
                                                    L['theta'], self.scale, self.native.ptr(tab), s)
                 self.native.check(rc, 'gptq_prompt_attn_f16')
                 if fp8:
-                    self._kv8_store(li, table, 1, s)
+                    self._kvq_store(li, table, 1, s)
             ids = ids.to(device=self.dev, dtype=torch.int64)
             x, _ = self._prompt_layers(ids, attn, s)
             if self.logits_process:
@@ -1523,9 +1541,9 @@ class DecodeEngine:
             raise ValueError('DecodeEngine.%s: max_rows must be positive' % what)
         total = sum(lens)
         offs = [sum(lens[:i]) for i in range(n)]                                    # first packed row of prompt i
-        fp8 = self.kv_cache == 'fp8'
+        fp8 = bool(self.kvq)                 # (any quantised cache, as in prefill)
         if fp8 and (score or any(st != 0 for st in starts) or total > max_rows):
-            raise ValueError("DecodeEngine.%s on a kv_cache='fp8' engine is not built yet: %s" % (what, (
+            raise ValueError("DecodeEngine.%s on a kv_cache='%s' engine is not built yet: %s" % (what, self.kv_cache, (
                 'scoring' if score else 'a start other than 0' if any(st != 0 for st in starts) else
                 '%d packed rows need more than one pass of max_rows = %d' % (total, max_rows)) +
                 ' (the prompt attention reads fp16 rows: only whole prompts from position 0 in one pass)'))
@@ -1568,7 +1586,7 @@ class DecodeEngine:
                                                              self.native.ptr(tab), s)
                     self.native.check(rc, 'gptq_prompt_attn_batch_f16')
                     if fp8:
-                        self._kv8_store(li, table, len(segs), s)
+                        self._kvq_store(li, table, len(segs), s)
                 x, h = self._prompt_layers(ids[p0:p0 + M], attn, s)
                 if ends:
                     dst = torch.tensor([i for i, _ in ends], dtype=torch.int64, device=self.dev)
@@ -2134,8 +2152,8 @@ def _prompt_into_engine(model, input_ids, eng, prefill):
     from transformers.cache_utils import DynamicCache
     cache = DynamicCache(config=model.config)
     out = model(input_ids, past_key_values=cache, use_cache=True)
-    fp8 = eng.kv_cache == 'fp8'
-    if fp8:                                                      # the module cache goes through the staging layer, as the engine's own prefill does
+    fp8 = bool(eng.kvq)
+    if fp8:                                                      # a quantised cache: the module cache goes through the staging layer, as the engine's own prefill does
         table, s = (eng.native.PromptSeg * 1)(eng.native.PromptSeg(0, T, 0, 0)), eng.native.stream_ptr(eng.dev)
     for li in range(len(eng.layers)):
         k, v = _cache_layer_kv(cache, li)
@@ -2143,7 +2161,7 @@ def _prompt_into_engine(model, input_ids, eng, prefill):
         kc[:T].copy_(k[0].transpose(0, 1).reshape(T, -1))
         vc[:T].copy_(v[0].transpose(0, 1).reshape(T, -1))
         if fp8:
-            eng._kv8_store(li, table, 1, s)
+            eng._kvq_store(li, table, 1, s)
     eng.pos.fill_(T)
     if eng.logits_process:
         eng.set_history(0, input_ids[0])
@@ -2546,12 +2564,13 @@ def _constrain_setting(what, constrain, n, speculate, engine):
 
 
 def _kv_cache_setting(what, kv_cache, speculate, engine):
-    """the kv_cache= argument of `what` (engine_generate / engine_generate_batch), validated: 'fp16' or 'fp8'; ValueError for 'fp8' under
-    speculate= and for an engine passed in of the other kind"""
-    if kv_cache not in ('fp16', 'fp8'):
-        raise ValueError("%s: kv_cache must be 'fp16' or 'fp8', not %r" % (what, kv_cache))
-    if kv_cache == 'fp8' and speculate is not None:
-        raise ValueError("%s: kv_cache='fp8' together with speculate is not built yet (the verify step's chunk attention reads an fp16 cache)" % what)
+    """the kv_cache= argument of `what` (engine_generate / engine_generate_batch), validated: 'fp16', 'fp8' or 'int4'; ValueError for a
+    quantised cache under speculate= and for an engine passed in of another kind"""
+    if kv_cache != 'fp16' and kv_cache not in KV_QUANT:
+        raise ValueError("%s: kv_cache must be 'fp16', 'fp8' or 'int4', not %r" % (what, kv_cache))
+    if kv_cache in KV_QUANT and speculate is not None:
+        raise ValueError("%s: kv_cache='%s' together with speculate is not built yet (the verify step's chunk attention reads an fp16 cache)" % (
+            what, kv_cache))
     if engine is not None and engine.kv_cache != kv_cache:
         raise ValueError('%s: kv_cache=%r for an engine built with kv_cache=%r' % (what, kv_cache, engine.kv_cache))
 

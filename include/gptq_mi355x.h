@@ -626,6 +626,32 @@ int gptq_decode_attn_batch_kv8_f16(const void *qkv, int64_t ldq, const int64_t *
                                    int64_t ldo, void *workspace, size_t workspace_bytes, int batch, int heads, int head_dim, int t_max, float base,
                                    float scale, const float *rope_table, const int32_t *out_perm, int tokens_per_split, gptq_stream_t stream);
 
+/* ---- int4 KV cache: the decode attention over 4-bit codes with an fp16 scale and minimum per group of 32 values (csrc/decode_attn_kv4.hip) ------
+ * The weights are 4-bit; this brings the other large stream of a decode step to 80 bytes per (token, head) and array, against 256 (fp16) and 129
+ * (fp8).  A head row of 128 fp16 values is four GROUPS of 32 consecutive values.  One cache (K or V) of `slots` sequences is two arrays:
+ *     k4 / v4         uint8 [slot][t_max][heads * 64]      the codes c in 0 .. 15, two per byte: 16 bytes per group, groups in order
+ *     kmeta / vmeta   fp16  [slot][t_max][heads][4][2]     {d, m} per group; the stored value means m + d c
+ * Nibble order: the 16 bytes of a group are four little-endian 32-bit words; word w holds elements 8w .. 8w + 7 of the group; its nibble s (bits
+ * 4s .. 4s + 3), s = 0 .. 3, is element 8w + 2s and nibble 4 + s is element 8w + 2s + 1.  (So bytes 4w .. 4w + 3 hold, low nibble first, elements
+ * {0, 2}, {4, 6}, {1, 3}, {5, 7} of the word: one shift and one mask turn a word into a PAIR of neighbouring elements.)
+ * Quantising a group r[0 .. 32) (for K: the bits the fp16 cache would hold -- rotated, rounded to fp16).  Every step is ONE IEEE fp32 operation,
+ * no contraction to fused multiply-add, no fast-math:
+ *     m = min r_i (an fp16 value: exact; a zero minimum or maximum counts as +0, whatever the signs of the zeros);  d = fp16_rne((max r_i - m) / 15.0f);
+ *     d == 0: every code is 0;  otherwise c_i = clamp(rint((r_i - m) * (1.0f / (float)d)), 0, 15), rint to nearest even.
+ * tests/kv4_ref.py restates this in PyTorch on the CPU; that restatement is the specification.  Rows with NaN / inf are outside the contract;
+ * they cannot fault (no index depends on data).
+ *
+ * gptq_decode_attn_batch_kv4_f16   gptq_decode_attn_batch_kv8_f16 on such a cache, argument for argument: the new token is rotated, quantised,
+ *     attended to in its quantised form and appended (codes and metadata), so a step is a function of the cache alone; idle rows, the run-time
+ *     split count, the deterministic merge, out_perm, tokens_per_split and the workspace of gptq_decode_attn_batch_workspace_bytes are that
+ *     entry's, and so are its checks in their order -- with kmeta / vmeta aligned to 4 bytes (GPTQ_E_ALIGN).
+ * gptq_kv4_store_f16               gptq_kv8_store_f16 into this format: the rows of nseq <= 16 segments of an fp16 cache -> the same rows of the int4
+ *     cache, by the rule above.  One launch, no atomics; nothing outside the segments is written.  The checks of that entry, with kmeta / vmeta
+ *     aligned to 4 bytes. */
+int gptq_decode_attn_batch_kv4_f16(const void *qkv, int64_t ldq, const int64_t *positions, void *k4, void *v4, void *kmeta, void *vmeta, void *out,
+                                   int64_t ldo, void *workspace, size_t workspace_bytes, int batch, int heads, int head_dim, int t_max, float base,
+                                   float scale, const float *rope_table, const int32_t *out_perm, int tokens_per_split, gptq_stream_t stream);
+
 /* ---- grouped-query decode attention: one K/V stream per group of query heads (csrc/decode_attn_gqa.hip) -----------------------------------------
  * Llama-2-70B, Llama-3, Mistral and Qwen2 keep kv_heads < heads K/V heads; query head h attends over K/V head h / G, G = heads / kv_heads (HF's
  * repeat_kv in front of F.scaled_dot_product_attention).  The entry below is gptq_decode_attn_batch_f16 for such a layer WITHOUT the repeat: one
@@ -684,6 +710,9 @@ int gptq_prompt_attn_batch_f16(const void *qkv, int64_t ldq, int total_rows, con
 /* ("fp8 KV cache" above: the rows such a call appended to an fp16 staging cache, converted into the fp8 cache) */
 int gptq_kv8_store_f16(const void *k16, const void *v16, int64_t slot_stride, const gptq_prompt_seg_t *segs, int nseq, void *k8, void *v8,
                        void *kexp, void *vexp, int heads, int head_dim, int t_max, gptq_stream_t stream);
+/* ("int4 KV cache" above: the same into the int4 cache) */
+int gptq_kv4_store_f16(const void *k16, const void *v16, int64_t slot_stride, const gptq_prompt_seg_t *segs, int nseq, void *k4, void *v4,
+                       void *kmeta, void *vmeta, int heads, int head_dim, int t_max, gptq_stream_t stream);
 
 /* ---- speculative decoding: attention of a CHUNK of a decoding sequence with the position in device memory (csrc/chunk_attn.hip) ----------------
  * Replaces what HF generate's one-token loop (llama_inference.py:109-115) does R times between qkv_proj and o_proj: `rows` (1 .. 16, a host value: it
